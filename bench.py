@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- megapixels/s of the full raw->sRGB pipe on a 100 MP f32 Bayer frame (BASELINE.json's metric).
 
-  python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5|c5b] [--batch B --width X --height Y]
+  python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5|c5b] [--batch B --width X --height Y] [--full] [--dump-outputs DIR]
   N > 1: one rank per GPU.  Either the caller starts the ranks (python -m torch.distributed.run --nnodes=1 --nproc-per-node N
   --master-addr 127.0.0.1 ... bench.py --gpus N ...) or, invoked plainly, bench.py starts them itself the same way (relaunch_as_ranks).
   A line whose n_gpus differs from --gpus is never printed: fewer visible GPUs than N, or a WORLD_SIZE that is not N, is a non-zero exit.
@@ -15,10 +15,13 @@ rank i mod N with no data-path collective; value = all frames' pixels / max-rank
   --config c4            configs[3]: a batch of 64 x 24 MP frames sharded frame i -> rank i mod N (strong scaling; = --batch 64
                          --width 6000 --height 4000), with a second figure that includes the all-gather of the f32 results
   --config c5 / c5b      configs[4]: 8640x5760 X-Trans -> 2160x1440 (scaled demosaic + point-wise chain) / the same at full size
-The default run also reports, as extra objects of the same line: the cold-clock time, the median, the measured device-copy
-ceiling, two more data kinds (smooth, photo), the 64 x 24 MP batch (configs[3]) and the VALU-issue model of the kernel; with N > 1 also
-`band_mode`: ONE frame row-sharded over the N GPUs on the library's RCCL transport (halo exchange, band kernel, all-gather), measured in child
-processes so that it cannot cost the line.
+A plain run sets up, warms up, times the K steps and prints the line (the VALU-issue model and the traffic figure come from the committed
+profiles/).  With --full the default workload also reports, as extra objects of the same line: the parity check against the CPU oracle, the
+cold-clock time, the median, the box state, the live HBM traffic, the measured device-copy ceiling, two more data kinds (smooth, photo), the
+64 x 24 MP batch (configs[3]) and the CPU baseline; with N > 1 also `scale` and `band_mode`: ONE frame row-sharded over the N GPUs on the
+library's RCCL transport (halo exchange, band kernel, all-gather), measured in child processes so that it cannot cost the line.
+--dump-outputs DIR writes what the last timed step computed (rank 0's frames) as DIR/<name>.npy; the inputs are seeded, so two builds compare
+output for output.
 """
 import argparse
 import ctypes
@@ -65,13 +68,18 @@ def parse():
                          "(the op is a no-op unless --exposure is set); user5 = five user points (7 knots: the binary search of SplineFunc::interpolate)")
     ap.add_argument("--exposure", type=float, default=0.0, help="OpBaseCurve.exposure")
     ap.add_argument("--linear", action="store_true", help="PipelineSettings.linear: no OpGamma (src/ops/gamma.rs:17); u16 output forces it as output_16bit does")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the oracle parity check, the median pass, the secondary measurements (--no-extras), the box state, "
+                         "live PMC traffic, the gather / scale legs, the CPU baseline.  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; a fixed, seeded row sample of large outputs)")
     ap.add_argument("--kernel-stats", type=int, default=0, metavar="N",
                     help="additionally time N single launches with an event pair each and report min / median / p95 / max / stddev (roofline.launch_stats)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline leg")
-    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the parity check against the CPU oracle")
     ap.add_argument("--no-live-traffic", action="store_true", help="keep the committed PMC traffic figure instead of measuring it in two short child runs under rocprofv3 (at most 45 s each)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (cold clock, copy ceiling, other data kinds, 64-frame batch)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the secondary measurements (cold clock, copy ceiling, other data kinds, 64-frame batch)")
     ap.add_argument("--prewarm-ms", type=float, default=250.0,
                     help="untimed launches before the W warmup steps, to bring the shader clock to its loaded steady state (0 = off); "
                          "the same workload without it is reported as config.cold_ms")
@@ -89,7 +97,10 @@ def parse():
                                                     "development: two contexts on the one GPU of a 1-GPU box)")
     ap.add_argument("--sp-child", default=None, metavar="DEVICES", help=argparse.SUPPRESS)
     ap.add_argument("--band-child", nargs=4, metavar=("RANK", "WORLD", "LOCAL_RANK", "IDHEX"), default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:           # a plain run measures the headline only; legs asked for by name (--kernel-stats, --host-boundary, --band) still run
+        args.no_check = args.no_extras = args.no_cpu_baseline = args.no_box_state = args.no_live_traffic = True
+    return args
 
 
 def synth_frame(torch, h, w, kind, seed):
@@ -211,10 +222,10 @@ class Ctx:
         return [float(v) for v in t]
 
 
-def timed(ctx, step, steps, warmup, prewarm_ms=0.0):
+def timed(ctx, step, steps, warmup, prewarm_ms=0.0, median=True):
     """W untimed warm-ups, then EXACTLY `steps` steps between barrier + synchronize on both sides.  Returns (wall seconds for the
     K steps, max over ranks; mean HIP-event milliseconds per step over that region and the median of a second, per-step-evented pass of K
-    steps, on the launch stream, max over ranks)."""
+    steps, on the launch stream, max over ranks).  median=False skips the second pass and returns None for the median."""
     torch = ctx.torch
     ctx.barrier()
     if prewarm_ms > 0:
@@ -237,6 +248,9 @@ def timed(ctx, step, steps, warmup, prewarm_ms=0.0):
     ctx.barrier()
     elapsed = time.perf_counter() - t0
     mean_ms = ev_a.elapsed_time(ev_b) / steps
+    if not median:
+        elapsed, mean_ms = ctx.max_over_ranks([elapsed, mean_ms])
+        return elapsed, mean_ms, None
     # the median comes from a second pass of K steps with an event between every two (outside the timed region: each event is a marker
     # in the queue that costs the GPU a few microseconds of idle time, which matters for the 0.1 ms configurations)
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
@@ -249,6 +263,39 @@ def timed(ctx, step, steps, warmup, prewarm_ms=0.0):
     median_ms = per[steps // 2] if steps % 2 else 0.5 * (per[steps // 2 - 1] + per[steps // 2])
     elapsed, mean_ms, median_ms = ctx.max_over_ranks([elapsed, mean_ms, median_ms])
     return elapsed, mean_ms, median_ms
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: float32 bytes written in all (the row indices of sampled frames come on top)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(torch, outdir, frames):
+    """--dump-outputs: the output buffers as the timed path's last step left them, one DIR/<name>.npy (float32) per (name, tensor, rows, colors).
+    A frame that fits its share of DUMP_BYTES is written whole as (rows, width, colors); a larger one as a fixed, seeded sample of its rows, the
+    first and the last row always among them, with their indices in DIR/<name>_rows.npy; a single row larger than the share is cut to it."""
+    import numpy as np
+    if not frames:
+        return
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BYTES // len(frames)
+    for name, t, rows, colors in frames:
+        t2 = t.view(rows, -1)
+        n = max(1, share // (4 * t2.shape[1]))
+        idx = None
+        if n < rows or 4 * t2.shape[1] > share:
+            rng = np.random.default_rng(DUMP_SEED)
+            pick = rng.choice(np.arange(1, rows - 1), size=n - 2, replace=False) if n > 2 else []
+            idx = np.unique(np.concatenate(([0, rows - 1][:n], pick))).astype(np.int64)
+            t2 = t2.index_select(0, torch.as_tensor(idx, device=t.device))[:, : share // 4]
+        a = t2.cpu().numpy()
+        if a.dtype == np.int16:                          # the 16-bit output lives in an int16 tensor: its bits are u16 samples
+            a = a.view(np.uint16)
+        a = a.astype(np.float32)
+        if a.shape[1] % colors == 0:
+            a = a.reshape(a.shape[0], -1, colors)
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        if idx is not None:
+            np.save(os.path.join(outdir, name + "_rows.npy"), idx.astype(np.float64))
 
 
 class FusedBatch:
@@ -728,7 +775,9 @@ def main():
         ctx.barrier(); time.sleep(0.5)
         _, cold_ms, _ = timed(ctx, wl.step, args.steps, 0, 0.0)
 
-    elapsed, mean_ms, median_ms = timed(ctx, wl.step, args.steps, args.warmup, args.prewarm_ms)
+    elapsed, mean_ms, median_ms = timed(ctx, wl.step, args.steps, args.warmup, args.prewarm_ms, median=args.full)
+    if args.dump_outputs and rank == 0:                         # rank 0's frames (each rank's results stay on its GPU)
+        dump_outputs(torch, args.dump_outputs, [("frame%d" % i, d, H, 3) for i, d in zip(wl.mine, wl.dsts)])
     kernel_ms = mean_ms / wl.launches_per_step                  # HIP events on the launch stream: average launch duration over the timed region
     mp_total = args.steps * B * (H * W) / 1e6
     value = mp_total / elapsed
@@ -742,8 +791,7 @@ def main():
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None,
         "value_basis": "all frames' pixels / wall time of the K timed steps (barrier + synchronize on both sides, max over ranks), i.e. the MEAN step; "
-                       "the median step is roofline.kernel_ms_median, the run without clock pre-warm config.cold_ms",
-        "value_from_median_step": round(B * (H * W) / 1e6 / (median_ms * 1e-3), 1),
+                       "the median step is roofline.kernel_ms_median, the run without clock pre-warm config.cold_ms (both with --full)",
         "dtype": "f32", "data": "synthetic (%s, 14-bit %s sensor values, torch Philox seed 0x%X+frame)" % (args.data, cfa if len(cfa) == 4 else "X-Trans", util.SEED + 2),
         "config": {"workload": "%dx%d (%.0f MP) synthetic %s %s mosaic -> fused gofloat+demosaic+tolab+basecurve+fromlab+gamma -> %s RGB, %s"
                                % (W, H, H * W / 1e6, cfa if len(cfa) == 4 else "X-Trans", args.src, args.out,
@@ -755,9 +803,11 @@ def main():
                    "host_cbrtf_matches_device": ipa.lib().ipk_host_libm_matches(None) == 1},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                     "kernel": "k_fused_bayer", "kernel_ms": round(kernel_ms, 4), "kernel_ms_median": round(median_ms / wl.launches_per_step, 4),
-                     "algorithmic_bytes_per_launch": alg_bytes},
+                     "kernel": "k_fused_bayer", "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": alg_bytes},
     }
+    if median_ms is not None:
+        result["value_from_median_step"] = round(B * (H * W) / 1e6 / (median_ms * 1e-3), 1)
+        result["roofline"]["kernel_ms_median"] = round(median_ms / wl.launches_per_step, 4)
     if world > 1:
         # what a reader of an N > 1 line must not miss: `value` is weak scaling of independent frames (one frame per GPU per step, nothing exchanged), so it
         # grows ~N x by construction and proves nothing about a node; the judgeable object is `scale` (BASELINE.json configs[3]: the SAME 64 x 24 MP batch on
@@ -870,7 +920,7 @@ def main():
         result["band_mode"] = band_children(ctx, args, W, H)
         ctx.barrier()
 
-    if args.config == "c4" or (args.batch is not None and args.batch > world):
+    if args.full and (args.config == "c4" or (args.batch is not None and args.batch > world)):
         result["with_gather"] = gather_leg(ctx, wl, steps=max(2, args.steps // 4)) if world > 1 else {
             "note": "one GPU: every result is already resident on it, the gather is a no-op"}
         if world > 1:
@@ -884,7 +934,7 @@ def main():
     # ---- CPU baseline: the oracle's reference-shaped pipeline (unfused, one task per row) on this host ----
     if rank == 0 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(util, args.data, args.cpu_seconds)
-    if world > 1:
+    if world > 1 and args.full:
         try:
             result["config"]["ipk_comm"] = ctx.comm_info()      # what the library's own transport saw (ipk_comm_info): rank count and transport
             if result["config"]["ipk_comm"]["ranks"] != world:
@@ -895,7 +945,7 @@ def main():
     if world > 1:
         result["scale_is_the_claim"] = "scale" in result          # value_basis points at `scale`: say whether this run carries one
         if "scale" not in result:
-            result["value_basis"] += " -- THIS run carries no `scale` object (it is emitted by the default run, --config c4 or --batch > N)"
+            result["value_basis"] += " -- THIS run carries no `scale` object (it is emitted by --full runs: the default workload, --config c4 or --batch > N)"
     result["failed_legs"] = ctx.failed
     assert result["n_gpus"] == args.gpus, (result["n_gpus"], args.gpus)
     if rank == 0:
@@ -1112,6 +1162,8 @@ def main_single_process(args):
         wl.step()
     wl.sync()
     ms = wl.time(args.steps, args.warmup, args.prewarm_ms)
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, [("frame%d" % i, d, H, 3) for i, d in enumerate(wl.dsts)])
     alg = 16.0 * W * H
     result = {
         "metric": "megapixels/sec full raw->sRGB pipe, 100 MP f32 frame", "value": round(N * W * H / 1e6 / (ms * 1e-3), 1), "unit": "MP/s",
@@ -1489,8 +1541,11 @@ def main_xtrans(args, ctx, ipa, util, W, H, cfa, maxw):
 
     def step():
         pipe.run(out=out.data)
-    elapsed, mean_ms, median_ms = timed(ctx, step, args.steps, args.warmup, args.prewarm_ms)
-    if maxw:
+    elapsed, mean_ms, median_ms = timed(ctx, step, args.steps, args.warmup, args.prewarm_ms, median=args.full)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(torch, args.dump_outputs, [("frame%d" % ctx.rank, out.data, nH, 3)])
+    kernel_ms = None                           # c5's roofline is its scaled-demosaic kernel's, timed in a run of its own (--full)
+    if maxw and args.full:
         dst4 = torch.empty(nW * nH * 4, dtype=torch.float32, device="cuda")
         L = ipa.lib()
         stream = torch.cuda.current_stream().cuda_stream
@@ -1501,9 +1556,8 @@ def main_xtrans(args, ctx, ipa, util, W, H, cfa, maxw):
             assert rc == 0, rc
         _, kernel_ms, kmed = timed(ctx, kstep, args.steps, args.warmup, 0.0)
         kname, alg_bytes = "k_raw_scaled_demosaic_w8m", 4.0 * W * H + 16.0 * nW * nH
-    else:
+    elif not maxw:
         kernel_ms, kmed, kname, alg_bytes = mean_ms, median_ms, "k_fused_bayer (generic-CFA mode)", 16.0 * W * H
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
     result = {
         "metric": "megapixels/sec full raw->sRGB pipe (input mosaic pixels)",
         "value": round(args.steps * ctx.world * H * W / 1e6 / elapsed, 1), "unit": "MP/s",
@@ -1514,9 +1568,13 @@ def main_xtrans(args, ctx, ipa, util, W, H, cfa, maxw):
                                % (W, H, H * W / 1e6, nW, nH, "gofloat+scaled_demosaic, then tolab+basecurve+fromlab+gamma in one pass" if maxw else "fused, generic-CFA mode"),
                    "baseline_config": "BASELINE.json configs[4]", "frame": [W, H], "out_frame": [nW, nH], "output_MP_per_s": round(args.steps * ctx.world * nW * nH / 1e6 / elapsed, 1),
                    "used_fused": bool(pipe.last_used_fused), "host_glibc": glibc_version()},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": None, "kernel": kname, "kernel_ms": round(kernel_ms, 4), "kernel_ms_median": round(kmed, 4), "algorithmic_bytes_per_launch": alg_bytes},
     }
+    if kernel_ms is not None:
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+        result["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                              "traffic": None, "kernel": kname, "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": alg_bytes}
+        if kmed is not None:
+            result["roofline"]["kernel_ms_median"] = round(kmed, 4)
     if ctx.rank == 0:
         print(json.dumps(result), flush=True)
     if ctx.dist is not None:

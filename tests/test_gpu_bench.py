@@ -19,7 +19,7 @@ def _last_json(out):
 
 
 def test_bench_contract_single_gpu():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--width", "6000", "--height", "4000", "--cpu-seconds", "1"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--width", "6000", "--height", "4000", "--cpu-seconds", "1"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -30,6 +30,39 @@ def test_bench_contract_single_gpu():
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(d["roofline"])
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(d["cpu_baseline"])
     assert "bit-identical" in d["parity_check"] and d["value"] > 1000 and 0 < d["roofline"]["frac"] < 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps steps and prints the headline line without the secondary legs; --dump-outputs writes what
+    the last timed step computed as float32 .npy files, the same in two runs (seeded inputs) and bit-identical to the CPU oracle on that input"""
+    import numpy as np
+    import torch
+    import bench
+    import oracle
+    import util
+    H, W = 1024, 2048
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--width", str(W), "--height", str(H), "--dump-outputs", str(out)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["value"] > 0
+        for key in ("parity_check", "cpu_baseline", "other_data", "batch_64x24MP", "host_boundary", "value_from_median_step"):
+            assert key not in d, key
+        assert "cold_ms" not in d["config"] and "launch_stats" not in d["roofline"] and "kernel_ms_median" not in d["roofline"]
+        assert sorted(p.name for p in out.iterdir()) == ["frame0.npy"]
+        a = np.load(out / "frame0.npy")
+        assert a.dtype == np.float32 and a.shape == (H, W, 3)        # 24 MB: under the budget, written whole
+        dumps.append(a)
+    assert np.array_equal(dumps[0].view(np.int32), dumps[1].view(np.int32))
+    src = bench.synth_frame(torch, H, W, "noise", util.SEED + 2)[:66].to(torch.float32).cpu().numpy()      # frame 0's input, as bench.py makes it
+    desc = oracle.make_pipeline(src, cfa="RGGB", source_kind=1, blacklevels=[util.BLACK] * 4, whitelevels=[util.WHITE] * 4, wb_coeffs=util.WB,
+                                cam_to_xyz_normalized=util.cam_matrix())
+    util.assert_bits_equal(dumps[0][:64], oracle.pipeline_run(desc)[:64], "bench --dump-outputs vs oracle")
 
 
 def test_bench_two_ranks_control_flow():
@@ -47,7 +80,7 @@ def test_bench_gpus_n_invoked_plainly_starts_n_ranks_or_refuses():
     one rank; with the development hook that lets ranks share the GPU it starts the two ranks itself (torch.distributed.run) and the line says so --
     n_gpus 2, and the rank count the library's own communicator saw (ipk_comm_info)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "IPK_BENCH_SHARE_GPU")}
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "2048", "--height", "1024", "--no-cpu-baseline", "--prewarm-ms", "0"]
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "2048", "--height", "1024", "--no-cpu-baseline", "--prewarm-ms", "0"]
     import torch
     if torch.cuda.device_count() < 2:
         r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
@@ -69,7 +102,7 @@ def test_bench_default_control_flow_with_extras(nproc):
     leg with its gather -- on small frames (IPK_BENCH_DEV_SMALL), alone and with two ranks sharing the GPU: every extra object is present
     and the ranks stay in step (a rank that skipped a barrier would hang this test)"""
     env = dict(os.environ, IPK_BENCH_DEV_SMALL="1", IPK_BENCH_SHARE_GPU="1")
-    cmd = [sys.executable, "bench.py", "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--prewarm-ms", "10"]
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--prewarm-ms", "10"]
     if nproc > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1", "--master-port", "29535"] + cmd[1:]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
@@ -112,7 +145,7 @@ def test_bench_single_process_over_two_contexts():
     """python bench.py --gpus 2 --single-process: ONE process, one ipk_ctx per device (two on this box's one GPU), frame i -> member i mod 2 through
     ipk_pipeline_run_batch_multi; the line keeps the contract and carries the `scale` object of that mode, device-resident and host-to-host"""
     env = dict(os.environ, IPK_BENCH_DEV_SMALL="1")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--single-process", "--devices", "0,0", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--single-process", "--devices", "0,0", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5",
                         "--prewarm-ms", "10"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -131,7 +164,7 @@ def test_bench_single_process_over_two_contexts():
 def test_bench_reports_the_box_state_and_the_host_boundary():
     """config.shader_clock_GHz / socket_power_W (the box's state under the timed workload: a slow box and a slow kernel can be told apart) and the
     host_boundary object (host Vec in, host Vec out: what a drop-in behind Pipeline::run crosses) in the line"""
-    r = subprocess.run([sys.executable, "bench.py", "--config", "c2", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--host-boundary"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--config", "c2", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--host-boundary"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -151,13 +184,13 @@ def test_bench_reports_the_box_state_and_the_host_boundary():
 def test_bench_batch_mode_and_configs():
     """bench.py --batch (BASELINE.json configs[3] shape, small here; the full 64 x 24 MP batch is tests/test_gpu_fused.py's) and the
     per-config modes: one JSON line each, strong scaling for a fixed batch, a roofline object per config"""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "6", "--width", "1200", "--height", "800", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "6", "--width", "1200", "--height", "800", "--no-cpu-baseline",
                         "--prewarm-ms", "0"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert d["scaling"] == "strong" and d["config"]["frames_per_step"] == 6 and d["value"] > 0 and "with_gather" in d and "bit-identical" in d["parity_check"]
     for cfg, kern in (("c5", "k_raw_scaled_demosaic"), ("c5b", "k_fused_bayer"), ("c2", "k_fused_bayer")):
-        r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--config", cfg, "--no-cpu-baseline", "--no-check", "--prewarm-ms", "0"],
+        r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--config", cfg, "--no-cpu-baseline", "--no-check", "--prewarm-ms", "0"],
                            cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         d = _last_json(r.stdout)
@@ -167,7 +200,7 @@ def test_bench_batch_mode_and_configs():
 def test_bench_batch_two_ranks():
     env = dict(os.environ, IPK_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29534",
-                        "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "6", "--width", "1024", "--height", "512", "--no-cpu-baseline", "--prewarm-ms", "0"],
+                        "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "6", "--width", "1024", "--height", "512", "--no-cpu-baseline", "--prewarm-ms", "0"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)

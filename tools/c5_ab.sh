@@ -6,7 +6,7 @@ for rep in 1 2; do
 for v in main ${VARIANTS}; do
   if [ $v = main ]; then so=""; else so="$PWD/imagepipe_amd/csrc/build/ablate/lib$v.so"; fi
   OUT=/tmp/c5ab_$v; rm -rf $OUT
-  IPK_SO_OVERRIDE=$so rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o s -- python bench.py --config c5 --no-cpu-baseline --no-check --steps 400 --warmup 20 > $OUT.log 2>&1
+  IPK_SO_OVERRIDE=$so rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o s -- python bench.py --full --config c5 --no-cpu-baseline --no-check --steps 400 --warmup 20 > $OUT.log 2>&1
   f=$(find $OUT -name "*kernel_stats.csv" | head -1)
   python3 - <<PY
 import csv

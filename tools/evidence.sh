@@ -27,7 +27,7 @@ pmc ubench "SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRB
 # 4. configs[3] (the batch kernel), configs[1] (24 MP), configs[4] (scaled X-Trans): kernel-trace stats at the loaded clock + traffic
 for c in c4 c2 c5; do
   extra=""; [ $c = c4 ] && extra="--steps 5 --warmup 1"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$c -o s -- python bench.py --config $c --no-cpu-baseline --no-check --no-box-state $extra > $OUT/bench_$c.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$c -o s -- python bench.py --full --config $c --no-cpu-baseline --no-check --no-box-state $extra > $OUT/bench_$c.log 2>&1
   pmc fetch_$c FETCH_SIZE python bench.py --config $c --no-cpu-baseline --no-check --steps 3 --warmup 1 --prewarm-ms 0
   pmc write_$c WRITE_SIZE python bench.py --config $c --no-cpu-baseline --no-check --steps 3 --warmup 1 --prewarm-ms 0
 done
@@ -41,11 +41,11 @@ for src in f32 u16; do
   vrun --src $src --out f32 --curve none --exposure 0.5 --linear
 done
 # 4c. the stream probe (the fused kernel's memory skeleton) under the kernel trace, and the staged kernels of the 100 MP pipeline
-IPK_BENCH_NO_LIVE_PMC=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_probe -o s -- python bench.py --no-cpu-baseline --no-check --steps 20 > $OUT/bench_probe.log 2>&1
+IPK_BENCH_NO_LIVE_PMC=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_probe -o s -- python bench.py --full --no-cpu-baseline --no-check --steps 20 > $OUT/bench_probe.log 2>&1
 ONLY=C3 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_staged -o s -- python tools/bench_configs.py > $OUT/bench_staged.log 2>&1
 # 4d. the single-process multi-device mode on the hardware there is: two contexts on the one GPU
-python bench.py --gpus 2 --single-process --devices 0,0 --no-cpu-baseline > $OUT/bench_sp.json 2> $OUT/bench_sp.err
-# 5. the plain default run, exactly as the driver issues it
-python bench.py > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+python bench.py --full --gpus 2 --single-process --devices 0,0 --no-cpu-baseline > $OUT/bench_sp.json 2> $OUT/bench_sp.err
+# 5. the default workload with every leg (--full): the line the generated doc blocks quote
+python bench.py --full > $OUT/bench_plain.json 2> $OUT/bench_plain.err
 tail -n 1 $OUT/bench_plain.json | cut -c1-400
 ls $OUT | head -60

@@ -46,7 +46,7 @@ def glance():
     b = C.get("bench_line")
     if b:
         r = b["roofline"]
-        rows.append(("bench line of that session (`python bench.py`)", "value %.0f MP/s, ms_per_step %.4f, kernel_ms %.4f (median %.4f), frac %.4f, cold %.4f ms" % (
+        rows.append(("bench line of that session (`python bench.py --full`)", "value %.0f MP/s, ms_per_step %.4f, kernel_ms %.4f (median %.4f), frac %.4f, cold %.4f ms" % (
             b["value"], b["ms_per_step"], r["kernel_ms"], r["kernel_ms_median"], r["frac"], b["config"].get("cold_ms", float("nan")))))
         if "ceiling_ms" in r:
             rows.append(("measured ceiling: the kernel's memory skeleton (`ipk_stream_probe`)", "ceiling_ms %.4f = %.3f of peak; **frac_of_ceiling %.3f**; 1:1 copy ceiling %.0f GB/s (frac_of_copy_ceiling %.3f)" % (
@@ -90,7 +90,7 @@ def glance():
         h2 = sp1.get("host_in_host_out_u8", {})
         if "ms_per_frame" in h2:
             t += "; host-to-host 8-bit %.2f ms per frame; same bytes as one context: %s" % (h2["ms_per_frame"], h2.get("same_bytes_as_one_context"))
-        rows.append(("single-process multi-device mode (`bench.py --gpus 2 --single-process --devices 0,0`; no second GPU exists here)", t))
+        rows.append(("single-process multi-device mode (`bench.py --full --gpus 2 --single-process --devices 0,0`; no second GPU exists here)", t))
     if "stream_probe" in C:
         sp = C["stream_probe"]
         rows.append(("stream probe under rocprofv3", "%d calls, average %.1f µs = %.3f of peak" % (sp["calls"], sp["average_us"], sp["frac_of_8TBps"])))

@@ -87,7 +87,7 @@ if f:
         if "k_fused_bayer<float, true, 4," in r.get("Name", ""):
             out["stream_probe"] = {"kernel": r["Name"][:100], "calls": int(r["Calls"]), "average_us": float(r["AverageNs"]) / 1e3, "min_us": float(r["MinNs"]) / 1e3,
                                    "algorithmic_bytes_per_launch": 16e8, "frac_of_8TBps": round(16e8 / (float(r["AverageNs"]) * 1e-9) / 8e12, 4),
-                                   "command": "python bench.py --no-cpu-baseline --no-check --steps 20 (its ceiling leg: ipk_stream_probe on the headline frame)"}
+                                   "command": "python bench.py --full --no-cpu-baseline --no-check --steps 20 (its ceiling leg: ipk_stream_probe on the headline frame)"}
     bl = bench_line(os.path.join(src, "bench_probe.log"))
     if bl:
         out["stream_probe_bench_roofline"] = bl.get("roofline")
@@ -149,7 +149,7 @@ if bl:
     out["bench_line"] = bl
 bl = bench_line(os.path.join(src, "bench_sp.json"))
 if bl:
-    out["single_process_two_contexts_one_gpu"] = {"command": "python bench.py --gpus 2 --single-process --devices 0,0 --no-cpu-baseline", "value": bl.get("value"),
+    out["single_process_two_contexts_one_gpu"] = {"command": "python bench.py --full --gpus 2 --single-process --devices 0,0 --no-cpu-baseline", "value": bl.get("value"),
                                                   "ms_per_step": bl.get("ms_per_step"), "scale": bl.get("scale")}
 json.dump(out, open(os.path.join(dst, tag + "_counters.json"), "w"), indent=1, sort_keys=True)
 

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in main ${VARIANTS}; do
   if [ $v = main ]; then so=""; else so="$PWD/imagepipe_amd/csrc/build/ablate/lib$v.so"; fi
   for src in u16 f32; do
-    IPK_SO_OVERRIDE=$so python bench.py --no-cpu-baseline --no-extras --steps 3 --prewarm-ms 0 --src $src --out ${OUTK:-u8} > /tmp/chk.out 2> /tmp/chk.err && echo "check $v $src->${OUTK:-u8} ok" || { echo "check $v $src FAILED"; tail -3 /tmp/chk.err; }
+    IPK_SO_OVERRIDE=$so python bench.py --full --no-cpu-baseline --no-extras --steps 3 --prewarm-ms 0 --src $src --out ${OUTK:-u8} > /tmp/chk.out 2> /tmp/chk.err && echo "check $v $src->${OUTK:-u8} ok" || { echo "check $v $src FAILED"; tail -3 /tmp/chk.err; }
   done
 done
 for rep in 1 2; do

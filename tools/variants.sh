@@ -3,7 +3,7 @@
 # usage (GPU box): tools/variants.sh [outfile] [extra bench args]   -- one JSON line per variant
 OUT=${1:-gpurun_out/variants.jsonl}; shift
 : > $OUT
-run() { python bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 3 "$@" 2>>${OUT%.jsonl}.err | tail -n 1 >> $OUT; }
+run() { python bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 3 "$@" 2>>${OUT%.jsonl}.err | tail -n 1 >> $OUT; }
 for src in f32 u16; do
   for out in f32 u8 u16; do
     for curve in default none user5; do
