@@ -494,3 +494,110 @@ def test_sixteen_letter_patterns_known_answers(orc):
         orc.cfa_shift(L16, 0, 0)
     with pytest.raises(Exception):
         orc.cfa_shift("5x2:RGBGRGBGRG", 0, 0)                          # 5 does not divide 48
+
+
+# ---- special values through transform_buffer, and whole mono / three-sample pipelines -------------------------------------------
+def _specials_buffer(seed, h, w, comps):
+    """uniform samples with util.SPECIALS scattered over them and lone -inf / -3e38 samples inside the frame (gofloat lets both
+    through: it clips only from above)"""
+    rng = np.random.default_rng(seed)
+    buf = util.uniform_f32(util.SEED + seed, h * w * comps, -0.1, 1.1)
+    pos = rng.choice(buf.size, util.SPECIALS.size + 6, replace=False)
+    buf[pos[:util.SPECIALS.size]] = util.SPECIALS
+    buf[pos[util.SPECIALS.size:]] = np.array([-np.inf, -np.inf, -np.inf, -3e38, -3e38, -3e38], np.float32)
+    return buf
+
+
+@pytest.mark.parametrize("comps", [1, 3, 4])
+def test_transform_buffer_with_specials_against_a_second_restatement(orc, comps):
+    """every tap of a window is accumulated, including taps whose factor is 0: 0 * inf and 0 * -inf make the sum NaN
+    (scaling.rs:94-118).  Axis-aligned windows (scale_down_buffer's corners, and a crop-only window with unit skips whose right and
+    lower neighbours are zero-weight taps) and rotated ones (negative skips, windows clamped at the frame edge)."""
+    h, w = 16, 19
+    src = _specials_buffer(4000 + comps, h, w, comps)
+    windows = [((0, 0), (w - 1, 0), (0, h - 1), 7, 5), ((0, 0), (w - 1, 0), (0, h - 1), 12, 11), ((2, 3), (15, 3), (2, 13), 14, 11),
+               ((2, 1), (17, 4), (0, 13), 9, 7), ((17, 2), (3, 1), (16, 14), 8, 6)]
+    saw_nan_from_zero_tap = False
+    for tl, tr, bl, nw, nh in windows:
+        with np.errstate(all="ignore"):
+            want = _transform_buffer(src, w, h, tl, tr, bl, nw, nh, comps)
+        got = orc.transform_buffer(src.reshape(h, w, comps), w, h, tl, tr, bl, nw, nh, comps)
+        util.assert_bits_equal(np.asarray(got).ravel(), want, "transform_buffer %d components %r" % (comps, (tl, tr, bl, nw, nh)))
+        if tl == (2, 3):
+            # unit skips: output (r, c) is input (r + 3, c + 2) exactly where its own sample is finite and its zero-weight neighbours are not infinite
+            g = np.asarray(got).reshape(nh, nw, comps)
+            inner = src.reshape(h, w, comps)[3:3 + nh + 1, 2:2 + nw + 1]
+            own = inner[:nh, :nw]
+            nbr_inf = np.isinf(inner[:nh, 1:nw + 1]) | np.isinf(inner[1:nh + 1, :nw]) | np.isinf(inner[1:nh + 1, 1:nw + 1])
+            saw_nan_from_zero_tap |= bool((np.isnan(g) & np.isfinite(own) & nbr_inf).any())
+    assert saw_nan_from_zero_tap, "no infinite sample fell on a zero-weight tap: the frame does not test what it is meant to"
+
+
+def _gofloat_restated(data, x, y, w, h, black, white):
+    """ops/gofloat.rs:95-120: ((v - black) / (white - black)).min(1.0) per sample; mono copies the value to R, G, B; E is 0"""
+    out = np.zeros((h, w, 4), np.float32)
+    for row in range(h):
+        for col in range(w):
+            v = data[row + y, col + x]
+            if np.ndim(v) == 0:
+                out[row, col, :3] = _rmin(F(F(F(v) - F(black[0])) / F(F(white[0]) - F(black[0]))), F(1.0))
+            else:
+                for c in range(3):
+                    out[row, col, c] = _rmin(F(F(F(v[c]) - F(black[c])) / F(F(white[c]) - F(black[c]))), F(1.0))
+    return out
+
+
+def _pipeline_restated(data, crops, black, white, wb, cam, monochrome, points, demosaic_size=None):
+    """Pipeline::run for a mono or three-sample raw with default rotatecrop / orientation: gofloat, OpDemosaic's scale_down_opbuf when the
+    negotiation scales, to_lab (the monochrome flag selects SRGB_D65_43 and unit multipliers, colorspaces.rs:90-101), basecurve, from_lab, gamma"""
+    oh, ow = data.shape[:2]
+    top, right, bottom, left = crops
+    w, h = ow - left - right, oh - top - bottom
+    buf = _gofloat_restated(data, left, top, w, h, black, white)
+    if demosaic_size is not None and demosaic_size != (w, h):
+        nw, nh = demosaic_size
+        buf = _transform_buffer(buf.ravel(), w, h, (0, 0), (w - 1, 0), (0, h - 1), nw, nh, 4).reshape(nh, nw, 4)
+        w, h = nw, nh
+    if monochrome:
+        mul, cm = [F(1.0)] * 4, [row + [F(0.0)] for row in _SRGB]
+    else:
+        mul, cm = _normalize_wbs([F(v) for v in wb]), [[F(v) for v in row] for row in cam]
+    sp = _Spline([(F(a), F(b)) for a, b in points])
+    m = _inverse(_SRGB)
+    g = _tab("gamma")
+    out = np.zeros((h, w, 3), np.float32)
+    for row in range(h):
+        for col in range(w):
+            l, a, b = _camera_to_lab(mul, cm, buf[row, col])
+            rgb = _lab_to_rgb(m, sp.interpolate(l), a, b)
+            out[row, col] = [g.lookup(_rmin(_rmax(v, F(0.0)), F(1.0))) for v in rgb]
+    return out
+
+
+@pytest.mark.parametrize("case", ["mono_u16", "mono_f32_specials", "mono_u16_scaled", "rgb3_u16", "rgb3_f32_specials"])
+def test_mono_and_three_sample_pipelines_against_a_second_restatement(orc, case):
+    """whole pipelines of the sources the CFA tests never use: cpp == 1 without a CFA (monochrome) and cpp == 3, with sensor crops; the
+    white balance and camera matrix are not neutral, so a mono run that used them (or a three-sample run that did not) differs"""
+    h, w = 14, 17
+    crops = (1, 2, 2, 3)
+    wb = (1.8, 0.9, 1.4, float("nan"))
+    cam = util.cam_matrix().copy()
+    cam[:, 3] = [0.05, -0.03, 0.08]
+    mono = case.startswith("mono")
+    if mono:
+        black, white = (96.0, 0.0, 0.0, 0.0), (4095.0, 0.0, 0.0, 0.0)
+        data = util.noise_u16(util.SEED + 4100, h, w, 4600)
+    else:
+        black, white = (64.0, 70.0, 80.0, 0.0), (4000.0, 3900.0, 4095.0, 0.0)
+        data = util.noise_u16(util.SEED + 4101, h, w * 3, 4600).reshape(h, w, 3)
+    if case.endswith("specials"):
+        data = data.astype(np.float32) + np.float32(0.375)
+        flat = data.reshape(-1)
+        flat[[5, 40, 77, 100, 150]] = [-np.inf, -3e38, np.inf, np.nan, -1e-40]
+    maxwidth = 8 if case.endswith("scaled") else 0
+    desc = orc.make_pipeline(data, cfa="", cpp=1 if mono else 3, crops=crops, blacklevels=black, whitelevels=white, wb_coeffs=wb,
+                             cam_to_xyz_normalized=cam, maxwidth=maxwidth)
+    (dw, dh), _ = orc.pipeline_sizes(desc)
+    with np.errstate(all="ignore"):
+        want = _pipeline_restated(data, crops, black, white, wb, cam, mono, [(0.5, 0.6)], (dw, dh))
+    util.assert_bits_equal(orc.pipeline_run(desc), want, "pipeline %s" % case)
