@@ -1356,15 +1356,20 @@ int ipk_selftest_cbrtf(const float *in, float *out, size_t n, int variant, void 
 // ------------------------------------------------------------------------------------------
 // Pipeline::run (src/pipeline.rs:311-375) for one source, cache == None
 // ------------------------------------------------------------------------------------------
+// the descriptor's OpRotateCrop in its reset() state (pipeline.rs:314-316)
+static ipk::RotateCrop rotatecrop_of(const ipk_pipeline_desc *d) {
+  ipk::RotateCrop rc;
+  rc.crop_top = d->rotatecrop[0]; rc.crop_right = d->rotatecrop[1]; rc.crop_bottom = d->rotatecrop[2];
+  rc.crop_left = d->rotatecrop[3]; rc.rotation = d->rotatecrop[4];
+  return rc;
+}
 // rc_state (may be null): the OpRotateCrop as the two folds of the negotiation leave it (input_ratio, output size) -- the state
 // its Serialize impl exposes to the hash chain (pipeline.rs:318-335, rotatecrop.rs:10-18)
 static int pipeline_sizes_impl(const ipk_pipeline_desc *d, size_t *demosaic_w, size_t *demosaic_h, size_t *final_w, size_t *final_h,
                                ipk::RotateCrop *rc_state) {
   if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
   if (d->rotation < 0 || d->rotation > 3) return fail(IPK_ERR_INVALID, "bad rotation");
-  ipk::RotateCrop rc;                                                     // reset() state (pipeline.rs:314-316)
-  rc.crop_top = d->rotatecrop[0]; rc.crop_right = d->rotatecrop[1]; rc.crop_bottom = d->rotatecrop[2];
-  rc.crop_left = d->rotatecrop[3]; rc.rotation = d->rotatecrop[4];
+  ipk::RotateCrop rc = rotatecrop_of(d);
   ipk::Rect r;
   if (!ipk::size_image(d->crop_top, d->crop_right, d->crop_bottom, d->crop_left, d->width, d->height, r))
     return fail(IPK_ERR_INVALID, "source smaller than 10x10");
@@ -1384,11 +1389,8 @@ static int pipeline_sizes_impl(const ipk_pipeline_desc *d, size_t *demosaic_w, s
   size_t pw = r.width, ph = r.height;
   if (ipk::calculate_scaling_total(pw, ph, w, h).scale > 1.0f) { pw = w; ph = h; }
   {
-    ipk::RotateCrop run_rc;
-    run_rc.crop_top = d->rotatecrop[0]; run_rc.crop_right = d->rotatecrop[1]; run_rc.crop_bottom = d->rotatecrop[2];
-    run_rc.crop_left = d->rotatecrop[3]; run_rc.rotation = d->rotatecrop[4];
     int64_t pts[6]; size_t nw, nh;
-    if (run_rc.corners(pw, ph, pts, nw, nh)) { pw = nw; ph = nh; }
+    if (rotatecrop_of(d).corners(pw, ph, pts, nw, nh)) { pw = nw; ph = nh; }
   }
   {
     bool transpose, fx, fy;
@@ -1501,173 +1503,171 @@ int ipk_timing_end(ipk_stage_time *out, int max_stages, int *n_stages) {
   return rc;
 }
 
-int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int out_type, int *used_fused, void *stream) {
-  REQUIRE_INIT();
-  if (!d || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
+namespace {
+// Everything a driver derives from a descriptor for one call, negotiated once
+struct Negotiated {
+  ipk::Rect r; size_t dw, dh, fw, fh; ipk::RotateCrop rc; int linear; int orientation; bool transform_noop;
+  bool raw, cfa_branch;                  // a raw source, and one OpGoFloat treats as a CFA mosaic (gofloat.rs:95,109,121)
+  float scale;                           // OpDemosaic's scale: the cropped source against the demosaic size
+};
+int negotiate(const ipk_pipeline_desc *d, int out_type, Negotiated &n) {
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {
-    if (used_fused) *used_fused = 0;
-    if (d->width < 1 || d->height < 1) return fail(IPK_ERR_INVALID, "empty source");
-    StageTimer tmf(S(stream)); tmf.rest = "fastpath";
-    return run_fastpath(d, src, dst, out_type, stream);
-  }
-  size_t dw, dh, fw, fh;
-  int rc = ipk_pipeline_sizes(d, &dw, &dh, &fw, &fh); if (rc) return rc;
-  StageTimer tm(S(stream));
+  // one negotiation: the sizes and the rotatecrop state both come from pipeline_sizes_impl's folds (the reverse fold is seeded
+  // with scaling_size of the forward result, pipeline.rs:328-335 -- not with the size run() produces)
+  int rc = pipeline_sizes_impl(d, &n.dw, &n.dh, &n.fw, &n.fh, &n.rc); if (rc) return rc;
+  ipk::size_image(d->crop_top, d->crop_right, d->crop_bottom, d->crop_left, d->width, d->height, n.r);
+  n.scale = ipk::calculate_scaling_total(n.r.width, n.r.height, n.dw, n.dh).scale;
+  n.raw = d->src_type == IPK_SRC_U16 || d->src_type == IPK_SRC_F32;
+  n.cfa_branch = n.raw && !(d->cpp == 1 && !d->is_cfa) && d->cpp != 3;
   // output_8bit forces linear=false (pipeline.rs:405), output_16bit linear=true (:452)
-  const int linear = out_type == IPK_OUT_U8 ? 0 : (out_type == IPK_OUT_U16 ? 1 : d->linear);
-  ipk::Rect r;
-  ipk::size_image(d->crop_top, d->crop_right, d->crop_bottom, d->crop_left, d->width, d->height, r);
-  const bool raw = d->src_type == IPK_SRC_U16 || d->src_type == IPK_SRC_F32;
-  const bool cfa_branch = raw && !(d->cpp == 1 && !d->is_cfa) && d->cpp != 3;          // gofloat.rs:95,109,121
-  const int orientation = ipk::transform_orientation(d->rotation, d->fliph != 0, d->flipv != 0);
-  const bool transform_noop = orientation == IPK_OR_NORMAL || orientation == IPK_OR_UNKNOWN;
-  ipk::RotateCrop rcop;
-  rcop.crop_top = d->rotatecrop[0]; rcop.crop_right = d->rotatecrop[1]; rcop.crop_bottom = d->rotatecrop[2];
-  rcop.crop_left = d->rotatecrop[3]; rcop.rotation = d->rotatecrop[4];
+  n.linear = out_type == IPK_OUT_U8 ? 0 : (out_type == IPK_OUT_U16 ? 1 : (d->linear != 0));
+  n.orientation = ipk::transform_orientation(d->rotation, d->fliph != 0, d->flipv != 0);
+  n.transform_noop = n.orientation == IPK_OR_NORMAL || n.orientation == IPK_OR_UNKNOWN;
+  return IPK_OK;
+}
+// the size run() produced against the negotiated one; the cached driver also states its OpBuffer's colours (0: not stated), which must be 3
+int check_produced(const Negotiated &n, size_t w, size_t h, size_t colors = 0) {
+  if (w == n.fw && h == n.fh && (colors == 0 || colors == 3)) return IPK_OK;
+  return colors ? fail(IPK_ERR_INVALID, "internal: produced %zux%zux%zu, negotiated %zux%zu", w, h, colors, n.fw, n.fh)
+                : fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", w, h, n.fw, n.fh);
+}
+size_t out_elem_size(int t) { return t == IPK_OUT_F32 ? 4 : t == IPK_OUT_U8 ? 1 : 2; }
 
-  // ---- fused path: legal when every op between gofloat and gamma is point-wise or demosaic::full ----
-  if (used_fused) *used_fused = 0;
-  if (d->allow_fused && cfa_branch && d->cpp == 1 && rcop.noop()) {
-    const float scale = ipk::calculate_scaling_total(r.width, r.height, dw, dh).scale;
-    ipk::Cfa cfa; int xo, yo;
-    if (scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) && (cfa.bayer_phase(xo, yo) || cfa.three_colour())) {
-      ipk_fused_params fp;
-      std::memset(&fp, 0, sizeof(fp));
-      fp.struct_size = (uint32_t)sizeof(fp);
-      fp.src_type = d->src_type; fp.owidth = d->width; fp.x = r.x; fp.y = r.y; fp.width = r.width; fp.height = r.height;
-      fp.black0 = d->blacklevels[0]; fp.white0 = d->whitelevels[0];
-      std::memcpy(fp.cfa, d->cfa, sizeof(fp.cfa));
-      std::memcpy(fp.wb_coeffs, d->wb_coeffs, sizeof(fp.wb_coeffs));
-      std::memcpy(fp.cam_to_xyz_normalized, d->cam_to_xyz_normalized, sizeof(fp.cam_to_xyz_normalized));
-      fp.exposure = d->exposure; fp.npoints = d->npoints; std::memcpy(fp.points, d->points, sizeof(fp.points));
-      fp.linear = linear; fp.out_type = out_type; fp.schedule = d->schedule;
-      tm.rest = "fused gofloat+demosaic+to_lab+basecurve+from_lab+gamma(+transform)";
-      if (transform_noop) {
-        rc = ipk_raw_to_srgb(&fp, src, dst, stream);
-        if (rc == IPK_OK && used_fused) *used_fused = 1;
-        return rc;
-      }
-      // An orientation other than Normal (every portrait shot): OpTransform is the last op and a pure permutation of
-      // pixels, so gofloat..gamma still run as the one fused launch, into a scratch buffer, and rotate_buffer (+ the
-      // quantise loop) follows -- 2 or 3 launches instead of 7.
-      size_t ow = 0, oh = 0;
-      // Rotate90 / Rotate270 of a Bayer frame (the portrait shot): permute the 1-channel mosaic and run the fused kernel in rotated
-      // space -- no pass over the 3-channel result at all
-      rc = ipk_raw_to_srgb_oriented(&fp, src, orientation, dst, &ow, &oh, stream);
-      if (rc == IPK_OK) {
-        if (ow != fw || oh != fh) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", ow, oh, fw, fh);
-        if (used_fused) *used_fused = 1;
-        return IPK_OK;
-      }
-      if (rc != IPK_ERR_UNSUPPORTED) return rc;
-      Scratch sc2(S(stream));
-      void *tmp = nullptr;
-      // otherwise: the fused kernel quantises on the way out; the permutation then runs on the 3- or 6-byte pixels (it commutes with the
-      // per-sample output8bit / output16bit)
-      rc = sc2.get(r.width * r.height * 3 * (out_type == IPK_OUT_F32 ? sizeof(float) : (out_type == IPK_OUT_U8 ? 1 : 2)), &tmp); if (rc) return rc;
-      rc = ipk_raw_to_srgb(&fp, src, tmp, stream); if (rc < 0) return rc;
-      if (out_type == IPK_OUT_F32) rc = ipk_rotate_buffer(static_cast<const float *>(tmp), r.width, r.height, orientation, static_cast<float *>(dst), &ow, &oh, stream);
-      else if (out_type == IPK_OUT_U8) rc = ipk_rotate_image_u8(static_cast<const uint8_t *>(tmp), r.width, r.height, orientation, static_cast<uint8_t *>(dst), &ow, &oh, stream);
-      else rc = ipk_rotate_image_u16(static_cast<const uint16_t *>(tmp), r.width, r.height, orientation, static_cast<uint16_t *>(dst), &ow, &oh, stream);
-      if (rc < 0) return rc;
-      if (ow != fw || oh != fh) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", ow, oh, fw, fh);
-      if (used_fused) *used_fused = 1;
-      return IPK_OK;
-    }
-  }
+// ---- fused raw path: legal when every op between gofloat and gamma is point-wise or demosaic::full.  Does this descriptor run gofloat..gamma
+// as the one fused raw->sRGB launch?  Then fp holds its parameters.  OpTransform does not enter: ipk_pipeline_run folds any orientation in ----
+bool fused_raw_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp) {
+  ipk::Cfa cfa; int xo, yo;
+  if (!(d->allow_fused && n.cfa_branch && d->cpp == 1 && n.rc.noop() && n.scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) &&
+        (cfa.bayer_phase(xo, yo) || cfa.three_colour())))
+    return false;
+  std::memset(&fp, 0, sizeof(fp));
+  fp.struct_size = (uint32_t)sizeof(fp);
+  fp.src_type = d->src_type; fp.owidth = d->width; fp.x = n.r.x; fp.y = n.r.y; fp.width = n.r.width; fp.height = n.r.height;
+  fp.black0 = d->blacklevels[0]; fp.white0 = d->whitelevels[0];
+  std::memcpy(fp.cfa, d->cfa, sizeof(fp.cfa));
+  std::memcpy(fp.wb_coeffs, d->wb_coeffs, sizeof(fp.wb_coeffs));
+  std::memcpy(fp.cam_to_xyz_normalized, d->cam_to_xyz_normalized, sizeof(fp.cam_to_xyz_normalized));
+  fp.exposure = d->exposure; fp.npoints = d->npoints; std::memcpy(fp.points, d->points, sizeof(fp.points));
+  fp.linear = n.linear; fp.out_type = out_type; fp.schedule = d->schedule;
+  return true;
+}
+// ---- raster sources, same idea: run_other + tolab..gamma (+ quantisation) as one launch when OpDemosaic (a 4-channel buffer at
+// scale <= 1: pass-through, demosaic.rs:39-44) and OpRotateCrop are no-ops ----
+bool fused_raster_route(const ipk_pipeline_desc *d, const Negotiated &n) {
+  return d->allow_fused && !n.raw && n.rc.noop() && n.r.x == 0 && n.r.y == 0 && n.r.width == d->width && n.r.height == d->height &&
+         n.r.width * n.r.height >= 256 && n.scale <= 1.0f;
+}
 
-  // ---- raster sources, same idea: run_other + tolab..gamma (+ quantisation) as one launch when OpDemosaic (a 4-channel buffer at
-  // scale <= 1: pass-through, demosaic.rs:39-44) and OpRotateCrop are no-ops ----
-  if (d->allow_fused && !raw && rcop.noop() && r.x == 0 && r.y == 0 && r.width == d->width && r.height == d->height &&
-      r.width * r.height >= 256 && ipk::calculate_scaling_total(r.width, r.height, dw, dh).scale <= 1.0f) {
-    tm.rest = "fused gofloat+to_lab+basecurve+from_lab+gamma(+transform)";
-    if (transform_noop) {
-      rc = ipk_raster_to_srgb(src, d->src_type, r.width, r.height, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
-                              linear, out_type, dst, stream);
-      if (rc == IPK_OK && used_fused) *used_fused = 1;
-      return rc;
-    }
-    // a non-Normal orientation: the same launch into a scratch image of the output type, then the permutation
-    Scratch sc2(S(stream));
-    void *tmp = nullptr;
-    size_t ow = 0, oh = 0;
-    rc = sc2.get(r.width * r.height * 3 * (out_type == IPK_OUT_F32 ? sizeof(float) : (out_type == IPK_OUT_U8 ? 1 : 2)), &tmp); if (rc) return rc;
-    rc = ipk_raster_to_srgb(src, d->src_type, r.width, r.height, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
-                            linear, out_type, tmp, stream);
-    if (rc < 0) return rc;
-    if (out_type == IPK_OUT_F32) rc = ipk_rotate_buffer(static_cast<const float *>(tmp), r.width, r.height, orientation, static_cast<float *>(dst), &ow, &oh, stream);
-    else if (out_type == IPK_OUT_U8) rc = ipk_rotate_image_u8(static_cast<const uint8_t *>(tmp), r.width, r.height, orientation, static_cast<uint8_t *>(dst), &ow, &oh, stream);
-    else rc = ipk_rotate_image_u16(static_cast<const uint16_t *>(tmp), r.width, r.height, orientation, static_cast<uint16_t *>(dst), &ow, &oh, stream);
-    if (rc < 0) return rc;
-    if (ow != fw || oh != fh) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", ow, oh, fw, fh);
-    if (used_fused) *used_fused = 1;
-    return IPK_OK;
-  }
-
-  // ---- staged path: the eight ops in the reference's order (pipeline.rs:155-164) ----
+// output8bit / output16bit (pipeline.rs:408-414 / :455-461): cnt f32 samples into the quantised output type
+int quantise(const void *src, size_t cnt, int out_type, void *dst, void *stream) {
+  return out_type == IPK_OUT_U8 ? ipk_output8bit(static_cast<const float *>(src), cnt, static_cast<uint8_t *>(dst), stream)
+                                : ipk_output16bit(static_cast<const float *>(src), cnt, static_cast<uint16_t *>(dst), stream);
+}
+// OpTransform's permutation of a 3-sample image of the output type.  On the 8- and 16-bit outputs it runs after the quantisation: output8bit /
+// output16bit act per sample, so the permutation commutes with them and then moves 3 or 6 bytes per pixel instead of 12
+int orient(const void *src, size_t w, size_t h, int orientation, int out_type, void *dst, size_t *ow, size_t *oh, void *stream) {
+  if (out_type == IPK_OUT_F32) return ipk_rotate_buffer(static_cast<const float *>(src), w, h, orientation, static_cast<float *>(dst), ow, oh, stream);
+  if (out_type == IPK_OUT_U8) return ipk_rotate_image_u8(static_cast<const uint8_t *>(src), w, h, orientation, static_cast<uint8_t *>(dst), ow, oh, stream);
+  return ipk_rotate_image_u16(static_cast<const uint16_t *>(src), w, h, orientation, static_cast<uint16_t *>(dst), ow, oh, stream);
+}
+// One fused launch of the cropped frame -- the raw->sRGB kernel with fp, the raster chain without -- then OpTransform: the launch writes the
+// image of the output type into dst itself when the orientation is Normal, else into a scratch image that the permutation moves into dst
+int fused_then_orient(const ipk_pipeline_desc *d, const Negotiated &n, const ipk_fused_params *fp, int out_type, const void *src, void *dst, void *stream) {
+  auto launch = [&](void *o) {
+    return fp ? ipk_raw_to_srgb(fp, src, o, stream)
+              : ipk_raster_to_srgb(src, d->src_type, n.r.width, n.r.height, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
+                                   n.linear, out_type, o, stream);
+  };
+  if (n.transform_noop) return launch(dst);
   Scratch sc(S(stream));
-  hipStream_t st = S(stream); (void)st;
-  size_t w = r.width, h = r.height, colors;
-  int monochrome = 0;
+  void *tmp = nullptr;
+  size_t ow = 0, oh = 0;
+  int rc = sc.get(n.r.width * n.r.height * 3 * out_elem_size(out_type), &tmp); if (rc) return rc;
+  rc = launch(tmp); if (rc < 0) return rc;
+  rc = orient(tmp, n.r.width, n.r.height, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
+  return check_produced(n, ow, oh);
+}
+int run_fused_raw(const ipk_pipeline_desc *d, const Negotiated &n, const ipk_fused_params &fp, const void *src, void *dst, StageTimer &tm, void *stream) {
+  tm.rest = "fused gofloat+demosaic+to_lab+basecurve+from_lab+gamma(+transform)";
+  if (!n.transform_noop) {
+    // An orientation other than Normal (every portrait shot): OpTransform is the last op and a pure permutation of pixels, so gofloat..gamma
+    // still run as the one fused launch -- 2 or 3 launches instead of 7.  Rotate90 / Rotate270 of a Bayer frame (the portrait shot): permute
+    // the 1-channel mosaic and run the fused kernel in rotated space -- no pass over the 3-channel result at all.  Otherwise the fused kernel
+    // quantises on the way out into scratch, and the permutation runs on the 3- or 6-byte pixels.
+    size_t ow = 0, oh = 0;
+    const int rc = ipk_raw_to_srgb_oriented(&fp, src, n.orientation, dst, &ow, &oh, stream);
+    if (rc == IPK_OK) return check_produced(n, ow, oh);
+    if (rc != IPK_ERR_UNSUPPORTED) return rc;
+  }
+  return fused_then_orient(d, n, &fp, fp.out_type, src, dst, stream);
+}
+
+// ---- OpGoFloat (gofloat.rs:95-130): what it produces for a descriptor, and the launch that writes it ----
+int gofloat_shape(const ipk_pipeline_desc *d, const Negotiated &n, size_t &colors, int &monochrome) {
+  colors = 4; monochrome = 0;
+  if (!n.raw || d->cpp == 3) return IPK_OK;
+  if (d->cpp == 1 && !d->is_cfa) { monochrome = 1; return IPK_OK; }
+  if (d->cpp != 1) return fail(IPK_ERR_UNSUPPORTED, "cpp=%d sources are not supported", d->cpp);
+  colors = 1;
+  return IPK_OK;
+}
+int launch_gofloat(const ipk_pipeline_desc *d, const Negotiated &n, const void *src, float *dst, void *stream) {
+  const size_t x = n.r.x, y = n.r.y, w = n.r.width, h = n.r.height;
+  const bool u16 = d->src_type == IPK_SRC_U16;
+  const uint16_t *s16 = static_cast<const uint16_t *>(src);
+  const float *s32 = static_cast<const float *>(src);
+  if (!n.raw)
+    return d->src_type == IPK_SRC_RGB8 ? ipk_gofloat_other_u8(static_cast<const uint8_t *>(src), d->width, x, y, w, h, dst, stream)
+                                       : ipk_gofloat_other_u16(s16, d->width, x, y, w, h, dst, stream);
+  if (d->cpp == 1 && !d->is_cfa)
+    return u16 ? ipk_gofloat_mono_u16(s16, d->width, x, y, w, h, d->blacklevels[0], d->whitelevels[0], dst, stream)
+               : ipk_gofloat_mono_f32(s32, d->width, x, y, w, h, d->blacklevels[0], d->whitelevels[0], dst, stream);
+  if (d->cpp == 3)
+    return u16 ? ipk_gofloat_rgb_u16(s16, d->width, x, y, w, h, d->blacklevels, d->whitelevels, dst, stream)
+               : ipk_gofloat_rgb_f32(s32, d->width, x, y, w, h, d->blacklevels, d->whitelevels, dst, stream);
+  return u16 ? ipk_gofloat_cfa_u16(s16, d->width, x, y, w, h, d->blacklevels[0], d->whitelevels[0], dst, stream)
+             : ipk_gofloat_cfa_f32(s32, d->width, x, y, w, h, d->blacklevels[0], d->whitelevels[0], dst, stream);
+}
+// OpGoFloat + OpDemosaic in one pass, into a dw x dh 4-channel buffer, when OpDemosaic::run would scale: its scaled_demosaic branch for a
+// mosaic (demosaic.rs:47-50), its scale_down_opbuf branch for a raster source under a size limit (demosaic.rs:44-46)
+bool gofloat_demosaic_one_pass(const ipk_pipeline_desc *d, const Negotiated &n) {
+  if (!d->allow_fused) return false;
+  if (!n.raw) return n.scale > 1.0f;
+  ipk::Cfa cfa;
+  return n.cfa_branch && d->cpp == 1 && ipk::Cfa::parse(d->cfa, cfa) && cfa.valid() && n.scale >= ipk::demosaic_minscale(cfa.width);
+}
+int launch_gofloat_demosaic(const ipk_pipeline_desc *d, const Negotiated &n, const void *src, float *dst, void *stream) {
+  if (!n.raw) return ipk_raster_scale_down(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, n.dw, n.dh, dst, stream);
+  return ipk_raw_scaled_demosaic(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, d->blacklevels[0], d->whitelevels[0], d->cfa,
+                                 n.dw, n.dh, dst, stream);
+}
+
+// ---- staged path: the eight ops in the reference's order (pipeline.rs:155-164) ----
+int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, const void *src, void *dst, StageTimer &tm, void *stream) {
+  Scratch sc(S(stream));
+  size_t w = n.r.width, h = n.r.height, colors;
+  int monochrome, rc;
   void *buf = nullptr;
-  // gofloat (+ demosaic when OpDemosaic::run would take its scaled_demosaic branch: one pass over the raw frame)
-  bool demosaic_done = false;
-  if (d->allow_fused && cfa_branch && d->cpp == 1) {
-    ipk::Cfa cfa;
-    const float scale = ipk::calculate_scaling_total(w, h, dw, dh).scale;
-    if (ipk::Cfa::parse(d->cfa, cfa) && cfa.valid() && scale >= ipk::demosaic_minscale(cfa.width)) {          // demosaic.rs:47-50
-      rc = sc.get(dw * dh * 4 * sizeof(float), &buf); if (rc) return rc;
-      rc = ipk_raw_scaled_demosaic(src, d->src_type, d->width, r.x, r.y, w, h, d->blacklevels[0], d->whitelevels[0], d->cfa, dw, dh,
-                                   static_cast<float *>(buf), stream);
-      if (rc < 0) return rc;
-      w = dw; h = dh; colors = 4; demosaic_done = true;
-    }
-  }
-  if (d->allow_fused && !raw && !demosaic_done && ipk::calculate_scaling_total(w, h, dw, dh).scale > 1.0f) {
-    // raster source under a size limit: run_other + OpDemosaic's scale_down_opbuf branch (demosaic.rs:44-46) in one pass
-    rc = sc.get(dw * dh * 4 * sizeof(float), &buf); if (rc) return rc;
-    rc = ipk_raster_scale_down(src, d->src_type, d->width, r.x, r.y, w, h, dw, dh, static_cast<float *>(buf), stream);
-    if (rc < 0) return rc;
-    w = dw; h = dh; colors = 4; demosaic_done = true;
-  }
+  // gofloat (+ demosaic when OpDemosaic::run would scale: one pass over the source)
+  const bool demosaic_done = gofloat_demosaic_one_pass(d, n);
   if (demosaic_done) {
-  } else if (raw) {
-    if (d->cpp == 1 && !d->is_cfa) {
-      colors = 4; monochrome = 1;
-      rc = sc.get(w * h * 4 * sizeof(float), &buf); if (rc) return rc;
-      rc = d->src_type == IPK_SRC_U16
-        ? ipk_gofloat_mono_u16(static_cast<const uint16_t *>(src), d->width, r.x, r.y, w, h, d->blacklevels[0], d->whitelevels[0], static_cast<float *>(buf), stream)
-        : ipk_gofloat_mono_f32(static_cast<const float *>(src), d->width, r.x, r.y, w, h, d->blacklevels[0], d->whitelevels[0], static_cast<float *>(buf), stream);
-    } else if (d->cpp == 3) {
-      colors = 4;
-      rc = sc.get(w * h * 4 * sizeof(float), &buf); if (rc) return rc;
-      rc = d->src_type == IPK_SRC_U16
-        ? ipk_gofloat_rgb_u16(static_cast<const uint16_t *>(src), d->width, r.x, r.y, w, h, d->blacklevels, d->whitelevels, static_cast<float *>(buf), stream)
-        : ipk_gofloat_rgb_f32(static_cast<const float *>(src), d->width, r.x, r.y, w, h, d->blacklevels, d->whitelevels, static_cast<float *>(buf), stream);
-    } else {
-      if (d->cpp != 1) return fail(IPK_ERR_UNSUPPORTED, "cpp=%d sources are not supported", d->cpp);
-      colors = 1;
-      rc = sc.get(w * h * sizeof(float), &buf); if (rc) return rc;
-      rc = d->src_type == IPK_SRC_U16
-        ? ipk_gofloat_cfa_u16(static_cast<const uint16_t *>(src), d->width, r.x, r.y, w, h, d->blacklevels[0], d->whitelevels[0], static_cast<float *>(buf), stream)
-        : ipk_gofloat_cfa_f32(static_cast<const float *>(src), d->width, r.x, r.y, w, h, d->blacklevels[0], d->whitelevels[0], static_cast<float *>(buf), stream);
-    }
+    colors = 4; monochrome = 0;
+    rc = sc.get(n.dw * n.dh * 4 * sizeof(float), &buf); if (rc) return rc;
+    rc = launch_gofloat_demosaic(d, n, src, static_cast<float *>(buf), stream);
+    w = n.dw; h = n.dh;
   } else {
-    colors = 4;
-    rc = sc.get(w * h * 4 * sizeof(float), &buf); if (rc) return rc;
-    rc = d->src_type == IPK_SRC_RGB8
-      ? ipk_gofloat_other_u8(static_cast<const uint8_t *>(src), d->width, r.x, r.y, w, h, static_cast<float *>(buf), stream)
-      : ipk_gofloat_other_u16(static_cast<const uint16_t *>(src), d->width, r.x, r.y, w, h, static_cast<float *>(buf), stream);
+    rc = gofloat_shape(d, n, colors, monochrome); if (rc) return rc;
+    rc = sc.get(w * h * colors * sizeof(float), &buf); if (rc) return rc;
+    rc = launch_gofloat(d, n, src, static_cast<float *>(buf), stream);
   }
   if (rc < 0) return rc;
   tm.mark(demosaic_done ? "gofloat+demosaic" : "gofloat");
   // demosaic
   if (!demosaic_done) {
     void *o = nullptr; size_t ow, oh;
-    rc = sc.get(std::max(w * h, dw * dh) * 4 * sizeof(float), &o); if (rc) return rc;
-    rc = ipk_demosaic_run(static_cast<const float *>(buf), w, h, colors, d->cfa, dw, dh, static_cast<float *>(o), &ow, &oh, stream);
+    rc = sc.get(std::max(w * h, n.dw * n.dh) * 4 * sizeof(float), &o); if (rc) return rc;
+    rc = ipk_demosaic_run(static_cast<const float *>(buf), w, h, colors, d->cfa, n.dw, n.dh, static_cast<float *>(o), &ow, &oh, stream);
     if (rc < 0) return rc;
     if (rc == IPK_NOOP) sc.release(o); else { sc.release(buf); buf = o; w = ow; h = oh; colors = 4; }
     tm.mark("demosaic");
@@ -1687,13 +1687,13 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
     tm.mark("rotatecrop");
   }
   const size_t n3 = w * h * 3 * sizeof(float);
-  const bool f32_out0 = out_type == IPK_OUT_F32;
+  const bool f32_out = out_type == IPK_OUT_F32;
   bool chained = false;
-  if (d->allow_fused && colors == 4 && !f32_out0 && transform_noop && w * h >= 256) {
+  if (d->allow_fused && colors == 4 && !f32_out && n.transform_noop && w * h >= 256) {
     // ... and with output8bit / output16bit in the same pass when the caller wants 8 or 16 bits and nothing follows: the f32 image never exists
-    if (w != fw || h != fh) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", w, h, fw, fh);
+    rc = check_produced(n, w, h); if (rc) return rc;
     rc = ipk_pointwise_chain_out(static_cast<const float *>(buf), w, h, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
-                                 linear, out_type, dst, stream);
+                                 n.linear, out_type, dst, stream);
     if (rc < 0) return rc;
     tm.rest = nullptr;
     tm.mark("to_lab+basecurve+from_lab+gamma+quantise");
@@ -1702,9 +1702,9 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
   if (d->allow_fused && colors == 4) {
     // tolab + basecurve + fromlab + gamma in one pass (no cache wants the three intermediates)
     void *o = nullptr;
-    if (f32_out0 && transform_noop) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
+    if (f32_out && n.transform_noop) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
     rc = ipk_pointwise_chain(static_cast<const float *>(buf), w, h, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
-                             linear, static_cast<float *>(o), stream);
+                             n.linear, static_cast<float *>(o), stream);
     if (rc < 0) return rc;
     sc.release(buf); buf = o; colors = 3; chained = true;
     tm.mark("to_lab+basecurve+from_lab+gamma");
@@ -1728,12 +1728,11 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
     tm.mark("basecurve");
   }
   // the last f32 stage writes straight into dst when the caller wants f32
-  const bool gamma_runs = !linear;
-  const bool f32_out = out_type == IPK_OUT_F32;
+  const bool gamma_runs = !n.linear;
   // fromlab
   if (!chained) {
     void *o = nullptr;
-    const bool last = f32_out && !gamma_runs && transform_noop;
+    const bool last = f32_out && !gamma_runs && n.transform_noop;
     if (last) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
     rc = ipk_fromlab(static_cast<const float *>(buf), w, h, static_cast<float *>(o), stream);
     if (rc < 0) return rc;
@@ -1743,64 +1742,67 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
   // gamma
   if (gamma_runs && !chained) {
     void *o = nullptr;
-    const bool last = f32_out && transform_noop;
+    const bool last = f32_out && n.transform_noop;
     if (last) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
     rc = ipk_gamma(static_cast<const float *>(buf), w, h, 3, 0, static_cast<float *>(o), stream);
     if (rc < 0) return rc;
     sc.release(buf); buf = o;
     tm.mark("gamma");
   }
-  // transform -- for the 8- and 16-bit outputs after the quantise loop instead of before it: output8bit / output16bit act
-  // per sample, so the permutation commutes with them and then moves 3 or 6 bytes per pixel instead of 12
-  if (!transform_noop && !f32_out) {
+  // transform -- for the 8- and 16-bit outputs after the quantise loop instead of before it (orient)
+  if (!n.transform_noop && !f32_out) {
     tm.rest = "quantise+transform";
     void *q = nullptr; size_t ow, oh;
-    rc = sc.get(w * h * 3 * (out_type == IPK_OUT_U8 ? 1 : 2), &q); if (rc) return rc;
-    rc = out_type == IPK_OUT_U8 ? ipk_output8bit(static_cast<const float *>(buf), w * h * 3, static_cast<uint8_t *>(q), stream)
-                                : ipk_output16bit(static_cast<const float *>(buf), w * h * 3, static_cast<uint16_t *>(q), stream);
-    if (rc < 0) return rc;
-    rc = out_type == IPK_OUT_U8 ? ipk_rotate_image_u8(static_cast<const uint8_t *>(q), w, h, orientation, static_cast<uint8_t *>(dst), &ow, &oh, stream)
-                                : ipk_rotate_image_u16(static_cast<const uint16_t *>(q), w, h, orientation, static_cast<uint16_t *>(dst), &ow, &oh, stream);
-    if (rc < 0) return rc;
-    if (ow != fw || oh != fh) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", ow, oh, fw, fh);
-    return IPK_OK;
+    rc = sc.get(w * h * 3 * out_elem_size(out_type), &q); if (rc) return rc;
+    rc = quantise(buf, w * h * 3, out_type, q, stream); if (rc < 0) return rc;
+    rc = orient(q, w, h, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
+    return check_produced(n, ow, oh);
   }
-  if (!transform_noop) {
+  if (!n.transform_noop) {
     void *o = nullptr; size_t ow, oh;
     if (f32_out) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
-    rc = ipk_rotate_buffer(static_cast<const float *>(buf), w, h, orientation, static_cast<float *>(o), &ow, &oh, stream);
+    rc = ipk_rotate_buffer(static_cast<const float *>(buf), w, h, n.orientation, static_cast<float *>(o), &ow, &oh, stream);
     if (rc < 0) return rc;
     sc.release(buf); buf = o; w = ow; h = oh;
     tm.mark("transform");
   }
-  if (w != fw || h != fh) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", w, h, fw, fh);
-  // quantise (pipeline.rs:408-414 / :455-461)
-  if (out_type != IPK_OUT_F32) tm.rest = "quantise";
-  if (out_type == IPK_OUT_U8) rc = ipk_output8bit(static_cast<const float *>(buf), w * h * 3, static_cast<uint8_t *>(dst), stream);
-  else if (out_type == IPK_OUT_U16) rc = ipk_output16bit(static_cast<const float *>(buf), w * h * 3, static_cast<uint16_t *>(dst), stream);
-  else rc = IPK_OK;
+  rc = check_produced(n, w, h); if (rc) return rc;
+  if (out_type != IPK_OUT_F32) { tm.rest = "quantise"; rc = quantise(buf, w * h * 3, out_type, dst, stream); }
   return rc < 0 ? rc : IPK_OK;
+}
+}  // namespace
+
+int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int out_type, int *used_fused, void *stream) {
+  REQUIRE_INIT();
+  if (!d || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
+  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {
+    if (used_fused) *used_fused = 0;
+    if (d->width < 1 || d->height < 1) return fail(IPK_ERR_INVALID, "empty source");
+    StageTimer tmf(S(stream)); tmf.rest = "fastpath";
+    return run_fastpath(d, src, dst, out_type, stream);
+  }
+  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
+  StageTimer tm(S(stream));
+  if (used_fused) *used_fused = 0;
+  ipk_fused_params fp;
+  if (fused_raw_route(d, n, out_type, fp)) {
+    rc = run_fused_raw(d, n, fp, src, dst, tm, stream);
+  } else if (fused_raster_route(d, n)) {
+    tm.rest = "fused gofloat+to_lab+basecurve+from_lab+gamma(+transform)";
+    rc = fused_then_orient(d, n, nullptr, out_type, src, dst, stream);
+  } else {
+    return run_staged(d, n, out_type, src, dst, tm, stream);
+  }
+  if (rc == IPK_OK && used_fused) *used_fused = 1;
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------------
 // Pipeline::run with a cache (src/pipeline.rs:341-372): hash chain + memoised device OpBuffers
 // ------------------------------------------------------------------------------------------
 namespace {
-struct Negotiated {
-  ipk::Rect r; size_t dw, dh, fw, fh; ipk::RotateCrop rc; int linear; int orientation; bool transform_noop;
-};
-int negotiate(const ipk_pipeline_desc *d, int out_type, Negotiated &n) {
-  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
-  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
-  // one negotiation: the sizes and the rotatecrop state both come from pipeline_sizes_impl's folds (the reverse fold is seeded
-  // with scaling_size of the forward result, pipeline.rs:328-335 -- not with the size run() produces)
-  int rc = pipeline_sizes_impl(d, &n.dw, &n.dh, &n.fw, &n.fh, &n.rc); if (rc) return rc;
-  ipk::size_image(d->crop_top, d->crop_right, d->crop_bottom, d->crop_left, d->width, d->height, n.r);
-  n.linear = out_type == IPK_OUT_U8 ? 0 : (out_type == IPK_OUT_U16 ? 1 : (d->linear != 0));
-  n.orientation = ipk::transform_orientation(d->rotation, d->fliph != 0, d->flipv != 0);
-  n.transform_noop = n.orientation == IPK_OR_NORMAL || n.orientation == IPK_OR_UNKNOWN;
-  return IPK_OK;
-}
 // ophashes[0..7] of pipeline.rs:342-361.  Field order follows the reference structs.
 void hash_chain(const ipk_pipeline_desc *d, const Negotiated &n, uint64_t source_id, ipk::BufHash out[8]) {
   ipk::BufHasher h;
@@ -1914,75 +1916,34 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   // the latest op whose output is memoised (pipeline.rs:352-361: every hash is looked up, the last hit wins)
   CBufP buf; int startpos = 0;
   for (int i = 0; i < 8; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
-
-  const bool raw = d->src_type == IPK_SRC_U16 || d->src_type == IPK_SRC_F32;
-  const bool cfa_branch = raw && !(d->cpp == 1 && !d->is_cfa) && d->cpp != 3;
-  const size_t w0 = n.r.width, h0 = n.r.height;
   int mask = 0;
 
   // Nothing memoised and the whole chain is one fused launch: cheaper on this machine than materialising seven
   // intermediates; only the final buffer enters the cache.
-  if (startpos == 0 && d->allow_fused && cfa_branch && d->cpp == 1 && n.rc.noop()) {   // any orientation: ipk_pipeline_run folds OpTransform in
-    const float scale = ipk::calculate_scaling_total(w0, h0, n.dw, n.dh).scale;
-    ipk::Cfa cfa; int xo, yo;
-    if (scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) && (cfa.bayer_phase(xo, yo) || cfa.three_colour())) {
-      ipk_pipeline_desc d2 = *d; d2.linear = n.linear;
-      CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
-      int fused = 0;
-      rc = ipk_pipeline_run(&d2, src, o->p, IPK_OUT_F32, &fused, stream); if (rc < 0) return rc;
-      cache->lru.put(hs[7], o, o->bytes());
-      buf = o; startpos = 8; mask = 0xFF;
-      if (used_fused) *used_fused = fused;
-    }
+  ipk_fused_params fp;
+  if (startpos == 0 && fused_raw_route(d, n, IPK_OUT_F32, fp)) {          // any orientation: the fused route folds OpTransform in
+    CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
+    { StageTimer tm(st); rc = run_fused_raw(d, n, fp, src, o->p, tm, stream); }
+    if (rc < 0) return rc;
+    cache->lru.put(hs[7], o, o->bytes());
+    buf = o; startpos = 8; mask = 0xFF;
+    if (used_fused) *used_fused = rc == IPK_OK;
   }
 
   for (int i = startpos; i < 8; ++i) {
     CBufP o;
     switch (i) {
       case 0: {                                                          // gofloat
-        if (d->allow_fused && cfa_branch && d->cpp == 1) {               // + demosaic in the same pass when it would scale
-          ipk::Cfa cfa;
-          const float scale = ipk::calculate_scaling_total(w0, h0, n.dw, n.dh).scale;
-          if (ipk::Cfa::parse(d->cfa, cfa) && cfa.valid() && scale >= ipk::demosaic_minscale(cfa.width) && !cache->lru.contains(hs[1])) {
-            rc = cbuf_new(n.dw, n.dh, 4, 0, o); if (rc) return rc;
-            rc = ipk_raw_scaled_demosaic(src, d->src_type, d->width, n.r.x, n.r.y, w0, h0, d->blacklevels[0], d->whitelevels[0], d->cfa, n.dw, n.dh,
-                                         static_cast<float *>(o->p), stream);
-            if (rc < 0) return rc;
-            mask |= 3; buf = o; cache->lru.put(hs[1], o, o->bytes()); i = 1;   // op 1's output; op 0's is never materialised
-            continue;
-          }
-        }
-        if (d->allow_fused && !raw && ipk::calculate_scaling_total(w0, h0, n.dw, n.dh).scale > 1.0f && !cache->lru.contains(hs[1])) {
-          rc = cbuf_new(n.dw, n.dh, 4, 0, o); if (rc) return rc;                 // raster under a size limit: run_other + scale_down_opbuf in one pass
-          rc = ipk_raster_scale_down(src, d->src_type, d->width, n.r.x, n.r.y, w0, h0, n.dw, n.dh, static_cast<float *>(o->p), stream);
-          if (rc < 0) return rc;
-          mask |= 3; buf = o; cache->lru.put(hs[1], o, o->bytes()); i = 1;
+        if (gofloat_demosaic_one_pass(d, n) && !cache->lru.contains(hs[1])) {   // + demosaic in the same pass when it would scale
+          rc = cbuf_new(n.dw, n.dh, 4, 0, o); if (rc) return rc;
+          rc = launch_gofloat_demosaic(d, n, src, static_cast<float *>(o->p), stream); if (rc < 0) return rc;
+          mask |= 3; buf = o; cache->lru.put(hs[1], o, o->bytes()); i = 1;   // op 1's output; op 0's is never materialised
           continue;
         }
-        if (raw) {
-          if (d->cpp == 1 && !d->is_cfa) {
-            rc = cbuf_new(w0, h0, 4, 1, o); if (rc) return rc;
-            rc = d->src_type == IPK_SRC_U16
-              ? ipk_gofloat_mono_u16(static_cast<const uint16_t *>(src), d->width, n.r.x, n.r.y, w0, h0, d->blacklevels[0], d->whitelevels[0], static_cast<float *>(o->p), stream)
-              : ipk_gofloat_mono_f32(static_cast<const float *>(src), d->width, n.r.x, n.r.y, w0, h0, d->blacklevels[0], d->whitelevels[0], static_cast<float *>(o->p), stream);
-          } else if (d->cpp == 3) {
-            rc = cbuf_new(w0, h0, 4, 0, o); if (rc) return rc;
-            rc = d->src_type == IPK_SRC_U16
-              ? ipk_gofloat_rgb_u16(static_cast<const uint16_t *>(src), d->width, n.r.x, n.r.y, w0, h0, d->blacklevels, d->whitelevels, static_cast<float *>(o->p), stream)
-              : ipk_gofloat_rgb_f32(static_cast<const float *>(src), d->width, n.r.x, n.r.y, w0, h0, d->blacklevels, d->whitelevels, static_cast<float *>(o->p), stream);
-          } else {
-            if (d->cpp != 1) return fail(IPK_ERR_UNSUPPORTED, "cpp=%d sources are not supported", d->cpp);
-            rc = cbuf_new(w0, h0, 1, 0, o); if (rc) return rc;
-            rc = d->src_type == IPK_SRC_U16
-              ? ipk_gofloat_cfa_u16(static_cast<const uint16_t *>(src), d->width, n.r.x, n.r.y, w0, h0, d->blacklevels[0], d->whitelevels[0], static_cast<float *>(o->p), stream)
-              : ipk_gofloat_cfa_f32(static_cast<const float *>(src), d->width, n.r.x, n.r.y, w0, h0, d->blacklevels[0], d->whitelevels[0], static_cast<float *>(o->p), stream);
-          }
-        } else {
-          rc = cbuf_new(w0, h0, 4, 0, o); if (rc) return rc;
-          rc = d->src_type == IPK_SRC_RGB8
-            ? ipk_gofloat_other_u8(static_cast<const uint8_t *>(src), d->width, n.r.x, n.r.y, w0, h0, static_cast<float *>(o->p), stream)
-            : ipk_gofloat_other_u16(static_cast<const uint16_t *>(src), d->width, n.r.x, n.r.y, w0, h0, static_cast<float *>(o->p), stream);
-        }
+        size_t colors; int mono;
+        rc = gofloat_shape(d, n, colors, mono); if (rc) return rc;
+        rc = cbuf_new(n.r.width, n.r.height, colors, mono, o); if (rc) return rc;
+        rc = launch_gofloat(d, n, src, static_cast<float *>(o->p), stream);
         break;
       }
       case 1: {                                                          // demosaic
@@ -2033,11 +1994,9 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
     cache->lru.put(hs[i], buf, buf->bytes());
   }
   if (ops_run) *ops_run = mask;
-  if (buf->w != n.fw || buf->h != n.fh || buf->colors != 3)
-    return fail(IPK_ERR_INVALID, "internal: produced %zux%zux%zu, negotiated %zux%zu", buf->w, buf->h, buf->colors, n.fw, n.fh);
+  rc = check_produced(n, buf->w, buf->h, buf->colors); if (rc) return rc;
   const size_t cnt = buf->w * buf->h * 3;
-  if (out_type == IPK_OUT_U8) rc = ipk_output8bit(static_cast<const float *>(buf->p), cnt, static_cast<uint8_t *>(dst), stream);
-  else if (out_type == IPK_OUT_U16) rc = ipk_output16bit(static_cast<const float *>(buf->p), cnt, static_cast<uint16_t *>(dst), stream);
+  if (out_type != IPK_OUT_F32) rc = quantise(buf->p, cnt, out_type, dst, stream);
   else { HIPCHK(hipMemcpyAsync(dst, buf->p, cnt * sizeof(float), hipMemcpyDeviceToDevice, st)); rc = IPK_OK; }
   if (rc < 0) return rc;
   // `buf` may be evicted (and its memory freed) as soon as we return; hipFree waits for the device, so the copy above is safe
@@ -2056,7 +2015,6 @@ struct DevBuf {
   int download(void *h, size_t bytes) { HIPCHK(hipMemcpy(h, p, bytes, hipMemcpyDeviceToHost)); return IPK_OK; }
 };
 size_t src_elem_size(int t) { return t == IPK_SRC_U16 ? 2 : t == IPK_SRC_F32 ? 4 : t == IPK_SRC_RGB8 ? 1 : 2; }
-size_t out_elem_size(int t) { return t == IPK_OUT_F32 ? 4 : t == IPK_OUT_U8 ? 1 : 2; }
 }  // namespace
 
 #define HOST_TRY(expr) do { int rc_ = (expr); if (rc_ < 0) return rc_; } while (0)
@@ -2108,40 +2066,6 @@ void HostLanes::release() {
 // ------------------------------------------------------------------------------------------
 // A caller looping Pipeline::run over the frames of a shoot (src/pipeline.rs:246-249: frames are independent), device pointers
 // ------------------------------------------------------------------------------------------
-namespace {
-// Is Pipeline::run for this descriptor exactly one fused launch per frame with nothing in front of or behind it (the conditions of
-// ipk_pipeline_run's first branch, with OpTransform a no-op)?  Then a batch of such frames is one persistent launch per 64 (ipk_raw_to_srgb_batch).
-bool desc_is_one_fused_launch(const ipk_pipeline_desc *d, int out_type, ipk_fused_params &fp) {
-  size_t dw, dh, fw, fh;
-  if (pipeline_sizes_impl(d, &dw, &dh, &fw, &fh, nullptr) != IPK_OK) return false;
-  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return false;
-  ipk::Rect r;
-  if (!ipk::size_image(d->crop_top, d->crop_right, d->crop_bottom, d->crop_left, d->width, d->height, r)) return false;
-  const bool raw = d->src_type == IPK_SRC_U16 || d->src_type == IPK_SRC_F32;
-  const bool cfa_branch = raw && !(d->cpp == 1 && !d->is_cfa) && d->cpp != 3;
-  const int orientation = ipk::transform_orientation(d->rotation, d->fliph != 0, d->flipv != 0);
-  ipk::RotateCrop rcop;
-  rcop.crop_top = d->rotatecrop[0]; rcop.crop_right = d->rotatecrop[1]; rcop.crop_bottom = d->rotatecrop[2];
-  rcop.crop_left = d->rotatecrop[3]; rcop.rotation = d->rotatecrop[4];
-  if (!(d->allow_fused && cfa_branch && d->cpp == 1 && rcop.noop())) return false;
-  if (!(orientation == IPK_OR_NORMAL || orientation == IPK_OR_UNKNOWN)) return false;
-  if (ipk::calculate_scaling_total(r.width, r.height, dw, dh).scale > 1.0f) return false;
-  ipk::Cfa cfa; int xo, yo;
-  if (!ipk::Cfa::parse(d->cfa, cfa) || !(cfa.bayer_phase(xo, yo) || cfa.three_colour())) return false;
-  std::memset(&fp, 0, sizeof(fp));
-  fp.struct_size = (uint32_t)sizeof(fp);
-  fp.src_type = d->src_type; fp.owidth = d->width; fp.x = r.x; fp.y = r.y; fp.width = r.width; fp.height = r.height;
-  fp.black0 = d->blacklevels[0]; fp.white0 = d->whitelevels[0];
-  std::memcpy(fp.cfa, d->cfa, sizeof(fp.cfa));
-  std::memcpy(fp.wb_coeffs, d->wb_coeffs, sizeof(fp.wb_coeffs));
-  std::memcpy(fp.cam_to_xyz_normalized, d->cam_to_xyz_normalized, sizeof(fp.cam_to_xyz_normalized));
-  fp.exposure = d->exposure; fp.npoints = d->npoints; std::memcpy(fp.points, d->points, sizeof(fp.points));
-  fp.linear = out_type == IPK_OUT_U8 ? 0 : (out_type == IPK_OUT_U16 ? 1 : d->linear);   // pipeline.rs:405, :452
-  fp.out_type = out_type; fp.schedule = d->schedule;
-  return true;
-}
-}  // namespace
-
 int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *srcs, void *const *dsts, size_t n, int out_type, int *used_fused, void *stream) {
   REQUIRE_INIT();
   if (!d || (n && (!srcs || !dsts))) return fail(IPK_ERR_INVALID, "null argument");
@@ -2151,8 +2075,10 @@ int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *srcs, 
   for (size_t i = 0; i < n; ++i) if (!srcs[i] || !dsts[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
   if (used_fused) *used_fused = 0;
   if (n == 0) return IPK_OK;
-  ipk_fused_params fp;
-  if (n > 1 && desc_is_one_fused_launch(d, out_type, fp)) {
+  // Is Pipeline::run for each frame exactly the fused raw launch with nothing behind it (OpTransform a no-op)?  Then the batch is one
+  // persistent launch per 64 frames (ipk_raw_to_srgb_batch).
+  Negotiated ng; ipk_fused_params fp;
+  if (n > 1 && negotiate(d, out_type, ng) == IPK_OK && ng.transform_noop && fused_raw_route(d, ng, out_type, fp)) {
     const int rc = ipk_raw_to_srgb_batch(&fp, srcs, dsts, n, stream);
     if (rc == IPK_OK && used_fused) *used_fused = 1;
     return rc;

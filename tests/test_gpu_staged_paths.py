@@ -3,6 +3,7 @@ oracle: the sources the fused launch never takes (mono raws, three-sample raws, 
 and without rotation, orientations, sensor crops, the three output types, the cache, special values and full-size frames.
 Bar: bit-exact (0 ULP, any NaN == any NaN)."""
 import ctypes as C
+import itertools
 import math
 import os
 
@@ -203,6 +204,48 @@ def _matrix_case(orc, name, i):
 def test_staged_source_branch_matrix(ipa, orc, name, i):
     data, src, crops, ops, out_type, scale, tag = _matrix_case(orc, name, i)
     _check_driver(ipa, orc, data, src, crops, ops, out_type, _must_stage(name, ops, scale), tag)
+
+
+# ---------------------------------------------------------------------------------------------
+# one routing decision: ipk_pipeline_run, a cold ipk_pipeline_run_cached and ipk_pipeline_run_batch (two frames, OpTransform a no-op) report
+# the same used_fused for every raw descriptor
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", SOURCES)
+def test_drivers_agree_on_the_fused_route(ipa, name):
+    import torch
+    j = SOURCES.index(name)
+    data, src = _source(name, 40 + 2 * j, 72 + 6 * j, util.SEED + 9100 + j)
+    w = data.shape[1]
+    dtypes = {F32: torch.float32, U8: torch.uint8, U16: torch.int16}
+    codes = {F32: ipa.OUT_F32, U8: ipa.OUT_U8, U16: ipa.OUT_U16}
+    seen = set()
+    for crops, rc, orient, mw, fused, out_type in itertools.product(CROPS.values(), ("none", "crop"), ORIENTS, (0, w // 2, w // 5), (True, False),
+                                                                    (F32, U8, U16)):
+        ops = _case_ops(rc, orient)
+        if mw:
+            ops["maxwidth"] = mw
+        pipe = _pipeline(ipa, data, src, crops, ops)
+        pipe.allow_fused = fused
+        tag = "%s crops %r rotatecrop %s %s maxwidth %d allow_fused %s %s" % (name, crops, rc, orient, mw, fused, out_type)
+        pipe._run(codes[out_type])
+        run = pipe.last_used_fused
+        cache = ipa.PipelineCache(1 << 28)
+        pipe._run(codes[out_type], cache=cache)
+        cache.close()
+        assert pipe.last_used_fused == run, tag + ": cold cached run"
+        seen.add(run)
+        if orient != "normal":
+            continue
+        _, (fw, fh) = pipe.sizes()
+        outs = [torch.empty(fw * fh * 3, dtype=dtypes[out_type], device="cuda") for _ in range(2)]
+        p = pipe.globals.image.data.data_ptr()
+        srcs, dsts = (C.c_void_p * 2)(p, p), (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
+        used = C.c_int(-1)
+        assert ipa.lib().ipk_pipeline_run_batch(C.byref(pipe.desc()), srcs, dsts, 2, codes[out_type], C.byref(used), ipa._stream()) == 0, tag
+        assert bool(used.value) == run, tag + ": batch of two"
+    torch.cuda.synchronize()
+    if src["cfa"] in ("GRBG", XT):
+        assert seen == {False, True}, name + ": the matrix reaches both routes"
 
 
 @pytest.mark.parametrize("out_type", [F32, U8, U16])
