@@ -558,7 +558,8 @@ class Pipeline:
         self.ops = PipelineOps(img)
         self.allow_fused = True
         self.last_used_fused = None
-        self.last_ops_run = None              # bit i set when op i executed in the last run (0 = served from the cache)
+        self.last_region_windowed = None      # run_region: True when only the region's part of the fused launch ran
+        self.last_ops_run = None             # bit i set when op i executed in the last run (0 = served from the cache)
         self.source_id = 0                    # extension of the hash chain: identifies the frame inside a shared PipelineCache
         self.schedule = 0                     # ipk_pipeline_desc.schedule (IPK_SCHED_AUTO / IPK_SCHED_SPLIT): how a fused launch shares the rows out
 
@@ -656,6 +657,29 @@ class Pipeline:
             self.last_ops_run = mask.value
         self.last_used_fused = bool(used.value)
         return out, fw, fh
+
+    def region(self, x, y, w, h, out_type=OUT_F32):
+        """Plan the region (x, y, w, h) of the result (ipk_pipeline_region, host-only): (windowed, (sx, sy, sw, sh)) -- windowed = 1 when the
+        run computes only that part of the fused launch and reads only the sensor window (sx, sy, sw, sh), 0 when it computes the whole
+        frame (the window is then the crop window)."""
+        d = self.desc()
+        sx, sy, sw, sh = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        rc = _lib.check(lib().ipk_pipeline_region(C.byref(d), out_type, x, y, w, h, C.byref(sx), C.byref(sy), C.byref(sw), C.byref(sh)),
+                        "ipk_pipeline_region")
+        return rc, (sx.value, sy.value, sw.value, sh.value)
+
+    def run_region(self, x, y, w, h, out_type=OUT_F32, out: Optional[torch.Tensor] = None):
+        """Columns [x, x+w) and rows [y, y+h) of what run() / output_8bit() / output_16bit() return, without the rest of the frame
+        (ipk_pipeline_run_region): an h*w*3 device tensor of the output type; sets last_region_windowed."""
+        d = self.desc()
+        dt = {OUT_F32: torch.float32, OUT_U8: torch.uint8, OUT_U16: torch.int16}[out_type]
+        if out is None:
+            out = torch.empty(w * h * 3, dtype=dt, device="cuda")
+        win = C.c_int(0)
+        _lib.check(lib().ipk_pipeline_run_region(C.byref(d), _ptr(self.globals.image.data), x, y, w, h, _ptr(out), out_type, C.byref(win), _stream()),
+                   "ipk_pipeline_run_region")
+        self.last_region_windowed = bool(win.value)
+        return out
 
     def run_timed(self, out_type=OUT_F32):
         """do_timing! (pipeline.rs:68-80): one run with per-stage hipEvent times; returns (output tensor, [(stage name, ms), ...])"""

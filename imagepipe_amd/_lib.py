@@ -146,6 +146,9 @@ SIGNATURES = {
     "ipk_pipeline_sizes": (C.c_int, [C.POINTER(PipelineDesc), _szp, _szp, _szp, _szp]),
     "ipk_pipeline_run": (C.c_int, [C.POINTER(PipelineDesc), _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp]),
     "ipk_host_pipeline_run": (C.c_int, [C.POINTER(PipelineDesc), _vp, _vp, C.c_int, C.POINTER(C.c_int)]),
+    "ipk_pipeline_region": (C.c_int, [C.POINTER(PipelineDesc), C.c_int, _sz, _sz, _sz, _sz, _szp, _szp, _szp, _szp]),
+    "ipk_pipeline_run_region": (C.c_int, [C.POINTER(PipelineDesc), _vp, _sz, _sz, _sz, _sz, _vp, C.c_int, C.POINTER(C.c_int), _vp]),
+    "ipk_host_pipeline_run_region": (C.c_int, [C.POINTER(PipelineDesc), _vp, _sz, _sz, _sz, _sz, _vp, C.c_int, C.POINTER(C.c_int)]),
     "ipk_host_pipeline_run_batch": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int)]),
     "ipk_pipeline_run_batch": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int), _vp]),
     "ipk_pipeline_run_batch_multi": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int)]),

@@ -1027,8 +1027,10 @@ static int get_rot_cells(const char *pat, const ipk::Cfa &cfa, int ori, size_t w
 // output orientation (1 channel: 2 or 4 bytes per pixel instead of the 12 of the result) and the kernel works in rotated space,
 // so that dst receives OpTransform's output directly; IPK_ERR_UNSUPPORTED (nothing launched) when no such variant exists.
 // nbatch > 0: the frames srcs[0..nbatch) -> dsts[0..nbatch), all with the geometry and parameters of *p (src / dst = the first pair)
+// win_c1 > 0: a region -- only the columns [win_c0, win_c1) of the band's rows are computed and stored, packed, into dst (ori 0, one frame)
 static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, void *stream, int ori,
-                      size_t nbatch = 0, const void *const *srcs = nullptr, void *const *dsts = nullptr, bool probe = false) {
+                      size_t nbatch = 0, const void *const *srcs = nullptr, void *const *dsts = nullptr, bool probe = false,
+                      size_t win_c0 = 0, size_t win_c1 = 0) {
   REQUIRE_INIT();
   if (!p || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
   IPK_FOLD_CFA(ipk_fused_params, p)
@@ -1147,6 +1149,8 @@ static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, voi
   f.num_cus = cx().num_cus; f.queues = cx().queues; f.gam_q8 = cx().lut_q8;
   if (p->schedule != IPK_SCHED_AUTO && p->schedule != IPK_SCHED_SPLIT) return fail(IPK_ERR_INVALID, "bad schedule");
   f.schedule = p->schedule;
+  if (win_c1 != 0 && (ori != 0 || nbatch || probe || win_c0 >= win_c1 || win_c1 > p->width)) return fail(IPK_ERR_INVALID, "bad column window");
+  f.win_c0 = win_c0; f.win_c1 = win_c1;
   { const int lrc = ipk::launch_fused_bayer(f, S(stream));
     if (lrc == -4) return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued; the stream's task queue is untouched)");
     if (lrc != 0) return fail(IPK_ERR_UNSUPPORTED, probe ? "the stream probe exists for Bayer frames of 256+ columns with validated levels" : "no rotated-space variant for these parameters"); }
@@ -1800,6 +1804,84 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
 }
 
 // ------------------------------------------------------------------------------------------
+// A region of ipk_pipeline_run's result (a viewer's viewport, one tile of a tiled render)
+// ------------------------------------------------------------------------------------------
+namespace {
+// windowed = 1 (the run is the one fused raw launch, fused_raw_route): the region comes from the unrotated rectangle [c0, c1) x [r0, r1) of the
+// cropped frame, which the window launch computes and OpTransform's permutation (dihedral: rectangles map to rectangles) turns into the region
+struct RegionPlan { int windowed; size_t c0, c1, r0, r1; };
+int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n, ipk_fused_params &fp, RegionPlan &pl) {
+  int rc = negotiate(d, out_type, n); if (rc) return rc;
+  if (d->npoints < 0 || d->npoints > 64) return fail(IPK_ERR_INVALID, "npoints out of range");
+  if (n.fw == 0 || n.fh == 0) return fail(IPK_ERR_INVALID, "the result is empty");
+  if (w == 0 || h == 0 || x > n.fw || w > n.fw - x || y > n.fh || h > n.fh - y)
+    return fail(IPK_ERR_INVALID, "region (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", x, y, w, h, n.fw, n.fh);
+  pl.windowed = fused_raw_route(d, n, out_type, fp) ? 1 : 0;
+  if (!pl.windowed) return IPK_OK;
+  bool t = false, fx = false, fy = false;
+  if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
+  const size_t W = n.r.width, H = n.r.height;
+  if ((t ? H : W) != n.fw || (t ? W : H) != n.fh) return fail(IPK_ERR_INVALID, "internal: fused result %zux%zu, negotiated %zux%zu", W, H, n.fw, n.fh);
+  // rotate_buffer's walk (transform.rs:102-128): result pixel (ox, oy) is source pixel (fx ? W-1-u : u, fy ? H-1-v : v) with (u, v) = t ? (oy, ox) : (ox, oy)
+  const size_t u0 = t ? y : x, un = t ? h : w, v0 = t ? x : y, vn = t ? w : h;
+  pl.c0 = fx ? W - u0 - un : u0; pl.c1 = pl.c0 + un;
+  pl.r0 = fy ? H - v0 - vn : v0; pl.r1 = pl.r0 + vn;
+  return IPK_OK;
+}
+}  // namespace
+
+int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, size_t *src_x, size_t *src_y, size_t *src_w,
+                        size_t *src_h) {
+  if (!d || !src_x || !src_y || !src_w || !src_h) return fail(IPK_ERR_INVALID, "null argument");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; ipk_fused_params fp; RegionPlan pl;
+  const int rc = plan_region(d, out_type, x, y, w, h, n, fp, pl); if (rc) return rc;
+  if (!pl.windowed) { *src_x = n.r.x; *src_y = n.r.y; *src_w = n.r.width; *src_h = n.r.height; return 0; }
+  // demosaic::full's one-pixel halo, clipped to the crop window, in sensor coordinates
+  const size_t c0 = pl.c0 > 0 ? pl.c0 - 1 : 0, c1 = std::min(n.r.width, pl.c1 + 1), r0 = pl.r0 > 0 ? pl.r0 - 1 : 0, r1 = std::min(n.r.height, pl.r1 + 1);
+  *src_x = n.r.x + c0; *src_y = n.r.y + r0; *src_w = c1 - c0; *src_h = r1 - r0;
+  return 1;
+}
+
+int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t x, size_t y, size_t w, size_t h, void *dst, int out_type, int *windowed,
+                            void *stream) {
+  REQUIRE_INIT();
+  if (!d || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
+  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; ipk_fused_params fp; RegionPlan pl;
+  int rc = plan_region(d, out_type, x, y, w, h, n, fp, pl); if (rc) return rc;
+  if (windowed) *windowed = pl.windowed;
+  const size_t esz = out_elem_size(out_type);
+  if (!pl.windowed) {
+    // every other route: the whole result into scratch, then the region's rows in one 2-D copy
+    Scratch sc(S(stream));
+    void *full = nullptr;
+    rc = sc.get(n.fw * n.fh * 3 * esz, &full); if (rc) return rc;
+    rc = ipk_pipeline_run(d, src, full, out_type, nullptr, stream); if (rc < 0) return rc;
+    StageTimer tc(S(stream)); tc.rest = "region copy";
+    HIPCHK(hipMemcpy2DAsync(dst, w * 3 * esz, static_cast<const char *>(full) + (y * n.fw + x) * 3 * esz, n.fw * 3 * esz, w * 3 * esz, h,
+                            hipMemcpyDeviceToDevice, S(stream)));
+    return IPK_OK;
+  }
+  StageTimer tm(S(stream));
+  tm.rest = "fused region gofloat+demosaic+to_lab+basecurve+from_lab+gamma(+transform)";
+  // the rows are a band whose source is the whole cropped frame (src then starts at the crop's first row); the columns are the launch's window
+  fp.band_src_row0 = 0; fp.band_src_rows = n.r.height; fp.band_out_row0 = pl.r0; fp.band_out_rows = pl.r1 - pl.r0;
+  const void *top = static_cast<const char *>(src) + n.r.y * d->width * (d->src_type == IPK_SRC_U16 ? 2 : 4);
+  if (n.transform_noop) return fused_impl(&fp, top, dst, stream, 0, 0, nullptr, nullptr, false, pl.c0, pl.c1);
+  Scratch sc(S(stream));
+  void *tmp = nullptr;
+  const size_t cw = pl.c1 - pl.c0, ch = pl.r1 - pl.r0;
+  rc = sc.get(cw * ch * 3 * esz, &tmp); if (rc) return rc;
+  rc = fused_impl(&fp, top, tmp, stream, 0, 0, nullptr, nullptr, false, pl.c0, pl.c1); if (rc < 0) return rc;
+  size_t ow = 0, oh = 0;
+  rc = orient(tmp, cw, ch, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
+  if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: oriented region %zux%zu, asked for %zux%zu", ow, oh, w, h);
+  return IPK_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // Pipeline::run with a cache (src/pipeline.rs:341-372): hash chain + memoised device OpBuffers
 // ------------------------------------------------------------------------------------------
 namespace {
@@ -2218,6 +2300,39 @@ int ipk_host_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *s
   const hipError_t e0 = hipStreamSynchronize(L.up), e1 = hipStreamSynchronize(L.run), e2 = hipStreamSynchronize(L.down);
   if (rc < 0) return rc;
   HIPCHK(e0); HIPCHK(e1); HIPCHK(e2);
+  return IPK_OK;
+}
+
+// A region from a HOST frame into a HOST buffer: on the windowed route only the sensor window ipk_pipeline_region reports crosses the link (one pitched
+// copy into its place in a frame-sized device buffer -- the launch reads nothing else), and only the region comes back.
+int ipk_host_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t x, size_t y, size_t w, size_t h, void *dst, int out_type,
+                                 int *windowed) {
+  REQUIRE_INIT();
+  if (!d || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  size_t sx, sy, sw, sh;
+  const int route = ipk_pipeline_region(d, out_type, x, y, w, h, &sx, &sy, &sw, &sh);
+  if (route < 0) return route;
+  const bool raw = d->src_type == IPK_SRC_U16 || d->src_type == IPK_SRC_F32;
+  const size_t px = (raw ? (size_t)d->cpp : 3) * src_elem_size(d->src_type), pitch = d->width * px;
+  const size_t in_bytes = d->height * pitch, out_bytes = w * h * 3 * out_elem_size(out_type);
+  HostLanes &L = cx().lanes;
+  std::lock_guard<std::mutex> lk(L.mu);
+  HIPCHK(hipDeviceSynchronize());   // as ipk_host_pipeline_run_batch: nothing enqueued earlier may still use the lanes
+  HOST_TRY(L.ensure(in_bytes, out_bytes));
+  int rc = IPK_OK;
+  if (route == 1) {
+    const size_t off = sy * pitch + sx * px;
+    if (hipMemcpy2DAsync(static_cast<char *>(L.in[0]) + off, pitch, static_cast<const char *>(src) + off, pitch, sw * px, sh, hipMemcpyHostToDevice, L.run) != hipSuccess)
+      rc = fail(IPK_ERR_HIP, "window upload failed");
+  } else if (hipMemcpyAsync(L.in[0], src, in_bytes, hipMemcpyHostToDevice, L.run) != hipSuccess) {
+    rc = fail(IPK_ERR_HIP, "frame upload failed");
+  }
+  if (rc == IPK_OK) rc = ipk_pipeline_run_region(d, L.in[0], x, y, w, h, L.out[0], out_type, windowed, L.run);
+  if (rc >= 0 && hipMemcpyAsync(dst, L.out[0], out_bytes, hipMemcpyDeviceToHost, L.run) != hipSuccess) rc = fail(IPK_ERR_HIP, "region download failed");
+  const hipError_t e = hipStreamSynchronize(L.run);   // the caller's buffers are not touched after the return
+  if (rc < 0) return rc;
+  HIPCHK(e);
   return IPK_OK;
 }
 

@@ -2177,8 +2177,31 @@ struct RgbeStage {
 // the frames of a batch launch: up to kBatchMax per launch, passed by value as the second kernel argument (1 KB of kernarg)
 constexpr int kBatchMax = 64;
 struct BatchPtrs { const void *src[kBatchMax]; void *dst[kBatchMax]; };
-template <typename SrcT, bool VEC, int OUT, bool FULL, bool GEN, bool PXG, int CM, bool ROT, bool BATCH>
-__device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const BatchPtrs *bp) {
+// WIN variants (k_fused_bayer_window, ipk_pipeline_run_region): the launch computes the cropped frame's columns [x0, x1) -- the region's columns rounded
+// out to whole 4-pixel lane groups and clipped to the frame -- and stores only the region's columns [c0, c1), packed at `pitch` pixels per output row.
+// Strips tile [x0, x1) the way they tile [0, W) in a whole-frame launch; halo columns, frame-edge taps, Bayer phase and generic-CFA cells are decided on
+// absolute columns, as rows are against H in a band.  x0 is a multiple of 4 and x1 is one or W, so a partly filled lane still sits at the frame's edge.
+struct FusedWindow { uint32_t x0, x1, c0, c1; uint64_t pitch; };
+// a WIN variant's store of one lane's pixels: those in [c0, c1) only, at their column's place in the packed region row `rowpix` (BITS: u8 samples that
+// arrive quantised in the floats' bits, the Q8 form)
+template <int OUT, bool BITS>
+__device__ __forceinline__ void win_store(void *dst, size_t rowpix, uint32_t col0, uint32_t c0, uint32_t c1, const PixOut o[4]) {
+  // one address per lane (its first pixel's place, left of the region's start for a lane that straddles it) and immediate offsets from it
+  const int64_t e = ((int64_t)rowpix + (int64_t)col0 - (int64_t)c0) * 3;
+  #pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t c = col0 + j;
+    if (c < c0 || c >= c1) continue;
+    if (OUT == 0) { float *p = reinterpret_cast<float *>(dst) + e + 3 * j; p[0] = o[j].r; p[1] = o[j].g; p[2] = o[j].b; }
+    else if (OUT == 1) {
+      uint8_t *p = reinterpret_cast<uint8_t *>(dst) + e + 3 * j;
+      if (BITS) { p[0] = (uint8_t)__float_as_uint(o[j].r); p[1] = (uint8_t)__float_as_uint(o[j].g); p[2] = (uint8_t)__float_as_uint(o[j].b); }
+      else { p[0] = output8bit(o[j].r); p[1] = output8bit(o[j].g); p[2] = output8bit(o[j].b); }
+    } else { uint16_t *p = reinterpret_cast<uint16_t *>(dst) + e + 3 * j; p[0] = output16bit(o[j].r); p[1] = output16bit(o[j].g); p[2] = output16bit(o[j].b); }
+  }
+}
+template <typename SrcT, bool VEC, int OUT, bool FULL, bool GEN, bool PXG, int CM, bool ROT, bool BATCH, bool WIN = false>
+__device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const BatchPtrs *bp, const FusedWindow *win = nullptr) {
   constexpr bool CMN = CM != 0;                          // 1: common parameters with the 3-knot curve compiled in; 2: with the grid form (four or more knots)
   // f32 sources can hold denormal/huge samples: guard the normalisation's dividends.  u16 samples minus a
   // host-validated black level cannot leave the proven zone.
@@ -2356,7 +2379,10 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
     const uint32_t lc0 = FULL ? 0u : strip * a.lc_base + min(strip, a.lc_rem);
     const uint32_t nl = FULL ? 64u : a.lc_base + (strip < a.lc_rem ? 1u : 0u);
     const bool lane_on = FULL ? true : lane < nl;
-    const uint32_t pc0 = FULL ? min(strip * 256u, a.W - 256u) : 4u * lc0;   // first pixel column of the strip
+    // (WIN: the strips tile the window [x0, x1) instead of [0, W); every column below is the frame's)
+    const uint32_t pc0 = (WIN ? win->x0 : 0u) + (FULL ? min(strip * 256u, (WIN ? win->x1 - win->x0 : a.W) - 256u) : 4u * lc0);   // first pixel column of the strip
+    // WIN, full strips: a strip inside the region keeps the staged, lane-contiguous stores (wave-uniform)
+    const bool win_inner = WIN && FULL && pc0 >= win->c0 && pc0 + 256u <= win->c1;
     // lanes past the strip shadow its last lane: their loads stay in bounds and need no predicate
     const uint32_t col0 = pc0 + 4u * min(lane, nl - 1);
     const uint32_t nvalid = FULL ? 4u : min(4u, a.W - col0);
@@ -2635,7 +2661,7 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
       bool fNN;
       const RowWin NN = finish_row(raw_next, fNN);         // row r+2: the wait for its loads sits before this row's stores
       __builtin_amdgcn_sched_barrier(0);
-      if (FULL) {
+      if (FULL && (!WIN || win_inner)) {
         // Lane-blocked -> lane-interleaved through the wave's LDS staging buffer, then three stores per lane whose
         // addresses are contiguous across the wave (whole cache lines per instruction; a 48-byte lane stride would
         // touch every line of the 3 KB span with each of its stores).
@@ -2645,8 +2671,12 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
         // and the wave barrier emit no instructions (the hardware already runs one wave's LDS operations in order).
         if constexpr (Q8) OutStage<1>::stage_bits(stg, lane, o); else OutStage<OUTS>::stage(stg, lane, o);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        OutStage<OUTS>::flush(stg, lane, frame_dst, (size_t)(r - a.out_r0) * a.W + pc0);
+        if (WIN) OutStage<OUTS>::flush(stg, lane, frame_dst, (size_t)(r - a.out_r0) * win->pitch + (pc0 - win->c0));
+        else OutStage<OUTS>::flush(stg, lane, frame_dst, (size_t)(r - a.out_r0) * a.W + pc0);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      } else if (WIN) {
+        // a strip that straddles the region's edge (or a narrow window): each lane stores the pixels of its own that the region holds
+        if (lane_on) win_store<OUTS, Q8>(frame_dst, (size_t)(r - a.out_r0) * win->pitch, col0, win->c0, win->c1, o);
       } else {
         if (lane_on) OutStore<OUTS>::store(frame_dst, (size_t)(r - a.out_r0) * a.W + col0, nvalid, o, store_aligned);
       }
@@ -2691,6 +2721,9 @@ __global__ __launch_bounds__(1024) void k_fused_bayer(FusedArgs a) { fused_bayer
 // the persistent batch form; instantiated for the common parameter set only (launch_fused_bayer_batch)
 template <typename SrcT, bool VEC, int OUT, bool PXG>
 __global__ __launch_bounds__(1024) void k_fused_bayer_batch(FusedArgs a, BatchPtrs bp) { fused_bayer_body<SrcT, VEC, OUT, true, false, PXG, 1, false, true>(a, &bp); }
+// the region form (launch_fused_window_t): the column window is a kernel argument of its own, so the whole-frame variants above keep their code
+template <typename SrcT, bool VEC, int OUT, bool FULL, bool GEN, bool PXG, int CM>
+__global__ __launch_bounds__(1024) void k_fused_bayer_window(FusedArgs a, FusedWindow w) { fused_bayer_body<SrcT, VEC, OUT, FULL, GEN, PXG, CM, false, false, true>(a, nullptr, &w); }
 
 static void fused_task_grid(FusedArgs &a, int num_cus, unsigned &blocks, uint32_t frames = 1, uint32_t waves_per_block = 16);
 static bool task_counters_for(TaskQueues *q, hipStream_t s, FusedArgs &a, std::unique_lock<std::mutex> &lk);
@@ -2771,6 +2804,27 @@ static void launch_fused_t(const FusedArgs &a, unsigned grid, hipStream_t s) {
   }
   if (a.W >= 256u) hipLaunchKernelGGL((k_fused_bayer<SrcT, VEC, OUT, true, false>), dim3(grid), dim3(tpb), 0, s, a);
   else hipLaunchKernelGGL((k_fused_bayer<SrcT, VEC, OUT, false, false>), dim3(grid), dim3(tpb), 0, s, a);
+}
+// A region's launch.  The common parameter set takes launch_fused_t's template flags (the headline descriptor's window runs its whole-frame kernel's
+// code); everything else takes the runtime-flag form (CM = 0, per-pixel guards on), Bayer or generic-CFA.  u16 sources take the loads that accept any
+// alignment.  Full 256-pixel strips need a window of 256 columns or more.
+template <typename SrcT, int OUT>
+static void launch_fused_window_t(const FusedArgs &a, const FusedWindow &w, unsigned grid, hipStream_t s) {
+  constexpr bool V = sizeof(SrcT) == 4;
+  const bool full = w.x1 - w.x0 >= 256u;
+  const bool common = full && a.fast_ok && a.has_curve && !a.exact_norm && (a.linear != 0) == (OUT == 2) && std::fabs(a.min0) >= 0x1p-70f &&
+                      std::fabs(a.min0) <= 0x1p70f && a.spline.npoints == 3 && spline3_arith_ok(a.spline);
+#define IPK_WIN_LAUNCH(FL, G, P, C) hipLaunchKernelGGL((k_fused_bayer_window<SrcT, V, OUT, FL, G, P, C>), dim3(grid), dim3(1024), 0, s, a, w)
+  if (a.gen_cells) {
+    if (common) IPK_WIN_LAUNCH(true, true, true, 1);
+    else if (full) IPK_WIN_LAUNCH(true, true, true, 0);
+    else IPK_WIN_LAUNCH(false, true, true, 0);
+  }
+  else if (common && a.px_guard == 0) IPK_WIN_LAUNCH(true, false, false, 1);
+  else if (common) IPK_WIN_LAUNCH(true, false, true, 1);
+  else if (full) IPK_WIN_LAUNCH(true, false, true, 0);
+  else IPK_WIN_LAUNCH(false, false, true, 0);
+#undef IPK_WIN_LAUNCH
 }
 
 // The task queue of a stream (fused_bayer_body): a counter and an arrival counter, zero between launches -- a launch leaves them as it found
@@ -2920,6 +2974,26 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s) {
     const bool common = a.fast_ok && a.has_curve && a.spline.npoints == 3 && spline3_arith_ok(a.spline) && !a.exact_norm && (a.linear != 0) == (f.out_type == 2) && a.W >= 256u &&
                         std::fabs(a.min0) >= 0x1p-70f && std::fabs(a.min0) <= 0x1p70f;
     if (!common || f.ori < 1 || f.ori > 7) return -2;
+  }
+  if (f.win_c1 != 0) {                                    // a region (k_fused_bayer_window): one frame in its own orientation, output types 0..2
+    if (f.ori != 0 || f.batch_n > 0 || f.out_type < 0 || f.out_type > 2 || f.win_c0 >= f.win_c1 || f.win_c1 > f.width) return -2;
+    FusedWindow w;
+    w.c0 = (uint32_t)f.win_c0; w.c1 = (uint32_t)f.win_c1; w.pitch = f.win_c1 - f.win_c0;
+    w.x0 = w.c0 & ~3u; w.x1 = std::min(a.W, (w.c1 + 3u) & ~3u);        // whole lane groups, inside the frame
+    std::unique_lock<std::mutex> queue_lock;
+    (void)task_counters_for(f.queues, s, a, queue_lock);
+    unsigned blocks;
+    a.W = w.x1 - w.x0; fused_task_grid(a, f.num_cus, blocks); a.W = (uint32_t)f.width;   // the strips tile the window
+    if (!f.src_is_u16) {
+      if (f.out_type == 0) launch_fused_window_t<float, 0>(a, w, blocks, s);
+      else if (f.out_type == 1) launch_fused_window_t<float, 1>(a, w, blocks, s);
+      else launch_fused_window_t<float, 2>(a, w, blocks, s);
+    } else {
+      if (f.out_type == 0) launch_fused_window_t<uint16_t, 0>(a, w, blocks, s);
+      else if (f.out_type == 1) launch_fused_window_t<uint16_t, 1>(a, w, blocks, s);
+      else launch_fused_window_t<uint16_t, 2>(a, w, blocks, s);
+    }
+    return launch_status();
   }
 
   const bool vec = f.src_is_u16 ? f.src_aligned4 : true;

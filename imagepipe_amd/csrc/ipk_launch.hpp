@@ -90,6 +90,9 @@ struct FusedLaunch {
   // launch_fused_bayer only: batch_n > 0 = that many frames of this shape and these parameters (host arrays of device pointers, src already
   // offset like `src`); one persistent launch per 64 frames where a batch variant of the kernel exists, one launch per frame otherwise
   int batch_n; const void *const *batch_src; void *const *batch_dst;
+  // launch_fused_bayer only: win_c1 > 0 = a region launch (ipk_pipeline_run_region): the output columns [win_c0, win_c1) of the rows [out_r0, out_r1),
+  // packed win_c1 - win_c0 pixels per row into dst.  Columns, like rows, are the cropped frame's: CFA phase and cells are not shifted
+  size_t win_c0 = 0, win_c1 = 0;
 };
 // returns 0, -2 when f.ori != 0 and the parameters have no rotated-space variant (nothing is launched), -4 when a launch could not be enqueued
 int launch_fused_bayer(const FusedLaunch &f, hipStream_t s);

@@ -437,6 +437,23 @@ IPK_API int ipk_timing_begin(void);
 IPK_API int ipk_timing_end(ipk_stage_time *out, int max_stages, int *n_stages);
 /* Same with HOST source and destination buffers; synchronous. */
 IPK_API int ipk_host_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int out_type, int *used_fused);
+/* Regions: columns [x, x+w) and rows [y, y+h) of the final_w x final_h result of ipk_pipeline_run (after OpTransform, in its orientation),
+ * bit-identical to that rectangle of the whole result and written row-major and packed: w*h*3 samples of out_type.  An empty region, one
+ * that leaves the result, or a descriptor ipk_pipeline_run rejects fails with IPK_ERR_INVALID and writes nothing.
+ * ipk_pipeline_region plans one (no GPU needed) and returns its route: 1 = windowed -- the run is the fused raw->sRGB launch, restricted to the
+ * rectangle of the cropped frame the region comes from, and reads only the sensor window reported (that rectangle plus demosaic::full's
+ * one-pixel halo, clipped to the crop window, in sensor coordinates); 0 = whole frame -- staged, scaled, rotatecrop, four-colour, mono/RGB and
+ * raster routes and allow_fused = 0 compute the whole result and copy the region out, and the window reported is the crop window. */
+IPK_API int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h,
+                                size_t *src_x, size_t *src_y, size_t *src_w, size_t *src_h);
+/* The region from the DEVICE source ipk_pipeline_run takes (the whole sensor frame) into the DEVICE buffer dst, enqueued on `stream`.
+ * *windowed (may be NULL) receives the route.  ipk_timing_begin/end see its stages. */
+IPK_API int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t x, size_t y, size_t w, size_t h, void *dst,
+                                    int out_type, int *windowed, void *stream);
+/* The same from the whole HOST frame into a HOST buffer; synchronous.  The windowed route uploads only the reported sensor window (one
+ * pitched copy), the whole route the frame; only the region's w*h*3 samples come back. */
+IPK_API int ipk_host_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t x, size_t y, size_t w, size_t h, void *dst,
+                                         int out_type, int *windowed);
 /* A batch of n same-shaped HOST frames through one descriptor (a caller looping Pipeline::run / output_8bit over a shoot,
  * src/pipeline.rs:311-372, :404-421): three HIP streams (upload, compute, download) over two device slots, so frame i's kernels
  * run while frame i+1 crosses PCIe upwards and frame i-1 downwards; per-frame cost tends to max(upload, compute, download)

@@ -324,6 +324,17 @@ class Pipeline {
     DeviceArray o(fw * fh * 6); drive(cache, IPK_OUT_U16, o.get());
     SRGBImage16 img{fw, fh, std::vector<uint16_t>(fw * fh * 3)}; o.download(img.data.data()); return img;
   }
+  // Columns [x, x+w) and rows [y, y+h) of what run() / output_8bit / output_16bit return (ipk_pipeline_run_region): a viewer's viewport or one tile,
+  // w*h*3 samples of out_type on the device, without the rest of the frame where the run is the fused launch (last_region_windowed)
+  DeviceArray run_region(size_t x, size_t y, size_t w, size_t h, int out_type = IPK_OUT_F32) {
+    ipk_pipeline_desc d = desc(); int win = 0;
+    DeviceArray o(w * h * 3 * (out_type == IPK_OUT_F32 ? 4 : out_type == IPK_OUT_U8 ? 1 : 2));
+    check(ipk_pipeline_run_region(&d, globals.image.data.get(), x, y, w, h, o.get(), out_type, &win, nullptr), "pipeline_run_region");
+    check(ipk_stream_sync(nullptr), "sync");
+    last_region_windowed = win != 0;
+    return o;
+  }
+  bool last_region_windowed = false;
   // ophashes of pipeline.rs:342-361
   std::vector<std::array<uint8_t, 32>> hashes(int out_type = IPK_OUT_F32) const {
     ipk_pipeline_desc d = desc(); uint8_t raw[256];
