@@ -1265,6 +1265,39 @@ int ipk_raster_to_srgb(const void *src, int src_type, size_t width, size_t heigh
   return IPK_OK;
 }
 
+// ipk_raw_to_srgb with scaling::transform_buffer (src/scaling.rs:51-130) between demosaic::full and OpToLab, the corner points being the three
+// OpRotateCrop::run computes (src/ops/rotatecrop.rs:39-64): one launch (k_fused_resample).  Arguments as for ipk_transform_buffer_f32.
+int ipk_raw_to_srgb_resampled(const ipk_fused_params *p, const void *src, int64_t tlx, int64_t tly, int64_t trx, int64_t try_,
+                              int64_t blx, int64_t bly, size_t nwidth, size_t nheight, void *dst, void *stream) {
+  REQUIRE_INIT();
+  if (!p || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
+  IPK_FOLD_CFA(ipk_fused_params, p)
+  if (p->src_type != IPK_SRC_U16 && p->src_type != IPK_SRC_F32) return fail(IPK_ERR_INVALID, "the resampled fused path takes u16 or f32 CFA data");
+  if (!dims_ok(p->width, p->height) || p->owidth < p->x + p->width) return fail(IPK_ERR_INVALID, "bad geometry");
+  if (p->out_type < 0 || p->out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
+  if (p->band_out_rows != 0) return fail(IPK_ERR_INVALID, "the resampled fused path takes whole frames, not bands");
+  ipk::Cfa cfa; DevCfa dev;
+  { int rc = get_cfa(p->cfa, cfa, dev); if (rc) return rc; }
+  if (!cfa.three_colour()) return fail(IPK_ERR_UNSUPPORTED, "CFA \"%s\" has a fourth colour; run the staged ops", p->cfa);
+  ipk::ResamplePlan plan;
+  if (!ipk::resample_plan(p->width, p->height, tlx, tly, trx, try_, blx, bly, nwidth, nheight, plan))
+    return fail(IPK_ERR_UNSUPPORTED, "not a transform the resampled fused path takes (output sides >= 2, finite skips whose magnitudes sum to less than 2 per axis, sides below 2^24); run the staged ops");
+  PointwisePrep pp;
+  { int rc = pp.prepare(0, p->wb_coeffs, p->cam_to_xyz_normalized, p->exposure, p->points, p->npoints, p->linear); if (rc) return rc; }
+  const size_t esz = p->src_type == IPK_SRC_U16 ? 2 : 4;
+  pp.f.src = static_cast<const char *>(src) + (p->y * p->owidth + p->x) * esz;      // the cropped frame's first sample
+  pp.f.dst = dst;
+  pp.f.src_is_u16 = p->src_type == IPK_SRC_U16;
+  pp.f.width = p->width; pp.f.height = p->height; pp.f.owidth = p->owidth;
+  pp.f.black0 = p->black0; pp.f.white0 = p->white0;
+  pp.f.exact_norm = validate_cdiv_for_range(p->black0, p->white0 - p->black0, pp.f.src_is_u16) ? 0 : 1;
+  pp.f.out_type = p->out_type;
+  if (ipk::launch_fused_resample(pp.f, plan, nwidth, nheight, dev.lookups, S(stream)) != 0)
+    return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
+  HIPCHK(hipGetLastError());
+  return IPK_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // self-test hooks
 // ------------------------------------------------------------------------------------------
@@ -1517,6 +1550,7 @@ struct Negotiated {
 int negotiate(const ipk_pipeline_desc *d, int out_type, Negotiated &n) {
   if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
+  if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
   // one negotiation: the sizes and the rotatecrop state both come from pipeline_sizes_impl's folds (the reverse fold is seeded
   // with scaling_size of the forward result, pipeline.rs:328-335 -- not with the size run() produces)
   int rc = pipeline_sizes_impl(d, &n.dw, &n.dh, &n.fw, &n.fh, &n.rc); if (rc) return rc;
@@ -1540,11 +1574,7 @@ size_t out_elem_size(int t) { return t == IPK_OUT_F32 ? 4 : t == IPK_OUT_U8 ? 1 
 
 // ---- fused raw path: legal when every op between gofloat and gamma is point-wise or demosaic::full.  Does this descriptor run gofloat..gamma
 // as the one fused raw->sRGB launch?  Then fp holds its parameters.  OpTransform does not enter: ipk_pipeline_run folds any orientation in ----
-bool fused_raw_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp) {
-  ipk::Cfa cfa; int xo, yo;
-  if (!(d->allow_fused && n.cfa_branch && d->cpp == 1 && n.rc.noop() && n.scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) &&
-        (cfa.bayer_phase(xo, yo) || cfa.three_colour())))
-    return false;
+void fused_params_of(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp) {
   std::memset(&fp, 0, sizeof(fp));
   fp.struct_size = (uint32_t)sizeof(fp);
   fp.src_type = d->src_type; fp.owidth = d->width; fp.x = n.r.x; fp.y = n.r.y; fp.width = n.r.width; fp.height = n.r.height;
@@ -1554,6 +1584,28 @@ bool fused_raw_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_ty
   std::memcpy(fp.cam_to_xyz_normalized, d->cam_to_xyz_normalized, sizeof(fp.cam_to_xyz_normalized));
   fp.exposure = d->exposure; fp.npoints = d->npoints; std::memcpy(fp.points, d->points, sizeof(fp.points));
   fp.linear = n.linear; fp.out_type = out_type; fp.schedule = d->schedule;
+}
+bool fused_raw_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp) {
+  ipk::Cfa cfa; int xo, yo;
+  if (!(d->allow_fused && n.cfa_branch && d->cpp == 1 && n.rc.noop() && n.scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) &&
+        (cfa.bayer_phase(xo, yo) || cfa.three_colour())))
+    return false;
+  fused_params_of(d, n, out_type, fp);
+  return true;
+}
+// ---- the same with an ACTIVE OpRotateCrop between demosaic::full and OpToLab (ipk_raw_to_srgb_resampled): opted into with fuse_rotatecrop.  Then fp
+// holds the launch's parameters and rcp what OpRotateCrop::run hands to transform_buffer.  corners() fails for crops outside the image, where the op
+// returns its input -- and the frame stays staged, as it does when OpDemosaic scales (with an angle the reverse size fold often negotiates a demosaic
+// size one pixel short of the source) or the transform is not one the launch admits (resample_plan) ----
+struct RotateCropPoints { int64_t pts[6]; size_t nw, nh; };
+bool fused_resample_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp, RotateCropPoints &rcp) {
+  ipk::Cfa cfa; ipk::ResamplePlan plan;
+  if (!(d->fuse_rotatecrop == 1 && d->allow_fused && n.cfa_branch && d->cpp == 1 && !n.rc.noop() && n.scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) &&
+        cfa.three_colour()))
+    return false;
+  if (!rotatecrop_of(d).corners(n.r.width, n.r.height, rcp.pts, rcp.nw, rcp.nh)) return false;
+  if (!ipk::resample_plan(n.r.width, n.r.height, rcp.pts[0], rcp.pts[1], rcp.pts[2], rcp.pts[3], rcp.pts[4], rcp.pts[5], rcp.nw, rcp.nh, plan)) return false;
+  fused_params_of(d, n, out_type, fp);
   return true;
 }
 // ---- raster sources, same idea: run_other + tolab..gamma (+ quantisation) as one launch when OpDemosaic (a 4-channel buffer at
@@ -1605,6 +1657,46 @@ int run_fused_raw(const ipk_pipeline_desc *d, const Negotiated &n, const ipk_fus
     if (rc != IPK_ERR_UNSUPPORTED) return rc;
   }
   return fused_then_orient(d, n, &fp, fp.out_type, src, dst, stream);
+}
+// fused_resample_route's run: the one launch writes the image of the output type into dst, or into a scratch image that OpTransform's permutation
+// moves into dst (as fused_then_orient does)
+// Crop-only shortcut.  Without an angle the corner points are integers, both skips are exactly 1.0 and the cross terms 0, so the
+// window of output pixel (row, col) is the 2x2 block at (x + col, y + row) with the weights {1, 0, 0, 0}: the result is the demosaiced pixel
+// itself PROVIDED its three zero-weight neighbours are finite (0 * inf is NaN) and it is not -0.0 ((-0) + (+0) is +0).  For a u16 source whose
+// every normalised sample is zero or ordinary (gen_levels_ok_u16 walks all 65 536) both hold: the samples are finite and never -0.0, and a
+// demosaic output is a sum that starts at +0.0 over a positive count.  The launch is then the fused kernel's window form over the rectangle,
+// exactly as ipk_pipeline_run_region calls it.  f32 sources can hold -inf and always take k_fused_resample.
+bool crop_only_shortcut(const ipk_fused_params &fp, const RotateCropPoints &r) {
+  const float range = fp.white0 - fp.black0;
+  const size_t lim = size_t(1) << 22;                          // x + col + 0.5 is exact in f32 far beyond any frame this holds for
+  if (fp.src_type != IPK_SRC_U16 || !(range > 0.0f) || !std::isfinite(fp.black0) || !std::isfinite(range) || !gen_levels_ok_u16(fp.black0, range)) return false;
+  if (fp.width >= lim || fp.height >= lim || r.pts[0] < 0 || r.pts[1] < 0) return false;
+  const int64_t x = r.pts[0], y = r.pts[1];
+  return r.pts[2] == x + (int64_t)r.nw - 1 && r.pts[3] == y && r.pts[4] == x && r.pts[5] == y + (int64_t)r.nh - 1 &&    // skips 1, 0, 0, 1
+         (size_t)x + r.nw <= fp.width && (size_t)y + r.nh <= fp.height;                                                 // the rectangle lies inside the frame
+}
+int run_fused_resample(const Negotiated &n, const ipk_fused_params &fp, const RotateCropPoints &rcp, const void *src, void *dst, StageTimer &tm, void *stream) {
+  tm.rest = "fused gofloat+demosaic+rotatecrop+to_lab+basecurve+from_lab+gamma(+transform)";
+  auto launch = [&](void *o) {
+    if (crop_only_shortcut(fp, rcp)) {
+      ipk_fused_params b = fp;                                 // the rows as a band of the whole cropped frame, the columns as the launch's window
+      b.band_src_row0 = 0; b.band_src_rows = fp.height; b.band_out_row0 = (size_t)rcp.pts[1]; b.band_out_rows = rcp.nh;
+      const void *top = static_cast<const char *>(src) + fp.y * fp.owidth * 2;
+      return fused_impl(&b, top, o, stream, 0, 0, nullptr, nullptr, false, (size_t)rcp.pts[0], (size_t)rcp.pts[0] + rcp.nw);
+    }
+    return ipk_raw_to_srgb_resampled(&fp, src, rcp.pts[0], rcp.pts[1], rcp.pts[2], rcp.pts[3], rcp.pts[4], rcp.pts[5], rcp.nw, rcp.nh, o, stream);
+  };
+  if (n.transform_noop) {
+    int rc = check_produced(n, rcp.nw, rcp.nh); if (rc) return rc;
+    return launch(dst);
+  }
+  Scratch sc(S(stream));
+  void *tmp = nullptr;
+  size_t ow = 0, oh = 0;
+  int rc = sc.get(rcp.nw * rcp.nh * 3 * out_elem_size(fp.out_type), &tmp); if (rc) return rc;
+  rc = launch(tmp); if (rc < 0) return rc;
+  rc = orient(tmp, rcp.nw, rcp.nh, n.orientation, fp.out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
+  return check_produced(n, ow, oh);
 }
 
 // ---- OpGoFloat (gofloat.rs:95-130): what it produces for a descriptor, and the launch that writes it ----
@@ -1781,6 +1873,7 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
   if (!d || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {
     if (used_fused) *used_fused = 0;
     if (d->width < 1 || d->height < 1) return fail(IPK_ERR_INVALID, "empty source");
@@ -1790,9 +1883,11 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
   Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
   StageTimer tm(S(stream));
   if (used_fused) *used_fused = 0;
-  ipk_fused_params fp;
+  ipk_fused_params fp; RotateCropPoints rcp;
   if (fused_raw_route(d, n, out_type, fp)) {
     rc = run_fused_raw(d, n, fp, src, dst, tm, stream);
+  } else if (fused_resample_route(d, n, out_type, fp, rcp)) {
+    rc = run_fused_resample(n, fp, rcp, src, dst, tm, stream);
   } else if (fused_raster_route(d, n)) {
     tm.rest = "fused gofloat+to_lab+basecurve+from_lab+gamma(+transform)";
     rc = fused_then_orient(d, n, nullptr, out_type, src, dst, stream);
@@ -1801,6 +1896,15 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
   }
   if (rc == IPK_OK && used_fused) *used_fused = 1;
   return rc;
+}
+// which route an active rotatecrop takes, for callers and CPU tests: the drivers' own predicate on the drivers' own negotiation (no GPU)
+int ipk_pipeline_fuses_rotatecrop(const ipk_pipeline_desc *d, int out_type) {
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return 0;
+  ipk_fused_params fp; RotateCropPoints rcp;
+  return fused_resample_route(d, n, out_type, fp, rcp) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1984,6 +2088,7 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   if (cache->owner != ipk_ctx_current()) return fail(IPK_ERR_INVALID, "the cache belongs to another context (its buffers live on that context's device)");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
   if (d->npoints < 0 || d->npoints > 64) return fail(IPK_ERR_INVALID, "npoints out of range");
+  if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // returns before the cache is consulted (pipeline.rs:381-402)
     if (ops_run) *ops_run = 0;
     if (used_fused) *used_fused = 0;
@@ -2006,6 +2111,15 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   if (startpos == 0 && fused_raw_route(d, n, IPK_OUT_F32, fp)) {          // any orientation: the fused route folds OpTransform in
     CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
     { StageTimer tm(st); rc = run_fused_raw(d, n, fp, src, o->p, tm, stream); }
+    if (rc < 0) return rc;
+    cache->lru.put(hs[7], o, o->bytes());
+    buf = o; startpos = 8; mask = 0xFF;
+    if (used_fused) *used_fused = rc == IPK_OK;
+  }
+  RotateCropPoints rcp;
+  if (startpos == 0 && fused_resample_route(d, n, IPK_OUT_F32, fp, rcp)) {   // the same with an active rotatecrop inside the launch
+    CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
+    { StageTimer tm(st); rc = run_fused_resample(n, fp, rcp, src, o->p, tm, stream); }
     if (rc < 0) return rc;
     cache->lru.put(hs[7], o, o->bytes());
     buf = o; startpos = 8; mask = 0xFF;

@@ -503,4 +503,44 @@ struct RotateCrop {
   }
 };
 
+// ---- the one-launch route through an active OpRotateCrop (k_fused_resample, ipk_raw_to_srgb_resampled) ----
+// A block of that kernel owns a tile of the OUTPUT image and keeps the tile's source footprint -- the bounding box of its pixels' windows
+// (src/scaling.rs:84-87) -- in LDS: the normalised mosaic with demosaic::full's one-pixel halo, then the demosaiced box as RGB.
+constexpr uint32_t kResampleRgbCap = 3456;      // box pixels a tile may hold (three floats each)
+constexpr uint32_t kResampleMosCap = 4096;      // mosaic samples of the box and its halo (four per thread of the block)
+struct ResamplePlan {
+  float tlx, tly, skip_x_x, skip_x_y, skip_y_x, skip_y_y;   // scaling.rs:68-71
+  uint32_t tile_w, tile_h;                                   // output tile: tile_w even, tile_w * tile_h <= 2048 (two pixels per lane)
+};
+// Admission (everything else runs the staged ops): a transform whose windows are at most 3x3 -- |skip_x_x| + |skip_y_x| < 2 and |skip_x_y| + |skip_y_y| < 2,
+// finite -- on frames with sides below 2^24, and an output tile whose box fits the LDS above.  The box bound: along one axis the tile's windows lie between
+// the floors of two values of the same f32 expression that are tile_w * |skip_x| + tile_h * |skip_y| apart, hence cover at most floor(span) + 2 integers;
+// the expressions carry at most four roundings of half an ulp each, below 2^-6 in all while every term stays under 2^17 (sides below 2^16) and below 8
+// for the largest admitted frames, so `slop` columns are added.  The kernel clips every window to the box it computed, so a bound that were ever too
+// small could cost correctness, never memory safety.
+inline bool resample_plan(size_t width, size_t height, int64_t tlx, int64_t tly, int64_t trx, int64_t try_, int64_t blx, int64_t bly,
+                          size_t nwidth, size_t nheight, ResamplePlan &p) {
+  const size_t lim = size_t(1) << 24;
+  if (nwidth < 2 || nheight < 2 || width < 1 || height < 1 || width >= lim || height >= lim || nwidth >= lim || nheight >= lim) return false;
+  if ((uint64_t)nwidth * nheight >= (uint64_t(1) << 36)) return false;      // the kernel counts tiles (256 pixels or more each) in 32 bits
+  p.tlx = (float)tlx; p.tly = (float)tly;
+  p.skip_x_x = ((float)trx - (float)tlx) / ((float)(nwidth - 1));
+  p.skip_x_y = ((float)try_ - (float)tly) / ((float)(nwidth - 1));
+  p.skip_y_x = ((float)blx - (float)tlx) / ((float)(nheight - 1));
+  p.skip_y_y = ((float)bly - (float)tly) / ((float)(nheight - 1));
+  if (!std::isfinite(p.tlx) || !std::isfinite(p.tly) || !std::isfinite(p.skip_x_x) || !std::isfinite(p.skip_x_y) || !std::isfinite(p.skip_y_x) ||
+      !std::isfinite(p.skip_y_y))
+    return false;
+  const double ax = std::fabs((double)p.skip_x_x), bx = std::fabs((double)p.skip_y_x), ay = std::fabs((double)p.skip_x_y), by = std::fabs((double)p.skip_y_y);
+  if (!(ax + bx < 2.0) || !(ay + by < 2.0)) return false;
+  const bool small = width < 65536 && height < 65536 && nwidth < 65536 && nheight < 65536;
+  const double slop = small ? 1.0 / 64.0 : 8.0;
+  static const uint32_t tiles[][2] = {{64, 32}, {48, 40}, {40, 40}, {32, 32}, {24, 24}, {16, 16}};
+  for (const auto &t : tiles) {
+    const uint64_t bw = (uint64_t)std::floor(t[0] * ax + t[1] * bx + slop) + 3, bh = (uint64_t)std::floor(t[0] * ay + t[1] * by + slop) + 3;
+    if (bw * bh <= kResampleRgbCap && (bw + 2) * (bh + 2) <= kResampleMosCap) { p.tile_w = t[0]; p.tile_h = t[1]; return true; }
+  }
+  return false;
+}
+
 }  // namespace ipk

@@ -3304,6 +3304,274 @@ int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const
 }
 
 // ------------------------------------------------------------------------------------------
+// A CFA mosaic through an ACTIVE OpRotateCrop in one pass: OpGoFloat (gofloat.rs:122-130) + demosaic::full (demosaic.rs:93-116) +
+// transform_buffer with rotatecrop's corner points (scaling.rs:51-130, rotatecrop.rs:39-64) + OpToLab..OpGamma (+ output8bit / output16bit).
+// The normalised mosaic, the demosaiced 4-channel frame and the resampled 4-channel frame never exist in memory.
+//
+// One persistent 1024-thread block per CU (the tables fill most of its LDS) walks tiles of the OUTPUT image.  Per tile:
+//   box      the bounding box of the tile's windows.  from_x / to_x / from_y / to_y (scaling.rs:84-87) are floors of f32 expressions that are monotone
+//            in row and in col, so their extremes sit at the tile's four corner pixels: the box comes from those four, by the same expressions
+//   stage 1  the box plus demosaic::full's one-pixel halo (clipped to the cropped frame), normalised exactly as k_gofloat_cfa does, into LDS
+//   stage 2  demosaic::full of every box pixel into LDS as R, G, B: the reference's tap order, out-of-frame taps skipped, sums / counts as true
+//            divisions, colours from the 48x48 table on absolute cropped-frame coordinates (any three-colour filter; E is +0.0 for those)
+//   stage 3  two neighbouring output pixels per lane: the window walk of k_transform_buffer's 4-channel branch over the LDS box (y outer, x inner; taps
+//            outside the window are not accumulated at all; an empty window gives 0.0), then the point-wise chain as pointwise_chain_body runs it
+//            (pointwise4_fast, literal redo behind a wave-uniform branch), the quantiser, and lane-contiguous stores
+// The three colour components share their weights (the reference keeps one count per component, all fed the same factors); E is 0 * factor summed over
+// a positive count, or the zero fill: +0.0 either way, which is what the fast point-wise form assumes.
+// The NEXT tile's mosaic loads are issued in front of stage 3 and land in LDS behind it (the mosaic buffer is idle meanwhile), so the memory round trip
+// hides behind the arithmetic: two barriers per tile.
+// ------------------------------------------------------------------------------------------
+struct ResampleArgs {
+  uint32_t nw, nh, tw, th, tiles_x, n_tiles;
+  float tlx, tly, skip_x_x, skip_x_y, skip_y_x, skip_y_y, inv_skip_x_x, inv_skip_y_y;
+  int fast_x, fast_y;
+  const uint32_t *lookups;
+};
+struct RsWin { uint32_t fx, tx, fy, ty; };
+__device__ __forceinline__ RsWin rs_window(const ResampleArgs &t, uint32_t W, uint32_t H, uint32_t row, uint32_t col) {
+  // scaling.rs:77-87, expression for expression as k_transform_buffer writes them
+  const float from_x_r = t.tlx + t.skip_y_x * (float)row;
+  const float to_x_r = t.tlx + t.skip_y_x * (float)(row + 1);
+  const float from_y_r = t.tly + t.skip_y_y * (float)row;
+  const float to_y_r = t.tly + t.skip_y_y * (float)(row + 1);
+  RsWin w;
+  w.fx = min(W - 1, f32_as_u32_sat(floorf(from_x_r + (t.skip_x_x * (float)col))));
+  w.tx = min(W - 1, f32_as_u32_sat(floorf(to_x_r + (t.skip_x_x * (float)(col + 1)))));
+  w.fy = min(H - 1, f32_as_u32_sat(floorf(from_y_r + (t.skip_x_y * (float)col))));
+  w.ty = min(H - 1, f32_as_u32_sat(floorf(to_y_r + (t.skip_x_y * (float)(col + 1)))));
+  return w;
+}
+// a tile's box [x0, x0 + w) x [y0, y0 + h) and its mosaic region (the box and its halo inside the frame), cropped-frame coordinates; w == 0: no window has a tap
+struct RsBox { uint32_t x0, y0, w, h, mx0, my0, mw, mh; };
+__device__ __forceinline__ RsBox rs_box(const ResampleArgs &t, uint32_t W, uint32_t H, uint32_t tile) {
+  const uint32_t tyi = tile / t.tiles_x, txi = tile - tyi * t.tiles_x;
+  const uint32_t r0 = tyi * t.th, c0 = txi * t.tw, r1 = min(r0 + t.th, t.nh) - 1u, c1 = min(c0 + t.tw, t.nw) - 1u;
+  const RsWin a = rs_window(t, W, H, r0, c0), b = rs_window(t, W, H, r0, c1), c = rs_window(t, W, H, r1, c0), d = rs_window(t, W, H, r1, c1);
+  const uint32_t x0 = min(min(a.fx, b.fx), min(c.fx, d.fx)), x1 = max(max(a.tx, b.tx), max(c.tx, d.tx));
+  const uint32_t y0 = min(min(a.fy, b.fy), min(c.fy, d.fy)), y1 = max(max(a.ty, b.ty), max(c.ty, d.ty));
+  RsBox o;
+  o.x0 = x0; o.y0 = y0;
+  o.w = x1 >= x0 ? x1 - x0 + 1u : 0u; o.h = y1 >= y0 ? y1 - y0 + 1u : 0u;
+  if (o.w == 0u || o.h == 0u) { o.w = 0u; o.h = 0u; }
+  // the host sized the tile so that this never applies (resample_plan); the LDS buffers are safe whatever it computed
+  if (IPK_RARE(o.w > 1024u || o.h > kResampleRgbCap || o.w * o.h > kResampleRgbCap || (o.w + 2u) * (o.h + 2u) > kResampleMosCap)) {
+    o.w = min(o.w, 1024u);
+    o.h = min(min(o.h, kResampleRgbCap / o.w), kResampleMosCap / (o.w + 2u) - 2u);
+  }
+  o.mx0 = o.x0 > 0u ? o.x0 - 1u : 0u; o.my0 = o.y0 > 0u ? o.y0 - 1u : 0u;
+  o.mw = o.w ? min(o.x0 + o.w, W - 1u) - o.mx0 + 1u : 0u;
+  o.mh = o.w ? min(o.y0 + o.h, H - 1u) - o.my0 + 1u : 0u;
+  return o;
+}
+// i / d and i % d for i, d < 2^16 through one multiplication: floor(i * ceil(2^32 / d) / 2^32) == i / d there
+struct RsDiv { uint32_t d, magic; };
+__device__ __forceinline__ RsDiv rs_div_make(uint32_t d) { RsDiv r; r.d = d; r.magic = d > 1u ? 0xFFFFFFFFu / d + 1u : 0u; return r; }
+__device__ __forceinline__ uint32_t rs_div(const RsDiv &r, uint32_t i) { return r.d > 1u ? __umulhi(i, r.magic) : i; }
+
+constexpr int kRsMosPerThread = (int)(kResampleMosCap / 1024u);
+template <typename SrcT>
+__device__ __forceinline__ void rs_load_mosaic(const FusedArgs &a, const RsBox &b, float v[kRsMosPerThread]) {
+  const SrcT *src = reinterpret_cast<const SrcT *>(a.src);
+  const RsDiv dv = rs_div_make(b.mw);
+  const uint32_t n = b.mw * b.mh;
+  #pragma unroll
+  for (int k = 0; k < kRsMosPerThread; ++k) {
+    const uint32_t i = threadIdx.x + 1024u * k;
+    v[k] = 0.0f;
+    if (i < n) { const uint32_t r = rs_div(dv, i), c = i - r * b.mw; v[k] = (float)src[(size_t)(b.my0 + r) * a.owidth + b.mx0 + c]; }
+  }
+}
+template <typename SrcT>
+__device__ __forceinline__ void rs_store_mosaic(const FusedArgs &a, const RsBox &b, const float v[kRsMosPerThread], float *__restrict__ s_mos) {
+  const uint32_t n = b.mw * b.mh;
+  #pragma unroll
+  for (int k = 0; k < kRsMosPerThread; ++k) {
+    const uint32_t i = threadIdx.x + 1024u * k;
+    if (i < n) {
+      // gofloat.rs:126 / :162 as k_gofloat_cfa computes it: the host-validated multiply-fma division inside its proven zone, the IEEE division otherwise
+      // (u16 dividends were all walked by the host; f32 ones are tested here)
+      const float d = v[k] - a.min0;
+      const bool ieee = a.exact_norm != 0 || (!std::is_same<SrcT, uint16_t>::value && cdiv_guard(d));
+      s_mos[i] = rs_min(ieee ? d / a.range0 : cdiv_fast(d, a.range0, a.inv_range0), 1.0f);
+    }
+  }
+}
+
+template <typename SrcT, int OUT>
+__global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleArgs t) {
+  __shared__ __attribute__((aligned(16))) LabTab s_lab[kLutPairs + 4];
+  __shared__ __attribute__((aligned(16))) float s_gam[kLutPairs + 4];
+  __shared__ __attribute__((aligned(16))) float s_knots[kKnotFloats];
+  __shared__ __attribute__((aligned(16))) float s_grid[kGridFloats];
+  __shared__ float s_par[32];
+  __shared__ __attribute__((aligned(16))) float s_mos[kResampleMosCap];
+  __shared__ __attribute__((aligned(16))) float s_rgb[3 * kResampleRgbCap];
+  stage_table_direct(s_lab, a.lab_table, a.lab_pairs);
+  stage_table_direct(s_gam, a.gam_table, a.gam_pairs);
+  if (threadIdx.x < 4) s_par[threadIdx.x] = a.tolab.mul[threadIdx.x];
+  else if (threadIdx.x < 16) s_par[threadIdx.x] = a.tolab.cm[threadIdx.x - 4];
+  else if (threadIdx.x < 25) s_par[threadIdx.x] = a.rgbm.m[threadIdx.x - 16];
+  if (threadIdx.x < kSplineMaxKnots) fill_knots(s_knots, a.spline, (int)threadIdx.x);
+  if (a.spline.grid_ok) fill_grid(s_grid, a.spline, (int)threadIdx.x);
+
+  uint32_t tile = blockIdx.x;                                           // the grid never exceeds the tile count
+  RsBox box = rs_box(t, a.W, a.H, tile);
+  {
+    float mv[kRsMosPerThread];
+    rs_load_mosaic<SrcT>(a, box, mv);
+    rs_store_mosaic<SrcT>(a, box, mv, s_mos);
+  }
+  sync_after_lds_direct();                                              // the tables and the first tile's mosaic
+  // the lane's two pixels inside a tile: neighbours in one tile row (tile_w is even)
+  const uint32_t p0 = 2u * threadIdx.x;
+  const uint32_t trow = p0 / t.tw, tcol = p0 - trow * t.tw;
+  for (;;) {
+    // ---- stage 2: demosaic::full over the box ----
+    {
+      const RsDiv dv = rs_div_make(box.w);
+      const uint32_t n = box.w * box.h;
+      for (uint32_t i = threadIdx.x; i < n; i += 1024u) {
+        const uint32_t r = rs_div(dv, i), c = i - r * box.w;
+        const uint32_t row = box.y0 + r, col = box.x0 + c;
+        const uint32_t colors = t.lookups[(row % 48u) * 48u + (col % 48u)];   // demosaic.rs:95
+        const float *m = s_mos + (row - box.my0) * box.mw + (col - box.mx0);
+        // DemosaicAcc's sums and counts (demosaic.rs:105-106, :110-114) for the three colours such a filter has, as selects: a tap outside the frame or
+        // of the discard bucket leaves every sum and count as it is (its load is pointed at the centre sample, which always exists)
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
+        #pragma unroll
+        for (int k = 0; k < 9; ++k) {                                     // tap order of demosaic.rs:70-74
+          const int dy = k / 3 - 1, dx = k % 3 - 1;
+          const bool in = (dy >= 0 || row > 0u) && (dy <= 0 || row + 1u < a.H) && (dx >= 0 || col > 0u) && (dx <= 0 || col + 1u < a.W);
+          const uint32_t cc = in ? (colors >> (3 * k)) & 7u : 4u;
+          const float v = m[in ? dy * (int)box.mw + dx : 0];
+          s0 = cc == 0u ? s0 + v : s0; n0 = cc == 0u ? n0 + 1.0f : n0;
+          s1 = cc == 1u ? s1 + v : s1; n1 = cc == 1u ? n1 + 1.0f : n1;
+          s2 = cc == 2u ? s2 + v : s2; n2 = cc == 2u ? n2 + 1.0f : n2;
+        }
+        s_rgb[3u * i] = n0 > 0.0f ? s0 / n0 : 0.0f; s_rgb[3u * i + 1u] = n1 > 0.0f ? s1 / n1 : 0.0f; s_rgb[3u * i + 2u] = n2 > 0.0f ? s2 / n2 : 0.0f;
+      }
+    }
+    __syncthreads();
+    // ---- the next tile's mosaic: issued here, written to LDS behind stage 3 ----
+    const uint32_t next = tile + gridDim.x;
+    const bool more = next < t.n_tiles;
+    RsBox nbox = box;
+    float mv[kRsMosPerThread];
+    if (more) { nbox = rs_box(t, a.W, a.H, next); rs_load_mosaic<SrcT>(a, nbox, mv); }
+    // ---- stage 3: resample, chain, store ----
+    {
+      const uint32_t tyi = tile / t.tiles_x, txi = tile - tyi * t.tiles_x;
+      const uint32_t row = tyi * t.th + trow, col0 = txi * t.tw + tcol;
+      const bool row_ok = trow < t.th && row < t.nh;
+      const uint32_t bx1 = box.x0 + box.w, by1 = box.y0 + box.h;        // one past the box
+      // per-row values (scaling.rs:79-82)
+      const float center_x_r = t.tlx + (t.skip_y_x * (float)row) + (t.skip_y_x / 2.0f) - 0.5f;
+      const float center_y_r = t.tly + (t.skip_y_y * (float)row) + (t.skip_y_y / 2.0f) - 0.5f;
+      float4 px[2];
+      bool ok[2];
+      #pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const uint32_t col = col0 + (uint32_t)j;
+        ok[j] = row_ok && col < t.nw;
+        const RsWin w = rs_window(t, a.W, a.H, row, col);
+        // the window lies inside the box by construction; the clip keeps the LDS reads in bounds even where the box had to be cut (rs_box).
+        // x_end / y_end: one past the last tap (window ends are frame coordinates, below 2^24); a lane without a pixel walks nothing
+        const uint32_t fx = max(w.fx, box.x0), fy = max(w.fy, box.y0);
+        const uint32_t x_end = ok[j] ? min(w.tx + 1u, bx1) : 0u, y_end = ok[j] ? min(w.ty + 1u, by1) : 0u;
+        const float center_x = center_x_r + (t.skip_x_x * (float)col) + (t.skip_x_x / 2.0f);
+        const float center_y = center_y_r + (t.skip_x_y * (float)col) + (t.skip_x_y / 2.0f);
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, n = 0.0f;
+        for (uint32_t y = fy; y < y_end; ++y) {
+          const float dyv = (float)y - center_y;
+          const float delta_y = tb_div(dyv, t.skip_y_y, t.inv_skip_y_y, t.fast_y);
+          const float dy2 = delta_y * delta_y;
+          const uint32_t rowi = (y - box.y0) * box.w;
+          for (uint32_t x = fx; x < x_end; ++x) {
+            const float dxv = (float)x - center_x;
+            const float delta_x = tb_div(dxv, t.skip_x_x, t.inv_skip_x_x, t.fast_x);
+            float factor = 1.0f - (delta_x * delta_x) - dy2;              // scaling.rs:106
+            factor = (factor < 0.0f) ? 0.0f : factor;
+            const float *p = s_rgb + 3u * (rowi + (x - box.x0));
+            s0 += p[0] * factor; s1 += p[1] * factor; s2 += p[2] * factor; n += factor;
+          }
+        }
+        // scaling.rs:122-126: components without weight keep the zero fill
+        const bool has = n > 0.0f;
+        px[j] = make_float4(has ? s0 / n : 0.0f, has ? s1 / n : 0.0f, has ? s2 / n : 0.0f, 0.0f);
+      }
+      PixOut o[2];
+      bool bad = a.fast_ok == 0;
+      if (a.fast_ok) bad |= pointwise4_fast<true, false, 1>(a, s_par, s_lab, s_gam, s_knots, px, o, a.has_curve != 0, a.linear != 0, 0, nullptr, s_grid);
+      if (__builtin_amdgcn_ballot_w64(bad) != 0) {
+        #pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const PixOut e = pointwise_exact(a, s_lab, s_gam, s_knots, px[j]);
+          if (bad) o[j] = e;
+        }
+      }
+      // the wave's pixels are neighbours in the output row: each lane's 24 / 6 / 12 bytes continue its neighbour's
+      const size_t e = ((size_t)row * t.nw + col0) * 3u;
+      if (OUT == 0) {
+        float *g = reinterpret_cast<float *>(a.dst) + e;
+        if (ok[1]) {
+          typedef float f2a __attribute__((ext_vector_type(2), aligned(4)));
+          f2a v0, v1, v2; v0.x = o[0].r; v0.y = o[0].g; v1.x = o[0].b; v1.y = o[1].r; v2.x = o[1].g; v2.y = o[1].b;
+          f2a *gv = reinterpret_cast<f2a *>(g);
+          __builtin_nontemporal_store(v0, gv); __builtin_nontemporal_store(v1, gv + 1); __builtin_nontemporal_store(v2, gv + 2);
+        } else if (ok[0]) { st_stream(g, o[0].r); st_stream(g + 1, o[0].g); st_stream(g + 2, o[0].b); }
+      } else if (OUT == 1) {
+        uint8_t *g = reinterpret_cast<uint8_t *>(a.dst) + e;
+        const uint32_t lo = output8bit_x4(o[0].r, o[0].g, o[0].b, o[1].r);
+        if (ok[1]) {
+          typedef uint32_t u32a __attribute__((aligned(1)));
+          typedef uint16_t u16a __attribute__((aligned(1)));
+          __builtin_nontemporal_store(lo, reinterpret_cast<u32a *>(g));
+          __builtin_nontemporal_store((uint16_t)((uint32_t)output8bit(o[1].g) | ((uint32_t)output8bit(o[1].b) << 8)), reinterpret_cast<u16a *>(g + 4));
+        } else if (ok[0]) { g[0] = (uint8_t)lo; g[1] = (uint8_t)(lo >> 8); g[2] = (uint8_t)(lo >> 16); }
+      } else {
+        uint16_t *g = reinterpret_cast<uint16_t *>(a.dst) + e;
+        const uint32_t w0 = output16bit_x2(o[0].r, o[0].g), w1 = output16bit_x2(o[0].b, o[1].r), w2 = output16bit_x2(o[1].g, o[1].b);
+        if (ok[1]) {
+          typedef uint32_t u32h __attribute__((aligned(2)));
+          u32h *gv = reinterpret_cast<u32h *>(g);
+          __builtin_nontemporal_store(w0, gv); __builtin_nontemporal_store(w1, gv + 1); __builtin_nontemporal_store(w2, gv + 2);
+        } else if (ok[0]) { g[0] = (uint16_t)w0; g[1] = (uint16_t)(w0 >> 16); g[2] = (uint16_t)w1; }
+      }
+    }
+    if (!more) break;
+    rs_store_mosaic<SrcT>(a, nbox, mv, s_mos);
+    __syncthreads();
+    box = nbox; tile = next;
+  }
+}
+
+int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s) {
+  FusedArgs a = chain_args(f);
+  a.W = (uint32_t)f.width; a.H = (uint32_t)f.height; a.owidth = f.owidth;
+  a.min0 = f.black0; a.range0 = f.white0 - f.black0;                       // gofloat.rs:86-89
+  a.inv_range0 = 1.0f / a.range0;
+  a.exact_norm = f.exact_norm;
+  ResampleArgs t;
+  t.nw = (uint32_t)nwidth; t.nh = (uint32_t)nheight; t.tw = plan.tile_w; t.th = plan.tile_h;
+  t.tiles_x = (t.nw + t.tw - 1u) / t.tw;
+  const uint64_t tiles = (uint64_t)t.tiles_x * ((t.nh + t.th - 1u) / t.th);   // below 2^24 / 16 squared
+  t.n_tiles = (uint32_t)tiles;
+  t.tlx = plan.tlx; t.tly = plan.tly;
+  t.skip_x_x = plan.skip_x_x; t.skip_x_y = plan.skip_x_y; t.skip_y_x = plan.skip_y_x; t.skip_y_y = plan.skip_y_y;
+  t.inv_skip_x_x = 1.0f / t.skip_x_x; t.inv_skip_y_y = 1.0f / t.skip_y_y;
+  t.fast_x = cdiv_host_ok(t.skip_x_x); t.fast_y = cdiv_host_ok(t.skip_y_y);
+  t.lookups = lookups_dev;
+  const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
+  const unsigned blocks = (unsigned)std::min<uint64_t>(cus, tiles);
+  #define IPK_RS_LAUNCH(T, O) hipLaunchKernelGGL((k_fused_resample<T, O>), dim3(blocks), dim3(1024), 0, s, a, t)
+  if (f.src_is_u16) { if (f.out_type == 0) IPK_RS_LAUNCH(uint16_t, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(uint16_t, 1); else IPK_RS_LAUNCH(uint16_t, 2); }
+  else { if (f.out_type == 0) IPK_RS_LAUNCH(float, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(float, 1); else IPK_RS_LAUNCH(float, 2); }
+  #undef IPK_RS_LAUNCH
+  return launch_status();
+}
+
+// ------------------------------------------------------------------------------------------
 // Self-test kernels: exhaustive on-device proofs of the arithmetic shortcuts the fused kernel uses
 // (tests/test_gpu_selftest.py).  Each compares a shortcut with the plain IEEE expression over every
 // f32 bit pattern and reports the mismatches.

@@ -96,6 +96,11 @@ struct FusedLaunch {
 };
 // returns 0, -2 when f.ori != 0 and the parameters have no rotated-space variant (nothing is launched), -4 when a launch could not be enqueued
 int launch_fused_bayer(const FusedLaunch &f, hipStream_t s);
+// gofloat + demosaic::full + transform_buffer(plan) + tolab..gamma (+ quantisation) as one launch (k_fused_resample): f.src = the cropped frame's first
+// sample (pitch f.owidth), f.width x f.height the cropped frame, f.dst = nwidth * nheight * 3 samples of f.out_type; `lookups` = the device image of
+// Cfa::demosaic_lookups of a three-colour filter.  Of f, the geometry, the levels, exact_norm and what launch_pointwise_chain reads are used.
+// returns 0, or -4 when the launch could not be enqueued
+int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s);
 // rotate_buffer's permutation on a 1-channel image through an arbitrary source pitch / window (steps in source elements)
 template <typename T>
 void launch_rotate1(const T *src, size_t owidth, size_t oheight, int64_t base_offset, int64_t x_step, int64_t y_step, T *dst, hipStream_t s);

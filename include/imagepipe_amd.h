@@ -349,6 +349,18 @@ IPK_API int ipk_raw_to_srgb_batch(const ipk_fused_params *p, const void *const *
 IPK_API int ipk_raw_to_srgb_oriented(const ipk_fused_params *p, const void *src, int orientation, void *dst,
                                      size_t *out_width, size_t *out_height, void *stream);
 
+/* ipk_raw_to_srgb with OpBuffer::transform(topleft, topright, bottomleft, nwidth, nheight) between demosaic::full and OpToLab -- what Pipeline::run
+ * computes for a CFA mosaic whose OpRotateCrop is active (src/ops/rotatecrop.rs:39-64 hands its three corner points to transform_buffer,
+ * src/scaling.rs:51-130) -- as ONE launch: the normalised mosaic, the demosaiced frame and the resampled frame never exist in memory.  The corner
+ * points mean what they mean for ipk_transform_buffer_f32 (coordinates in the p->width x p->height cropped frame; they may lie outside it, windows
+ * are clamped as the reference clamps them); dst receives nwidth * nheight * 3 samples of p->out_type, bit-identical to ipk_gofloat_cfa_* +
+ * ipk_demosaic_full + ipk_transform_buffer_f32 (4 components) + ipk_pointwise_chain(_out).  Whole frames (no band) of a three-colour filter.
+ * IPK_ERR_UNSUPPORTED (nothing written) for transforms the launch does not take: nwidth or nheight below 2, a skip that is not finite,
+ * |skip_x_x| + |skip_y_x| >= 2 or |skip_x_y| + |skip_y_y| >= 2 (windows larger than 3x3: scaling down is OpDemosaic's business), frame sides
+ * of 2^24 or more.  A zero skip is taken: its division by zero is the reference's and comes out the same. */
+IPK_API int ipk_raw_to_srgb_resampled(const ipk_fused_params *p, const void *src, int64_t tlx, int64_t tly, int64_t trx, int64_t try_,
+                                      int64_t blx, int64_t bly, size_t nwidth, size_t nheight, void *dst, void *stream);
+
 /* OpToLab::run + OpBaseCurve::run + OpFromLab::run + OpGamma::run (src/ops/colorspaces.rs:89-112, src/ops/curves.rs:33-49,
  * src/ops/colorspaces.rs:127-137, src/ops/gamma.rs:16-26) in one pass over a 4-channel OpBuffer: the ops Pipeline::run applies
  * between rotatecrop and transform, for callers that do not need the three intermediate buffers (cache == None).
@@ -401,7 +413,9 @@ typedef struct {
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
   /* third layout */
   int schedule;                    /* ipk_schedule, handed to the fused launch when the run is one */
-  int reserved0;                   /* 0 */
+  int fuse_rotatecrop;             /* 1: an active OpRotateCrop on a CFA mosaic runs as ONE launch where ipk_pipeline_fuses_rotatecrop says so; 0 (the default, and
+                                      what every earlier caller has always written into this formerly reserved field): such frames take the staged ops.  Other
+                                      values are refused with IPK_ERR_INVALID.  Results do not depend on it; like allow_fused it does not enter the hashes. */
   int reserved1, reserved2;        /* 0 (the struct's end moves past the second layout's tail padding, so that a size tells the layouts apart) */
 } ipk_pipeline_desc;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
@@ -427,6 +441,14 @@ IPK_API int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *
  * conversion if the depths differ (image 0.24: c*257, (c+128)/257 -- crate absent, parity unpinned) and
  * scale_down_srgb / scale_down_srgb16 (scaling.rs:162-182) if a size limit applies.  Returns 1 / 0. */
 IPK_API int ipk_pipeline_takes_fastpath(const ipk_pipeline_desc *d, int out_type);
+/* Does ipk_pipeline_run (and the cached, batch and host drivers) run this descriptor's active OpRotateCrop inside ONE launch
+ * (ipk_raw_to_srgb_resampled, then OpTransform's permutation if there is one)?  1 when d->fuse_rotatecrop and d->allow_fused are set, the source is
+ * a one-sample-per-pixel CFA mosaic with a three-colour filter, the rotatecrop is not a no-op and accepts its crops (RotateCrop::corners), the
+ * transform is one the launch takes, and OpDemosaic does not scale (scale <= 1).  The last is a real restriction: with an angle the reference's
+ * reverse size fold often negotiates a demosaic size one pixel short of the source (6000x4000 at rotation 0.05: 5999x3999), OpDemosaic then
+ * scales by 1.00025 and the frame stays staged, whatever the flag says.  0 otherwise; a negative error code for a descriptor ipk_pipeline_sizes
+ * refuses, and for a fuse_rotatecrop other than 0 or 1.  No GPU needed. */
+IPK_API int ipk_pipeline_fuses_rotatecrop(const ipk_pipeline_desc *d, int out_type);
 /* do_timing! (src/pipeline.rs:68-80: the reference logs the wall time of every op of Pipeline::run): ipk_timing_begin arms the calling
  * thread, the following ipk_pipeline_run call(s) on it bracket every stage they enqueue with hipEvents on their stream, ipk_timing_end
  * waits for the last one and returns the stages in execution order under the reference's op names ("gofloat", "demosaic", "rotatecrop",
