@@ -6,6 +6,7 @@ interface names (OpBuffer, OpGoFloat ... OpTransform, Pipeline, PipelineSettings
 the reference's.  All pixel work happens in the shared library on the GPU; nothing here computes
 pixels and nothing falls back to the CPU.
 """
+import contextlib
 import ctypes as C
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -103,6 +104,41 @@ def deal_frames(n_frames, n_devices, index):
     f, s, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
     _lib.check(lib().ipk_deal_frames(n_frames, n_devices, index, C.byref(f), C.byref(s), C.byref(c)), "ipk_deal_frames")
     return [f.value + k * s.value for k in range(c.value)]
+
+
+def read_launch_log():
+    """The launch log as it stands (ipk_selftest_launch_log_read): a set of `ipk::<kernel><template arguments>` names, demangled, without return
+    type and parameter list, each followed by the launcher's `[key=value,...]` tag where it attaches one (imagepipe_amd/csrc/ipk_launch.hpp)."""
+    import re                    # a test hook: what only it needs is imported here, not with the package
+    import shutil
+    import subprocess
+    L = lib()
+    n = L.ipk_selftest_launch_log_read(None, 0)
+    buf = C.create_string_buffer(n)
+    L.ipk_selftest_launch_log_read(buf, n)
+    lines = [l for l in buf.value.decode().split("\n") if l]
+    if not lines:
+        return set()
+    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    if not filt:
+        raise IpkError("launch_log: no c++filt / llvm-cxxfilt to demangle the kernel names with")
+    syms, tags = zip(*[(l.split("[", 1) + [""])[:2] for l in lines])
+    names = subprocess.run([filt], input="\n".join(syms), capture_output=True, text=True, check=True).stdout.split("\n")
+    return {re.sub(r"\(.*$", "", d.replace("void ", "", 1)) + ("[" + t if t else "") for d, t in zip(names, tags)}
+
+
+@contextlib.contextmanager
+def launch_log():
+    """Test hook: `with launch_log() as ran:` records which kernels the library launches inside the block (process-wide, host side only);
+    `ran` is a set that is filled, in read_launch_log()'s form, when the block ends."""
+    L = lib()
+    L.ipk_selftest_launch_log(1)
+    ran = set()
+    try:
+        yield ran
+        ran.update(read_launch_log())
+    finally:
+        L.ipk_selftest_launch_log(0)
 
 
 def _stream():

@@ -1077,7 +1077,8 @@ static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, voi
   if (ori != 0) {
     bool t, fx, fy;
     ipk::orientation_to_flips(ori, t, fx, fy);
-    if (band || ori < 1 || ori > 7 || (t ? p->height : p->width) < 256)               // the rotated frame must be at least one 256-pixel strip wide
+    if (band || ori < 1 || ori > 7 || (t ? p->height : p->width) < 256 ||             // the rotated frame must be at least one 256-pixel strip wide
+        (t && p->width > ipk::kRotate1MaxTransposedRows))                              // and no taller than the transposing permutation's grid
       return fail(IPK_ERR_UNSUPPORTED, "no rotated-space variant for this frame");
     // rotate_buffer's index walk (transform.rs:102-128) over the crop window of the pitched 1-channel source
     int64_t width = (int64_t)p->width, height = (int64_t)p->height, x_step = 1, y_step = (int64_t)p->owidth, off = 0;
@@ -1353,6 +1354,9 @@ int ipk_clock_probe(uint64_t *out2_dev, uint32_t spin_us, void *stream) {
   ipk::launch_clock_probe(out2_dev, (unsigned long long)spin_us * 100ull, S(stream)); HIPCHK(hipGetLastError());
   return IPK_OK;
 }
+// no REQUIRE_INIT: the log is host state, and an empty log needs no device
+int ipk_selftest_launch_log(int enabled) { ipk::launch_log_enable(enabled != 0); return IPK_OK; }
+size_t ipk_selftest_launch_log_read(char *buf, size_t cap) { return ipk::launch_log_read(buf, cap); }
 int ipk_selftest_task_queue(int enabled) { REQUIRE_INIT(); ipk::selftest_task_queue(enabled != 0); return IPK_OK; }
 int ipk_selftest_spline3(float exposure, const float *points, int npoints, uint64_t *n_bad, uint32_t *first_bad_bits) {
   REQUIRE_INIT();

@@ -9,8 +9,11 @@
 #include <cstring>
 #include <cmath>
 #include <type_traits>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <set>
+#include <string>
 #include <utility>
 #include <vector>
 #include "ipk_device.hpp"
@@ -32,6 +35,39 @@ constexpr uint32_t kMinTaskRows = 4;   // one task per wave: at least this many 
 constexpr uint32_t kStealMin = 4;      // a takeover needs at least this many rows left behind the owner's current one
 
 namespace ipk {
+
+// Launch log (test hook, ipk_selftest_launch_log; entry format in ipk_launch.hpp): every launch of this file goes through IPK_LAUNCH / IPK_LAUNCH_TAG.
+// Disabled, the wrapper costs one relaxed atomic load.  Enabled, it inserts {host function pointer, tag} into a process-wide set under a mutex and
+// then launches: no HIP call, so launches under stream capture and from several threads stay legal.  Names are resolved when the log is read.
+static std::atomic<bool> g_log_on{false};
+static std::mutex g_log_mu;
+static std::set<std::pair<const void *, const char *>> g_log;
+template <typename... A> static inline const void *kernel_ptr(void (*k)(A...)) { return reinterpret_cast<const void *>(k); }
+static void launch_log_insert(const void *k, const char *tag) { std::lock_guard<std::mutex> g(g_log_mu); g_log.insert({k, tag}); }
+static inline void launch_log_note(const void *k, const char *tag) { if (IPK_RARE(g_log_on.load(std::memory_order_relaxed))) launch_log_insert(k, tag); }
+#define IPK_LAUNCH_TAG(TAG, K, ...) do { ::ipk::launch_log_note(::ipk::kernel_ptr(K), TAG); hipLaunchKernelGGL(K, __VA_ARGS__); } while (0)
+#define IPK_LAUNCH(K, ...) IPK_LAUNCH_TAG(nullptr, K, __VA_ARGS__)
+void launch_log_enable(bool on) {
+  std::lock_guard<std::mutex> g(g_log_mu);
+  g_log.clear();
+  g_log_on.store(on, std::memory_order_relaxed);
+}
+size_t launch_log_read(char *buf, size_t cap) {
+  std::set<std::string> names;
+  {
+    std::lock_guard<std::mutex> g(g_log_mu);
+    for (const auto &e : g_log) {
+      const char *n = hipKernelNameRefByPtr(e.first, nullptr);
+      std::string s = n ? n : "?";
+      if (e.second) { s += '['; s += e.second; s += ']'; }
+      names.insert(s);
+    }
+  }
+  std::string all;
+  for (const auto &s : names) { if (!all.empty()) all += '\n'; all += s; }
+  if (buf && cap) { const size_t k = std::min(cap - 1, all.size()); std::memcpy(buf, all.data(), k); buf[k] = '\0'; }
+  return all.size() + 1;
+}
 
 typedef LutPair LabTab;
 typedef LutPair GamTab;
@@ -247,20 +283,25 @@ void launch_gofloat_cfa(const T *src, size_t owidth, size_t x, size_t y, size_t 
                         float *dst, hipStream_t s) {
   if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0) {
     const dim3 grid((unsigned)((w / 4 + 255) / 256), (unsigned)(h < 4096 ? h : 4096), 1);
-    // u16: the 8-byte load wants the first sample of every row on a dword boundary
-    if (sizeof(T) == 4 || ((owidth & 1) == 0 && (x & 1) == 0))
-      hipLaunchKernelGGL((k_gofloat_cfa_v4<T, true>), grid, dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h, black0, white0 - black0, dst);
-    else
-      hipLaunchKernelGGL((k_gofloat_cfa_v4<T, false>), grid, dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h, black0, white0 - black0, dst);
+    const char *tag = h > 4096 ? "rowwrap=1" : "rowwrap=0";   // more rows than grid rows: the kernel's row loop turns
+    // u16: the 8-byte load wants the first sample of every row on a dword boundary.  f32 has one load form (ALIGNED is not read): <float, false> is never built
+    if constexpr (sizeof(T) == 4) {
+      IPK_LAUNCH_TAG(tag, (k_gofloat_cfa_v4<T, true>), grid, dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h, black0, white0 - black0, dst);
+    } else {
+      if ((owidth & 1) == 0 && (x & 1) == 0)
+        IPK_LAUNCH_TAG(tag, (k_gofloat_cfa_v4<T, true>), grid, dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h, black0, white0 - black0, dst);
+      else
+        IPK_LAUNCH_TAG(tag, (k_gofloat_cfa_v4<T, false>), grid, dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h, black0, white0 - black0, dst);
+    }
     return;
   }
-  hipLaunchKernelGGL(k_gofloat_cfa<T>, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
+  IPK_LAUNCH(k_gofloat_cfa<T>, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
                      black0, white0 - black0, dst);
 }
 template <typename T>
 void launch_gofloat_mono(const T *src, size_t owidth, size_t x, size_t y, size_t w, size_t h, float black0, float white0,
                          float *dst4, hipStream_t s) {
-  hipLaunchKernelGGL(k_gofloat_mono<T>, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
+  IPK_LAUNCH(k_gofloat_mono<T>, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
                      black0, white0 - black0, reinterpret_cast<float4 *>(dst4));
 }
 template <typename T>
@@ -268,7 +309,7 @@ void launch_gofloat_rgb(const T *src, size_t owidth, size_t x, size_t y, size_t 
                         float *dst4, hipStream_t s) {
   Levels4 lv;
   for (int i = 0; i < 4; ++i) { lv.mins[i] = black4[i]; lv.ranges[i] = white4[i] - black4[i]; }   // gofloat.rs:86-89
-  hipLaunchKernelGGL(k_gofloat_rgb<T>, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
+  IPK_LAUNCH(k_gofloat_rgb<T>, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
                      lv, reinterpret_cast<float4 *>(dst4));
 }
 template void launch_gofloat_cfa<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, float *, hipStream_t);
@@ -280,11 +321,11 @@ template void launch_gofloat_rgb<float>(const float *, size_t, size_t, size_t, s
 
 void launch_gofloat_other_u8(const uint8_t *src, size_t owidth, size_t x, size_t y, size_t w, size_t h,
                              const void *gamma_reverse_pairs, float *dst4, hipStream_t s) {
-  hipLaunchKernelGGL(k_gofloat_other_u8, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
+  IPK_LAUNCH(k_gofloat_other_u8, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
                      reinterpret_cast<const LutPair *>(gamma_reverse_pairs), reinterpret_cast<float4 *>(dst4));
 }
 void launch_gofloat_other_u16(const uint16_t *src, size_t owidth, size_t x, size_t y, size_t w, size_t h, float *dst4, hipStream_t s) {
-  hipLaunchKernelGGL(k_gofloat_other_u16, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
+  IPK_LAUNCH(k_gofloat_other_u16, grid_rows(w, h, 256), dim3(256), 0, s, src, owidth, x, y, (uint32_t)w, (uint32_t)h,
                      reinterpret_cast<float4 *>(dst4));
 }
 
@@ -332,7 +373,7 @@ __global__ void k_demosaic_full(const float *__restrict__ src, uint32_t width, u
 }
 void launch_demosaic_full(const float *src, size_t width, size_t img_height, size_t src_row0, size_t out_row0, size_t out_rows,
                           const uint32_t *lookups_dev, float *dst4, hipStream_t s) {
-  hipLaunchKernelGGL(k_demosaic_full, grid_rows(width, out_rows, 256), dim3(256), 0, s, src, (uint32_t)width, (uint32_t)img_height,
+  IPK_LAUNCH(k_demosaic_full, grid_rows(width, out_rows, 256), dim3(256), 0, s, src, (uint32_t)width, (uint32_t)img_height,
                      (uint32_t)src_row0, (uint32_t)out_row0, (uint32_t)out_rows, lookups_dev, reinterpret_cast<float4 *>(dst4));
 }
 
@@ -533,7 +574,7 @@ void launch_transform_buffer(const T *src, size_t width, size_t height, int64_t 
   a.norm = 0; a.min0 = 0.0f; a.range0 = 1.0f; a.src_pitch = width; a.src_x = 0; a.src_y = 0; a.norm_fast = 0; a.inv_range0 = 1.0f;
   a.plain_axis = (tlx == 0 && tly == 0 && a.skip_x_y == 0.0f && a.skip_y_x == 0.0f && a.skip_x_x >= 1.0f && a.skip_y_y >= 1.0f &&
                   a.skip_x_x <= 0x1p24f && a.skip_y_y <= 0x1p24f && width < (size_t(1) << 24) && height < (size_t(1) << 24)) ? 1 : 0;
-  hipLaunchKernelGGL(k_transform_buffer<T>, grid_rows_few(nwidth, nheight, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst);
+  IPK_LAUNCH(k_transform_buffer<T>, grid_rows_few(nwidth, nheight, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst);
 }
 
 // OpGoFloat::run_other + scaling::scale_down_opbuf in one pass over an RGB8 / RGB16 raster: dst4 = scale_down_opbuf(run_other(src))
@@ -610,8 +651,8 @@ void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, si
   a.fast_x = cdiv_host_ok(a.skip_x_x); a.fast_y = cdiv_host_ok(a.skip_y_y);
   a.src_pitch = owidth; a.src_x = x; a.src_y = y;
   const LutPair *gr = reinterpret_cast<const LutPair *>(gamma_reverse_pairs);
-  if (src_is_u16) hipLaunchKernelGGL(k_raster_scale_down<uint16_t>, grid_rows_few(nwidth, nheight, 128, 8192), dim3(128), 0, s, static_cast<const uint16_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
-  else hipLaunchKernelGGL(k_raster_scale_down<uint8_t>, grid_rows_few(nwidth, nheight, 128, 8192), dim3(128), 0, s, static_cast<const uint8_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
+  if (src_is_u16) IPK_LAUNCH(k_raster_scale_down<uint16_t>, grid_rows_few(nwidth, nheight, 128, 8192), dim3(128), 0, s, static_cast<const uint16_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
+  else IPK_LAUNCH(k_raster_scale_down<uint8_t>, grid_rows_few(nwidth, nheight, 128, 8192), dim3(128), 0, s, static_cast<const uint8_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
 }
 
 // OpGoFloat (CFA branch) + scaling::scaled_demosaic in one pass over the raw sensor frame: dst4 = scaled_demosaic(gofloat(src)).
@@ -1033,6 +1074,20 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
   if (band_out_rows) { a.out_r0 = (uint32_t)band_out_row0; a.out_r1 = (uint32_t)(band_out_row0 + band_out_rows); a.src_y = (uint64_t)0 - (uint64_t)band_src_row0; }
   const size_t out_rows = a.out_r1 - a.out_r0;
   a.xcd_gx = 0; a.xcd_gy = 0; a.xcd_group = 0;
+  // launch-log tag: the host-known switches the kernels branch on, "norm_fast=.,norm_light=.,fast_x=.,fast_y=.,xcd=." (xcd: 0 plain grid, 1 XCD row
+  // grouping with no leftover rows, 2 grouping with leftover rows)
+  auto tag = [&](int xcd) -> const char * {
+    if (!g_log_on.load(std::memory_order_relaxed)) return nullptr;         // the table is built, and read, only while the log is on
+    static const std::vector<std::string> tags = [] {
+      std::vector<std::string> t;
+      for (int i = 0; i < 48; ++i) {
+        char b[80]; snprintf(b, sizeof(b), "norm_fast=%d,norm_light=%d,fast_x=%d,fast_y=%d,xcd=%d", i & 1, (i >> 1) & 1, (i >> 2) & 1, (i >> 3) & 1, i >> 4);
+        t.push_back(b);
+      }
+      return t;
+    }();
+    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4))].c_str();
+  };
   a.components = has_fourth_colour ? 4 : 3;               // the w8 kernel skips the fourth bin for three-colour filters (it stays 0.0)
   // windows of at most 8 x 8 samples: floor(skip*(c+1)) - floor(skip*c) + 1 <= ceil(skip) + 1
   if (a.skip_x_x >= 1.0f && a.skip_x_x <= 7.0f && a.skip_y_y >= 1.0f && a.skip_y_y <= 7.0f && width >= 8 &&
@@ -1058,21 +1113,22 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
           grid = dim3(a.xcd_gx * a.xcd_gy, 1, 1);
         }
       }
+      const char *t = tag(a.xcd_group == 0 ? 0 : (out_rows > a.xcd_gy ? 2 : 1));
       if (has_fourth_colour) {
-        if (a.skip_x_x >= 4.0f) hipLaunchKernelGGL((k_raw_scaled_demosaic_w8m<T, 5, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
-        else if (a.skip_x_x >= 2.0f) hipLaunchKernelGGL((k_raw_scaled_demosaic_w8m<T, 3, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
-        else hipLaunchKernelGGL((k_raw_scaled_demosaic_w8m<T, 2, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
+        if (a.skip_x_x >= 4.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 5, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
+        else if (a.skip_x_x >= 2.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 3, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
+        else IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 2, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
       } else {
-        if (a.skip_x_x >= 4.0f) hipLaunchKernelGGL((k_raw_scaled_demosaic_w8m<T, 5, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
-        else if (a.skip_x_x >= 2.0f) hipLaunchKernelGGL((k_raw_scaled_demosaic_w8m<T, 3, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
-        else hipLaunchKernelGGL((k_raw_scaled_demosaic_w8m<T, 2, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
+        if (a.skip_x_x >= 4.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 5, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
+        else if (a.skip_x_x >= 2.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 3, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
+        else IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 2, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
       }
       return;
     }
-    hipLaunchKernelGGL(k_raw_scaled_demosaic_w8<T>, grid, dim3(256), 0, s, src, a, cfa48_dev, dst4);
+    IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic_w8<T>, grid, dim3(256), 0, s, src, a, cfa48_dev, dst4);
     return;
   }
-  hipLaunchKernelGGL(k_raw_scaled_demosaic<T>, grid_rows_few(nwidth, out_rows, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst4);
+  IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(nwidth, out_rows, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst4);
 }
 template void launch_raw_scaled_demosaic<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t);
 template void launch_raw_scaled_demosaic<float>(const float *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t);
@@ -1126,6 +1182,7 @@ __global__ __launch_bounds__(1024) void k_gamma(const float *__restrict__ src, s
   load_lut_pairs(s_gam, gam_pairs);
   __syncthreads();
   // four samples per thread (16-byte accesses) while whole groups remain, then the tail one by one
+  // (launch_gamma restates this test for its launch-log tag `vec4=`: change both together)
   const size_t n4 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 ? n / 4 : 0;
   // Four 16-byte groups per thread and iteration, all four loads issued before the first lookup, and the four ADJACENT: a block covers 64 KB of
   // contiguous input per step, blocks side by side, and the launch holds sixteen blocks per CU slot so that the dispatcher keeps the chip on one
@@ -1168,6 +1225,7 @@ __global__ void k_rotate(const Px3<T> *__restrict__ src, uint32_t owidth, uint32
 }
 // output8bit / output16bit loops (src/pipeline.rs:408-414, :455-461)
 __global__ void k_output8(const float *__restrict__ src, size_t n, uint8_t *__restrict__ dst) {
+  // (launch_output8 restates this test for its launch-log tag `vec4=`: change both together)
   const size_t n4 = ((reinterpret_cast<uintptr_t>(src) & 15) | (reinterpret_cast<uintptr_t>(dst) & 3)) == 0 ? n / 4 : 0;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const float4 v = ld_stream4(src + 4 * i);
@@ -1176,6 +1234,7 @@ __global__ void k_output8(const float *__restrict__ src, size_t n, uint8_t *__re
   for (size_t i = 4 * n4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = output8bit(src[i]);
 }
 __global__ void k_output16(const float *__restrict__ src, size_t n, uint16_t *__restrict__ dst) {
+  // (launch_output16 restates this test for its launch-log tag `vec4=`: change both together)
   const size_t n4 = ((reinterpret_cast<uintptr_t>(src) & 15) | (reinterpret_cast<uintptr_t>(dst) & 7)) == 0 ? n / 4 : 0;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const float4 v = ld_stream4(src + 4 * i);
@@ -1231,22 +1290,25 @@ static SplineDev make_spline(const SplineHost &h) {
 
 void launch_tolab(const float *src4, size_t npix, const float *mul4, const float *cm12, const void *lab_pairs, float *dst3,
                   int num_cus, hipStream_t s) {
-  hipLaunchKernelGGL(k_tolab, dim3(grid_1d(npix, 1024, (unsigned)num_cus * 2)), dim3(1024), 0, s,
+  IPK_LAUNCH(k_tolab, dim3(grid_1d(npix, 1024, (unsigned)num_cus * 2)), dim3(1024), 0, s,
                      reinterpret_cast<const float4 *>(src4), npix, make_tolab(mul4, cm12),
                      reinterpret_cast<const LutPair *>(lab_pairs), reinterpret_cast<f3 *>(dst3));
 }
 void launch_basecurve(const float *src3, size_t npix, const SplineHost &sp, float *dst3, int num_cus, hipStream_t s) {
-  hipLaunchKernelGGL(k_basecurve, dim3(grid_1d(npix, 256, flat_cap((unsigned)num_cus * 16))), dim3(256), 0, s,
+  IPK_LAUNCH(k_basecurve, dim3(grid_1d(npix, 256, flat_cap((unsigned)num_cus * 16))), dim3(256), 0, s,
                      reinterpret_cast<const f3 *>(src3), npix, make_spline(sp), reinterpret_cast<f3 *>(dst3));
 }
 void launch_fromlab(const float *src3, size_t npix, const float *m9, float *dst3, int num_cus, hipStream_t s) {
   Mat9 m; for (int i = 0; i < 9; ++i) m.m[i] = m9[i];
-  hipLaunchKernelGGL(k_fromlab, dim3(grid_1d(npix, 256, flat_cap((unsigned)num_cus * 16))), dim3(256), 0, s,
+  IPK_LAUNCH(k_fromlab, dim3(grid_1d(npix, 256, flat_cap((unsigned)num_cus * 16))), dim3(256), 0, s,
                      reinterpret_cast<const f3 *>(src3), npix, m, reinterpret_cast<f3 *>(dst3));
 }
 void launch_gamma(const float *src, size_t n, const void *gam_pairs, float *dst, int num_cus, hipStream_t s) {
   // sixteen blocks per CU slot (two are resident at a time), each walking 64 KB-wide steps: see k_gamma
-  hipLaunchKernelGGL(k_gamma, dim3(grid_1d((n / 4 + 3) / 4, 1024, (unsigned)num_cus * 16)), dim3(1024), 0, s, src, n,
+  const bool vec4 = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;      // k_gamma's n4 != 0
+  const bool wrap = (n / 4 + 3) / 4 > (size_t)num_cus * 16 * 1024;                                          // the grid cap holds: the stride loop turns
+  IPK_LAUNCH_TAG(vec4 ? (wrap ? "vec4=1,wrap=1" : "vec4=1,wrap=0") : (wrap ? "vec4=0,wrap=1" : "vec4=0,wrap=0"),
+                 k_gamma, dim3(grid_1d((n / 4 + 3) / 4, 1024, (unsigned)num_cus * 16)), dim3(1024), 0, s, src, n,
                      reinterpret_cast<const LutPair *>(gam_pairs), dst);
 }
 // The transposing orientations (Rotate90/270, Transpose, Transverse: |y_step| == 1, |x_step| == source pitch): consecutive
@@ -1279,12 +1341,12 @@ template <typename T>
 void launch_rotate(const T *src3, size_t owidth, size_t oheight, int64_t base_offset_px, int64_t x_step_px, int64_t y_step_px,
                    T *dst3, hipStream_t s) {
   if ((y_step_px == 1 || y_step_px == -1) && x_step_px != 1 && x_step_px != -1 && (oheight + 31) / 32 <= 65535) {
-    hipLaunchKernelGGL(k_rotate_transposed<T>, dim3((unsigned)((owidth + 31) / 32), (unsigned)((oheight + 31) / 32), 1), dim3(256), 0, s,
+    IPK_LAUNCH(k_rotate_transposed<T>, dim3((unsigned)((owidth + 31) / 32), (unsigned)((oheight + 31) / 32), 1), dim3(256), 0, s,
                        reinterpret_cast<const Px3<T> *>(src3), (uint32_t)owidth, (uint32_t)oheight, base_offset_px, x_step_px, y_step_px,
                        reinterpret_cast<Px3<T> *>(dst3));
     return;
   }
-  hipLaunchKernelGGL(k_rotate<T>, grid_rows(owidth, oheight, 256), dim3(256), 0, s, reinterpret_cast<const Px3<T> *>(src3),
+  IPK_LAUNCH(k_rotate<T>, grid_rows(owidth, oheight, 256), dim3(256), 0, s, reinterpret_cast<const Px3<T> *>(src3),
                      (uint32_t)owidth, (uint32_t)oheight, base_offset_px, x_step_px, y_step_px, reinterpret_cast<Px3<T> *>(dst3));
 }
 template void launch_rotate<float>(const float *, size_t, size_t, int64_t, int64_t, int64_t, float *, hipStream_t);
@@ -1292,13 +1354,6 @@ template void launch_rotate<uint8_t>(const uint8_t *, size_t, size_t, int64_t, i
 template void launch_rotate<uint16_t>(const uint16_t *, size_t, size_t, int64_t, int64_t, int64_t, uint16_t *, hipStream_t);
 // The same permutation on a 1-channel image (the sensor mosaic, u16 or f32), source addressed through its own pitch and crop
 // window: `base`, `x_step`, `y_step` in source elements.  Feeds the fused kernel's rotated-space variants.
-template <typename T>
-__global__ void k_rotate1(const T *__restrict__ src, uint32_t owidth, uint32_t oheight, int64_t base_offset, int64_t x_step, int64_t y_step,
-                          T *__restrict__ dst) {
-  const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= owidth) return;
-  for (uint32_t row = blockIdx.y; row < oheight; row += gridDim.y) dst[(size_t)row * owidth + col] = src[base_offset + y_step * (int64_t)row + x_step * (int64_t)col];
-}
 // flips and 180 degrees (|x_step| == 1): 16 bytes per lane, reversed inside the lane when the walk descends
 template <typename T>
 __global__ void k_rotate1_rows(const T *__restrict__ src, uint32_t owidth, uint32_t oheight, int64_t base_offset, int64_t x_step, int64_t y_step,
@@ -1372,22 +1427,22 @@ __global__ __launch_bounds__(256) void k_rotate1_transposed(const T *__restrict_
 template <typename T>
 void launch_rotate1(const T *src, size_t owidth, size_t oheight, int64_t base_offset, int64_t x_step, int64_t y_step, T *dst, hipStream_t s) {
   constexpr size_t TW = 64;
-  if ((y_step == 1 || y_step == -1) && x_step != 1 && x_step != -1 && (oheight + TW - 1) / TW <= 65535) {
-    hipLaunchKernelGGL(k_rotate1_transposed<T>, dim3((unsigned)((owidth + TW - 1) / TW), (unsigned)((oheight + TW - 1) / TW), 1), dim3(256), 0, s,
+  // transposing orientations: one grid row per 64 output rows -- at most kRotate1MaxTransposedRows of them, which the caller checks (ipk_api.cpp
+  // fused_impl sends wider mosaics down the route that permutes the output)
+  if ((y_step == 1 || y_step == -1) && x_step != 1 && x_step != -1) {
+    IPK_LAUNCH(k_rotate1_transposed<T>, dim3((unsigned)((owidth + TW - 1) / TW), (unsigned)((oheight + TW - 1) / TW), 1), dim3(256), 0, s,
                        src, (uint32_t)owidth, (uint32_t)oheight, base_offset, x_step, y_step, dst);
     return;
   }
-  if (x_step == 1 || x_step == -1) {
-    constexpr size_t NV = 16 / sizeof(T);
-    hipLaunchKernelGGL(k_rotate1_rows<T>, grid_rows((owidth + NV - 1) / NV, oheight, 256), dim3(256), 0, s, src, (uint32_t)owidth, (uint32_t)oheight, base_offset, x_step, y_step, dst);
-    return;
-  }
-  hipLaunchKernelGGL(k_rotate1<T>, grid_rows(owidth, oheight, 256), dim3(256), 0, s, src, (uint32_t)owidth, (uint32_t)oheight, base_offset, x_step, y_step, dst);
+  // flips and 180 degrees: |x_step| == 1 (rotate_buffer's walk has no other case for a 1-channel image)
+  constexpr size_t NV = 16 / sizeof(T);
+  IPK_LAUNCH(k_rotate1_rows<T>, grid_rows((owidth + NV - 1) / NV, oheight, 256), dim3(256), 0, s, src, (uint32_t)owidth, (uint32_t)oheight, base_offset, x_step, y_step, dst);
 }
 template void launch_rotate1<float>(const float *, size_t, size_t, int64_t, int64_t, int64_t, float *, hipStream_t);
 template void launch_rotate1<uint16_t>(const uint16_t *, size_t, size_t, int64_t, int64_t, int64_t, uint16_t *, hipStream_t);
 void launch_output8(const float *src, size_t n, uint8_t *dst, int num_cus, hipStream_t s) {
-  hipLaunchKernelGGL(k_output8, dim3(grid_1d((n + 3) / 4, 256, flat_cap((unsigned)num_cus * 16))), dim3(256), 0, s, src, n, dst);
+  const bool vec4 = ((reinterpret_cast<uintptr_t>(src) & 15) | (reinterpret_cast<uintptr_t>(dst) & 3)) == 0;   // k_output8's n4 != 0
+  IPK_LAUNCH_TAG(vec4 ? "vec4=1" : "vec4=0", k_output8, dim3(grid_1d((n + 3) / 4, 256, flat_cap((unsigned)num_cus * 16))), dim3(256), 0, s, src, n, dst);
 }
 // The sample-depth changes of the raster fast path (src/pipeline.rs:381-402, :428-449): v * 257 and (v + 128) / 257, sixteen samples per lane -- 16-byte
 // loads and stores (round 5: one sample per lane and access ran at 3.8 / 4.5 TB/s of its 3 bytes per sample; see k_rotate1_transposed for the same finding)
@@ -1425,13 +1480,14 @@ __global__ __launch_bounds__(256) void k_chan_16_to_8(const uint16_t *__restrict
   }
 }
 void launch_chan_8_to_16(const uint8_t *src, size_t n, uint16_t *dst, int, hipStream_t s) {
-  hipLaunchKernelGGL(k_chan_8_to_16, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, src, n, dst);
+  IPK_LAUNCH(k_chan_8_to_16, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, src, n, dst);
 }
 void launch_chan_16_to_8(const uint16_t *src, size_t n, uint8_t *dst, int, hipStream_t s) {
-  hipLaunchKernelGGL(k_chan_16_to_8, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, src, n, dst);
+  IPK_LAUNCH(k_chan_16_to_8, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, src, n, dst);
 }
 void launch_output16(const float *src, size_t n, uint16_t *dst, int num_cus, hipStream_t s) {
-  hipLaunchKernelGGL(k_output16, dim3(grid_1d((n + 3) / 4, 256, flat_cap((unsigned)num_cus * 16))), dim3(256), 0, s, src, n, dst);
+  const bool vec4 = ((reinterpret_cast<uintptr_t>(src) & 15) | (reinterpret_cast<uintptr_t>(dst) & 7)) == 0;   // k_output16's n4 != 0
+  IPK_LAUNCH_TAG(vec4 ? "vec4=1" : "vec4=0", k_output16, dim3(grid_1d((n + 3) / 4, 256, flat_cap((unsigned)num_cus * 16))), dim3(256), 0, s, src, n, dst);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2749,11 +2805,11 @@ int launch_demosaic_bayer(const float *src, size_t width, size_t img_height, siz
   // (1 / 2 / 3 / 4 / 6 blocks per CU launched: 0.416 / 0.415 / 0.422 / 0.417 / 0.426 ms at 100 MP)
   fused_task_grid(a, gen_cells ? num_cus : 2 * (num_cus > 0 ? num_cus : 256), blocks);
   if (gen_cells) {
-    if (a.W >= 256u) hipLaunchKernelGGL((k_fused_bayer<float, true, 3, true, true>), dim3(blocks), dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL((k_fused_bayer<float, true, 3, false, true>), dim3(blocks), dim3(1024), 0, s, a);
+    if (a.W >= 256u) IPK_LAUNCH((k_fused_bayer<float, true, 3, true, true>), dim3(blocks), dim3(1024), 0, s, a);
+    else IPK_LAUNCH((k_fused_bayer<float, true, 3, false, true>), dim3(blocks), dim3(1024), 0, s, a);
   } else {
-    if (a.W >= 256u) hipLaunchKernelGGL((k_fused_bayer<float, true, 3, true, false>), dim3(blocks), dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL((k_fused_bayer<float, true, 3, false, false>), dim3(blocks), dim3(1024), 0, s, a);
+    if (a.W >= 256u) IPK_LAUNCH((k_fused_bayer<float, true, 3, true, false>), dim3(blocks), dim3(1024), 0, s, a);
+    else IPK_LAUNCH((k_fused_bayer<float, true, 3, false, false>), dim3(blocks), dim3(1024), 0, s, a);
   }
   return launch_status();
 }
@@ -2767,43 +2823,43 @@ static void launch_fused_t(const FusedArgs &a, unsigned grid, hipStream_t s) {
   // the same parameter set with a curve of four or more knots that qualifies for the grid form (a user's edited base curve): the Bayer variants only
   const bool common_grid = common_but_curve && a.spline.grid_ok != 0 && a.ori == 0 && !a.gen_cells;
   if (a.ori != 0) {                                      // rotated space: the common parameter set only (launch_fused_bayer checked)
-    if (a.gen_cells) { hipLaunchKernelGGL((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, true, true, true, true>), dim3(grid), dim3(tpb), 0, s, a); return; }
-    if (a.px_guard == 0) hipLaunchKernelGGL((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, false, false, true, true>), dim3(grid), dim3(tpb), 0, s, a);
-    else hipLaunchKernelGGL((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, false, true, true, true>), dim3(grid), dim3(tpb), 0, s, a);
+    if (a.gen_cells) { IPK_LAUNCH((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, true, true, true, true>), dim3(grid), dim3(tpb), 0, s, a); return; }
+    if (a.px_guard == 0) IPK_LAUNCH((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, false, false, true, true>), dim3(grid), dim3(tpb), 0, s, a);
+    else IPK_LAUNCH((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, false, true, true, true>), dim3(grid), dim3(tpb), 0, s, a);
     return;
   }
   if (a.gen_cells) {                                     // generic-CFA mode: one load flavour per source type
     constexpr bool V = sizeof(SrcT) == 4;
-    if (common) hipLaunchKernelGGL((k_fused_bayer<SrcT, V, OUT, true, true, true, true>), dim3(grid), dim3(tpb), 0, s, a);
-    else if (a.W >= 256u) hipLaunchKernelGGL((k_fused_bayer<SrcT, V, OUT, true, true>), dim3(grid), dim3(tpb), 0, s, a);
-    else hipLaunchKernelGGL((k_fused_bayer<SrcT, V, OUT, false, true>), dim3(grid), dim3(tpb), 0, s, a);
+    if (common) IPK_LAUNCH((k_fused_bayer<SrcT, V, OUT, true, true, true, true>), dim3(grid), dim3(tpb), 0, s, a);
+    else if (a.W >= 256u) IPK_LAUNCH((k_fused_bayer<SrcT, V, OUT, true, true>), dim3(grid), dim3(tpb), 0, s, a);
+    else IPK_LAUNCH((k_fused_bayer<SrcT, V, OUT, false, true>), dim3(grid), dim3(tpb), 0, s, a);
     return;
   }
   // u16 sources with ordinary levels and parameters (the common case for real sensors): no per-pixel input guards
   if constexpr (sizeof(SrcT) == 2) if (a.px_guard == 0 && a.W >= 256u) {
-    if (common) hipLaunchKernelGGL((k_fused_bayer<SrcT, false, OUT, true, false, false, true>), dim3(grid), dim3(tpb), 0, s, a);
-    else if (common_grid) hipLaunchKernelGGL((k_fused_bayer<SrcT, false, OUT, true, false, false, 2>), dim3(grid), dim3(tpb), 0, s, a);
-    else hipLaunchKernelGGL((k_fused_bayer<SrcT, false, OUT, true, false, false, false>), dim3(grid), dim3(tpb), 0, s, a);
+    if (common) IPK_LAUNCH((k_fused_bayer<SrcT, false, OUT, true, false, false, true>), dim3(grid), dim3(tpb), 0, s, a);
+    else if (common_grid) IPK_LAUNCH((k_fused_bayer<SrcT, false, OUT, true, false, false, 2>), dim3(grid), dim3(tpb), 0, s, a);
+    else IPK_LAUNCH((k_fused_bayer<SrcT, false, OUT, true, false, false, false>), dim3(grid), dim3(tpb), 0, s, a);
     return;
   }
   if (common_grid) {
     if constexpr (sizeof(SrcT) == 4) if (a.px_guard == 0) {
-      hipLaunchKernelGGL((k_fused_bayer<SrcT, true, OUT, true, false, false, 2>), dim3(grid), dim3(tpb), 0, s, a);
+      IPK_LAUNCH((k_fused_bayer<SrcT, true, OUT, true, false, false, 2>), dim3(grid), dim3(tpb), 0, s, a);
       return;
     }
-    hipLaunchKernelGGL((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, false, true, 2>), dim3(grid), dim3(tpb), 0, s, a);
+    IPK_LAUNCH((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, false, true, 2>), dim3(grid), dim3(tpb), 0, s, a);
     return;
   }
   if (common) {
     if constexpr (sizeof(SrcT) == 4) if (a.px_guard == 0) {   // f32: ordinary parameters and a black level of at least range/64
-      hipLaunchKernelGGL((k_fused_bayer<SrcT, true, OUT, true, false, false, true>), dim3(grid), dim3(tpb), 0, s, a);
+      IPK_LAUNCH((k_fused_bayer<SrcT, true, OUT, true, false, false, true>), dim3(grid), dim3(tpb), 0, s, a);
       return;
     }
-    hipLaunchKernelGGL((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, false, true, true>), dim3(grid), dim3(tpb), 0, s, a);
+    IPK_LAUNCH((k_fused_bayer<SrcT, sizeof(SrcT) == 4, OUT, true, false, true, true>), dim3(grid), dim3(tpb), 0, s, a);
     return;
   }
-  if (a.W >= 256u) hipLaunchKernelGGL((k_fused_bayer<SrcT, VEC, OUT, true, false>), dim3(grid), dim3(tpb), 0, s, a);
-  else hipLaunchKernelGGL((k_fused_bayer<SrcT, VEC, OUT, false, false>), dim3(grid), dim3(tpb), 0, s, a);
+  if (a.W >= 256u) IPK_LAUNCH((k_fused_bayer<SrcT, VEC, OUT, true, false>), dim3(grid), dim3(tpb), 0, s, a);
+  else IPK_LAUNCH((k_fused_bayer<SrcT, VEC, OUT, false, false>), dim3(grid), dim3(tpb), 0, s, a);
 }
 // A region's launch.  The common parameter set takes launch_fused_t's template flags (the headline descriptor's window runs its whole-frame kernel's
 // code); everything else takes the runtime-flag form (CM = 0, per-pixel guards on), Bayer or generic-CFA.  u16 sources take the loads that accept any
@@ -2814,7 +2870,7 @@ static void launch_fused_window_t(const FusedArgs &a, const FusedWindow &w, unsi
   const bool full = w.x1 - w.x0 >= 256u;
   const bool common = full && a.fast_ok && a.has_curve && !a.exact_norm && (a.linear != 0) == (OUT == 2) && std::fabs(a.min0) >= 0x1p-70f &&
                       std::fabs(a.min0) <= 0x1p70f && a.spline.npoints == 3 && spline3_arith_ok(a.spline);
-#define IPK_WIN_LAUNCH(FL, G, P, C) hipLaunchKernelGGL((k_fused_bayer_window<SrcT, V, OUT, FL, G, P, C>), dim3(grid), dim3(1024), 0, s, a, w)
+#define IPK_WIN_LAUNCH(FL, G, P, C) IPK_LAUNCH((k_fused_bayer_window<SrcT, V, OUT, FL, G, P, C>), dim3(grid), dim3(1024), 0, s, a, w)
   if (a.gen_cells) {
     if (common) IPK_WIN_LAUNCH(true, true, true, 1);
     else if (full) IPK_WIN_LAUNCH(true, true, true, 0);
@@ -3014,7 +3070,7 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s) {
         std::unique_lock<std::mutex> queue_lock;
         (void)task_counters_for(f.queues, s, a, queue_lock);
         fused_task_grid(a, f.num_cus, grid, (uint32_t)n);
-#define IPK_BATCH_LAUNCH(T, V, O) hipLaunchKernelGGL((k_fused_bayer_batch<T, V, O, false>), dim3(grid), dim3(1024), 0, s, a, bp)
+#define IPK_BATCH_LAUNCH(T, V, O) IPK_LAUNCH((k_fused_bayer_batch<T, V, O, false>), dim3(grid), dim3(1024), 0, s, a, bp)
         if (!f.src_is_u16) { if (f.out_type == 0) IPK_BATCH_LAUNCH(float, true, 0); else if (f.out_type == 1) IPK_BATCH_LAUNCH(float, true, 1); else IPK_BATCH_LAUNCH(float, true, 2); }
         else { if (f.out_type == 0) IPK_BATCH_LAUNCH(uint16_t, false, 0); else if (f.out_type == 1) IPK_BATCH_LAUNCH(uint16_t, false, 1); else IPK_BATCH_LAUNCH(uint16_t, false, 2); }
 #undef IPK_BATCH_LAUNCH
@@ -3040,8 +3096,8 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s) {
   }
   if (f.out_type == 4) {                                  // ipk_stream_probe: the skeleton of the headline variants (Bayer phase, full strips, no guards)
     if (a.gen_cells || a.ori != 0 || a.W < 256u || a.exact_norm || std::fabs(a.min0) < 0x1p-70f || std::fabs(a.min0) > 0x1p70f) return -2;
-    if (!f.src_is_u16) hipLaunchKernelGGL((k_fused_bayer<float, true, 4, true, false, false, true>), dim3(blocks), dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL((k_fused_bayer<uint16_t, false, 4, true, false, false, true>), dim3(blocks), dim3(1024), 0, s, a);
+    if (!f.src_is_u16) IPK_LAUNCH((k_fused_bayer<float, true, 4, true, false, false, true>), dim3(blocks), dim3(1024), 0, s, a);
+    else IPK_LAUNCH((k_fused_bayer<uint16_t, false, 4, true, false, false, true>), dim3(blocks), dim3(1024), 0, s, a);
     return launch_status();
   }
   if (!f.src_is_u16) {
@@ -3165,13 +3221,13 @@ int launch_pointwise_chain(const FusedLaunch &f, size_t npix, hipStream_t s) {
   const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   if (npix < (size_t)cus * 16u * 256u * 6u) {                              // fewer than six long chunks per wave (6.3 MP on 256 CUs): the two-pixel form
     const size_t chunks = (npix + 127) / 128;
-    hipLaunchKernelGGL(k_pointwise_chain_small, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(cus, (chunks + 15) / 16))), dim3(1024), 0, s, a, (uint64_t)npix);
+    IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), k_pointwise_chain_small, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(cus, (chunks + 15) / 16))), dim3(1024), 0, s, a, (uint64_t)npix);
     return 0;
   }
   const size_t chunks = (npix + 255) / 256;
   const unsigned cap = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);                      // (more blocks measured: 1 / 2 / 4 / 8 / 16 per CU 0.663 / 0.665 / 0.677 / 0.673 / 0.704 ms at 100 MP)
   const unsigned blocks = (unsigned)std::min<size_t>(cap, (chunks + 15) / 16);
-  hipLaunchKernelGGL(k_pointwise_chain<false>, dim3(blocks ? blocks : 1), dim3(1024), 0, s, a, (uint64_t)npix);
+  IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), k_pointwise_chain<false>, dim3(blocks ? blocks : 1), dim3(1024), 0, s, a, (uint64_t)npix);
   return 0;
 }
 // OpToLab::run on the fast form (the staged op): f.fast_ok / f.mul4 / f.cm12 / f.lab_table as for the chain
@@ -3182,7 +3238,7 @@ int launch_tolab_fast(const FusedLaunch &f, size_t npix, hipStream_t s) {
   // compact, advancing window of the buffer: 1 / 2 / 4 / 8 / 16 / 32 / 64 per CU 0.555 / 0.525 / 0.516 / 0.499 / 0.497 / 0.506 / 0.539 ms at 100 MP
   const unsigned cap = (unsigned)(f.num_cus > 0 ? f.num_cus : 256) * 16u;
   const unsigned blocks = (unsigned)std::min<size_t>(cap, (chunks + 15) / 16);
-  hipLaunchKernelGGL(k_pointwise_chain<true>, dim3(blocks ? blocks : 1), dim3(1024), 0, s, a, (uint64_t)npix);
+  IPK_LAUNCH(k_pointwise_chain<true>, dim3(blocks ? blocks : 1), dim3(1024), 0, s, a, (uint64_t)npix);
   return 0;
 }
 
@@ -3275,9 +3331,9 @@ __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npi
 template <typename SrcT>
 static void launch_raster_t(const FusedArgs &a, size_t npix, int out_type, const void *gamma_reverse, unsigned blocks, hipStream_t s) {
   const LutPair *gr = reinterpret_cast<const LutPair *>(gamma_reverse);
-  if (out_type == 0) hipLaunchKernelGGL((k_raster_chain<SrcT, 0>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
-  else if (out_type == 1) hipLaunchKernelGGL((k_raster_chain<SrcT, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
-  else hipLaunchKernelGGL((k_raster_chain<SrcT, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
+  if (out_type == 0) IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<SrcT, 0>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
+  else if (out_type == 1) IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<SrcT, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
+  else IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<SrcT, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
 }
 // OpToLab..OpGamma + output8bit / output16bit over a 4-channel f32 OpBuffer in one pass (f.out_type 1 or 2; npix >= 256)
 int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s) {
@@ -3287,8 +3343,8 @@ int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s) {
   const size_t chunks = (npix + 255) / 256;
   const unsigned cap = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = std::max(1u, (unsigned)std::min<size_t>(cap, (chunks + 15) / 16));
-  if (f.out_type == 1) hipLaunchKernelGGL((k_raster_chain<Rgbe32, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
-  else hipLaunchKernelGGL((k_raster_chain<Rgbe32, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
+  if (f.out_type == 1) IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<Rgbe32, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
+  else IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<Rgbe32, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
   return 0;
 }
 int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const void *gamma_reverse_pairs, hipStream_t s) {
@@ -3564,7 +3620,7 @@ int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t
   t.lookups = lookups_dev;
   const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = (unsigned)std::min<uint64_t>(cus, tiles);
-  #define IPK_RS_LAUNCH(T, O) hipLaunchKernelGGL((k_fused_resample<T, O>), dim3(blocks), dim3(1024), 0, s, a, t)
+  #define IPK_RS_LAUNCH(T, O) IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_fused_resample<T, O>), dim3(blocks), dim3(1024), 0, s, a, t)
   if (f.src_is_u16) { if (f.out_type == 0) IPK_RS_LAUNCH(uint16_t, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(uint16_t, 1); else IPK_RS_LAUNCH(uint16_t, 2); }
   else { if (f.out_type == 0) IPK_RS_LAUNCH(float, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(float, 1); else IPK_RS_LAUNCH(float, 2); }
   #undef IPK_RS_LAUNCH
@@ -3655,11 +3711,11 @@ __global__ __launch_bounds__(256) void k_mix_probe(const ipk_f4v *__restrict__ s
 }
 void launch_mix_probe(const void *src, void *dst, size_t src_bytes, hipStream_t s) {
   const size_t n16 = src_bytes / 16, per = 256 * kMixU;
-  hipLaunchKernelGGL(k_mix_probe, dim3((unsigned)std::max<size_t>(1, (n16 + per - 1) / per)), dim3(256), 0, s, reinterpret_cast<const ipk_f4v *>(src), reinterpret_cast<ipk_f4v *>(dst), n16);
+  IPK_LAUNCH(k_mix_probe, dim3((unsigned)std::max<size_t>(1, (n16 + per - 1) / per)), dim3(256), 0, s, reinterpret_cast<const ipk_f4v *>(src), reinterpret_cast<ipk_f4v *>(dst), n16);
 }
 void launch_copy_probe(const void *src, void *dst, size_t bytes, int, hipStream_t s) {
   const size_t n16 = bytes / 16;
-  hipLaunchKernelGGL(k_copy_probe, dim3((unsigned)std::max<size_t>(1, (n16 + 1023) / 1024)), dim3(256), 0, s, reinterpret_cast<const ipk_f4v *>(src), reinterpret_cast<ipk_f4v *>(dst), n16);
+  IPK_LAUNCH(k_copy_probe, dim3((unsigned)std::max<size_t>(1, (n16 + 1023) / 1024)), dim3(256), 0, s, reinterpret_cast<const ipk_f4v *>(src), reinterpret_cast<ipk_f4v *>(dst), n16);
 }
 // Shader clock during whatever else the device runs: one wave spins for spin_ticks of the fixed 100 MHz reference counter (s_memrealtime) and reports
 // how far the shader-clock counter (s_memtime) moved meanwhile.  Launched on a second stream beside the kernel under test (bench.py config.shader_clock_GHz).
@@ -3671,7 +3727,7 @@ __global__ __launch_bounds__(64) void k_clock_probe(unsigned long long *out2, un
   if (threadIdx.x == 0) { out2[0] = c1 - c0; out2[1] = r1 - r0; }
 }
 void launch_clock_probe(void *out2_dev, unsigned long long spin_ticks, hipStream_t s) {
-  hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned long long *>(out2_dev), spin_ticks);
+  IPK_LAUNCH(k_clock_probe, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned long long *>(out2_dev), spin_ticks);
 }
 // every f32 argument through the arithmetic 3-knot form against the literal search (curves.rs:126-157)
 __global__ void k_selftest_spline3(SplineDev sp, SelftestOut *out) {
@@ -3732,7 +3788,7 @@ __global__ void k_build_q8(const LutPair *__restrict__ pairs, Q8Entry *__restric
   out[i] = e;
 }
 void launch_build_q8(const void *gam_pairs, void *q8_out, hipStream_t s) {
-  hipLaunchKernelGGL(k_build_q8, dim3(kLutPairs / 256), dim3(256), 0, s, reinterpret_cast<const LutPair *>(gam_pairs), reinterpret_cast<Q8Entry *>(q8_out));
+  IPK_LAUNCH(k_build_q8, dim3(kLutPairs / 256), dim3(256), 0, s, reinterpret_cast<const LutPair *>(gam_pairs), reinterpret_cast<Q8Entry *>(q8_out));
 }
 // every f32 x: OpGamma's step on x followed by output8bit (the literal device forms) against clamp + step lookup (what the 8-bit kernels run)
 __global__ void k_selftest_q8(const LutPair *__restrict__ pairs, const Q8Entry *__restrict__ q8, SelftestOut *out) {
@@ -3758,9 +3814,9 @@ __global__ void k_selftest_quant16(SelftestOut *out) {
   }
   if (bad) { atomicAdd(&out->bad, bad); atomicMin(&out->first_bad, first); }
 }
-int launch_selftest_quant16(void *out_dev, hipStream_t s) { hipLaunchKernelGGL(k_selftest_quant16, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev)); return 0; }
+int launch_selftest_quant16(void *out_dev, hipStream_t s) { IPK_LAUNCH(k_selftest_quant16, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev)); return 0; }
 int launch_selftest_q8(const void *gam_pairs, const void *q8, void *out_dev, hipStream_t s) {
-  hipLaunchKernelGGL(k_selftest_q8, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<const LutPair *>(gam_pairs), reinterpret_cast<const Q8Entry *>(q8), reinterpret_cast<SelftestOut *>(out_dev));
+  IPK_LAUNCH(k_selftest_q8, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<const LutPair *>(gam_pairs), reinterpret_cast<const Q8Entry *>(q8), reinterpret_cast<SelftestOut *>(out_dev));
   return 0;
 }
 // device cbrt variants on an array (the host compares with libm): 0 literal glibc port, 1 select form, 2 fast form for (1,2)
@@ -3774,7 +3830,7 @@ __global__ void k_selftest_cbrt(const float *__restrict__ in, float *__restrict_
 int launch_selftest_cdiv(float c, int variant, unsigned lo_bits, unsigned hi_bits, int include_special, void *out_dev, hipStream_t s) {
   const float rc = 1.0f / c;
   const float rc_lo = (float)(1.0 / (double)c - (double)rc);
-  hipLaunchKernelGGL(k_selftest_cdiv, dim3(256 * 8), dim3(256), 0, s, c, rc, rc_lo, variant, lo_bits, hi_bits, include_special,
+  IPK_LAUNCH(k_selftest_cdiv, dim3(256 * 8), dim3(256), 0, s, c, rc, rc_lo, variant, lo_bits, hi_bits, include_special,
                      reinterpret_cast<SelftestOut *>(out_dev));
   return 0;
 }
@@ -3786,14 +3842,14 @@ int launch_selftest_spline3(const SplineHost &h, void *out_dev, hipStream_t s) {
     d.c1[1] = d.c1[0]; d.c2[1] = d.c2[0]; d.c3[1] = d.c3[0]; d.c1[2] = d.c1[1];
   }
   if (!d.grid_ok && (d.npoints != 3 || !spline3_arith_ok(d))) return -2;
-  hipLaunchKernelGGL(k_selftest_spline3, dim3(256 * 8), dim3(256), 0, s, d, reinterpret_cast<SelftestOut *>(out_dev));
+  IPK_LAUNCH(k_selftest_spline3, dim3(256 * 8), dim3(256), 0, s, d, reinterpret_cast<SelftestOut *>(out_dev));
   return 0;
 }
-int launch_selftest_fract(void *out_dev, hipStream_t s) { hipLaunchKernelGGL(k_selftest_fract, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev)); return 0; }
-int launch_selftest_clamp(void *out_dev, hipStream_t s) { hipLaunchKernelGGL(k_selftest_clamp, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev)); return 0; }
-int launch_selftest_quant8(void *out_dev, int variant, hipStream_t s) { hipLaunchKernelGGL(k_selftest_quant8, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev), variant); return 0; }
+int launch_selftest_fract(void *out_dev, hipStream_t s) { IPK_LAUNCH(k_selftest_fract, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev)); return 0; }
+int launch_selftest_clamp(void *out_dev, hipStream_t s) { IPK_LAUNCH(k_selftest_clamp, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev)); return 0; }
+int launch_selftest_quant8(void *out_dev, int variant, hipStream_t s) { IPK_LAUNCH(k_selftest_quant8, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev), variant); return 0; }
 int launch_selftest_cbrt(const float *in, float *out, size_t n, int variant, hipStream_t s) {
-  hipLaunchKernelGGL(k_selftest_cbrt, dim3(256 * 8), dim3(256), 0, s, in, out, n, variant); return 0;
+  IPK_LAUNCH(k_selftest_cbrt, dim3(256 * 8), dim3(256), 0, s, in, out, n, variant); return 0;
 }
 
 }  // namespace ipk

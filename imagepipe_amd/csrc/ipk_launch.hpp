@@ -36,6 +36,16 @@ void launch_demosaic_full(const float *src, size_t width, size_t img_height, siz
 int launch_demosaic_bayer(const float *src, size_t width, size_t img_height, size_t src_row0, size_t out_row0, size_t out_rows,
                           int xoff, int yoff, const float *gen_cells, int gen_pw, int gen_ph, float *dst4, int num_cus, TaskQueues *queues, hipStream_t s);
 void selftest_task_queue(bool enabled);   // test hook: false = every following launch runs the queue-less static schedule
+// Launch log (test hook, host side only): which kernels of this library were launched while the log was enabled.  One entry per distinct kernel
+// and tag, in the format
+//     <mangled kernel symbol>            or            <mangled kernel symbol>[key=value,key=value...]
+// The symbol is the code object's (hipKernelNameRefByPtr, resolved when the log is READ, never at launch).  The bracketed tag is attached by
+// launchers whose kernel also branches on a value the host knows: k_gamma [vec4=,wrap=], k_output8 / k_output16 [vec4=] (16-byte groups or sample by
+// sample; wrap: the grid cap holds), k_gofloat_cfa_v4 [rowwrap=] (more rows than grid rows), the ipk_raw_scaled_demosaic kernels
+// [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows),
+// k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form).
+void launch_log_enable(bool on);                 // clears the log, then switches it on or off
+size_t launch_log_read(char *buf, size_t cap);   // entries sorted, newline-separated, NUL-terminated (truncated to cap); returns the bytes a full read needs
 
 template <typename T>
 void launch_transform_buffer(const T *src, size_t width, size_t height, int64_t tlx, int64_t tly, int64_t trx, int64_t try_,
@@ -101,7 +111,9 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s);
 // Cfa::demosaic_lookups of a three-colour filter.  Of f, the geometry, the levels, exact_norm and what launch_pointwise_chain reads are used.
 // returns 0, or -4 when the launch could not be enqueued
 int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s);
-// rotate_buffer's permutation on a 1-channel image through an arbitrary source pitch / window (steps in source elements)
+// rotate_buffer's permutation on a 1-channel image through an arbitrary source pitch / window (steps in source elements): |x_step| == 1 (flips, 180
+// degrees) or |y_step| == 1 (the transposing orientations, oheight <= kRotate1MaxTransposedRows)
+constexpr size_t kRotate1MaxTransposedRows = 65535u * 64u;
 template <typename T>
 void launch_rotate1(const T *src, size_t owidth, size_t oheight, int64_t base_offset, int64_t x_step, int64_t y_step, T *dst, hipStream_t s);
 // OpToLab..OpGamma in one pass over a 4-channel f32 buffer (src/dst, mul4, cm12, rgbm9, curve, linear, tables, fast_ok are read)

@@ -343,7 +343,8 @@ IPK_API int ipk_raw_to_srgb_batch(const ipk_fused_params *p, const void *const *
  * 3-channel result: the 1-channel mosaic is permuted instead (rotate_buffer's index walk, :102-128) and the kernel works in
  * rotated space, adding the demosaic taps in the reference's order of the ORIGINAL orientation.  Whole frames (no band) of a
  * three-colour filter whose rotated width is at least 256 pixels, with the common parameter set (finite ordinary multipliers and
- * matrix, a 2- or 3-knot curve, validated levels).  dst receives out_width x out_height x 3 samples of p->out_type.
+ * matrix, a 2- or 3-knot curve, validated levels); for the transposing orientations (Transpose, Rotate90, Transverse, Rotate270) the frame is
+ * at most 65535 * 64 = 4 194 240 columns wide (the mosaic's transposing permutation covers 64 output rows per grid row).  dst receives out_width x out_height x 3 samples of p->out_type.
  * Normal / Unknown: ipk_raw_to_srgb.  Returns IPK_ERR_UNSUPPORTED (nothing written) otherwise: the caller then uses
  * ipk_raw_to_srgb + ipk_rotate_buffer / ipk_rotate_image_*, as ipk_pipeline_run does. */
 IPK_API int ipk_raw_to_srgb_oriented(const ipk_fused_params *p, const void *src, int orientation, void *dst,
@@ -676,6 +677,14 @@ IPK_API int ipk_selftest_cbrtf(const float *in, float *out, size_t n, int varian
  * (the queue-less static schedule: every wave walks the tasks of its index, a whole round of waves apart); 1 restores the queues.  The results
  * are the same bits either way -- which is what tests/test_gpu_fused.py checks for launches that hold more tasks than the chip has waves. */
 IPK_API int ipk_selftest_task_queue(int enabled);
+/* test hook, host side only: the launch log.  ipk_selftest_launch_log(1) clears the log and starts recording which of the library's kernels are
+ * launched (process-wide, any thread, any stream; legal under stream capture); (0) clears it and stops -- a launch then costs one atomic load.
+ * ipk_selftest_launch_log_read copies the log into buf (cap bytes, NUL-terminated, truncated when too small) and returns the bytes a complete read
+ * needs, terminator included; buf = NULL or cap = 0 only asks for that size.  One line per distinct entry, sorted: the kernel's code-object symbol
+ * (mangled), followed by [key=value,...] where the launcher's behaviour also depends on a host-known switch (imagepipe_amd/csrc/ipk_launch.hpp lists
+ * the tags).  Both may be called before ipk_init: the log is then empty (one byte, the terminator). */
+IPK_API int ipk_selftest_launch_log(int enabled);
+IPK_API size_t ipk_selftest_launch_log_read(char *buf, size_t cap);
 /* host-side test hooks of the caching contract: LRU bookkeeping without device memory; SHA-256 known answers */
 IPK_API int ipk_selftest_cache_put(ipk_cache *cache, const uint8_t *key32, size_t bytes);
 IPK_API int ipk_selftest_sha256(const void *data, size_t n, uint8_t *out32);

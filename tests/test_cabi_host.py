@@ -48,6 +48,26 @@ def test_compute_entry_points_fail_loudly_without_gpu(L):
         imagepipe_amd.init()
 
 
+def test_launch_log_calls_behave_without_a_device(L):
+    """ipk_selftest_launch_log / _read are host state: with the library not initialised (no launch has happened in this process) the log is empty
+    whether enabled or not, a NULL / zero-capacity read only reports the size, and a too-small buffer gets a terminated prefix and the full size"""
+    if L.ipk_is_initialized():
+        pytest.skip("the library is initialised in this process")
+    for enabled in (1, 0, 1):
+        assert L.ipk_selftest_launch_log(enabled) == 0
+        assert L.ipk_selftest_launch_log_read(None, 0) == 1              # the terminator alone
+        buf = C.create_string_buffer(b"\x55" * 8, 8)
+        assert L.ipk_selftest_launch_log_read(buf, 0) == 1 and buf.raw == b"\x55" * 8          # cap 0: nothing is written
+        assert L.ipk_selftest_launch_log_read(buf, 1) == 1 and buf.raw == b"\x00" + b"\x55" * 7  # too small for anything but the terminator
+        assert L.ipk_selftest_launch_log_read(buf, 8) == 1 and buf.value == b""
+    assert L.ipk_selftest_launch_log(0) == 0
+    import imagepipe_amd
+    assert imagepipe_amd.read_launch_log() == set()
+    with imagepipe_amd.launch_log() as ran:
+        pass
+    assert ran == set()
+
+
 def test_lut_tables_match_oracle_and_fixture(L, orc):
     for which in range(3):
         t = np.empty(8193, np.float32)
