@@ -447,7 +447,7 @@ static int ctx_build(Context &c, int device) {
     c.libm_matches = -1;
     if (hipMalloc(&din, n * 4) == hipSuccess && hipMalloc(&dout, n * 4) == hipSuccess &&
         hipMemcpy(din, in.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess) {
-      ipk::launch_selftest_cbrt(static_cast<const float *>(din), static_cast<float *>(dout), n, 1, nullptr);
+      ipk::launch_selftest_cbrt(static_cast<const float *>(din), static_cast<float *>(dout), n, 1, nullptr, nullptr);
       if (hipMemcpy(out.data(), dout, n * 4, hipMemcpyDeviceToHost) == hipSuccess) {
         size_t bad = 0;
         for (size_t i = 0; i < n; ++i) { const float h = cbrtf(in[i]); bad += std::memcmp(&h, &out[i], 4) != 0; }
@@ -1389,8 +1389,9 @@ int ipk_selftest_quant8(int variant, uint64_t *n_bad, uint32_t *first_bad_bits) 
 }
 int ipk_selftest_cbrtf(const float *in, float *out, size_t n, int variant, void *stream) {
   REQUIRE_INIT();
-  if (!in || !out || variant < 0 || variant > 2) return fail(IPK_ERR_INVALID, "bad selftest arguments");
-  ipk::launch_selftest_cbrt(in, out, n, variant, S(stream)); HIPCHK(hipGetLastError());
+  // variants 3-5 (one XYZ -> Lab lookup per element, see k_selftest_lab_slot) run whole waves: n in multiples of 256
+  if (!in || !out || variant < 0 || variant > 5 || (variant >= 3 && n % 256 != 0)) return fail(IPK_ERR_INVALID, "bad selftest arguments");
+  ipk::launch_selftest_cbrt(in, out, n, variant, cx().lut_pairs[ipk::kLutXyzLab], S(stream)); HIPCHK(hipGetLastError());
   return IPK_OK;
 }
 

@@ -1787,6 +1787,26 @@ __device__ __forceinline__ float lab_cbrt(float v, bool hi) {
   return cbrtf_glibc_sel(v);
 }
 
+// IPK_LAB_LEAN = 0 builds pointwise4_fast without the row class test: every wave-row takes the general out-of-table ladder (the form up to round 8; A/B builds)
+#ifndef IPK_LAB_LEAN
+#define IPK_LAB_LEAN 1
+#endif
+// unsigned maximum of N values as a tree of three-operand maxima (v_max3_u32): 6 instructions for 12 values
+template <int N>
+__device__ __forceinline__ uint32_t umax_tree(const uint32_t *b) {
+  if constexpr (N == 1) return b[0];
+  else if constexpr (N == 2) return b[0] > b[1] ? b[0] : b[1];
+  else if constexpr (N == 3) { const uint32_t m = b[0] > b[1] ? b[0] : b[1]; return m > b[2] ? m : b[2]; }
+  else {
+    constexpr int M = (N + 2) / 3;
+    uint32_t t[M];
+    #pragma unroll
+    for (int i = 0; i < N / 3; ++i) t[i] = umax_tree<3>(b + 3 * i);
+    if constexpr (N % 3 != 0) t[M - 1] = umax_tree<N % 3>(b + 3 * (N / 3));
+    return umax_tree<M>(t);
+  }
+}
+
 // OpToLab -> OpBaseCurve -> OpFromLab -> OpGamma for the FOUR pixels of a lane, fast form.  Bit-identical to the literal
 // form (pointwise_exact) whenever it returns false; returns true ("bad") for a lane whose inputs leave the zone where
 // that equivalence is proven, and the caller then recomputes the lane's pixels literally.
@@ -1853,54 +1873,9 @@ __device__ __forceinline__ bool pointwise4_fast(const FusedArgs &a, const float 
     const f2 zr = cdiv2s(z, rc_hi(kWhiteZ), rc_lo(kWhiteZ));
     v[6 * g] = xr.x; v[6 * g + 1] = xr.y; v[6 * g + 2] = y[g].x; v[6 * g + 3] = y[g].y; v[6 * g + 4] = zr.x; v[6 * g + 5] = zr.y;
   }
+  constexpr int NS = 6 * NP;
   {
-    float pos[6 * NP]; LutPair e[6 * NP];
-    #pragma unroll
-    for (int k = 0; k < 6 * NP; ++k) pos[k] = v[k] * kLutMaxF;
-    #pragma unroll
-    for (int k = 0; k < 6 * NP; ++k) e[k] = lut_pair_at(s_lab, f32_as_u32_sat(pos[k]));
-    #pragma unroll
-    for (int k = 0; k < 6 * NP; ++k) f[k] = e[k].x + __builtin_amdgcn_fractf(pos[k]) * e[k].y;
-  }
-  // (Tried and measured, round 1: compacting the v > 1 lanes of all 12 slots through a per-wave LDS queue -- ballot + mbcnt
-  // ranks, cbrtf on dense groups of 64, results scattered back -- instead of one cbrtf per slot with most lanes idle.  On
-  // uniform noise, where every slot has a few such lanes, it removes 7 % of the VALU instructions and 6 % of the time
-  // (0.633 -> 0.595 ms); on fully saturated regions it costs 16 %, and every hybrid that keeps the in-place form for dense
-  // slots or rows pays ~3 % on all other data for its extra scalar bookkeeping: photo-like +3.6 %, gradient +3.3 %.  Not kept.
-  // Also measured without effect (+-1 %): one v_max3 tree + a single branch in front of the 12 per-slot checks; one explicit
-  // s_waitcnt lgkmcnt(0) per table stage instead of the compiler's one per consumer.)
-  // (Round 2, the queue retried in two forms, all twelve slots counted first (ballot + s_bcnt1), packed by mbcnt rank into the wave's idle
-  // staging buffer when they fit 128 entries, slot-wise otherwise: noise 0.599 -> 0.668 / 0.739 ms, photo 0.482 -> 0.527, nothing-saturated
-  // 0.465 -> 0.513 / 0.483: the counting alone -- twelve more ballots and scalar adds per wave-row -- costs more than the dense evaluation saves.)
-  // (Round 2, the instruction mix per 256-pixel wave-row, tools/pmc_mix.sh: 920 VALU + 76 scalar + 62 branch/wait + 46 LDS + 6 memory = 1110 at 2.2
-  // wave-cycles each.  ONE s_waitcnt lgkmcnt(0) per table stage (compiler-visible builtin + scheduling barrier; the plain table's subtraction
-  // moved behind it) instead of the compiler's one per consumer removes 19 of them: noise 0.586 -> 0.594 ms, photo 0.470 -> 0.473 -- the
-  // progressive waits let the first lerps start while the last reads are still in flight, and a wait that is already satisfied costs little.)
-  // (Round 2, again without gain: ONE wave-level test -- the OR of the twelve compare masks -- in front of the per-slot tests: noise 0.591 ->
-  // 0.621 ms, photo 0.473 -> 0.480, smooth 0.572 -> 0.595.)
-  // One slot = one table-stage value of all 64 lanes.  Per slot that stays in the table this costs a compare and a branch; a slot with lanes above
-  // 1 adds one compare, the cube root and one select, and the negative / NaN lanes (their own compare: as a bit pattern they are exactly the
-  // values above +inf's) the linear branch.  (Round 2 derived the third mask from the first two -- hipcc moves such a mask through a VGPR to
-  // branch on it -- and copied each mask into vcc: 36 instructions per entered slot, 27 now; the uniform noise frame enters 8 of 12 per row.)
-  // (Round 3, two slots per test -- the x, y or z ratios of a pixel pair under one unsigned maximum and one compare: with the two cube roots side by
-  // side, two independent f64 chains in flight, noise 0.494 -> 0.533 ms, photo-like 0.388 -> 0.383 (a pair is evaluated whenever either slot needs
-  // it); with the slots evaluated one by one inside the pair's branch noise 0.511 -> 0.521, photo-like 0.400 -> 0.395, smooth 0.446 -> 0.450.  Not kept.)
-  #pragma unroll
-  for (int k = 0; k < 6 * NP; ++k) {
-    if (IPK_RARE(__builtin_amdgcn_ballot_w64(__float_as_uint(v[k]) > 0x3F800000u) != 0)) {   // some lane has v > 1, v < 0, -0 or NaN
-      const bool hi = v[k] > 1.0f;
-      // the cube root under the lanes' own mask: the same instructions are issued, but only the lanes above 1 -- a tenth to a third of them on
-      // the noise frame -- switch the f64 data path.  The kernel is bound by the socket's power cap, so what the idle lanes do not burn comes back as clock.
-      // In the common-parameter variants (cm != 0); the linear branch for negative ratios below is masked only where there are no per-pixel
-      // guards (PXG == false): with the guards' registers live as well BOTH masked regions spill (X-Trans full resolution 0.295 -> 0.338 ms with 36
-      // bytes of scratch), the cube root's alone does not (X-Trans noise 0.305 -> 0.288 ms).
-      if (cm != 0) { if (__builtin_amdgcn_ballot_w64(hi) != 0) { if (hi) f[k] = lab_cbrt(v[k], true); } }
-      else if (__builtin_amdgcn_ballot_w64(hi) != 0) { const float c = lab_cbrt(v[k], hi); f[k] = hi ? c : f[k]; }
-      const bool lo = __float_as_uint(v[k]) > 0x7F800000u;            // negative (or -0), or NaN: out of the table and not above 1
-      if (!PXG && cm != 0) { if (__builtin_amdgcn_ballot_w64(lo) != 0) { if (lo) { const float dv = kLabK * v[k] + 16.0f; f[k] = __builtin_fmaf(dv, rc_hi(116.0f), dv * rc_lo(116.0f)); } } }
-      else if (__builtin_amdgcn_ballot_w64(lo) != 0)
-      { const float dv = kLabK * v[k] + 16.0f; const float t = __builtin_fmaf(dv, rc_hi(116.0f), dv * rc_lo(116.0f)); f[k] = lo ? t : f[k]; }
-    }
+#include "ipk_lab_slots.inc"
   }
   f2 rr[NP], gg[NP], bb[NP];
   f2 Lq[NP], Aq[NP], Bq[NP];
@@ -3826,6 +3801,29 @@ __global__ void k_selftest_cbrt(const float *__restrict__ in, float *__restrict_
     out[i] = variant == 0 ? cbrtf_glibc(x) : (variant == 1 ? cbrtf_glibc_sel(x) : cbrtf_glibc_1to2(x));
   }
 }
+template <bool PXG>
+__device__ __forceinline__ void selftest_lab_slot(const LutPair *__restrict__ s_lab, const float (&v)[1], float (&f)[1], const int cm) {
+  constexpr int NS = 1;
+#include "ipk_lab_slots.inc"
+}
+// variants 3, 4, 5: XYZ_LAB_TRANSFORM.lookup of ONE ratio per lane -- 3 and 4 as pointwise4_fast evaluates a slot (table stage, row class test, lean body or general
+// ladder: ipk_lab_slots.inc in the common-parameter form without guards / the generic form with them), 5 the literal lab_lookup they must equal.  A wave's 64 lanes
+// take 64 consecutive inputs, so the caller decides which values share a wave and with it a class test.  n must be a multiple of the block size: every lane of a
+// wave then runs the same number of rounds and the ballots see whole waves.
+// The table sits in LDS as in the kernels it stands for: a ratio far out of the table gives a key far outside it, and only an LDS read may be out of range.
+__global__ __launch_bounds__(256) void k_selftest_lab_slot(const float *__restrict__ in, float *__restrict__ out, size_t n, int variant, const LutPair *__restrict__ lab_pairs) {
+  __shared__ __attribute__((aligned(16))) LutPair lab[kLutPairs + 4];
+  load_lut_pairs(lab, lab_pairs);
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float v[1] = {in[i]};
+    float f[1];
+    if (variant == 3) selftest_lab_slot<false>(lab, v, f, 1);
+    else if (variant == 4) selftest_lab_slot<true>(lab, v, f, 0);
+    else f[0] = lab_lookup(lab, v[0]);
+    out[i] = f[0];
+  }
+}
 
 int launch_selftest_cdiv(float c, int variant, unsigned lo_bits, unsigned hi_bits, int include_special, void *out_dev, hipStream_t s) {
   const float rc = 1.0f / c;
@@ -3848,8 +3846,10 @@ int launch_selftest_spline3(const SplineHost &h, void *out_dev, hipStream_t s) {
 int launch_selftest_fract(void *out_dev, hipStream_t s) { IPK_LAUNCH(k_selftest_fract, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev)); return 0; }
 int launch_selftest_clamp(void *out_dev, hipStream_t s) { IPK_LAUNCH(k_selftest_clamp, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev)); return 0; }
 int launch_selftest_quant8(void *out_dev, int variant, hipStream_t s) { IPK_LAUNCH(k_selftest_quant8, dim3(256 * 8), dim3(256), 0, s, reinterpret_cast<SelftestOut *>(out_dev), variant); return 0; }
-int launch_selftest_cbrt(const float *in, float *out, size_t n, int variant, hipStream_t s) {
-  IPK_LAUNCH(k_selftest_cbrt, dim3(256 * 8), dim3(256), 0, s, in, out, n, variant); return 0;
+int launch_selftest_cbrt(const float *in, float *out, size_t n, int variant, const void *lab_pairs, hipStream_t s) {
+  if (variant >= 3) IPK_LAUNCH(k_selftest_lab_slot, dim3(256 * 8), dim3(256), 0, s, in, out, n, variant, reinterpret_cast<const LutPair *>(lab_pairs));
+  else IPK_LAUNCH(k_selftest_cbrt, dim3(256 * 8), dim3(256), 0, s, in, out, n, variant);
+  return 0;
 }
 
 }  // namespace ipk

@@ -136,6 +136,7 @@ int launch_selftest_quant8(void *out_dev, int variant, hipStream_t s);
 int launch_selftest_quant16(void *out_dev, hipStream_t s);
 void launch_build_q8(const void *gam_pairs, void *q8_out, hipStream_t s);        // q8_out: 8192 x 8 bytes of device memory
 int launch_selftest_q8(const void *gam_pairs, const void *q8, void *out_dev, hipStream_t s);
-int launch_selftest_cbrt(const float *in, float *out, size_t n, int variant, hipStream_t s);
+// variants 0-2: the cube roots; 3-5: one Lab slot as pointwise4_fast evaluates it (3, 4) / the literal lab_lookup (5), on lab_pairs (the XYZ -> Lab pair table)
+int launch_selftest_cbrt(const float *in, float *out, size_t n, int variant, const void *lab_pairs, hipStream_t s);
 
 }  // namespace ipk
