@@ -21,7 +21,7 @@ from ._lib import (IpkError, FusedParams, PipelineDesc, OUT_F32, OUT_U8, OUT_U16
 
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
-           "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "FusedPlan", "IpkError"]
+           "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "FusedPlan", "IpkError"]
 
 _initialized_device = None
 
@@ -599,6 +599,7 @@ class Pipeline:
         self.source_id = 0                    # extension of the hash chain: identifies the frame inside a shared PipelineCache
         self.schedule = 0                     # ipk_pipeline_desc.schedule (IPK_SCHED_AUTO / IPK_SCHED_SPLIT): how a fused launch shares the rows out
         self.fuse_rotatecrop = False          # ipk_pipeline_desc.fuse_rotatecrop: an active OpRotateCrop inside the one launch where fuses_rotatecrop() says so
+        self.fuse_scaledown = False           # ipk_pipeline_desc.fuse_scaledown: OpDemosaic's full + scale_down_opbuf branch inside the one launch where fuses_scaledown() says so
 
     @staticmethod
     def new_from_source(img):
@@ -662,12 +663,18 @@ class Pipeline:
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
+        d.fuse_scaledown = int(self.fuse_scaledown)
         return d
 
     def fuses_rotatecrop(self, out_type=OUT_F32) -> bool:
         """Does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop, host-only)?"""
         d = self.desc()
         return bool(_lib.check(lib().ipk_pipeline_fuses_rotatecrop(C.byref(d), out_type), "ipk_pipeline_fuses_rotatecrop"))
+
+    def fuses_scaledown(self, out_type=OUT_F32) -> bool:
+        """Does the run take the one-launch route through OpDemosaic's full + scale_down_opbuf branch (ipk_pipeline_fuses_scaledown, host-only)?"""
+        d = self.desc()
+        return bool(_lib.check(lib().ipk_pipeline_fuses_scaledown(C.byref(d), out_type), "ipk_pipeline_fuses_scaledown"))
 
     def sizes(self):
         d = self.desc()
@@ -841,4 +848,14 @@ def raw_to_srgb_resampled(src: torch.Tensor, corners, nwidth, nheight, *, out: O
         out = torch.empty(nheight * nwidth * 3, dtype=plan.out_dtype, device="cuda")
     _lib.check(lib().ipk_raw_to_srgb_resampled(plan._ref, src.data_ptr(), *[int(c) for c in corners], nwidth, nheight, out.data_ptr(), _stream()),
                "ipk_raw_to_srgb_resampled")
+    return out
+
+
+def raw_to_srgb_scaled(src: torch.Tensor, nwidth, nheight, *, out: Optional[torch.Tensor] = None, **kw):
+    """ipk_raw_to_srgb_scaled: the fused kernel with scale_down_opbuf(nwidth, nheight) between demosaic and tolab, one launch (OpDemosaic's
+    branch for 1 < scale < minscale).  The keywords are FusedPlan's (no band).  Returns the nheight*nwidth*3 device tensor of the output type."""
+    plan = FusedPlan(**kw)
+    if out is None:
+        out = torch.empty(nheight * nwidth * 3, dtype=plan.out_dtype, device="cuda")
+    _lib.check(lib().ipk_raw_to_srgb_scaled(plan._ref, src.data_ptr(), nwidth, nheight, out.data_ptr(), _stream()), "ipk_raw_to_srgb_scaled")
     return out

@@ -61,7 +61,7 @@ class PipelineDesc(_SizedDesc):
         ("maxwidth", _sz), ("maxheight", _sz),
         ("linear", C.c_int), ("allow_fused", C.c_int), ("use_fastpath", C.c_int),
         ("cfa_width", C.c_int), ("cfa_height", C.c_int),
-        ("schedule", C.c_int), ("fuse_rotatecrop", C.c_int), ("reserved1", C.c_int), ("reserved2", C.c_int),
+        ("schedule", C.c_int), ("fuse_rotatecrop", C.c_int), ("reserved1", C.c_int), ("fuse_scaledown", C.c_int),
     ]
 
 
@@ -144,6 +144,7 @@ SIGNATURES = {
     "ipk_raw_to_srgb_batch": (C.c_int, [C.POINTER(FusedParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp]),
     "ipk_raw_to_srgb_oriented": (C.c_int, [C.POINTER(FusedParams), _vp, C.c_int, _vp, _szp, _szp, _vp]),
     "ipk_raw_to_srgb_resampled": (C.c_int, [C.POINTER(FusedParams), _vp] + _CORNERS + [_sz, _sz, _vp, _vp]),
+    "ipk_raw_to_srgb_scaled": (C.c_int, [C.POINTER(FusedParams), _vp, _sz, _sz, _vp, _vp]),
     "ipk_pipeline_sizes": (C.c_int, [C.POINTER(PipelineDesc), _szp, _szp, _szp, _szp]),
     "ipk_pipeline_run": (C.c_int, [C.POINTER(PipelineDesc), _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp]),
     "ipk_host_pipeline_run": (C.c_int, [C.POINTER(PipelineDesc), _vp, _vp, C.c_int, C.POINTER(C.c_int)]),
@@ -201,6 +202,7 @@ SIGNATURES = {
     "ipk_raster_to_srgb": (C.c_int, [_vp, C.c_int, _sz, _sz, _fp, _fp, C.c_float, _fp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "ipk_pipeline_takes_fastpath": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
     "ipk_pipeline_fuses_rotatecrop": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
+    "ipk_pipeline_fuses_scaledown": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
     "ipk_pipeline_hashes": (C.c_int, [C.POINTER(PipelineDesc), C.c_int, C.c_uint64, C.c_char_p]),
     "ipk_cache_new": (C.c_int, [_sz, C.POINTER(C.c_void_p)]),
     "ipk_cache_free": (C.c_int, [_vp]),

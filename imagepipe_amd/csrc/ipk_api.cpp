@@ -1266,23 +1266,24 @@ int ipk_raster_to_srgb(const void *src, int src_type, size_t width, size_t heigh
   return IPK_OK;
 }
 
-// ipk_raw_to_srgb with scaling::transform_buffer (src/scaling.rs:51-130) between demosaic::full and OpToLab, the corner points being the three
-// OpRotateCrop::run computes (src/ops/rotatecrop.rs:39-64): one launch (k_fused_resample).  Arguments as for ipk_transform_buffer_f32.
-int ipk_raw_to_srgb_resampled(const ipk_fused_params *p, const void *src, int64_t tlx, int64_t tly, int64_t trx, int64_t try_,
-                              int64_t blx, int64_t bly, size_t nwidth, size_t nheight, void *dst, void *stream) {
+// The launch behind ipk_raw_to_srgb_resampled (corners: its six corner coordinates) and ipk_raw_to_srgb_scaled (corners == NULL: scale_down_opbuf's
+// transform), k_fused_resample: the checks both share, then the plan from the cropped frame's sides, or the refusal (nothing is enqueued then)
+static int resampled_launch(const ipk_fused_params *p, const void *src, const int64_t *corners, size_t nwidth, size_t nheight, void *dst, void *stream,
+                            const char *what, const char *refusal) {
   REQUIRE_INIT();
   if (!p || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
   IPK_FOLD_CFA(ipk_fused_params, p)
-  if (p->src_type != IPK_SRC_U16 && p->src_type != IPK_SRC_F32) return fail(IPK_ERR_INVALID, "the resampled fused path takes u16 or f32 CFA data");
+  if (p->src_type != IPK_SRC_U16 && p->src_type != IPK_SRC_F32) return fail(IPK_ERR_INVALID, "the %s fused path takes u16 or f32 CFA data", what);
   if (!dims_ok(p->width, p->height) || p->owidth < p->x + p->width) return fail(IPK_ERR_INVALID, "bad geometry");
   if (p->out_type < 0 || p->out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
-  if (p->band_out_rows != 0) return fail(IPK_ERR_INVALID, "the resampled fused path takes whole frames, not bands");
+  if (p->band_out_rows != 0) return fail(IPK_ERR_INVALID, "the %s fused path takes whole frames, not bands", what);
   ipk::Cfa cfa; DevCfa dev;
   { int rc = get_cfa(p->cfa, cfa, dev); if (rc) return rc; }
   if (!cfa.three_colour()) return fail(IPK_ERR_UNSUPPORTED, "CFA \"%s\" has a fourth colour; run the staged ops", p->cfa);
   ipk::ResamplePlan plan;
-  if (!ipk::resample_plan(p->width, p->height, tlx, tly, trx, try_, blx, bly, nwidth, nheight, plan))
-    return fail(IPK_ERR_UNSUPPORTED, "not a transform the resampled fused path takes (output sides >= 2, finite skips whose magnitudes sum to less than 2 per axis, sides below 2^24); run the staged ops");
+  const bool admitted = corners ? ipk::resample_plan(p->width, p->height, corners[0], corners[1], corners[2], corners[3], corners[4], corners[5], nwidth, nheight, plan)
+                                : ipk::scaledown_plan(p->width, p->height, nwidth, nheight, plan);
+  if (!admitted) return fail(IPK_ERR_UNSUPPORTED, "%s", refusal);
   PointwisePrep pp;
   { int rc = pp.prepare(0, p->wb_coeffs, p->cam_to_xyz_normalized, p->exposure, p->points, p->npoints, p->linear); if (rc) return rc; }
   const size_t esz = p->src_type == IPK_SRC_U16 ? 2 : 4;
@@ -1297,6 +1298,20 @@ int ipk_raw_to_srgb_resampled(const ipk_fused_params *p, const void *src, int64_
     return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
   HIPCHK(hipGetLastError());
   return IPK_OK;
+}
+// ipk_raw_to_srgb with scaling::transform_buffer (src/scaling.rs:51-130) between demosaic::full and OpToLab, the corner points being the three
+// OpRotateCrop::run computes (src/ops/rotatecrop.rs:39-64): one launch (k_fused_resample).  Arguments as for ipk_transform_buffer_f32.
+int ipk_raw_to_srgb_resampled(const ipk_fused_params *p, const void *src, int64_t tlx, int64_t tly, int64_t trx, int64_t try_,
+                              int64_t blx, int64_t bly, size_t nwidth, size_t nheight, void *dst, void *stream) {
+  const int64_t corners[6] = {tlx, tly, trx, try_, blx, bly};
+  return resampled_launch(p, src, corners, nwidth, nheight, dst, stream, "resampled",
+                          "not a transform the resampled fused path takes (output sides >= 2, finite skips whose magnitudes sum to less than 2 per axis, sides below 2^24); run the staged ops");
+}
+// ipk_raw_to_srgb with scale_down_opbuf(nwidth, nheight) (src/scaling.rs:35-48: transform_buffer with the corners (0, 0), (width - 1, 0), (0, height - 1))
+// between demosaic::full and OpToLab -- OpDemosaic::run's last branch (src/ops/demosaic.rs:51-59) -- in the same launch, its axis-aligned mode
+int ipk_raw_to_srgb_scaled(const ipk_fused_params *p, const void *src, size_t nwidth, size_t nheight, void *dst, void *stream) {
+  return resampled_launch(p, src, nullptr, nwidth, nheight, dst, stream, "scaled",
+                          "not a size the scaled fused path takes (output sides >= 2, both skips (side - 1) / (new side - 1) at least 1 and below 3, sides below 2^24); run the staged ops");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1556,6 +1571,7 @@ int negotiate(const ipk_pipeline_desc *d, int out_type, Negotiated &n) {
   if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
+  if (d->fuse_scaledown != 0 && d->fuse_scaledown != 1) return fail(IPK_ERR_INVALID, "fuse_scaledown must be 0 or 1 (got %d)", d->fuse_scaledown);
   // one negotiation: the sizes and the rotatecrop state both come from pipeline_sizes_impl's folds (the reverse fold is seeded
   // with scaling_size of the forward result, pipeline.rs:328-335 -- not with the size run() produces)
   int rc = pipeline_sizes_impl(d, &n.dw, &n.dh, &n.fw, &n.fh, &n.rc); if (rc) return rc;
@@ -1610,6 +1626,18 @@ bool fused_resample_route(const ipk_pipeline_desc *d, const Negotiated &n, int o
     return false;
   if (!rotatecrop_of(d).corners(n.r.width, n.r.height, rcp.pts, rcp.nw, rcp.nh)) return false;
   if (!ipk::resample_plan(n.r.width, n.r.height, rcp.pts[0], rcp.pts[1], rcp.pts[2], rcp.pts[3], rcp.pts[4], rcp.pts[5], rcp.nw, rcp.nh, plan)) return false;
+  fused_params_of(d, n, out_type, fp);
+  return true;
+}
+// ---- OpDemosaic's `full` + scale_down_opbuf branch (demosaic.rs:51-59: 1 < scale < minscale, the near-full-size preview) inside the same launch
+// (ipk_raw_to_srgb_scaled): opted into with fuse_scaledown.  Then fp holds the launch's parameters; the launch resamples the cropped frame to the
+// negotiated n.dw x n.dh.  An active OpRotateCrop behind a scaling OpDemosaic would be a second resampling: such frames stay staged ----
+bool fused_scaledown_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp) {
+  ipk::Cfa cfa; ipk::ResamplePlan plan;
+  if (!(d->fuse_scaledown == 1 && d->allow_fused && n.cfa_branch && d->cpp == 1 && n.rc.noop() && n.scale > 1.0f && ipk::Cfa::parse(d->cfa, cfa) &&
+        cfa.three_colour() && n.scale < ipk::demosaic_minscale(cfa.width)))
+    return false;
+  if (!ipk::scaledown_plan(n.r.width, n.r.height, n.dw, n.dh, plan)) return false;
   fused_params_of(d, n, out_type, fp);
   return true;
 }
@@ -1701,6 +1729,23 @@ int run_fused_resample(const Negotiated &n, const ipk_fused_params &fp, const Ro
   int rc = sc.get(rcp.nw * rcp.nh * 3 * out_elem_size(fp.out_type), &tmp); if (rc) return rc;
   rc = launch(tmp); if (rc < 0) return rc;
   rc = orient(tmp, rcp.nw, rcp.nh, n.orientation, fp.out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
+  return check_produced(n, ow, oh);
+}
+
+// fused_scaledown_route's run, the same shape: the launch writes the n.dw x n.dh image of the output type into dst, or into scratch for orient()
+int run_fused_scaledown(const Negotiated &n, const ipk_fused_params &fp, const void *src, void *dst, StageTimer &tm, void *stream) {
+  tm.rest = "fused gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma";
+  if (n.transform_noop) {
+    int rc = check_produced(n, n.dw, n.dh); if (rc) return rc;
+    return ipk_raw_to_srgb_scaled(&fp, src, n.dw, n.dh, dst, stream);
+  }
+  Scratch sc(S(stream));
+  void *tmp = nullptr;
+  size_t ow = 0, oh = 0;
+  int rc = sc.get(n.dw * n.dh * 3 * out_elem_size(fp.out_type), &tmp); if (rc) return rc;
+  rc = ipk_raw_to_srgb_scaled(&fp, src, n.dw, n.dh, tmp, stream); if (rc < 0) return rc;
+  tm.mark(tm.rest); tm.rest = "transform";
+  rc = orient(tmp, n.dw, n.dh, n.orientation, fp.out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
   return check_produced(n, ow, oh);
 }
 
@@ -1879,6 +1924,7 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
   if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
+  if (d->fuse_scaledown != 0 && d->fuse_scaledown != 1) return fail(IPK_ERR_INVALID, "fuse_scaledown must be 0 or 1 (got %d)", d->fuse_scaledown);
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {
     if (used_fused) *used_fused = 0;
     if (d->width < 1 || d->height < 1) return fail(IPK_ERR_INVALID, "empty source");
@@ -1893,6 +1939,8 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
     rc = run_fused_raw(d, n, fp, src, dst, tm, stream);
   } else if (fused_resample_route(d, n, out_type, fp, rcp)) {
     rc = run_fused_resample(n, fp, rcp, src, dst, tm, stream);
+  } else if (fused_scaledown_route(d, n, out_type, fp)) {
+    rc = run_fused_scaledown(n, fp, src, dst, tm, stream);
   } else if (fused_raster_route(d, n)) {
     tm.rest = "fused gofloat+to_lab+basecurve+from_lab+gamma(+transform)";
     rc = fused_then_orient(d, n, nullptr, out_type, src, dst, stream);
@@ -1910,6 +1958,15 @@ int ipk_pipeline_fuses_rotatecrop(const ipk_pipeline_desc *d, int out_type) {
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return 0;
   ipk_fused_params fp; RotateCropPoints rcp;
   return fused_resample_route(d, n, out_type, fp, rcp) ? 1 : 0;
+}
+// the same report for fuse_scaledown: does OpDemosaic's full + scale_down_opbuf branch run inside the one launch?
+int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type) {
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return 0;
+  ipk_fused_params fp;
+  return fused_scaledown_route(d, n, out_type, fp) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2094,6 +2151,7 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
   if (d->npoints < 0 || d->npoints > 64) return fail(IPK_ERR_INVALID, "npoints out of range");
   if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
+  if (d->fuse_scaledown != 0 && d->fuse_scaledown != 1) return fail(IPK_ERR_INVALID, "fuse_scaledown must be 0 or 1 (got %d)", d->fuse_scaledown);
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // returns before the cache is consulted (pipeline.rs:381-402)
     if (ops_run) *ops_run = 0;
     if (used_fused) *used_fused = 0;
@@ -2125,6 +2183,14 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   if (startpos == 0 && fused_resample_route(d, n, IPK_OUT_F32, fp, rcp)) {   // the same with an active rotatecrop inside the launch
     CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
     { StageTimer tm(st); rc = run_fused_resample(n, fp, rcp, src, o->p, tm, stream); }
+    if (rc < 0) return rc;
+    cache->lru.put(hs[7], o, o->bytes());
+    buf = o; startpos = 8; mask = 0xFF;
+    if (used_fused) *used_fused = rc == IPK_OK;
+  }
+  if (startpos == 0 && fused_scaledown_route(d, n, IPK_OUT_F32, fp)) {       // the same for OpDemosaic's full + scale_down_opbuf branch
+    CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
+    { StageTimer tm(st); rc = run_fused_scaledown(n, fp, src, o->p, tm, stream); }
     if (rc < 0) return rc;
     cache->lru.put(hs[7], o, o->bytes());
     buf = o; startpos = 8; mask = 0xFF;

@@ -511,6 +511,7 @@ constexpr uint32_t kResampleMosCap = 4096;      // mosaic samples of the box and
 struct ResamplePlan {
   float tlx, tly, skip_x_x, skip_x_y, skip_y_x, skip_y_y;   // scaling.rs:68-71
   uint32_t tile_w, tile_h;                                   // output tile: tile_w even, tile_w * tile_h <= 2048 (two pixels per lane)
+  uint32_t axis = 0;                                         // 1: scaledown_plan's axis-aligned windows of up to 4x4 (the kernel's second stage-3 form)
 };
 // Admission (everything else runs the staged ops): a transform whose windows are at most 3x3 -- |skip_x_x| + |skip_y_x| < 2 and |skip_x_y| + |skip_y_y| < 2,
 // finite -- on frames with sides below 2^24, and an output tile whose box fits the LDS above.  The box bound: along one axis the tile's windows lie between
@@ -541,6 +542,44 @@ inline bool resample_plan(size_t width, size_t height, int64_t tlx, int64_t tly,
     if (bw * bh <= kResampleRgbCap && (bw + 2) * (bh + 2) <= kResampleMosCap) { p.tile_w = t[0]; p.tile_h = t[1]; return true; }
   }
   return false;
+}
+
+// ---- the same launch for OpDemosaic's `full` + scale_down_opbuf branch (demosaic.rs:51-59, ipk_raw_to_srgb_scaled): scale_down_opbuf is
+// transform_buffer with the corners (0, 0), (width - 1, 0), (0, height - 1) (scaling.rs:46), so both cross skips are exactly +0.0 and the window of
+// output pixel (row, col) is the axis-aligned floor(skip_x * col) ..= floor(skip_x * (col + 1)) by floor(skip_y * row) ..= floor(skip_y * (row + 1)) ----
+// Admission goes by the skips, not by the scale (width 101 at maxwidth 51 negotiates scale 1.98 and a skip of exactly 2.0): output sides >= 2, both skips
+// finite, >= 1 and < 3 -- windows of at most 4x4 --, sides below 2^24.
+// Tile choice.  A lane of the block owns two output pixels, so a tile of 2048 outputs would fill it; but the tile's source box has to fit the LDS caps
+// above, and at skip s a box holds about cap / s^2 outputs: ~1500 at 1.5, ~900 at 1.93, ~400 at 2.9.  The cap, not the lane count, is the limit, so the
+// plan takes the tile with the MOST outputs whose box fits (resample_plan's table stops at 32x32 = 1024 outputs at 1.5: half the lanes; 64x22 = 1408
+// fit).  Without an angle the box is exactly the tile's span (no bounding-box slack), so among equals the wider tile wins: longer contiguous mosaic rows
+// in stage 1, longer runs per output row in the stores, and the two-pixel halo weighs least on the long side.
+// The box bound: a tile's window ends along x are floor(fl(skip_x * c)) for c in [c0, c0 + tile_w] -- one rounding each, the cross products and the
+// corner being exact zeros -- so they cover at most floor(tile_w * skip_x + slop) + 2 integers, slop as in resample_plan.
+inline bool scaledown_plan(size_t width, size_t height, size_t nwidth, size_t nheight, ResamplePlan &p) {
+  const size_t lim = size_t(1) << 24;
+  if (nwidth < 2 || nheight < 2 || width < 1 || height < 1 || width >= lim || height >= lim || nwidth >= lim || nheight >= lim) return false;
+  if ((uint64_t)nwidth * nheight >= (uint64_t(1) << 36)) return false;
+  p.tlx = 0.0f; p.tly = 0.0f;
+  p.skip_x_x = ((float)(int64_t)(width - 1) - 0.0f) / ((float)(nwidth - 1));     // scaling.rs:69-72 with scaling.rs:46's corners
+  p.skip_x_y = (0.0f - 0.0f) / ((float)(nwidth - 1));
+  p.skip_y_x = (0.0f - 0.0f) / ((float)(nheight - 1));
+  p.skip_y_y = ((float)(int64_t)(height - 1) - 0.0f) / ((float)(nheight - 1));
+  if (!std::isfinite(p.skip_x_x) || !std::isfinite(p.skip_y_y)) return false;
+  if (!(p.skip_x_x >= 1.0f && p.skip_x_x < 3.0f && p.skip_y_y >= 1.0f && p.skip_y_y < 3.0f)) return false;
+  const bool small = width < 65536 && height < 65536 && nwidth < 65536 && nheight < 65536;
+  const double slop = small ? 1.0 / 64.0 : 8.0, sx = (double)p.skip_x_x, sy = (double)p.skip_y_y;
+  static const uint32_t widths[] = {128, 96, 64, 48, 32, 16};
+  uint32_t best = 0;
+  for (const uint32_t tw : widths) {
+    const uint64_t bw = (uint64_t)std::floor(tw * sx + slop) + 2;
+    for (uint32_t th = 2048 / tw; th >= 4 && tw * th > best; --th) {
+      const uint64_t bh = (uint64_t)std::floor(th * sy + slop) + 2;
+      if (bw * bh <= kResampleRgbCap && (bw + 2) * (bh + 2) <= kResampleMosCap) { best = tw * th; p.tile_w = tw; p.tile_h = th; break; }
+    }
+  }
+  p.axis = 1;
+  return best != 0;
 }
 
 }  // namespace ipk

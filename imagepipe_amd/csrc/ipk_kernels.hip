@@ -3357,6 +3357,7 @@ struct ResampleArgs {
   uint32_t nw, nh, tw, th, tiles_x, n_tiles;
   float tlx, tly, skip_x_x, skip_x_y, skip_y_x, skip_y_y, inv_skip_x_x, inv_skip_y_y;
   int fast_x, fast_y;
+  int axis;                              // 1: scale_down_opbuf's transform (scaledown_plan): corner (0, 0), cross skips exactly +0.0, windows of up to 4x4
   const uint32_t *lookups;
 };
 struct RsWin { uint32_t fx, tx, fy, ty; };
@@ -3426,6 +3427,71 @@ __device__ __forceinline__ void rs_store_mosaic(const FusedArgs &a, const RsBox 
       const bool ieee = a.exact_norm != 0 || (!std::is_same<SrcT, uint16_t>::value && cdiv_guard(d));
       s_mos[i] = rs_min(ieee ? d / a.range0 : cdiv_fast(d, a.range0, a.inv_range0), 1.0f);
     }
+  }
+}
+
+// Stage 3's window walk for the axis-aligned transform of scale_down_opbuf (t.axis; scaling.rs:46 hands transform_buffer the corners (0, 0), (w - 1, 0),
+// (0, h - 1)): the lane's two neighbouring pixels of one output row, the same sums in the same order as the general walk in the kernel.
+// What the structure gives.  skip_x_y and skip_y_x are exactly +0.0, so skip_x_y * col and skip_y_x * row are +0.0 for every row and col, and the general
+// expressions (kept as they are, zeros included: no term is dropped) yield window ends and a centre in y that are the same bits for both pixels of the
+// lane, and window ends and a centre in x that do not depend on the row.  Hence per lane ONE y range and one delta_y * delta_y per window row shared by
+// its two pixels, and per pixel its delta_x * delta_x terms computed once in front of the y loop -- (x - center_x) / skip_x_x is the same operation on the
+// same operands whichever window row asks for it -- instead of one division per tap.  Every product and sum is still rounded on its own (the file is
+// built without contraction): factor = 1 - dx2 - dy2, negative -> 0, sums += v * factor (0 * inf stays NaN: zero-weight taps are accumulated), counts +=
+// factor, y outer and x inner per pixel.  Admitted skips are below 3 and windows at most four wide; the four x terms live in registers (unrolled, no
+// indexing), and a tap past the fourth -- none exists for an admitted plan -- would still be walked, by the general per-tap form.
+__device__ __forceinline__ void rs_walk_axis(const ResampleArgs &t, const RsBox &box, uint32_t W, uint32_t H, const float *__restrict__ s_rgb, uint32_t row,
+                                             uint32_t col0, bool row_ok, float center_x_r, float center_y_r, float4 px[2], bool ok[2]) {
+  const uint32_t bx1 = box.x0 + box.w, by1 = box.y0 + box.h;            // one past the box
+  uint32_t fx[2], nx[2];
+  float dx2[2][4], ctr[2], s0[2], s1[2], s2[2], n[2];
+  uint32_t fy = 0u, y_end = 0u;
+  #pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const uint32_t col = col0 + (uint32_t)j;
+    ok[j] = row_ok && col < t.nw;
+    const RsWin w = rs_window(t, W, H, row, col);
+    // clipped to the box as the general walk clips (the window lies inside it by construction); a lane without a pixel walks nothing
+    fx[j] = max(w.fx, box.x0);
+    const uint32_t x_end = ok[j] ? min(w.tx + 1u, bx1) : 0u;
+    nx[j] = x_end > fx[j] ? x_end - fx[j] : 0u;
+    if (j == 0) { fy = max(w.fy, box.y0); y_end = ok[0] ? min(w.ty + 1u, by1) : 0u; }     // pixel 1's are the same bits (above)
+    ctr[j] = center_x_r + (t.skip_x_x * (float)col) + (t.skip_x_x / 2.0f);
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float delta_x = tb_div((float)(fx[j] + (uint32_t)k) - ctr[j], t.skip_x_x, t.inv_skip_x_x, t.fast_x);
+      dx2[j][k] = delta_x * delta_x;
+    }
+    s0[j] = 0.0f; s1[j] = 0.0f; s2[j] = 0.0f; n[j] = 0.0f;
+  }
+  const float center_y = center_y_r + (t.skip_x_y * (float)col0) + (t.skip_x_y / 2.0f);
+  for (uint32_t y = fy; y < y_end; ++y) {
+    const float delta_y = tb_div((float)y - center_y, t.skip_y_y, t.inv_skip_y_y, t.fast_y);
+    const float dy2 = delta_y * delta_y;
+    const float *rowp = s_rgb + 3u * ((y - box.y0) * box.w);
+    #pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const float *p = rowp + 3u * (fx[j] - box.x0);
+      #pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if ((uint32_t)k < nx[j]) {
+          float factor = 1.0f - dx2[j][k] - dy2;                        // scaling.rs:106
+          factor = (factor < 0.0f) ? 0.0f : factor;
+          s0[j] += p[3 * k] * factor; s1[j] += p[3 * k + 1] * factor; s2[j] += p[3 * k + 2] * factor; n[j] += factor;
+        }
+      }
+      for (uint32_t k = 4u; IPK_RARE(k < nx[j]); ++k) {
+        const float delta_x = tb_div((float)(fx[j] + k) - ctr[j], t.skip_x_x, t.inv_skip_x_x, t.fast_x);
+        float factor = 1.0f - (delta_x * delta_x) - dy2;
+        factor = (factor < 0.0f) ? 0.0f : factor;
+        s0[j] += p[3u * k] * factor; s1[j] += p[3u * k + 1u] * factor; s2[j] += p[3u * k + 2u] * factor; n[j] += factor;
+      }
+    }
+  }
+  #pragma unroll
+  for (int j = 0; j < 2; ++j) {                                         // scaling.rs:122-126: components without weight keep the zero fill
+    const bool has = n[j] > 0.0f;
+    px[j] = make_float4(has ? s0[j] / n[j] : 0.0f, has ? s1[j] / n[j] : 0.0f, has ? s2[j] / n[j] : 0.0f, 0.0f);
   }
 }
 
@@ -3501,35 +3567,39 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
       const float center_y_r = t.tly + (t.skip_y_y * (float)row) + (t.skip_y_y / 2.0f) - 0.5f;
       float4 px[2];
       bool ok[2];
-      #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const uint32_t col = col0 + (uint32_t)j;
-        ok[j] = row_ok && col < t.nw;
-        const RsWin w = rs_window(t, a.W, a.H, row, col);
-        // the window lies inside the box by construction; the clip keeps the LDS reads in bounds even where the box had to be cut (rs_box).
-        // x_end / y_end: one past the last tap (window ends are frame coordinates, below 2^24); a lane without a pixel walks nothing
-        const uint32_t fx = max(w.fx, box.x0), fy = max(w.fy, box.y0);
-        const uint32_t x_end = ok[j] ? min(w.tx + 1u, bx1) : 0u, y_end = ok[j] ? min(w.ty + 1u, by1) : 0u;
-        const float center_x = center_x_r + (t.skip_x_x * (float)col) + (t.skip_x_x / 2.0f);
-        const float center_y = center_y_r + (t.skip_x_y * (float)col) + (t.skip_x_y / 2.0f);
-        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, n = 0.0f;
-        for (uint32_t y = fy; y < y_end; ++y) {
-          const float dyv = (float)y - center_y;
-          const float delta_y = tb_div(dyv, t.skip_y_y, t.inv_skip_y_y, t.fast_y);
-          const float dy2 = delta_y * delta_y;
-          const uint32_t rowi = (y - box.y0) * box.w;
-          for (uint32_t x = fx; x < x_end; ++x) {
-            const float dxv = (float)x - center_x;
-            const float delta_x = tb_div(dxv, t.skip_x_x, t.inv_skip_x_x, t.fast_x);
-            float factor = 1.0f - (delta_x * delta_x) - dy2;              // scaling.rs:106
-            factor = (factor < 0.0f) ? 0.0f : factor;
-            const float *p = s_rgb + 3u * (rowi + (x - box.x0));
-            s0 += p[0] * factor; s1 += p[1] * factor; s2 += p[2] * factor; n += factor;
+      if (t.axis) {                                                     // block-uniform: the launch's mode
+        rs_walk_axis(t, box, a.W, a.H, s_rgb, row, col0, row_ok, center_x_r, center_y_r, px, ok);
+      } else {
+        #pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const uint32_t col = col0 + (uint32_t)j;
+          ok[j] = row_ok && col < t.nw;
+          const RsWin w = rs_window(t, a.W, a.H, row, col);
+          // the window lies inside the box by construction; the clip keeps the LDS reads in bounds even where the box had to be cut (rs_box).
+          // x_end / y_end: one past the last tap (window ends are frame coordinates, below 2^24); a lane without a pixel walks nothing
+          const uint32_t fx = max(w.fx, box.x0), fy = max(w.fy, box.y0);
+          const uint32_t x_end = ok[j] ? min(w.tx + 1u, bx1) : 0u, y_end = ok[j] ? min(w.ty + 1u, by1) : 0u;
+          const float center_x = center_x_r + (t.skip_x_x * (float)col) + (t.skip_x_x / 2.0f);
+          const float center_y = center_y_r + (t.skip_x_y * (float)col) + (t.skip_x_y / 2.0f);
+          float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, n = 0.0f;
+          for (uint32_t y = fy; y < y_end; ++y) {
+            const float dyv = (float)y - center_y;
+            const float delta_y = tb_div(dyv, t.skip_y_y, t.inv_skip_y_y, t.fast_y);
+            const float dy2 = delta_y * delta_y;
+            const uint32_t rowi = (y - box.y0) * box.w;
+            for (uint32_t x = fx; x < x_end; ++x) {
+              const float dxv = (float)x - center_x;
+              const float delta_x = tb_div(dxv, t.skip_x_x, t.inv_skip_x_x, t.fast_x);
+              float factor = 1.0f - (delta_x * delta_x) - dy2;              // scaling.rs:106
+              factor = (factor < 0.0f) ? 0.0f : factor;
+              const float *p = s_rgb + 3u * (rowi + (x - box.x0));
+              s0 += p[0] * factor; s1 += p[1] * factor; s2 += p[2] * factor; n += factor;
+            }
           }
+          // scaling.rs:122-126: components without weight keep the zero fill
+          const bool has = n > 0.0f;
+          px[j] = make_float4(has ? s0 / n : 0.0f, has ? s1 / n : 0.0f, has ? s2 / n : 0.0f, 0.0f);
         }
-        // scaling.rs:122-126: components without weight keep the zero fill
-        const bool has = n > 0.0f;
-        px[j] = make_float4(has ? s0 / n : 0.0f, has ? s1 / n : 0.0f, has ? s2 / n : 0.0f, 0.0f);
       }
       PixOut o[2];
       bool bad = a.fast_ok == 0;
@@ -3592,10 +3662,13 @@ int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t
   t.skip_x_x = plan.skip_x_x; t.skip_x_y = plan.skip_x_y; t.skip_y_x = plan.skip_y_x; t.skip_y_y = plan.skip_y_y;
   t.inv_skip_x_x = 1.0f / t.skip_x_x; t.inv_skip_y_y = 1.0f / t.skip_y_y;
   t.fast_x = cdiv_host_ok(t.skip_x_x); t.fast_y = cdiv_host_ok(t.skip_y_y);
+  t.axis = plan.axis ? 1 : 0;
   t.lookups = lookups_dev;
   const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = (unsigned)std::min<uint64_t>(cus, tiles);
-  #define IPK_RS_LAUNCH(T, O) IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_fused_resample<T, O>), dim3(blocks), dim3(1024), 0, s, a, t)
+  // the general mode's tags stay as they were; the axis-aligned mode (scaledown_plan) adds its own key
+  const char *tag = t.axis ? (a.fast_ok ? "fast_ok=1,axis=1" : "fast_ok=0,axis=1") : (a.fast_ok ? "fast_ok=1" : "fast_ok=0");
+  #define IPK_RS_LAUNCH(T, O) IPK_LAUNCH_TAG(tag, (k_fused_resample<T, O>), dim3(blocks), dim3(1024), 0, s, a, t)
   if (f.src_is_u16) { if (f.out_type == 0) IPK_RS_LAUNCH(uint16_t, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(uint16_t, 1); else IPK_RS_LAUNCH(uint16_t, 2); }
   else { if (f.out_type == 0) IPK_RS_LAUNCH(float, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(float, 1); else IPK_RS_LAUNCH(float, 2); }
   #undef IPK_RS_LAUNCH

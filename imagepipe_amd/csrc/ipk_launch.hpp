@@ -43,7 +43,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // launchers whose kernel also branches on a value the host knows: k_gamma [vec4=,wrap=], k_output8 / k_output16 [vec4=] (16-byte groups or sample by
 // sample; wrap: the grid cap holds), k_gofloat_cfa_v4 [rowwrap=] (more rows than grid rows), the ipk_raw_scaled_demosaic kernels
 // [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows),
-// k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form).
+// k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form);
+// k_fused_resample's axis-aligned mode (ipk_raw_to_srgb_scaled) [fast_ok=,axis=1].
 void launch_log_enable(bool on);                 // clears the log, then switches it on or off
 size_t launch_log_read(char *buf, size_t cap);   // entries sorted, newline-separated, NUL-terminated (truncated to cap); returns the bytes a full read needs
 
@@ -110,6 +111,7 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s);
 // sample (pitch f.owidth), f.width x f.height the cropped frame, f.dst = nwidth * nheight * 3 samples of f.out_type; `lookups` = the device image of
 // Cfa::demosaic_lookups of a three-colour filter.  Of f, the geometry, the levels, exact_norm and what launch_pointwise_chain reads are used.
 // returns 0, or -4 when the launch could not be enqueued
+// plan.axis (scaledown_plan): the kernel's axis-aligned stage 3, for scale_down_opbuf's transform
 int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s);
 // rotate_buffer's permutation on a 1-channel image through an arbitrary source pitch / window (steps in source elements): |x_step| == 1 (flips, 180
 // degrees) or |y_step| == 1 (the transposing orientations, oheight <= kRotate1MaxTransposedRows)

@@ -361,6 +361,15 @@ IPK_API int ipk_raw_to_srgb_oriented(const ipk_fused_params *p, const void *src,
  * of 2^24 or more.  A zero skip is taken: its division by zero is the reference's and comes out the same. */
 IPK_API int ipk_raw_to_srgb_resampled(const ipk_fused_params *p, const void *src, int64_t tlx, int64_t tly, int64_t trx, int64_t try_,
                                       int64_t blx, int64_t bly, size_t nwidth, size_t nheight, void *dst, void *stream);
+/* ipk_raw_to_srgb with scale_down_opbuf(nwidth, nheight) between demosaic::full and OpToLab -- what Pipeline::run computes for a CFA mosaic under a size
+ * limit that is close to its full size: OpDemosaic::run's last branch, `full` followed by scale_down_opbuf for 1 < scale < minscale
+ * (src/ops/demosaic.rs:51-59; scale_down_opbuf is transform_buffer with the corners (0, 0), (width - 1, 0), (0, height - 1), src/scaling.rs:35-48 and
+ * :51-130) -- as ONE launch, the axis-aligned mode of ipk_raw_to_srgb_resampled's kernel.  dst receives nwidth * nheight * 3 samples of p->out_type,
+ * bit-identical to ipk_gofloat_cfa_* + ipk_demosaic_full + ipk_scale_down_opbuf + ipk_pointwise_chain(_out).  Whole frames (no band) of a
+ * three-colour filter.  IPK_ERR_UNSUPPORTED (nothing written) for sizes the launch does not take: nwidth or nheight below 2, a skip
+ * (p->width - 1) / (nwidth - 1) or (p->height - 1) / (nheight - 1) (in f32, src/scaling.rs:69-72) that is not finite, below 1, or 3 or more (windows
+ * larger than 4x4: ipk_raw_scaled_demosaic's range for most filters), frame sides of 2^24 or more. */
+IPK_API int ipk_raw_to_srgb_scaled(const ipk_fused_params *p, const void *src, size_t nwidth, size_t nheight, void *dst, void *stream);
 
 /* OpToLab::run + OpBaseCurve::run + OpFromLab::run + OpGamma::run (src/ops/colorspaces.rs:89-112, src/ops/curves.rs:33-49,
  * src/ops/colorspaces.rs:127-137, src/ops/gamma.rs:16-26) in one pass over a 4-channel OpBuffer: the ops Pipeline::run applies
@@ -417,7 +426,11 @@ typedef struct {
   int fuse_rotatecrop;             /* 1: an active OpRotateCrop on a CFA mosaic runs as ONE launch where ipk_pipeline_fuses_rotatecrop says so; 0 (the default, and
                                       what every earlier caller has always written into this formerly reserved field): such frames take the staged ops.  Other
                                       values are refused with IPK_ERR_INVALID.  Results do not depend on it; like allow_fused it does not enter the hashes. */
-  int reserved1, reserved2;        /* 0 (the struct's end moves past the second layout's tail padding, so that a size tells the layouts apart) */
+  int reserved1;                   /* 0 (the struct's end moves past the second layout's tail padding, so that a size tells the layouts apart) */
+  int fuse_scaledown;              /* 1: OpDemosaic's `full` + scale_down_opbuf branch (1 < scale < minscale, demosaic.rs:51-59) runs inside ONE raw-to-sRGB launch where
+                                      ipk_pipeline_fuses_scaledown says so; 0 (the default, and what every earlier caller wrote into this formerly reserved field):
+                                      the staged ops.  The same contract as fuse_rotatecrop: other values are IPK_ERR_INVALID, results do not depend on it, it does
+                                      not enter the hashes, and it is not read from objects of an older layout. */
 } ipk_pipeline_desc;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -450,6 +463,14 @@ IPK_API int ipk_pipeline_takes_fastpath(const ipk_pipeline_desc *d, int out_type
  * scales by 1.00025 and the frame stays staged, whatever the flag says.  0 otherwise; a negative error code for a descriptor ipk_pipeline_sizes
  * refuses, and for a fuse_rotatecrop other than 0 or 1.  No GPU needed. */
 IPK_API int ipk_pipeline_fuses_rotatecrop(const ipk_pipeline_desc *d, int out_type);
+/* Does ipk_pipeline_run (and the cached, batch and host drivers) run OpDemosaic's `full` + scale_down_opbuf branch inside ONE launch
+ * (ipk_raw_to_srgb_scaled, then OpTransform's permutation if there is one)?  1 when d->fuse_scaledown and d->allow_fused are set, the source is a
+ * one-sample-per-pixel CFA mosaic with a three-colour filter, OpRotateCrop is a no-op, 1 < scale < minscale (src/ops/demosaic.rs:33-39) and the launch
+ * takes the negotiated demosaic size (both skips at least 1 and below 3: a 101-wide frame at maxwidth 51 has scale 1.98 and a skip of exactly 2.0 and is
+ * taken; a 150x100 X-Trans frame at maxwidth 52 has a scale below 3 but a skip of 3.0 and stays staged).  0 otherwise; a negative error code for a
+ * descriptor ipk_pipeline_sizes refuses, and for a fuse_scaledown other than 0 or 1.  ipk_pipeline_fuses_rotatecrop keeps answering 0 wherever
+ * OpDemosaic scales.  No GPU needed. */
+IPK_API int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type);
 /* do_timing! (src/pipeline.rs:68-80: the reference logs the wall time of every op of Pipeline::run): ipk_timing_begin arms the calling
  * thread, the following ipk_pipeline_run call(s) on it bracket every stage they enqueue with hipEvents on their stream, ipk_timing_end
  * waits for the last one and returns the stages in execution order under the reference's op names ("gofloat", "demosaic", "rotatecrop",

@@ -2,6 +2,7 @@
 """Writes the number-carrying parts of the documentation FROM the tracked evidence files, so that text cannot drift from them:
    DESIGN.md            the block between <!-- BEGIN GENERATED: at-a-glance --> and <!-- END GENERATED: at-a-glance -->
    profiles/README.md   the block between <!-- BEGIN GENERATED: round --> and <!-- END GENERATED: round -->
+   DESIGN.md            the block between <!-- BEGIN GENERATED: scaledown --> and <!-- END GENERATED: scaledown --> (profiles/r10_scaledown.txt, tools/scaledown_probe.py)
 Sources: profiles/<TAG>_counters.json, _variants.csv, _staged_kernels.csv, _valu_model.json (tools/evidence_summarize.py).
 usage: tools/evidence_readme.py [TAG]          rewrite both blocks
        tools/evidence_readme.py [TAG] --check  exit 1 when a block is stale (tests/test_docs_generated.py)"""
@@ -148,6 +149,23 @@ def round_block():
     return "\n".join(out)
 
 
+def scaledown():
+    """the acceptance lines of tools/scaledown_probe.py, condensed: parent -> flagged medians of the new route, and the old mode's ratio"""
+    new, old = [], []
+    f = os.path.join(P, "r10_scaledown.txt")
+    if not os.path.exists(f):
+        return "  Not measured yet: `tools/scaledown_probe.py` writes `profiles/r10_scaledown.txt`."
+    for line in open(f):
+        m = re.match(r"(\S+) .*?(\S+->\S+)\s+-> \S+\s+parent ([\d.]+) ms \(spread [\d.]+\)  flag 0 [\d.]+ ms  flag 1 ([\d.]+) ms  speed-up ([\d.]+)x  (accepted|NOT accepted)", line)
+        if m:
+            new.append(("%s %s %s → %s ms (%s×)" % (m.group(1), m.group(2).replace("->", "→"), m.group(3)[:-1], m.group(4)[:-1], m.group(5)), m.group(6) == "accepted"))
+        m = re.match(r".*parent [\d.]+ ms \(spread [\d.]+\)  this build [\d.]+ ms  ratio ([\d.]+)  (accepted|NOT accepted)", line)
+        if m:
+            old.append((float(m.group(1)), m.group(2) == "accepted"))
+    return "  `r10_scaledown.txt`, parent staged → flagged: %s; %d of %d beat the parent by more than its spread. `fuse_rotatecrop` cases, this build / parent: %.3f–%.3f, %d of %d within the spread." % (
+        ", ".join(t for t, _ in new), sum(ok for _, ok in new), len(new), min(r for r, _ in old), max(r for r, _ in old), sum(ok for _, ok in old), len(old))
+
+
 def splice(path, marker, text):
     s = open(path).read()
     a, b = "<!-- BEGIN GENERATED: %s -->" % marker, "<!-- END GENERATED: %s -->" % marker
@@ -166,4 +184,5 @@ def splice(path, marker, text):
 
 ok = splice(os.path.join(ROOT, "DESIGN.md"), "at-a-glance", glance())
 ok = splice(os.path.join(P, "README.md"), "round", round_block()) and ok
+ok = splice(os.path.join(ROOT, "DESIGN.md"), "scaledown", scaledown()) and ok
 sys.exit(0 if ok else 1)
