@@ -330,6 +330,10 @@ typedef struct {
 
 /* src: device pointer to the sensor data (element (0,0) of the uncropped frame, or of the band's
  * first source row); dst: device pointer to width*rows*3 elements of out_type.
+ * src and dst need only the alignment of their element type (u16 samples 2 bytes, f32 4, u8 results 1): a frame packed behind another in one
+ * allocation, a u16 frame 2 bytes off a dword boundary or an f32 buffer 4 bytes off a 16-byte boundary give the same bits, and nothing outside
+ * dst's width*rows*3 elements is written.  The same holds for the batch, oriented, resampled and scaled forms below, for ipk_pipeline_run and
+ * ipk_pipeline_run_region, ipk_demosaic_full and ipk_stream_probe (tests/test_gpu_buffer_bounds.py).
  * Any colour filter without a fourth colour is accepted (the four RGGB phases, X-Trans, 12x12, 16 letters with a stated shape ...; pattern strings: see ipk_cfa_shift); fails with
  * IPK_ERR_UNSUPPORTED for RGBE-style filters (callers then run the staged ops). */
 IPK_API int ipk_raw_to_srgb(const ipk_fused_params *p, const void *src, void *dst, void *stream);

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import util
-from util import assert_bits_equal
+from util import Guarded, assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -74,26 +74,6 @@ def _same(got, want, what):
         assert_bits_equal(got, want, what)
     else:
         assert got.shape == want.shape and np.array_equal(got, want), "%s: %d samples differ" % (what, int((got != want).sum()) if got.shape == want.shape else -1)
-
-
-class Guarded:
-    """a destination of n elements inside a larger allocation, `off` elements past a 256-byte boundary, with a band of sentinels on both sides"""
-    BAND = 64
-
-    def __init__(self, n, dtype, off=0):
-        import torch
-        self.n, self.off, self.np_dtype = n, off, {torch.float32: np.float32, torch.uint8: np.uint8, torch.int16: np.uint16}[dtype]
-        self.sentinel = {torch.float32: -7.0, torch.uint8: 0xA5, torch.int16: 0x5A5A}[dtype]
-        self.t = torch.full((n + 2 * self.BAND + off,), self.sentinel, dtype=dtype, device="cuda")
-        self.ptr = self.t.data_ptr() + (self.BAND + off) * self.t.element_size()
-
-    def result(self):
-        a = self.t.cpu().numpy()
-        a = a.view(np.uint16) if self.np_dtype == np.uint16 else a
-        lo, hi = self.BAND + self.off, self.BAND + self.off + self.n
-        s = np.array(self.sentinel).astype(a.dtype)
-        assert np.all(a[:lo] == s) and np.all(a[hi:] == s), "the guard band around the destination was written"
-        return a[lo:hi]
 
 
 # =============================================================================================
