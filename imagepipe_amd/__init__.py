@@ -600,6 +600,7 @@ class Pipeline:
         self.schedule = 0                     # ipk_pipeline_desc.schedule (IPK_SCHED_AUTO / IPK_SCHED_SPLIT): how a fused launch shares the rows out
         self.fuse_rotatecrop = False          # ipk_pipeline_desc.fuse_rotatecrop: an active OpRotateCrop inside the one launch where fuses_rotatecrop() says so
         self.fuse_scaledown = False           # ipk_pipeline_desc.fuse_scaledown: OpDemosaic's full + scale_down_opbuf branch inside the one launch where fuses_scaledown() says so
+        self.fuse_four_colour = False         # ipk_pipeline_desc.allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR): a filter with a fourth colour (RGBE ...) on the one-launch route where fuses_four_colour() says so
 
     @staticmethod
     def new_from_source(img):
@@ -660,6 +661,8 @@ class Pipeline:
         d.maxwidth, d.maxheight = st.maxwidth, st.maxheight
         d.linear = int(st.linear)
         d.allow_fused = int(self.allow_fused)
+        if self.fuse_four_colour and d.allow_fused:
+            d.allow_fused |= _lib.FUSED_FOUR_COLOUR
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -675,6 +678,11 @@ class Pipeline:
         """Does the run take the one-launch route through OpDemosaic's full + scale_down_opbuf branch (ipk_pipeline_fuses_scaledown, host-only)?"""
         d = self.desc()
         return bool(_lib.check(lib().ipk_pipeline_fuses_scaledown(C.byref(d), out_type), "ipk_pipeline_fuses_scaledown"))
+
+    def fuses_four_colour(self, out_type=OUT_F32) -> bool:
+        """Does the run take the one-launch route with its four-colour filter (ipk_pipeline_fuses_four_colour, host-only)?"""
+        d = self.desc()
+        return bool(_lib.check(lib().ipk_pipeline_fuses_four_colour(C.byref(d), out_type), "ipk_pipeline_fuses_four_colour"))
 
     def sizes(self):
         d = self.desc()
@@ -761,9 +769,10 @@ class FusedPlan:
 
     def __init__(self, *, width, height, owidth=None, x=0, y=0, is_float=True, black0=0.0, white0=1.0,
                  cfa="RGGB", wb_coeffs=(1.0, 1.0, 1.0, float("nan")), cam_to_xyz_normalized=None, exposure=0.0,
-                 points=((0.5, 0.6),), linear=False, out_type=OUT_F32, band=None, schedule=0):
+                 points=((0.5, 0.6),), linear=False, out_type=OUT_F32, band=None, schedule=0, four_colour=False):
         init()
         p = FusedParams()
+        p.four_colour = int(four_colour)            # 1: a filter with a fourth colour (RGBE ...) is taken (ipk_raw_to_srgb, its batch and host forms); 0: refused
         p.schedule = int(schedule)                  # ipk_schedule: IPK_SCHED_AUTO / IPK_SCHED_SPLIT (results do not depend on it)
         p.src_type = SRC_F32 if is_float else SRC_U16
         p.owidth = owidth if owidth is not None else width
@@ -832,7 +841,8 @@ class FusedBatchPlan:
 
 
 def raw_to_srgb(src: torch.Tensor, *, out: Optional[torch.Tensor] = None, **kw):
-    """The fused kernel through the C ABI (ipk_raw_to_srgb); `band` = (src_row0, src_rows, out_row0, out_rows)."""
+    """The fused kernel through the C ABI (ipk_raw_to_srgb); `band` = (src_row0, src_rows, out_row0, out_rows); `four_colour=True` admits
+    filters with a fourth colour (RGBE ...), which are refused otherwise."""
     plan = FusedPlan(**kw)
     if out is None:
         out = plan.new_output()

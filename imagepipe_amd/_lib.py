@@ -13,6 +13,7 @@ IPK_OK, IPK_NOOP = 0, 1
 SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16 = 0, 1, 2, 3
 OUT_F32, OUT_U8, OUT_U16 = 0, 1, 2
 SCHED_AUTO, SCHED_SPLIT = 0, 1
+FUSED_ON, FUSED_FOUR_COLOUR = 1, 2          # ipk_pipeline_desc.allow_fused
 OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN = range(9)
 ROT_NORMAL, ROT_90, ROT_180, ROT_270 = range(4)
 
@@ -43,7 +44,7 @@ class FusedParams(_SizedDesc):
         ("linear", C.c_int), ("out_type", C.c_int),
         ("band_src_row0", _sz), ("band_src_rows", _sz), ("band_out_row0", _sz), ("band_out_rows", _sz),
         ("cfa_width", C.c_int), ("cfa_height", C.c_int),           # later additions are appended, never inserted
-        ("schedule", C.c_int), ("reserved0", C.c_int),
+        ("schedule", C.c_int), ("four_colour", C.c_int),
     ]
 
 
@@ -203,6 +204,7 @@ SIGNATURES = {
     "ipk_pipeline_takes_fastpath": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
     "ipk_pipeline_fuses_rotatecrop": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
     "ipk_pipeline_fuses_scaledown": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
+    "ipk_pipeline_fuses_four_colour": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
     "ipk_pipeline_hashes": (C.c_int, [C.POINTER(PipelineDesc), C.c_int, C.c_uint64, C.c_char_p]),
     "ipk_cache_new": (C.c_int, [_sz, C.POINTER(C.c_void_p)]),
     "ipk_cache_free": (C.c_int, [_vp]),

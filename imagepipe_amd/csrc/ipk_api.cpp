@@ -35,7 +35,7 @@ int fail(int code, const char *fmt, ...) {
   do { hipError_t e_ = (expr);                                                                     \
        if (e_ != hipSuccess) return fail(IPK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
 
-struct DevCfa { uint32_t *lookups = nullptr; uint8_t *cfa48 = nullptr; float *gen_cells = nullptr; int gen_pw = 0, gen_ph = 0; };   // gen_cells: null for filters with a fourth colour
+struct DevCfa { uint32_t *lookups = nullptr; uint8_t *cfa48 = nullptr; float *gen_cells = nullptr; int gen_pw = 0, gen_ph = 0; };   // gen_cells: the row-walking kernel's cell records (Cfa::gen_cells; a filter with a fourth colour has them too)
 
 }  // namespace
 
@@ -768,7 +768,7 @@ int ipk_demosaic_full_band(const float *src, size_t width, size_t img_height, si
   int lrc = 0;
   if (cfa.bayer_phase(xoff, yoff))       // the four RGGB phases: row-walking kernel (coalesced loads, register window, staged stores)
     lrc = ipk::launch_demosaic_bayer(src, width, img_height, src_row0, out_row0, out_rows, xoff, yoff, nullptr, 0, 0, dst4, cx().num_cus, cx().queues, S(stream));
-  else if (dev.gen_cells)                // any other three-colour filter (X-Trans ...): same kernel, generic-CFA mode
+  else if (dev.gen_cells && cfa.three_colour())   // any other three-colour filter (X-Trans ...): same kernel, generic-CFA mode
     lrc = ipk::launch_demosaic_bayer(src, width, img_height, src_row0, out_row0, out_rows, 0, 0, dev.gen_cells, dev.gen_pw, dev.gen_ph, dst4, cx().num_cus, cx().queues, S(stream));
   else ipk::launch_demosaic_full(src, width, img_height, src_row0, out_row0, out_rows, dev.lookups, dst4, S(stream));
   if (lrc) return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
@@ -1005,7 +1005,7 @@ static int get_rot_cells(const char *pat, const ipk::Cfa &cfa, int ori, size_t w
   auto it = cx().rot_cells.find(key);
   if (it != cx().rot_cells.end()) { *out = it->second; return IPK_OK; }
   std::vector<float> cells;
-  if (!cfa.gen_cells(cells)) return fail(IPK_ERR_UNSUPPORTED, "CFA has a fourth colour");
+  if (!cfa.three_colour() || !cfa.gen_cells(cells)) return fail(IPK_ERR_UNSUPPORTED, "CFA has a fourth colour");
   const int rpw = t ? ph : pw, rph = t ? pw : ph;          // rotated pattern: width follows the sensor rows when transposed
   std::vector<float> rot((size_t)rpw * rph * ipk::Cfa::kGenCellFloats);
   for (int y = 0; y < rph; ++y)
@@ -1028,20 +1028,34 @@ static int get_rot_cells(const char *pat, const ipk::Cfa &cfa, int ori, size_t w
 // so that dst receives OpTransform's output directly; IPK_ERR_UNSUPPORTED (nothing launched) when no such variant exists.
 // nbatch > 0: the frames srcs[0..nbatch) -> dsts[0..nbatch), all with the geometry and parameters of *p (src / dst = the first pair)
 // win_c1 > 0: a region -- only the columns [win_c0, win_c1) of the band's rows are computed and stored, packed, into dst (ori 0, one frame)
-static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, void *stream, int ori,
-                      size_t nbatch = 0, const void *const *srcs = nullptr, void *const *dsts = nullptr, bool probe = false,
-                      size_t win_c0 = 0, size_t win_c1 = 0) {
+// four_ok: the entry point honours p->four_colour (ipk_raw_to_srgb, its batch and host forms, the region launch say so); every other caller, and any
+// added later, refuses a fourth colour whatever the field says
+struct FusedOpts {
+  size_t nbatch = 0; const void *const *srcs = nullptr; void *const *dsts = nullptr;
+  bool probe = false;
+  size_t win_c0 = 0, win_c1 = 0;
+  bool four_ok = false;
+};
+static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, void *stream, int ori, const FusedOpts &o = FusedOpts()) {
+  const size_t nbatch = o.nbatch, win_c0 = o.win_c0, win_c1 = o.win_c1;
+  const void *const *const srcs = o.srcs; void *const *const dsts = o.dsts;
+  const bool probe = o.probe, four_ok = o.four_ok;
   REQUIRE_INIT();
   if (!p || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
   IPK_FOLD_CFA(ipk_fused_params, p)
   if (p->src_type != IPK_SRC_U16 && p->src_type != IPK_SRC_F32) return fail(IPK_ERR_INVALID, "fused path takes u16 or f32 CFA data");
   if (!dims_ok(p->width, p->height) || p->owidth < p->x + p->width) return fail(IPK_ERR_INVALID, "bad geometry");
   if (p->out_type < 0 || p->out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
+  if (p->four_colour != 0 && p->four_colour != 1) return fail(IPK_ERR_INVALID, "four_colour must be 0 or 1 (got %d)", p->four_colour);
   ipk::Cfa cfa; DevCfa dev;
   { int rc = get_cfa(p->cfa, cfa, dev); if (rc) return rc; }
   int xoff = 0, yoff = 0;
   const bool bayer = cfa.bayer_phase(xoff, yoff);
-  if (!bayer && !dev.gen_cells) return fail(IPK_ERR_UNSUPPORTED, "CFA \"%s\" has a fourth colour; run the staged ops", p->cfa);
+  const bool four = !cfa.three_colour();
+  if (four && !(four_ok && p->four_colour == 1 && ori == 0 && !probe && dev.gen_cells))
+    return fail(IPK_ERR_UNSUPPORTED, (four_ok && ori == 0 && !probe) ? "CFA \"%s\" has a fourth colour; set four_colour = 1, or run the staged ops"
+                                                                     : "CFA \"%s\" has a fourth colour; run the staged ops", p->cfa);
+  if (!bayer && !dev.gen_cells) return fail(IPK_ERR_UNSUPPORTED, "CFA \"%s\": no cell records; run the staged ops", p->cfa);
 
   ipk::FusedLaunch f;
   const size_t esz = p->src_type == IPK_SRC_U16 ? 2 : 4;
@@ -1116,6 +1130,7 @@ static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, voi
   // generic-CFA mode sums up to nine normalised samples and divides by a constant: u16 kernels check their samples only
   // when the levels allow one outside [2^-60, 2^60] (f32 kernels always check)
   f.gen_check = (!bayer && f.src_is_u16 && !gen_levels_ok_u16(p->black0, p->white0 - p->black0)) ? 1 : 0;
+  f.four = four ? 1 : 0;                                   // a fourth colour: literal demosaic with a fourth bin, literal point-wise form (launch_fused_bayer)
   float mul[4];
   ipk::normalize_wbs(p->wb_coeffs, mul);                                                                   // colorspaces.rs:100
   f.mul4 = mul; f.cm12 = p->cam_to_xyz_normalized; f.rgbm9 = g_host.xyz_d65_33;
@@ -1158,13 +1173,14 @@ static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, voi
   HIPCHK(hipGetLastError());
   return IPK_OK;
 }
-int ipk_raw_to_srgb(const ipk_fused_params *p, const void *src, void *dst, void *stream) { return fused_impl(p, src, dst, stream, 0); }
+int ipk_raw_to_srgb(const ipk_fused_params *p, const void *src, void *dst, void *stream) { FusedOpts o; o.four_ok = true; return fused_impl(p, src, dst, stream, 0, o); }
 // Measurement aid: the fused kernel's memory skeleton (its launch, task walk, row loads, OpGoFloat, demosaic::full, LDS staging, nontemporal stores) without
 // the point-wise stages -- dst receives the demosaiced R, G, B as width*rows*3 f32.  bench.py times it next to ipk_raw_to_srgb (roofline.ceiling_ms).
 int ipk_stream_probe(const ipk_fused_params *p, const void *src, void *dst, void *stream) {
   IPK_FOLD_CFA(ipk_fused_params, p)
   if (p && p->band_out_rows != 0) return fail(IPK_ERR_INVALID, "the stream probe takes whole frames");
-  return fused_impl(p, src, dst, stream, 0, 0, nullptr, nullptr, true);
+  FusedOpts o; o.probe = true;
+  return fused_impl(p, src, dst, stream, 0, o);
 }
 // A batch of same-shaped frames through one descriptor: Pipeline::run over a shoot.  One persistent launch per 64 frames where the
 // kernel has a batch variant (ordinary Bayer parameters), one launch per frame otherwise -- the results are the single-frame ones.
@@ -1174,11 +1190,14 @@ int ipk_raw_to_srgb_batch(const ipk_fused_params *p, const void *const *srcs, vo
   if (n > (size_t)1 << 20) return fail(IPK_ERR_INVALID, "batch too large");
   IPK_FOLD_CFA(ipk_fused_params, p)
   if (p->band_out_rows != 0) return fail(IPK_ERR_INVALID, "a batch takes whole frames, not bands");
-  return fused_impl(p, srcs[0], dsts[0], stream, 0, n, srcs, dsts);
+  FusedOpts o; o.nbatch = n; o.srcs = srcs; o.dsts = dsts; o.four_ok = true;
+  return fused_impl(p, srcs[0], dsts[0], stream, 0, o);
 }
 int ipk_raw_to_srgb_oriented(const ipk_fused_params *p, const void *src, int orientation, void *dst, size_t *out_width, size_t *out_height, void *stream) {
   if (!p || !out_width || !out_height) return fail(IPK_ERR_INVALID, "null argument");
   IPK_FOLD_CFA(ipk_fused_params, p)
+  // (a fourth colour is refused here for every orientation: the rotated-space variants compile the fast point-wise form in, and callers with a Normal
+  // orientation have ipk_raw_to_srgb)
   if (orientation == IPK_OR_NORMAL || orientation == IPK_OR_UNKNOWN) { *out_width = p->width; *out_height = p->height; return fused_impl(p, src, dst, stream, 0); }
   if (orientation < 0 || orientation > 8) return fail(IPK_ERR_INVALID, "bad orientation");
   { bool t, fx, fy; ipk::orientation_to_flips(orientation, t, fx, fy); *out_width = t ? p->height : p->width; *out_height = t ? p->width : p->height; }
@@ -1277,6 +1296,7 @@ static int resampled_launch(const ipk_fused_params *p, const void *src, const in
   if (!dims_ok(p->width, p->height) || p->owidth < p->x + p->width) return fail(IPK_ERR_INVALID, "bad geometry");
   if (p->out_type < 0 || p->out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   if (p->band_out_rows != 0) return fail(IPK_ERR_INVALID, "the %s fused path takes whole frames, not bands", what);
+  if (p->four_colour != 0 && p->four_colour != 1) return fail(IPK_ERR_INVALID, "four_colour must be 0 or 1 (got %d)", p->four_colour);
   ipk::Cfa cfa; DevCfa dev;
   { int rc = get_cfa(p->cfa, cfa, dev); if (rc) return rc; }
   if (!cfa.three_colour()) return fail(IPK_ERR_UNSUPPORTED, "CFA \"%s\" has a fourth colour; run the staged ops", p->cfa);
@@ -1606,12 +1626,18 @@ void fused_params_of(const ipk_pipeline_desc *d, const Negotiated &n, int out_ty
   fp.exposure = d->exposure; fp.npoints = d->npoints; std::memcpy(fp.points, d->points, sizeof(fp.points));
   fp.linear = n.linear; fp.out_type = out_type; fp.schedule = d->schedule;
 }
-bool fused_raw_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp) {
+// A filter with a fourth colour (RGBE ...) takes the route only where the caller opted in: allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR); the launch then
+// runs with fp.four_colour = 1.  `four` (optional) reports whether that is the case.
+bool fused_raw_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp, bool *four = nullptr) {
   ipk::Cfa cfa; int xo, yo;
-  if (!(d->allow_fused && n.cfa_branch && d->cpp == 1 && n.rc.noop() && n.scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) &&
-        (cfa.bayer_phase(xo, yo) || cfa.three_colour())))
+  if (four) *four = false;
+  if (!(d->allow_fused && n.cfa_branch && d->cpp == 1 && n.rc.noop() && n.scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) && cfa.valid()))
     return false;
+  const bool three = cfa.bayer_phase(xo, yo) || cfa.three_colour();
+  if (!three && !(d->allow_fused & IPK_FUSED_FOUR_COLOUR)) return false;
   fused_params_of(d, n, out_type, fp);
+  fp.four_colour = three ? 0 : 1;
+  if (four) *four = !three;
   return true;
 }
 // ---- the same with an ACTIVE OpRotateCrop between demosaic::full and OpToLab (ipk_raw_to_srgb_resampled): opted into with fuse_rotatecrop.  Then fp
@@ -1715,7 +1741,7 @@ int run_fused_resample(const Negotiated &n, const ipk_fused_params &fp, const Ro
       ipk_fused_params b = fp;                                 // the rows as a band of the whole cropped frame, the columns as the launch's window
       b.band_src_row0 = 0; b.band_src_rows = fp.height; b.band_out_row0 = (size_t)rcp.pts[1]; b.band_out_rows = rcp.nh;
       const void *top = static_cast<const char *>(src) + fp.y * fp.owidth * 2;
-      return fused_impl(&b, top, o, stream, 0, 0, nullptr, nullptr, false, (size_t)rcp.pts[0], (size_t)rcp.pts[0] + rcp.nw);
+      { FusedOpts fo; fo.win_c0 = (size_t)rcp.pts[0]; fo.win_c1 = (size_t)rcp.pts[0] + rcp.nw; return fused_impl(&b, top, o, stream, 0, fo); }
     }
     return ipk_raw_to_srgb_resampled(&fp, src, rcp.pts[0], rcp.pts[1], rcp.pts[2], rcp.pts[3], rcp.pts[4], rcp.pts[5], rcp.nw, rcp.nh, o, stream);
   };
@@ -1959,6 +1985,15 @@ int ipk_pipeline_fuses_rotatecrop(const ipk_pipeline_desc *d, int out_type) {
   ipk_fused_params fp; RotateCropPoints rcp;
   return fused_resample_route(d, n, out_type, fp, rcp) ? 1 : 0;
 }
+// the same report for allow_fused's IPK_FUSED_FOUR_COLOUR bit: does a frame whose filter has a fourth colour run as the one raw->sRGB launch?
+int ipk_pipeline_fuses_four_colour(const ipk_pipeline_desc *d, int out_type) {
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return 0;
+  ipk_fused_params fp; bool four = false;
+  return fused_raw_route(d, n, out_type, fp, &four) && four ? 1 : 0;
+}
 // the same report for fuse_scaledown: does OpDemosaic's full + scale_down_opbuf branch run inside the one launch?
 int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type) {
   if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
@@ -2035,12 +2070,13 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
   // the rows are a band whose source is the whole cropped frame (src then starts at the crop's first row); the columns are the launch's window
   fp.band_src_row0 = 0; fp.band_src_rows = n.r.height; fp.band_out_row0 = pl.r0; fp.band_out_rows = pl.r1 - pl.r0;
   const void *top = static_cast<const char *>(src) + n.r.y * d->width * (d->src_type == IPK_SRC_U16 ? 2 : 4);
-  if (n.transform_noop) return fused_impl(&fp, top, dst, stream, 0, 0, nullptr, nullptr, false, pl.c0, pl.c1);
+  FusedOpts fo; fo.win_c0 = pl.c0; fo.win_c1 = pl.c1; fo.four_ok = true;
+  if (n.transform_noop) return fused_impl(&fp, top, dst, stream, 0, fo);
   Scratch sc(S(stream));
   void *tmp = nullptr;
   const size_t cw = pl.c1 - pl.c0, ch = pl.r1 - pl.r0;
   rc = sc.get(cw * ch * 3 * esz, &tmp); if (rc) return rc;
-  rc = fused_impl(&fp, top, tmp, stream, 0, 0, nullptr, nullptr, false, pl.c0, pl.c1); if (rc < 0) return rc;
+  rc = fused_impl(&fp, top, tmp, stream, 0, fo); if (rc < 0) return rc;
   size_t ow = 0, oh = 0;
   rc = orient(tmp, cw, ch, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
   if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: oriented region %zux%zu, asked for %zux%zu", ow, oh, w, h);

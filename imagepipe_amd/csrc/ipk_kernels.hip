@@ -1491,7 +1491,8 @@ void launch_output16(const float *src, size_t n, uint16_t *dst, int num_cus, hip
 }
 
 // ------------------------------------------------------------------------------------------
-// Fused raw -> sRGB for every colour filter without a fourth colour (RGGB phases: role formulas; others: generic-CFA mode):
+// Fused raw -> sRGB for every colour filter (RGGB phases: role formulas; others: generic-CFA mode; a fourth colour -- RGBE ...: a run-time mode of the
+// generic-CFA runtime-flag variants, FusedArgs::four):
 //   OpGoFloat::run_raw (CFA branch) + demosaic::full + OpToLab + OpBaseCurve + OpFromLab + OpGamma
 //   [+ output8bit/output16bit], one pass: 4 (or 2) bytes in, 12 (or 3/6) bytes out per pixel.
 //
@@ -1546,7 +1547,11 @@ struct FusedArgs {
   int roles[4];               // ROT variants: demosaic role (0 R, 1 G on the R row, 2 G on the B row, 3 B) of the rotated-space pixel with
                               // parities (row & 1, column & 1) -> roles[2 * (row & 1) + (column & 1)]
   SplineDev spline;
+  int four;                   // generic-CFA mode, the CM = 0 whole-frame and window variants: 1 = the filter has a fourth colour (RGBE ...): every pixel's
+                              // demosaic takes the literal form with a fourth bin and its point-wise stages the literal form, which keeps E.  Wave-uniform,
+                              // host-set; sits in what was the struct's tail padding, so no other argument moved
 };
+static_assert(sizeof(FusedArgs) == 1640 && offsetof(FusedArgs, four) == 1636, "FusedArgs: `four` fills the tail padding; every other kernel argument keeps its offset");
 
 // one image row as a lane sees it: its 4 samples and the neighbours left/right of them
 struct RowWin { float l, v0, v1, v2, v3, r; };
@@ -1698,7 +1703,7 @@ __device__ __forceinline__ float4 demosaic_inner_role(int role, const float t[9]
   return demosaic_inner_px<3>(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8]);
 }
 
-// ---- generic-CFA mode (X-Trans and any other filter without a fourth colour) --------------------------------------
+// ---- generic-CFA mode (X-Trans and any other filter; one with a fourth colour takes the literal form below for every pixel) ----
 // Interior pixel from the pattern cell's record (see Cfa::gen_cells): masked sums in the reference's tap order, then the
 // proven two-step division by the tap count.  `cell` points at 36 floats, 16-byte aligned, in LDS.
 constexpr int kGenCellFloats = 36;
@@ -1718,20 +1723,24 @@ __device__ __forceinline__ float4 demosaic_gen_px(const float *__restrict__ cell
 }
 // The literal form (demosaic.rs:99-114) from the packed tap colours: frame-edge pixels (taps outside the image are
 // skipped) and rows whose samples are outside the zone where the arithmetic form is proven.
+// NB = 4: a fourth bin (tap code 3 = E, the reference's fourth, demosaic.rs:77-114), .w = E: every pixel of a four-colour launch comes from here
+// (fused_bayer_body).  A colour with no tap in the window stays 0.0.
+template <int NB = 3>
 __device__ __forceinline__ float4 demosaic_gen_literal_px(uint32_t lk, const float t[9], uint32_t valid_mask) {
-  float s[3] = {0.0f, 0.0f, 0.0f}, n[3] = {0.0f, 0.0f, 0.0f};
+  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   #pragma unroll
   for (int i = 0; i < 9; ++i) {
     const uint32_t code = (lk >> (3 * i)) & 7u;
     const bool ok = (valid_mask >> i) & 1u;
     #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < NB; ++k) {
       const bool hit = ok && code == (uint32_t)k;
       s[k] = hit ? s[k] + t[i] : s[k];
       n[k] = hit ? n[k] + 1.0f : n[k];
     }
   }
-  return make_float4(n[0] > 0.0f ? s[0] / n[0] : 0.0f, n[1] > 0.0f ? s[1] / n[1] : 0.0f, n[2] > 0.0f ? s[2] / n[2] : 0.0f, 0.0f);
+  return make_float4(n[0] > 0.0f ? s[0] / n[0] : 0.0f, n[1] > 0.0f ? s[1] / n[1] : 0.0f, n[2] > 0.0f ? s[2] / n[2] : 0.0f,
+                     (NB == 4 && n[3] > 0.0f) ? s[3] / n[3] : 0.0f);
 }
 // An "ordinary" normalised sample: zero, or finite with 2^-20 <= |v| <= 2^20 (every real sensor value is: the smallest
 // nonzero (v - black)/range of a 16-bit sensor is about 2^-16).  The generic-CFA demosaic needs its rows made of such
@@ -2262,6 +2271,18 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
   __shared__ float s_par[32];                            // mul[0..3], cm[4..15], rgbm[16..24]
   __shared__ __attribute__((aligned(16))) float s_cells[GEN ? kGenMaxCells * kGenCellFloats : 4];   // generic-CFA cell records
   if (GEN) for (uint32_t i = threadIdx.x; i < a.gen_pw * a.gen_ph * kGenCellFloats; i += blockDim.x) s_cells[i] = a.gen_cells[i];
+  // A filter with a fourth colour (a.four, wave-uniform): the runtime-flag generic-CFA variants only -- the host never picks another one for it, and
+  // those keep their code (a compile-time false).  Such a launch redoes every pixel's demosaic in a block of its own behind the frame-edge block
+  // (compute_px: the literal form with a fourth bin), parks the lane's four E values in LDS (16 KB, these variants only; s_e4[j * 1024 + thread]: a wave's
+  // stores are lane-contiguous) and, with the host's fast_ok = 0, takes the literal point-wise form, which reads E back.  Three-colour launches keep the
+  // parent's row loop, frame-edge path included, to the instruction where it matters: what was tried in its place -- a four-bin interior demosaic as a
+  // branch in the row loop, a second row loop, every pixel through the frame-edge path (E in px.w or in LDS), a branch around the point-wise block --
+  // cost the three-colour frames of these variants 15-25 % on u16 -> 8-bit (profiles/r11_fourcolour.txt); this form 1-2 %.
+  // The masked-sum demosaic (and the three-bin literal form of a flagged row) of a four-colour launch is computed and then overwritten: the demosaic
+  // runs twice per pixel there.  An interior arithmetic form with a fourth bin (record stride 48) is not built.
+  constexpr bool FOUR_CAPABLE = GEN && CM == 0 && !ROT && !BATCH && !DEMO && !SKEL;
+  float *e4 = nullptr;
+  if constexpr (FOUR_CAPABLE) { __shared__ float s_e4[4 * 1024]; e4 = s_e4 + threadIdx.x; }
   constexpr int STG = DEMO ? 1024 : (OUTS == 0 ? 768 : (OUTS == 1 ? 192 : 384));   // dwords of staging per wave: one output row segment
   __shared__ __attribute__((aligned(16))) uint32_t s_stage[FULL ? 16 * STG : 4];
   if (threadIdx.x < 4) s_par[threadIdx.x] = a.tolab.mul[threadIdx.x];
@@ -2429,6 +2450,7 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
     // for all 65 536 values
     // (a compile-time false for the Bayer variants, so that they carry no trace of it)
     const bool gen_guard = GEN && (sizeof(SrcT) == 4 || DEMO || a.gen_check != 0);
+    const bool four = FOUR_CAPABLE && a.four != 0;
     if (r0 >= r1) { arrive(); continue; }
     if (steal_on && lane == 0) {
       // this wave's task, for takers.  Takers read the descriptor first and the row second, and swap only against the descriptor they read; so the old
@@ -2639,6 +2661,23 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
           }
         }
       }
+      // a filter with a fourth colour: EVERY pixel again, by the literal form with a fourth bin (frame-edge taps masked as above); what the code above
+      // left in px is overwritten (see FOUR_CAPABLE).  E leaves through LDS, px.w stays 0.0 as in every other path
+      if constexpr (FOUR_CAPABLE) if (IPK_RARE(four)) {
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t c = col0 + j;
+          const float t[9] = {pw[j], pw[j + 1], pw[j + 2], cw[j], cw[j + 1], cw[j + 2], nw[j], nw[j + 1], nw[j + 2]};
+          uint32_t m = 0x1FFu;
+          if (r == 0) m &= ~0x007u;
+          if (r == Hm1) m &= ~0x1C0u;
+          if (c == 0) m &= ~0x049u;
+          if (c == Wm1) m &= ~0x124u;
+          const float4 q = demosaic_gen_literal_px<4>(__float_as_uint(rowcells[cxo[j] + 27]), t, m);
+          e4[1024 * j] = q.w;
+          px[j] = make_float4(q.x, q.y, q.z, 0.0f);
+        }
+      }
     };
     auto row_step = [&](RowWin &P, RowWin &C, RowWin &N, bool &fP, bool &fC, bool &fN, const uint32_t r) {
       // The four waves of a SIMD are served oldest first: left alone, the same 23 rows take one wave 83 us and another 164 (24 MP frame, one task per
@@ -2684,7 +2723,9 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
       if (IPK_RARE(__builtin_amdgcn_ballot_w64(bad) != 0)) {          // rare: an input outside the fast form's proven zone
         #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const PixOut e = pointwise_exact(a, s_lab, s_gam, s_knots, px[j]);
+          float4 p = px[j];
+          if constexpr (FOUR_CAPABLE) { if (four) p.w = e4[1024 * j]; }      // a fourth colour: the pixel's E, as the demosaic left it (same lane, same row)
+          const PixOut e = pointwise_exact(a, s_lab, s_gam, s_knots, p);
           if (bad) o[j] = e;
         }
       }
@@ -2805,9 +2846,10 @@ static void launch_fused_t(const FusedArgs &a, unsigned grid, hipStream_t s) {
   }
   if (a.gen_cells) {                                     // generic-CFA mode: one load flavour per source type
     constexpr bool V = sizeof(SrcT) == 4;
+    const char *const tag = a.four ? "four=1" : nullptr;   // four-colour launches are tagged; three-colour ones keep their bare log line
     if (common) IPK_LAUNCH((k_fused_bayer<SrcT, V, OUT, true, true, true, true>), dim3(grid), dim3(tpb), 0, s, a);
-    else if (a.W >= 256u) IPK_LAUNCH((k_fused_bayer<SrcT, V, OUT, true, true>), dim3(grid), dim3(tpb), 0, s, a);
-    else IPK_LAUNCH((k_fused_bayer<SrcT, V, OUT, false, true>), dim3(grid), dim3(tpb), 0, s, a);
+    else if (a.W >= 256u) IPK_LAUNCH_TAG(tag, (k_fused_bayer<SrcT, V, OUT, true, true>), dim3(grid), dim3(tpb), 0, s, a);
+    else IPK_LAUNCH_TAG(tag, (k_fused_bayer<SrcT, V, OUT, false, true>), dim3(grid), dim3(tpb), 0, s, a);
     return;
   }
   // u16 sources with ordinary levels and parameters (the common case for real sensors): no per-pixel input guards
@@ -2845,7 +2887,7 @@ static void launch_fused_window_t(const FusedArgs &a, const FusedWindow &w, unsi
   const bool full = w.x1 - w.x0 >= 256u;
   const bool common = full && a.fast_ok && a.has_curve && !a.exact_norm && (a.linear != 0) == (OUT == 2) && std::fabs(a.min0) >= 0x1p-70f &&
                       std::fabs(a.min0) <= 0x1p70f && a.spline.npoints == 3 && spline3_arith_ok(a.spline);
-#define IPK_WIN_LAUNCH(FL, G, P, C) IPK_LAUNCH((k_fused_bayer_window<SrcT, V, OUT, FL, G, P, C>), dim3(grid), dim3(1024), 0, s, a, w)
+#define IPK_WIN_LAUNCH(FL, G, P, C) IPK_LAUNCH_TAG((a.four ? "four=1" : nullptr), (k_fused_bayer_window<SrcT, V, OUT, FL, G, P, C>), dim3(grid), dim3(1024), 0, s, a, w)
   if (a.gen_cells) {
     if (common) IPK_WIN_LAUNCH(true, true, true, 1);
     else if (full) IPK_WIN_LAUNCH(true, true, true, 0);
@@ -2997,6 +3039,13 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s) {
   a.lab_pairs = reinterpret_cast<const LutPair *>(f.lab_pairs); a.gam_pairs = reinterpret_cast<const LutPair *>(f.gam_pairs);
   a.gam_q8 = reinterpret_cast<const Q8Entry *>(f.gam_q8);
   a.gen_cells = f.gen_cells; a.gen_pw = (uint32_t)f.gen_pw; a.gen_ph = (uint32_t)f.gen_ph; a.gen_check = f.gen_check; a.px_guard = f.px_guard;
+  a.four = f.four ? 1 : 0;
+  if (a.four) {
+    // a fourth colour: generic-CFA cells, one frame per launch in its own orientation, and the literal point-wise form for every pixel -- the fast form
+    // drops the E term (pointwise4_fast).  fast_ok = 0 also keeps the launch off every common-parameter variant, which compile the fast form in
+    if (!a.gen_cells || f.ori != 0 || f.out_type < 0 || f.out_type > 2) return -2;
+    a.fast_ok = 0;
+  }
   a.ori = f.ori;
   for (int i = 0; i < 4; ++i) a.roles[i] = f.roles[i];
   if (f.ori != 0) {

@@ -44,7 +44,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // sample; wrap: the grid cap holds), k_gofloat_cfa_v4 [rowwrap=] (more rows than grid rows), the ipk_raw_scaled_demosaic kernels
 // [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form);
-// k_fused_resample's axis-aligned mode (ipk_raw_to_srgb_scaled) [fast_ok=,axis=1].
+// k_fused_resample's axis-aligned mode (ipk_raw_to_srgb_scaled) [fast_ok=,axis=1]; the generic-CFA runtime-flag variants of k_fused_bayer /
+// k_fused_bayer_window [four=1] on the launches of a filter with a fourth colour only (FusedLaunch::four) -- three-colour launches carry no tag.
 void launch_log_enable(bool on);                 // clears the log, then switches it on or off
 size_t launch_log_read(char *buf, size_t cap);   // entries sorted, newline-separated, NUL-terminated (truncated to cap); returns the bytes a full read needs
 
@@ -93,6 +94,8 @@ struct FusedLaunch {
   const void *gam_q8;                  // 8192 x {k, threshold}: OpGamma + output8bit as one step lookup (launch_build_q8), the 8-bit variants' LDS image
   int px_guard;                  // 0: u16 source whose levels and parameters the host found ordinary (kernel variant without per-pixel input guards)
   const float *gen_cells; int gen_pw, gen_ph, gen_check;   // generic-CFA mode (device cell records) or null: RGGB phase (xoff, yoff)
+  int four = 0;                  // launch_fused_bayer only: 1 = the filter behind gen_cells has a fourth colour (RGBE ...): literal demosaic with a fourth bin and the
+                                 // literal point-wise form for every pixel; whole frames, bands, batches (a launch per frame) and regions, ori == 0 (else -2)
   int num_cus;
   int schedule;                  // ipk_schedule (launch_fused_bayer, single frames on the static schedule only)
   TaskQueues *queues;            // the launching context's task queues (launch_fused_bayer only; may be null)
@@ -105,7 +108,7 @@ struct FusedLaunch {
   // packed win_c1 - win_c0 pixels per row into dst.  Columns, like rows, are the cropped frame's: CFA phase and cells are not shifted
   size_t win_c0 = 0, win_c1 = 0;
 };
-// returns 0, -2 when f.ori != 0 and the parameters have no rotated-space variant (nothing is launched), -4 when a launch could not be enqueued
+// returns 0, -2 when f.ori != 0 and the parameters have no rotated-space variant or f.four is set without cells / with an orientation (nothing is launched), -4 when a launch could not be enqueued
 int launch_fused_bayer(const FusedLaunch &f, hipStream_t s);
 // gofloat + demosaic::full + transform_buffer(plan) + tolab..gamma (+ quantisation) as one launch (k_fused_resample): f.src = the cropped frame's first
 // sample (pitch f.owidth), f.width x f.height the cropped frame, f.dst = nwidth * nheight * 3 samples of f.out_type; `lookups` = the device image of

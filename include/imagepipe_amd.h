@@ -324,7 +324,10 @@ typedef struct {
                                       it from the string (a "WxH:" prefix, or the letter count 4 / 36 / 144).  16 letters need one of the two. */
   /* third layout */
   int schedule;                    /* ipk_schedule: how the launch shares a frame's rows out among the waves (results do not depend on it) */
-  int reserved0;                   /* 0 */
+  int four_colour;                 /* 0 (the default, and what every earlier caller wrote into this formerly reserved field): a filter with a fourth colour
+                                      (RGBE ...) is refused with IPK_ERR_UNSUPPORTED; 1: ipk_raw_to_srgb (bands included), ipk_raw_to_srgb_batch and
+                                      ipk_host_raw_to_srgb take it -- one launch, the fourth colour an ordinary lane of demosaic::full and camera_to_lab; other
+                                      values are IPK_ERR_INVALID.  Three-colour filters run the same either way.  No layout change. */
 } ipk_fused_params;
 #define IPK_FUSED_PARAMS_INIT {(uint32_t)sizeof(ipk_fused_params)}      /* ipk_fused_params p = IPK_FUSED_PARAMS_INIT;  (everything else zero) */
 
@@ -335,7 +338,11 @@ typedef struct {
  * dst's width*rows*3 elements is written.  The same holds for the batch, oriented, resampled and scaled forms below, for ipk_pipeline_run and
  * ipk_pipeline_run_region, ipk_demosaic_full and ipk_stream_probe (tests/test_gpu_buffer_bounds.py).
  * Any colour filter without a fourth colour is accepted (the four RGGB phases, X-Trans, 12x12, 16 letters with a stated shape ...; pattern strings: see ipk_cfa_shift); fails with
- * IPK_ERR_UNSUPPORTED for RGBE-style filters (callers then run the staged ops). */
+ * IPK_ERR_UNSUPPORTED for RGBE-style filters (callers then run the staged ops) unless p->four_colour is 1: then such a filter (RGBE, ERBG, 16 letters
+ * with a stated shape ...) runs as one launch too, bit-identical to the staged ops -- every pixel takes the literal demosaic with a fourth bin and the
+ * literal point-wise form, which keeps the e * cam_to_xyz[i][3] terms (src/ops/demosaic.rs:77-114, src/color_conversions.rs:42-55).  The flag is
+ * honoured here, by ipk_raw_to_srgb_batch (one launch per frame, as for every generic filter) and by ipk_host_raw_to_srgb; ipk_raw_to_srgb_oriented,
+ * _resampled, _scaled and ipk_stream_probe keep refusing a fourth colour whatever it says, and a pattern with an unknown letter stays refused. */
 IPK_API int ipk_raw_to_srgb(const ipk_fused_params *p, const void *src, void *dst, void *stream);
 /* n frames of ONE shape and ONE parameter set (a caller looping Pipeline::run over a shoot, src/pipeline.rs:246-249: frames are independent;
  * BASELINE.json configs[3]): srcs[i] -> dsts[i], host arrays of device pointers, whole frames only.  Where the kernel has a batch variant
@@ -421,7 +428,12 @@ typedef struct {
   int rotation, fliph, flipv;      /* OpTransform */
   size_t maxwidth, maxheight;      /* PipelineSettings */
   int linear;
-  int allow_fused;                 /* 1: use ipk_raw_to_srgb when legal (cache==None); 0: always staged */
+  int allow_fused;                 /* a small mask; 0: always staged.  Any non-zero value (IPK_FUSED_ON = 1): use ipk_raw_to_srgb when legal (cache==None).
+                                      Bit 1 (IPK_FUSED_FOUR_COLOUR = 2, e.g. allow_fused = 3) additionally admits filters with a fourth colour to that
+                                      one-launch route where ipk_pipeline_fuses_four_colour says so; without it they take the staged ops, as they always
+                                      did.  The opt-in lives here because the descriptor's tail is pinned (its last field and reserved1 are named by callers
+                                      and tests): no field could be added or renamed for it.  Like the rest of allow_fused it does not enter the hashes and
+                                      results do not depend on it. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -436,6 +448,11 @@ typedef struct {
                                       the staged ops.  The same contract as fuse_rotatecrop: other values are IPK_ERR_INVALID, results do not depend on it, it does
                                       not enter the hashes, and it is not read from objects of an older layout. */
 } ipk_pipeline_desc;
+/* the bits of ipk_pipeline_desc.allow_fused */
+typedef enum {
+  IPK_FUSED_ON = 1,                /* the one-launch routes where legal (any non-zero value means this) */
+  IPK_FUSED_FOUR_COLOUR = 2        /* bit 1: four-colour filters take the one-launch route too */
+} ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
 /* Size negotiation of Pipeline::run (src/pipeline.rs:314-338): demosaic_{w,h} as stored in the
@@ -475,6 +492,12 @@ IPK_API int ipk_pipeline_fuses_rotatecrop(const ipk_pipeline_desc *d, int out_ty
  * descriptor ipk_pipeline_sizes refuses, and for a fuse_scaledown other than 0 or 1.  ipk_pipeline_fuses_rotatecrop keeps answering 0 wherever
  * OpDemosaic scales.  No GPU needed. */
 IPK_API int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type);
+/* Does ipk_pipeline_run (and the cached, batch, host, multi-device and region drivers) run this descriptor's four-colour frame as ONE raw-to-sRGB
+ * launch (ipk_raw_to_srgb with four_colour = 1, then OpTransform's permutation if there is one; regions windowed)?  1 when d->allow_fused has
+ * IPK_FUSED_FOUR_COLOUR set, the source is a one-sample-per-pixel CFA mosaic whose filter has a fourth colour, OpRotateCrop is a no-op and OpDemosaic
+ * does not scale (scale <= 1).  0 otherwise -- three-colour filters included: their one-launch route does not depend on the bit --; a negative error
+ * code for a descriptor ipk_pipeline_sizes refuses.  No GPU needed. */
+IPK_API int ipk_pipeline_fuses_four_colour(const ipk_pipeline_desc *d, int out_type);
 /* do_timing! (src/pipeline.rs:68-80: the reference logs the wall time of every op of Pipeline::run): ipk_timing_begin arms the calling
  * thread, the following ipk_pipeline_run call(s) on it bracket every stage they enqueue with hipEvents on their stream, ipk_timing_end
  * waits for the last one and returns the stages in execution order under the reference's op names ("gofloat", "demosaic", "rotatecrop",
@@ -490,7 +513,8 @@ IPK_API int ipk_host_pipeline_run(const ipk_pipeline_desc *d, const void *src, v
  * that leaves the result, or a descriptor ipk_pipeline_run rejects fails with IPK_ERR_INVALID and writes nothing.
  * ipk_pipeline_region plans one (no GPU needed) and returns its route: 1 = windowed -- the run is the fused raw->sRGB launch, restricted to the
  * rectangle of the cropped frame the region comes from, and reads only the sensor window reported (that rectangle plus demosaic::full's
- * one-pixel halo, clipped to the crop window, in sensor coordinates); 0 = whole frame -- staged, scaled, rotatecrop, four-colour, mono/RGB and
+ * one-pixel halo, clipped to the crop window, in sensor coordinates); 0 = whole frame -- staged, scaled, rotatecrop, four-colour (without
+ * IPK_FUSED_FOUR_COLOUR in allow_fused; with it: windowed), mono/RGB and
  * raster routes and allow_fused = 0 compute the whole result and copy the region out, and the window reported is the crop window. */
 IPK_API int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h,
                                 size_t *src_x, size_t *src_y, size_t *src_w, size_t *src_h);

@@ -297,6 +297,7 @@ class Pipeline {
   int schedule = IPK_SCHED_AUTO;                        // ipk_pipeline_desc.schedule: how a fused launch shares a frame's rows out (results unaffected)
   bool fuse_rotatecrop = false;            // ipk_pipeline_desc.fuse_rotatecrop: an active OpRotateCrop inside the one launch where fuses_rotatecrop() says so
   bool fuse_scaledown = false;             // ipk_pipeline_desc.fuse_scaledown: OpDemosaic's full + scale_down_opbuf branch inside the one launch where fuses_scaledown() says so
+  bool fuse_four_colour = false;           // ipk_pipeline_desc.allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR): a filter with a fourth colour (RGBE ...) on the one-launch route where fuses_four_colour() says so
   int last_ops_run = 0xFF;                 // bit i: op i executed in the last run (0 = served from the cache)
   uint64_t source_id = 0;                  // identifies the frame inside a shared PipelineCache (extension, see the C header)
   static PipelineCache new_cache(size_t size) { return PipelineCache(size); }
@@ -375,12 +376,15 @@ class Pipeline {
     d.schedule = schedule;
     d.fuse_rotatecrop = fuse_rotatecrop ? 1 : 0;
     d.fuse_scaledown = fuse_scaledown ? 1 : 0;
+    if (fuse_four_colour && d.allow_fused) d.allow_fused |= IPK_FUSED_FOUR_COLOUR;
     return d;
   }
   // does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop; no GPU needed)?  out_type: IPK_OUT_*
   bool fuses_rotatecrop(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_fuses_rotatecrop(&d, out_type) == 1; }
   // the same for OpDemosaic's full + scale_down_opbuf branch (ipk_pipeline_fuses_scaledown)
   bool fuses_scaledown(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_fuses_scaledown(&d, out_type) == 1; }
+  // the same for a filter with a fourth colour (ipk_pipeline_fuses_four_colour)
+  bool fuses_four_colour(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_fuses_four_colour(&d, out_type) == 1; }
  private:
   explicit Pipeline(ImageSource img) : globals{std::move(img), PipelineSettings()}, ops(globals.image) {}
   std::pair<size_t, size_t> final_size() const {
