@@ -21,7 +21,8 @@ from ._lib import (IpkError, FusedParams, PipelineDesc, OUT_F32, OUT_U8, OUT_U16
 
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
-           "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "FusedPlan", "IpkError"]
+           "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "raw_to_srgb_resampled_window", "raw_to_srgb_scaled_window",
+           "transform_window_footprint", "FusedPlan", "IpkError"]
 
 _initialized_device = None
 
@@ -601,6 +602,7 @@ class Pipeline:
         self.fuse_rotatecrop = False          # ipk_pipeline_desc.fuse_rotatecrop: an active OpRotateCrop inside the one launch where fuses_rotatecrop() says so
         self.fuse_scaledown = False           # ipk_pipeline_desc.fuse_scaledown: OpDemosaic's full + scale_down_opbuf branch inside the one launch where fuses_scaledown() says so
         self.fuse_four_colour = False         # ipk_pipeline_desc.allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR): a filter with a fourth colour (RGBE ...) on the one-launch route where fuses_four_colour() says so
+        self.window_regions = False           # ipk_pipeline_desc.allow_fused bit 2 (IPK_FUSED_WINDOW_REGIONS): regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch
 
     @staticmethod
     def new_from_source(img):
@@ -663,6 +665,8 @@ class Pipeline:
         d.allow_fused = int(self.allow_fused)
         if self.fuse_four_colour and d.allow_fused:
             d.allow_fused |= _lib.FUSED_FOUR_COLOUR
+        if self.window_regions and d.allow_fused:
+            d.allow_fused |= _lib.FUSED_WINDOW_REGIONS
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -869,3 +873,44 @@ def raw_to_srgb_scaled(src: torch.Tensor, nwidth, nheight, *, out: Optional[torc
         out = torch.empty(nheight * nwidth * 3, dtype=plan.out_dtype, device="cuda")
     _lib.check(lib().ipk_raw_to_srgb_scaled(plan._ref, src.data_ptr(), nwidth, nheight, out.data_ptr(), _stream()), "ipk_raw_to_srgb_scaled")
     return out
+
+
+def _check_window(nwidth, nheight, window):
+    wx, wy, ww, wh = [int(v) for v in window]
+    if min(wx, wy) < 0 or ww < 1 or wh < 1 or wx + ww > nwidth or wy + wh > nheight:
+        raise ValueError("window %r is empty or outside the %dx%d result" % (tuple(window), nwidth, nheight))
+    return wx, wy, ww, wh
+
+
+def raw_to_srgb_resampled_window(src: torch.Tensor, corners, nwidth, nheight, window, *, out: Optional[torch.Tensor] = None, **kw):
+    """ipk_raw_to_srgb_resampled_window: the columns [wx, wx+ww) and rows [wy, wy+wh) of what raw_to_srgb_resampled returns, window = (wx, wy, ww, wh),
+    computed by the same one launch laid over the window only.  Returns the wh*ww*3 device tensor of the output type."""
+    wx, wy, ww, wh = _check_window(nwidth, nheight, window)
+    plan = FusedPlan(**kw)
+    if out is None:
+        out = torch.empty(wh * ww * 3, dtype=plan.out_dtype, device="cuda")
+    _lib.check(lib().ipk_raw_to_srgb_resampled_window(plan._ref, src.data_ptr(), *[int(c) for c in corners], nwidth, nheight, wx, wy, ww, wh,
+                                                      out.data_ptr(), _stream()), "ipk_raw_to_srgb_resampled_window")
+    return out
+
+
+def raw_to_srgb_scaled_window(src: torch.Tensor, nwidth, nheight, window, *, out: Optional[torch.Tensor] = None, **kw):
+    """ipk_raw_to_srgb_scaled_window: the same for raw_to_srgb_scaled.  Returns the wh*ww*3 device tensor of the output type."""
+    wx, wy, ww, wh = _check_window(nwidth, nheight, window)
+    plan = FusedPlan(**kw)
+    if out is None:
+        out = torch.empty(wh * ww * 3, dtype=plan.out_dtype, device="cuda")
+    _lib.check(lib().ipk_raw_to_srgb_scaled_window(plan._ref, src.data_ptr(), nwidth, nheight, wx, wy, ww, wh, out.data_ptr(), _stream()),
+               "ipk_raw_to_srgb_scaled_window")
+    return out
+
+
+def transform_window_footprint(width, height, corners, nwidth, nheight, window):
+    """ipk_transform_window_footprint (host-only): (x, y, w, h) of the width x height cropped frame that the window (wx, wy, ww, wh) of the resampled
+    nwidth x nheight image reads, demosaic::full's halo included; w = h = 0 when no pixel of it has a tap.  corners as for raw_to_srgb_resampled;
+    for raw_to_srgb_scaled they are (0, 0, width - 1, 0, 0, height - 1)."""
+    out4 = (C.c_size_t * 4)()
+    wx, wy, ww, wh = [int(v) for v in window]
+    _lib.check(lib().ipk_transform_window_footprint(width, height, *[int(c) for c in corners], nwidth, nheight, wx, wy, ww, wh, out4),
+               "ipk_transform_window_footprint")
+    return tuple(int(v) for v in out4)

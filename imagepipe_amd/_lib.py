@@ -13,7 +13,7 @@ IPK_OK, IPK_NOOP = 0, 1
 SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16 = 0, 1, 2, 3
 OUT_F32, OUT_U8, OUT_U16 = 0, 1, 2
 SCHED_AUTO, SCHED_SPLIT = 0, 1
-FUSED_ON, FUSED_FOUR_COLOUR = 1, 2          # ipk_pipeline_desc.allow_fused
+FUSED_ON, FUSED_FOUR_COLOUR, FUSED_WINDOW_REGIONS = 1, 2, 4          # ipk_pipeline_desc.allow_fused
 OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN = range(9)
 ROT_NORMAL, ROT_90, ROT_180, ROT_270 = range(4)
 
@@ -146,6 +146,9 @@ SIGNATURES = {
     "ipk_raw_to_srgb_oriented": (C.c_int, [C.POINTER(FusedParams), _vp, C.c_int, _vp, _szp, _szp, _vp]),
     "ipk_raw_to_srgb_resampled": (C.c_int, [C.POINTER(FusedParams), _vp] + _CORNERS + [_sz, _sz, _vp, _vp]),
     "ipk_raw_to_srgb_scaled": (C.c_int, [C.POINTER(FusedParams), _vp, _sz, _sz, _vp, _vp]),
+    "ipk_raw_to_srgb_resampled_window": (C.c_int, [C.POINTER(FusedParams), _vp] + _CORNERS + [_sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "ipk_raw_to_srgb_scaled_window": (C.c_int, [C.POINTER(FusedParams), _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "ipk_transform_window_footprint": (C.c_int, [_sz, _sz] + _CORNERS + [_sz, _sz, _sz, _sz, _sz, _sz, _szp]),
     "ipk_pipeline_sizes": (C.c_int, [C.POINTER(PipelineDesc), _szp, _szp, _szp, _szp]),
     "ipk_pipeline_run": (C.c_int, [C.POINTER(PipelineDesc), _vp, _vp, C.c_int, C.POINTER(C.c_int), _vp]),
     "ipk_host_pipeline_run": (C.c_int, [C.POINTER(PipelineDesc), _vp, _vp, C.c_int, C.POINTER(C.c_int)]),

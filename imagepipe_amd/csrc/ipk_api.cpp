@@ -1287,10 +1287,13 @@ int ipk_raster_to_srgb(const void *src, int src_type, size_t width, size_t heigh
 
 // The launch behind ipk_raw_to_srgb_resampled (corners: its six corner coordinates) and ipk_raw_to_srgb_scaled (corners == NULL: scale_down_opbuf's
 // transform), k_fused_resample: the checks both share, then the plan from the cropped frame's sides, or the refusal (nothing is enqueued then)
+// win (the window forms): the rectangle of the nwidth x nheight result the launch is laid over; dst then holds exactly its pixels
 static int resampled_launch(const ipk_fused_params *p, const void *src, const int64_t *corners, size_t nwidth, size_t nheight, void *dst, void *stream,
-                            const char *what, const char *refusal) {
+                            const char *what, const char *refusal, const ipk::ResampleWindow *win = nullptr) {
   REQUIRE_INIT();
   if (!p || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
+  if (win && (win->cols == 0 || win->rows == 0 || win->col0 > nwidth || win->cols > nwidth - win->col0 || win->row0 > nheight || win->rows > nheight - win->row0))
+    return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", win->col0, win->row0, win->cols, win->rows, nwidth, nheight);
   IPK_FOLD_CFA(ipk_fused_params, p)
   if (p->src_type != IPK_SRC_U16 && p->src_type != IPK_SRC_F32) return fail(IPK_ERR_INVALID, "the %s fused path takes u16 or f32 CFA data", what);
   if (!dims_ok(p->width, p->height) || p->owidth < p->x + p->width) return fail(IPK_ERR_INVALID, "bad geometry");
@@ -1314,24 +1317,51 @@ static int resampled_launch(const ipk_fused_params *p, const void *src, const in
   pp.f.black0 = p->black0; pp.f.white0 = p->white0;
   pp.f.exact_norm = validate_cdiv_for_range(p->black0, p->white0 - p->black0, pp.f.src_is_u16) ? 0 : 1;
   pp.f.out_type = p->out_type;
-  if (ipk::launch_fused_resample(pp.f, plan, nwidth, nheight, dev.lookups, S(stream)) != 0)
+  if (ipk::launch_fused_resample(pp.f, plan, nwidth, nheight, dev.lookups, S(stream), win) != 0)
     return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
   HIPCHK(hipGetLastError());
   return IPK_OK;
 }
+static const char *const kResampledRefusal =
+    "not a transform the resampled fused path takes (output sides >= 2, finite skips whose magnitudes sum to less than 2 per axis, sides below 2^24); run the staged ops";
+static const char *const kScaledRefusal =
+    "not a size the scaled fused path takes (output sides >= 2, both skips (side - 1) / (new side - 1) at least 1 and below 3, sides below 2^24); run the staged ops";
 // ipk_raw_to_srgb with scaling::transform_buffer (src/scaling.rs:51-130) between demosaic::full and OpToLab, the corner points being the three
 // OpRotateCrop::run computes (src/ops/rotatecrop.rs:39-64): one launch (k_fused_resample).  Arguments as for ipk_transform_buffer_f32.
 int ipk_raw_to_srgb_resampled(const ipk_fused_params *p, const void *src, int64_t tlx, int64_t tly, int64_t trx, int64_t try_,
                               int64_t blx, int64_t bly, size_t nwidth, size_t nheight, void *dst, void *stream) {
   const int64_t corners[6] = {tlx, tly, trx, try_, blx, bly};
-  return resampled_launch(p, src, corners, nwidth, nheight, dst, stream, "resampled",
-                          "not a transform the resampled fused path takes (output sides >= 2, finite skips whose magnitudes sum to less than 2 per axis, sides below 2^24); run the staged ops");
+  return resampled_launch(p, src, corners, nwidth, nheight, dst, stream, "resampled", kResampledRefusal);
 }
 // ipk_raw_to_srgb with scale_down_opbuf(nwidth, nheight) (src/scaling.rs:35-48: transform_buffer with the corners (0, 0), (width - 1, 0), (0, height - 1))
 // between demosaic::full and OpToLab -- OpDemosaic::run's last branch (src/ops/demosaic.rs:51-59) -- in the same launch, its axis-aligned mode
 int ipk_raw_to_srgb_scaled(const ipk_fused_params *p, const void *src, size_t nwidth, size_t nheight, void *dst, void *stream) {
-  return resampled_launch(p, src, nullptr, nwidth, nheight, dst, stream, "scaled",
-                          "not a size the scaled fused path takes (output sides >= 2, both skips (side - 1) / (new side - 1) at least 1 and below 3, sides below 2^24); run the staged ops");
+  return resampled_launch(p, src, nullptr, nwidth, nheight, dst, stream, "scaled", kScaledRefusal);
+}
+// the window forms of the two: the same launch laid over the rectangle [wx, wx + ww) x [wy, wy + wh) of the result (ResampleWindow)
+int ipk_raw_to_srgb_resampled_window(const ipk_fused_params *p, const void *src, int64_t tlx, int64_t tly, int64_t trx, int64_t try_, int64_t blx, int64_t bly,
+                                     size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, void *dst, void *stream) {
+  const int64_t corners[6] = {tlx, tly, trx, try_, blx, bly};
+  const ipk::ResampleWindow win = {wy, wx, wh, ww};
+  return resampled_launch(p, src, corners, nwidth, nheight, dst, stream, "resampled", kResampledRefusal, &win);
+}
+int ipk_raw_to_srgb_scaled_window(const ipk_fused_params *p, const void *src, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh,
+                                  void *dst, void *stream) {
+  const ipk::ResampleWindow win = {wy, wx, wh, ww};
+  return resampled_launch(p, src, nullptr, nwidth, nheight, dst, stream, "scaled", kScaledRefusal, &win);
+}
+// what such a window reads of the cropped frame (host only): ipk::resample_footprint on the skips of the corners
+int ipk_transform_window_footprint(size_t width, size_t height, int64_t tlx, int64_t tly, int64_t trx, int64_t try_, int64_t blx, int64_t bly,
+                                   size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, size_t *out4) {
+  if (!out4) return fail(IPK_ERR_INVALID, "null argument");
+  ipk::ResamplePlan plan;
+  if (!ipk::resample_skips(width, height, tlx, tly, trx, try_, blx, bly, nwidth, nheight, plan))
+    return fail(IPK_ERR_UNSUPPORTED, "not a transform the fused paths take (output sides >= 2, finite skips, sides below 2^24)");
+  if (ww == 0 || wh == 0 || wx > nwidth || ww > nwidth - wx || wy > nheight || wh > nheight - wy)
+    return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", wx, wy, ww, wh, nwidth, nheight);
+  const ipk::ResampleFootprint f = ipk::resample_footprint(plan, width, height, wy, wx, wh, ww);
+  out4[0] = f.x; out4[1] = f.y; out4[2] = f.w; out4[3] = f.h;
+  return IPK_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2010,7 +2040,9 @@ int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type) {
 namespace {
 // windowed = 1 (the run is the one fused raw launch, fused_raw_route): the region comes from the unrotated rectangle [c0, c1) x [r0, r1) of the
 // cropped frame, which the window launch computes and OpTransform's permutation (dihedral: rectangles map to rectangles) turns into the region
-struct RegionPlan { int windowed; size_t c0, c1, r0, r1; };
+// kind 1 / 2 (allow_fused has IPK_FUSED_WINDOW_REGIONS and the run is fused_resample_route's / fused_scaledown_route's one launch): the same with the
+// rectangle taken of the resampled pw x ph image that launch produces (rcp.nw x rcp.nh, n.dw x n.dh); the window launch of k_fused_resample computes it
+struct RegionPlan { int windowed; size_t c0, c1, r0, r1; int kind; RotateCropPoints rcp; size_t pw, ph; };
 int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n, ipk_fused_params &fp, RegionPlan &pl) {
   int rc = negotiate(d, out_type, n); if (rc) return rc;
   if (d->npoints < 0 || d->npoints > 64) return fail(IPK_ERR_INVALID, "npoints out of range");
@@ -2018,10 +2050,15 @@ int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, si
   if (w == 0 || h == 0 || x > n.fw || w > n.fw - x || y > n.fh || h > n.fh - y)
     return fail(IPK_ERR_INVALID, "region (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", x, y, w, h, n.fw, n.fh);
   pl.windowed = fused_raw_route(d, n, out_type, fp) ? 1 : 0;
+  pl.kind = 0; pl.pw = n.r.width; pl.ph = n.r.height;
+  if (!pl.windowed && (d->allow_fused & IPK_FUSED_WINDOW_REGIONS) && ipk_pipeline_takes_fastpath(d, out_type) != 1) {
+    if (fused_resample_route(d, n, out_type, fp, pl.rcp)) { pl.windowed = 1; pl.kind = 1; pl.pw = pl.rcp.nw; pl.ph = pl.rcp.nh; }
+    else if (fused_scaledown_route(d, n, out_type, fp)) { pl.windowed = 1; pl.kind = 2; pl.pw = n.dw; pl.ph = n.dh; }
+  }
   if (!pl.windowed) return IPK_OK;
   bool t = false, fx = false, fy = false;
   if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
-  const size_t W = n.r.width, H = n.r.height;
+  const size_t W = pl.pw, H = pl.ph;
   if ((t ? H : W) != n.fw || (t ? W : H) != n.fh) return fail(IPK_ERR_INVALID, "internal: fused result %zux%zu, negotiated %zux%zu", W, H, n.fw, n.fh);
   // rotate_buffer's walk (transform.rs:102-128): result pixel (ox, oy) is source pixel (fx ? W-1-u : u, fy ? H-1-v : v) with (u, v) = t ? (oy, ox) : (ox, oy)
   const size_t u0 = t ? y : x, un = t ? h : w, v0 = t ? x : y, vn = t ? w : h;
@@ -2038,6 +2075,16 @@ int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size
   Negotiated n; ipk_fused_params fp; RegionPlan pl;
   const int rc = plan_region(d, out_type, x, y, w, h, n, fp, pl); if (rc) return rc;
   if (!pl.windowed) { *src_x = n.r.x; *src_y = n.r.y; *src_w = n.r.width; *src_h = n.r.height; return 0; }
+  if (pl.kind != 0) {
+    // the window launch's footprint (ipk_transform_window_footprint) in sensor coordinates; empty where no pixel of the rectangle has a tap
+    ipk::ResamplePlan plan;
+    const bool ok = pl.kind == 1 ? ipk::resample_plan(n.r.width, n.r.height, pl.rcp.pts[0], pl.rcp.pts[1], pl.rcp.pts[2], pl.rcp.pts[3], pl.rcp.pts[4], pl.rcp.pts[5], pl.pw, pl.ph, plan)
+                                 : ipk::scaledown_plan(n.r.width, n.r.height, pl.pw, pl.ph, plan);
+    if (!ok) return fail(IPK_ERR_INVALID, "internal: the route's plan was refused");
+    const ipk::ResampleFootprint f = ipk::resample_footprint(plan, n.r.width, n.r.height, pl.r0, pl.c0, pl.r1 - pl.r0, pl.c1 - pl.c0);
+    *src_x = n.r.x + f.x; *src_y = n.r.y + f.y; *src_w = f.w; *src_h = f.h;
+    return 1;
+  }
   // demosaic::full's one-pixel halo, clipped to the crop window, in sensor coordinates
   const size_t c0 = pl.c0 > 0 ? pl.c0 - 1 : 0, c1 = std::min(n.r.width, pl.c1 + 1), r0 = pl.r0 > 0 ? pl.r0 - 1 : 0, r1 = std::min(n.r.height, pl.r1 + 1);
   *src_x = n.r.x + c0; *src_y = n.r.y + r0; *src_w = c1 - c0; *src_h = r1 - r0;
@@ -2066,6 +2113,33 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
     return IPK_OK;
   }
   StageTimer tm(S(stream));
+  if (pl.kind != 0) {
+    // the one-launch rotatecrop / scaledown routes: the window launch writes the rectangle into dst, or into scratch for orient()
+    tm.rest = pl.kind == 1 ? "fused region gofloat+demosaic+rotatecrop+to_lab+basecurve+from_lab+gamma(+transform)"
+                           : "fused region gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma(+transform)";
+    const size_t cw = pl.c1 - pl.c0, ch = pl.r1 - pl.r0;
+    const RotateCropPoints &r = pl.rcp;
+    auto launch = [&](void *o) {
+      if (pl.kind == 2) return ipk_raw_to_srgb_scaled_window(&fp, src, pl.pw, pl.ph, pl.c0, pl.r0, cw, ch, o, stream);
+      if (crop_only_shortcut(fp, r)) {                         // run_fused_resample's shortcut: the intersection of the two rectangles
+        ipk_fused_params b = fp;
+        b.band_src_row0 = 0; b.band_src_rows = fp.height; b.band_out_row0 = (size_t)r.pts[1] + pl.r0; b.band_out_rows = ch;
+        const void *top = static_cast<const char *>(src) + fp.y * fp.owidth * 2;
+        FusedOpts fo; fo.win_c0 = (size_t)r.pts[0] + pl.c0; fo.win_c1 = fo.win_c0 + cw;
+        return fused_impl(&b, top, o, stream, 0, fo);
+      }
+      return ipk_raw_to_srgb_resampled_window(&fp, src, r.pts[0], r.pts[1], r.pts[2], r.pts[3], r.pts[4], r.pts[5], pl.pw, pl.ph, pl.c0, pl.r0, cw, ch, o, stream);
+    };
+    if (n.transform_noop) return launch(dst);
+    Scratch sc(S(stream));
+    void *tmp = nullptr;
+    rc = sc.get(cw * ch * 3 * esz, &tmp); if (rc) return rc;
+    rc = launch(tmp); if (rc < 0) return rc;
+    size_t ow = 0, oh = 0;
+    rc = orient(tmp, cw, ch, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
+    if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: oriented region %zux%zu, asked for %zux%zu", ow, oh, w, h);
+    return IPK_OK;
+  }
   tm.rest = "fused region gofloat+demosaic+to_lab+basecurve+from_lab+gamma(+transform)";
   // the rows are a band whose source is the whole cropped frame (src then starts at the crop's first row); the columns are the launch's window
   fp.band_src_row0 = 0; fp.band_src_rows = n.r.height; fp.band_out_row0 = pl.r0; fp.band_out_rows = pl.r1 - pl.r0;
@@ -2543,8 +2617,12 @@ int ipk_host_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, si
   HOST_TRY(L.ensure(in_bytes, out_bytes));
   int rc = IPK_OK;
   if (route == 1) {
-    const size_t off = sy * pitch + sx * px;
-    if (hipMemcpy2DAsync(static_cast<char *>(L.in[0]) + off, pitch, static_cast<const char *>(src) + off, pitch, sw * px, sh, hipMemcpyHostToDevice, L.run) != hipSuccess)
+    // the window's rows, widened to 64-byte boundaries inside the frame's rows (at most 126 bytes more per row): pitched copies whose rows start at an
+    // odd u16 sample or hold an odd number of them measured 4-5 times slower than widened ones (profiles/r12_region_windows.txt)
+    const size_t b0 = sx * px / 64 * 64, b1 = std::min(pitch, (sx * px + sw * px + 63) / 64 * 64);
+    const size_t off = sy * pitch + b0;
+    if (sw != 0 && sh != 0 &&                                  // an empty window (no pixel of the region has a tap): the launch reads nothing
+        hipMemcpy2DAsync(static_cast<char *>(L.in[0]) + off, pitch, static_cast<const char *>(src) + off, pitch, b1 - b0, sh, hipMemcpyHostToDevice, L.run) != hipSuccess)
       rc = fail(IPK_ERR_HIP, "window upload failed");
   } else if (hipMemcpyAsync(L.in[0], src, in_bytes, hipMemcpyHostToDevice, L.run) != hipSuccess) {
     rc = fail(IPK_ERR_HIP, "frame upload failed");

@@ -544,6 +544,56 @@ inline bool resample_plan(size_t width, size_t height, int64_t tlx, int64_t tly,
   return false;
 }
 
+// ---- what a window of that launch's output reads (ipk_transform_window_footprint, ipk_pipeline_region under IPK_FUSED_WINDOW_REGIONS) ----
+// The kernel's own box rule (rs_window / rs_box in ipk_kernels.hip) applied to the whole window: from_x / to_x / from_y / to_y of scaling.rs:84-87, each
+// product and sum rounded to f32 on its own (this file is built without contraction, as the kernels are), converted as Rust's `as usize` converts
+// (negative and NaN to 0, saturating) and clamped to the frame.  Each is weakly monotone in row and in col -- rounding preserves that, negative and zero
+// skips included -- so over the rectangle their extremes sit at its four corner pixels, and every tile's box, which the kernel derives the same way from
+// the tile's corners, lies inside this one.  Then demosaic::full's one-pixel halo, clipped to the frame.  w == 0: no window has a tap, nothing is read.
+// Only the plan's corner and skips are read, so a plan that holds nothing else (resample_skips) serves.
+struct ResampleFootprint { size_t x, y, w, h; };
+inline uint32_t f32_as_u32_sat_host(float f) { return !(f > 0.0f) ? 0u : (f >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)f); }
+inline void resample_window_at(const ResamplePlan &p, uint32_t W, uint32_t H, uint32_t row, uint32_t col, uint32_t w[4]) {
+  const float from_x_r = p.tlx + p.skip_y_x * (float)row;
+  const float to_x_r = p.tlx + p.skip_y_x * (float)(row + 1);
+  const float from_y_r = p.tly + p.skip_y_y * (float)row;
+  const float to_y_r = p.tly + p.skip_y_y * (float)(row + 1);
+  w[0] = std::min(W - 1, f32_as_u32_sat_host(std::floor(from_x_r + (p.skip_x_x * (float)col))));
+  w[1] = std::min(W - 1, f32_as_u32_sat_host(std::floor(to_x_r + (p.skip_x_x * (float)(col + 1)))));
+  w[2] = std::min(H - 1, f32_as_u32_sat_host(std::floor(from_y_r + (p.skip_x_y * (float)col))));
+  w[3] = std::min(H - 1, f32_as_u32_sat_host(std::floor(to_y_r + (p.skip_x_y * (float)(col + 1)))));
+}
+inline ResampleFootprint resample_footprint(const ResamplePlan &p, size_t width, size_t height, size_t row0, size_t col0, size_t rows, size_t cols) {
+  const uint32_t W = (uint32_t)width, H = (uint32_t)height;
+  const uint32_t r[2] = {(uint32_t)row0, (uint32_t)(row0 + rows - 1)}, c[2] = {(uint32_t)col0, (uint32_t)(col0 + cols - 1)};
+  uint32_t x0 = 0xFFFFFFFFu, x1 = 0u, y0 = 0xFFFFFFFFu, y1 = 0u;
+  for (int i = 0; i < 4; ++i) {
+    uint32_t w[4];
+    resample_window_at(p, W, H, r[i >> 1], c[i & 1], w);
+    x0 = std::min(x0, w[0]); x1 = std::max(x1, w[1]); y0 = std::min(y0, w[2]); y1 = std::max(y1, w[3]);
+  }
+  ResampleFootprint f = {0, 0, 0, 0};
+  if (x1 < x0 || y1 < y0) return f;
+  const uint32_t mx0 = x0 > 0u ? x0 - 1u : 0u, my0 = y0 > 0u ? y0 - 1u : 0u, mx1 = std::min(x1 + 1u, W - 1u), my1 = std::min(y1 + 1u, H - 1u);
+  f.x = mx0; f.y = my0; f.w = mx1 - mx0 + 1u; f.h = my1 - my0 + 1u;
+  return f;
+}
+// the corner and the skips of scaling.rs:68-72 alone, for the footprint of either form (the scaled form's corners are (0, 0), (width - 1, 0),
+// (0, height - 1), for which these are scaledown_plan's expressions): sizes the launches could take and finite values, no admission by window size
+inline bool resample_skips(size_t width, size_t height, int64_t tlx, int64_t tly, int64_t trx, int64_t try_, int64_t blx, int64_t bly,
+                           size_t nwidth, size_t nheight, ResamplePlan &p) {
+  const size_t lim = size_t(1) << 24;
+  if (nwidth < 2 || nheight < 2 || width < 1 || height < 1 || width >= lim || height >= lim || nwidth >= lim || nheight >= lim) return false;
+  p.tlx = (float)tlx; p.tly = (float)tly;
+  p.skip_x_x = ((float)trx - (float)tlx) / ((float)(nwidth - 1));
+  p.skip_x_y = ((float)try_ - (float)tly) / ((float)(nwidth - 1));
+  p.skip_y_x = ((float)blx - (float)tlx) / ((float)(nheight - 1));
+  p.skip_y_y = ((float)bly - (float)tly) / ((float)(nheight - 1));
+  p.tile_w = 0; p.tile_h = 0;
+  return std::isfinite(p.tlx) && std::isfinite(p.tly) && std::isfinite(p.skip_x_x) && std::isfinite(p.skip_x_y) && std::isfinite(p.skip_y_x) &&
+         std::isfinite(p.skip_y_y);
+}
+
 // ---- the same launch for OpDemosaic's `full` + scale_down_opbuf branch (demosaic.rs:51-59, ipk_raw_to_srgb_scaled): scale_down_opbuf is
 // transform_buffer with the corners (0, 0), (width - 1, 0), (0, height - 1) (scaling.rs:46), so both cross skips are exactly +0.0 and the window of
 // output pixel (row, col) is the axis-aligned floor(skip_x * col) ..= floor(skip_x * (col + 1)) by floor(skip_y * row) ..= floor(skip_y * (row + 1)) ----

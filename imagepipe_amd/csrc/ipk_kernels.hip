@@ -3401,9 +3401,17 @@ int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const
 // a positive count, or the zero fill: +0.0 either way, which is what the fast point-wise form assumes.
 // The NEXT tile's mosaic loads are issued in front of stage 3 and land in LDS behind it (the mosaic buffer is idle meanwhile), so the memory round trip
 // hides behind the arithmetic: two barriers per tile.
+// A window launch (ResampleArgs::wr0 / wc0: regions, ipk_raw_to_srgb_*_window) walks the tiles of a rectangle of the output image instead: fewer tiles,
+// the same arithmetic per pixel.
 // ------------------------------------------------------------------------------------------
 struct ResampleArgs {
+  // nw x nh: the output window this launch computes and stores packed into dst -- the whole result, or (launch_fused_resample's ResampleWindow) the
+  // nh rows from wr0 and nw columns from wc0 of it.  Tiles are laid over the window from its origin; tile coordinates, the bounds and the store offset
+  // are the window's own, exactly as for a whole frame.  Every per-pixel expression -- rs_window, the centres, the CFA table, the frame-edge tests --
+  // works on the pixel's position in the RESULT, window position + (wr0, wc0), so a pixel's bits do not depend on the window or the tiling.
+  // The kernel runs at its scalar-register limit: the origin is read once in front of the tile loop and lives in two vector registers per lane
   uint32_t nw, nh, tw, th, tiles_x, n_tiles;
+  uint32_t wr0, wc0;
   float tlx, tly, skip_x_x, skip_x_y, skip_y_x, skip_y_y, inv_skip_x_x, inv_skip_y_y;
   int fast_x, fast_y;
   int axis;                              // 1: scale_down_opbuf's transform (scaledown_plan): corner (0, 0), cross skips exactly +0.0, windows of up to 4x4
@@ -3425,9 +3433,10 @@ __device__ __forceinline__ RsWin rs_window(const ResampleArgs &t, uint32_t W, ui
 }
 // a tile's box [x0, x0 + w) x [y0, y0 + h) and its mosaic region (the box and its halo inside the frame), cropped-frame coordinates; w == 0: no window has a tap
 struct RsBox { uint32_t x0, y0, w, h, mx0, my0, mw, mh; };
-__device__ __forceinline__ RsBox rs_box(const ResampleArgs &t, uint32_t W, uint32_t H, uint32_t tile) {
+__device__ __forceinline__ RsBox rs_box(const ResampleArgs &t, uint32_t W, uint32_t H, uint32_t tile, uint32_t wr0, uint32_t wc0) {
   const uint32_t tyi = tile / t.tiles_x, txi = tile - tyi * t.tiles_x;
-  const uint32_t r0 = tyi * t.th, c0 = txi * t.tw, r1 = min(r0 + t.th, t.nh) - 1u, c1 = min(c0 + t.tw, t.nw) - 1u;
+  const uint32_t q0 = tyi * t.th, p0 = txi * t.tw;                      // the tile inside the window; its corner pixels in the result:
+  const uint32_t r0 = wr0 + q0, c0 = wc0 + p0, r1 = wr0 + min(q0 + t.th, t.nh) - 1u, c1 = wc0 + min(p0 + t.tw, t.nw) - 1u;
   const RsWin a = rs_window(t, W, H, r0, c0), b = rs_window(t, W, H, r0, c1), c = rs_window(t, W, H, r1, c0), d = rs_window(t, W, H, r1, c1);
   const uint32_t x0 = min(min(a.fx, b.fx), min(c.fx, d.fx)), x1 = max(max(a.tx, b.tx), max(c.tx, d.tx));
   const uint32_t y0 = min(min(a.fy, b.fy), min(c.fy, d.fy)), y1 = max(max(a.ty, b.ty), max(c.ty, d.ty));
@@ -3490,7 +3499,7 @@ __device__ __forceinline__ void rs_store_mosaic(const FusedArgs &a, const RsBox 
 // factor, y outer and x inner per pixel.  Admitted skips are below 3 and windows at most four wide; the four x terms live in registers (unrolled, no
 // indexing), and a tap past the fourth -- none exists for an admitted plan -- would still be walked, by the general per-tap form.
 __device__ __forceinline__ void rs_walk_axis(const ResampleArgs &t, const RsBox &box, uint32_t W, uint32_t H, const float *__restrict__ s_rgb, uint32_t row,
-                                             uint32_t col0, bool row_ok, float center_x_r, float center_y_r, float4 px[2], bool ok[2]) {
+                                             uint32_t col0, uint32_t wcol0, bool row_ok, float center_x_r, float center_y_r, float4 px[2], bool ok[2]) {
   const uint32_t bx1 = box.x0 + box.w, by1 = box.y0 + box.h;            // one past the box
   uint32_t fx[2], nx[2];
   float dx2[2][4], ctr[2], s0[2], s1[2], s2[2], n[2];
@@ -3498,7 +3507,7 @@ __device__ __forceinline__ void rs_walk_axis(const ResampleArgs &t, const RsBox 
   #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const uint32_t col = col0 + (uint32_t)j;
-    ok[j] = row_ok && col < t.nw;
+    ok[j] = row_ok && wcol0 + (uint32_t)j < t.nw;                        // (wcol0: the pixel's column inside the window)
     const RsWin w = rs_window(t, W, H, row, col);
     // clipped to the box as the general walk clips (the window lies inside it by construction); a lane without a pixel walks nothing
     fx[j] = max(w.fx, box.x0);
@@ -3562,16 +3571,17 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
   if (a.spline.grid_ok) fill_grid(s_grid, a.spline, (int)threadIdx.x);
 
   uint32_t tile = blockIdx.x;                                           // the grid never exceeds the tile count
-  RsBox box = rs_box(t, a.W, a.H, tile);
+  // the lane's two pixels inside a tile: neighbours in one tile row (tile_w is even); the same two as positions in the result for the window's first tile
+  const uint32_t p0 = 2u * threadIdx.x;
+  const uint32_t trow = p0 / t.tw, tcol = p0 - trow * t.tw;
+  const uint32_t arow = t.wr0 + trow, acol = t.wc0 + tcol;
+  RsBox box = rs_box(t, a.W, a.H, tile, arow - trow, acol - tcol);
   {
     float mv[kRsMosPerThread];
     rs_load_mosaic<SrcT>(a, box, mv);
     rs_store_mosaic<SrcT>(a, box, mv, s_mos);
   }
   sync_after_lds_direct();                                              // the tables and the first tile's mosaic
-  // the lane's two pixels inside a tile: neighbours in one tile row (tile_w is even)
-  const uint32_t p0 = 2u * threadIdx.x;
-  const uint32_t trow = p0 / t.tw, tcol = p0 - trow * t.tw;
   for (;;) {
     // ---- stage 2: demosaic::full over the box ----
     {
@@ -3604,12 +3614,13 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
     const bool more = next < t.n_tiles;
     RsBox nbox = box;
     float mv[kRsMosPerThread];
-    if (more) { nbox = rs_box(t, a.W, a.H, next); rs_load_mosaic<SrcT>(a, nbox, mv); }
+    if (more) { nbox = rs_box(t, a.W, a.H, next, arow - trow, acol - tcol); rs_load_mosaic<SrcT>(a, nbox, mv); }
     // ---- stage 3: resample, chain, store ----
     {
       const uint32_t tyi = tile / t.tiles_x, txi = tile - tyi * t.tiles_x;
-      const uint32_t row = tyi * t.th + trow, col0 = txi * t.tw + tcol;
-      const bool row_ok = trow < t.th && row < t.nh;
+      const uint32_t wrow = tyi * t.th + trow, wcol0 = txi * t.tw + tcol;   // inside the window: the bounds and the store offset
+      const uint32_t row = tyi * t.th + arow, col0 = txi * t.tw + acol;     // in the result: everything that enters a pixel's value
+      const bool row_ok = trow < t.th && wrow < t.nh;
       const uint32_t bx1 = box.x0 + box.w, by1 = box.y0 + box.h;        // one past the box
       // per-row values (scaling.rs:79-82)
       const float center_x_r = t.tlx + (t.skip_y_x * (float)row) + (t.skip_y_x / 2.0f) - 0.5f;
@@ -3617,12 +3628,12 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
       float4 px[2];
       bool ok[2];
       if (t.axis) {                                                     // block-uniform: the launch's mode
-        rs_walk_axis(t, box, a.W, a.H, s_rgb, row, col0, row_ok, center_x_r, center_y_r, px, ok);
+        rs_walk_axis(t, box, a.W, a.H, s_rgb, row, col0, wcol0, row_ok, center_x_r, center_y_r, px, ok);
       } else {
         #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const uint32_t col = col0 + (uint32_t)j;
-          ok[j] = row_ok && col < t.nw;
+          ok[j] = row_ok && wcol0 + (uint32_t)j < t.nw;
           const RsWin w = rs_window(t, a.W, a.H, row, col);
           // the window lies inside the box by construction; the clip keeps the LDS reads in bounds even where the box had to be cut (rs_box).
           // x_end / y_end: one past the last tap (window ends are frame coordinates, below 2^24); a lane without a pixel walks nothing
@@ -3661,7 +3672,7 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
         }
       }
       // the wave's pixels are neighbours in the output row: each lane's 24 / 6 / 12 bytes continue its neighbour's
-      const size_t e = ((size_t)row * t.nw + col0) * 3u;
+      const size_t e = ((size_t)wrow * t.nw + wcol0) * 3u;
       if (OUT == 0) {
         float *g = reinterpret_cast<float *>(a.dst) + e;
         if (ok[1]) {
@@ -3696,7 +3707,8 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
   }
 }
 
-int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s) {
+int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s,
+                          const ResampleWindow *win) {
   FusedArgs a = chain_args(f);
   a.W = (uint32_t)f.width; a.H = (uint32_t)f.height; a.owidth = f.owidth;
   a.min0 = f.black0; a.range0 = f.white0 - f.black0;                       // gofloat.rs:86-89
@@ -3704,6 +3716,10 @@ int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t
   a.exact_norm = f.exact_norm;
   ResampleArgs t;
   t.nw = (uint32_t)nwidth; t.nh = (uint32_t)nheight; t.tw = plan.tile_w; t.th = plan.tile_h;
+  t.wr0 = 0u; t.wc0 = 0u;
+  if (win) {                                                                // the caller checked it: not empty, inside nwidth x nheight
+    t.wr0 = (uint32_t)win->row0; t.wc0 = (uint32_t)win->col0; t.nh = (uint32_t)win->rows; t.nw = (uint32_t)win->cols;
+  }
   t.tiles_x = (t.nw + t.tw - 1u) / t.tw;
   const uint64_t tiles = (uint64_t)t.tiles_x * ((t.nh + t.th - 1u) / t.th);   // below 2^24 / 16 squared
   t.n_tiles = (uint32_t)tiles;
@@ -3716,7 +3732,9 @@ int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t
   const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = (unsigned)std::min<uint64_t>(cus, tiles);
   // the general mode's tags stay as they were; the axis-aligned mode (scaledown_plan) adds its own key
-  const char *tag = t.axis ? (a.fast_ok ? "fast_ok=1,axis=1" : "fast_ok=0,axis=1") : (a.fast_ok ? "fast_ok=1" : "fast_ok=0");
+  // and a window launch (win) its own next to them
+  const char *tag = win ? (t.axis ? (a.fast_ok ? "fast_ok=1,axis=1,win=1" : "fast_ok=0,axis=1,win=1") : (a.fast_ok ? "fast_ok=1,win=1" : "fast_ok=0,win=1"))
+                        : (t.axis ? (a.fast_ok ? "fast_ok=1,axis=1" : "fast_ok=0,axis=1") : (a.fast_ok ? "fast_ok=1" : "fast_ok=0"));
   #define IPK_RS_LAUNCH(T, O) IPK_LAUNCH_TAG(tag, (k_fused_resample<T, O>), dim3(blocks), dim3(1024), 0, s, a, t)
   if (f.src_is_u16) { if (f.out_type == 0) IPK_RS_LAUNCH(uint16_t, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(uint16_t, 1); else IPK_RS_LAUNCH(uint16_t, 2); }
   else { if (f.out_type == 0) IPK_RS_LAUNCH(float, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(float, 1); else IPK_RS_LAUNCH(float, 2); }

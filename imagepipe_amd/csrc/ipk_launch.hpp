@@ -44,7 +44,9 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // sample; wrap: the grid cap holds), k_gofloat_cfa_v4 [rowwrap=] (more rows than grid rows), the ipk_raw_scaled_demosaic kernels
 // [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form);
-// k_fused_resample's axis-aligned mode (ipk_raw_to_srgb_scaled) [fast_ok=,axis=1]; the generic-CFA runtime-flag variants of k_fused_bayer /
+// k_fused_resample's axis-aligned mode (ipk_raw_to_srgb_scaled) [fast_ok=,axis=1]; k_fused_resample's window launches (launch_fused_resample with a
+// ResampleWindow: ipk_raw_to_srgb_resampled_window / _scaled_window, regions under IPK_FUSED_WINDOW_REGIONS) append win=1: [fast_ok=,win=1] /
+// [fast_ok=,axis=1,win=1] -- whole-frame launches never carry the key; the generic-CFA runtime-flag variants of k_fused_bayer /
 // k_fused_bayer_window [four=1] on the launches of a filter with a fourth colour only (FusedLaunch::four) -- three-colour launches carry no tag.
 void launch_log_enable(bool on);                 // clears the log, then switches it on or off
 size_t launch_log_read(char *buf, size_t cap);   // entries sorted, newline-separated, NUL-terminated (truncated to cap); returns the bytes a full read needs
@@ -115,7 +117,12 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s);
 // Cfa::demosaic_lookups of a three-colour filter.  Of f, the geometry, the levels, exact_norm and what launch_pointwise_chain reads are used.
 // returns 0, or -4 when the launch could not be enqueued
 // plan.axis (scaledown_plan): the kernel's axis-aligned stage 3, for scale_down_opbuf's transform
-int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s);
+// win (optional): only the rows [row0, row0 + rows) and columns [col0, col0 + cols) of the nwidth x nheight result are computed, and f.dst holds exactly
+// rows * cols * 3 packed samples (tiles are laid over the window from its origin; every pixel's bits are those of the whole-frame launch); it must be
+// non-empty and lie inside the result.  Null: the whole frame, whose log entries are unchanged; a window launch adds the key win=1
+struct ResampleWindow { size_t row0, col0, rows, cols; };
+int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s,
+                          const ResampleWindow *win = nullptr);
 // rotate_buffer's permutation on a 1-channel image through an arbitrary source pitch / window (steps in source elements): |x_step| == 1 (flips, 180
 // degrees) or |y_step| == 1 (the transposing orientations, oheight <= kRotate1MaxTransposedRows)
 constexpr size_t kRotate1MaxTransposedRows = 65535u * 64u;

@@ -381,6 +381,25 @@ IPK_API int ipk_raw_to_srgb_resampled(const ipk_fused_params *p, const void *src
  * (p->width - 1) / (nwidth - 1) or (p->height - 1) / (nheight - 1) (in f32, src/scaling.rs:69-72) that is not finite, below 1, or 3 or more (windows
  * larger than 4x4: ipk_raw_scaled_demosaic's range for most filters), frame sides of 2^24 or more. */
 IPK_API int ipk_raw_to_srgb_scaled(const ipk_fused_params *p, const void *src, size_t nwidth, size_t nheight, void *dst, void *stream);
+/* The window forms of the two: only the columns [wx, wx + ww) and rows [wy, wy + wh) of the nwidth x nheight result are computed, in the same one
+ * launch laid over the window instead of the frame.  Admission is exactly that of the whole-frame forms; an empty window or one that leaves
+ * nwidth x nheight is IPK_ERR_INVALID (nothing written).  dst receives ww * wh * 3 packed samples of p->out_type, bit-identical to that rectangle of
+ * the whole-frame call -- every pixel is computed from its absolute position, so nothing depends on the window -- and nothing outside them is written.
+ * src is still the whole sensor frame's first sample, but the launch reads only the window's footprint (ipk_transform_window_footprint, offset by
+ * p->x, p->y).  src and dst need only element alignment, as for the whole-frame forms. */
+IPK_API int ipk_raw_to_srgb_resampled_window(const ipk_fused_params *p, const void *src, int64_t tlx, int64_t tly, int64_t trx, int64_t try_,
+                                             int64_t blx, int64_t bly, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh,
+                                             void *dst, void *stream);
+IPK_API int ipk_raw_to_srgb_scaled_window(const ipk_fused_params *p, const void *src, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww,
+                                          size_t wh, void *dst, void *stream);
+/* What such a window reads of the width x height cropped frame, host-only (no GPU needed): out4 = {x, y, w, h} in cropped-frame coordinates, the
+ * bounding box of the source windows (src/scaling.rs:84-87) of the window's four corner pixels -- the expressions are monotone in row and in col, so
+ * the extremes sit there -- plus demosaic::full's one-pixel halo, clipped to the frame.  w = h = 0 when no pixel of the window has a tap (the launch
+ * then reads nothing).  It contains everything the launch reads and exceeds the exact box by at most 2 pixels per side.  The corners are those of
+ * ipk_raw_to_srgb_resampled; for the scaled form they are (0, 0), (width - 1, 0), (0, height - 1).  IPK_ERR_INVALID for an empty window or one that
+ * leaves nwidth x nheight, IPK_ERR_UNSUPPORTED for a transform ipk_raw_to_srgb_resampled refuses by its skips or sizes. */
+IPK_API int ipk_transform_window_footprint(size_t width, size_t height, int64_t tlx, int64_t tly, int64_t trx, int64_t try_, int64_t blx, int64_t bly,
+                                           size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, size_t *out4);
 
 /* OpToLab::run + OpBaseCurve::run + OpFromLab::run + OpGamma::run (src/ops/colorspaces.rs:89-112, src/ops/curves.rs:33-49,
  * src/ops/colorspaces.rs:127-137, src/ops/gamma.rs:16-26) in one pass over a 4-channel OpBuffer: the ops Pipeline::run applies
@@ -433,7 +452,11 @@ typedef struct {
                                       one-launch route where ipk_pipeline_fuses_four_colour says so; without it they take the staged ops, as they always
                                       did.  The opt-in lives here because the descriptor's tail is pinned (its last field and reserved1 are named by callers
                                       and tests): no field could be added or renamed for it.  Like the rest of allow_fused it does not enter the hashes and
-                                      results do not depend on it. */
+                                      results do not depend on it.
+                                      Bit 2 (IPK_FUSED_WINDOW_REGIONS = 4) concerns regions only (ipk_pipeline_region / _run_region / ipk_host_pipeline_run_region):
+                                      with it, a descriptor for which ipk_pipeline_fuses_rotatecrop or ipk_pipeline_fuses_scaledown answers 1 renders a region
+                                      as a window of that one launch instead of computing the whole result.  Same contract: no hash, no result, and no other
+                                      driver or report depends on it. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -451,7 +474,8 @@ typedef struct {
 /* the bits of ipk_pipeline_desc.allow_fused */
 typedef enum {
   IPK_FUSED_ON = 1,                /* the one-launch routes where legal (any non-zero value means this) */
-  IPK_FUSED_FOUR_COLOUR = 2        /* bit 1: four-colour filters take the one-launch route too */
+  IPK_FUSED_FOUR_COLOUR = 2,       /* bit 1: four-colour filters take the one-launch route too */
+  IPK_FUSED_WINDOW_REGIONS = 4     /* bit 2: regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -515,14 +539,18 @@ IPK_API int ipk_host_pipeline_run(const ipk_pipeline_desc *d, const void *src, v
  * rectangle of the cropped frame the region comes from, and reads only the sensor window reported (that rectangle plus demosaic::full's
  * one-pixel halo, clipped to the crop window, in sensor coordinates); 0 = whole frame -- staged, scaled, rotatecrop, four-colour (without
  * IPK_FUSED_FOUR_COLOUR in allow_fused; with it: windowed), mono/RGB and
- * raster routes and allow_fused = 0 compute the whole result and copy the region out, and the window reported is the crop window. */
+ * raster routes and allow_fused = 0 compute the whole result and copy the region out, and the window reported is the crop window.
+ * With IPK_FUSED_WINDOW_REGIONS in allow_fused the one-launch rotatecrop and scaledown routes (ipk_pipeline_fuses_rotatecrop / _scaledown answer 1)
+ * are windowed too: the region is mapped back through OpTransform to a rectangle of the resampled image, the launch runs over that rectangle only,
+ * and the window reported is its footprint (ipk_transform_window_footprint plus the crop offset; it can be empty, w = h = 0, where no pixel of the
+ * region has a tap).  Without the bit those routes answer 0, as they always did. */
 IPK_API int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h,
                                 size_t *src_x, size_t *src_y, size_t *src_w, size_t *src_h);
 /* The region from the DEVICE source ipk_pipeline_run takes (the whole sensor frame) into the DEVICE buffer dst, enqueued on `stream`.
  * *windowed (may be NULL) receives the route.  ipk_timing_begin/end see its stages. */
 IPK_API int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t x, size_t y, size_t w, size_t h, void *dst,
                                     int out_type, int *windowed, void *stream);
-/* The same from the whole HOST frame into a HOST buffer; synchronous.  The windowed route uploads only the reported sensor window (one
+/* The same from the whole HOST frame into a HOST buffer; synchronous.  The windowed route uploads only the reported sensor window, its rows widened to 64-byte boundaries of the frame's rows (one
  * pitched copy), the whole route the frame; only the region's w*h*3 samples come back. */
 IPK_API int ipk_host_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t x, size_t y, size_t w, size_t h, void *dst,
                                          int out_type, int *windowed);

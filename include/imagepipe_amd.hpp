@@ -298,6 +298,7 @@ class Pipeline {
   bool fuse_rotatecrop = false;            // ipk_pipeline_desc.fuse_rotatecrop: an active OpRotateCrop inside the one launch where fuses_rotatecrop() says so
   bool fuse_scaledown = false;             // ipk_pipeline_desc.fuse_scaledown: OpDemosaic's full + scale_down_opbuf branch inside the one launch where fuses_scaledown() says so
   bool fuse_four_colour = false;           // ipk_pipeline_desc.allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR): a filter with a fourth colour (RGBE ...) on the one-launch route where fuses_four_colour() says so
+  bool window_regions = false;             // ipk_pipeline_desc.allow_fused bit 2 (IPK_FUSED_WINDOW_REGIONS): regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch
   int last_ops_run = 0xFF;                 // bit i: op i executed in the last run (0 = served from the cache)
   uint64_t source_id = 0;                  // identifies the frame inside a shared PipelineCache (extension, see the C header)
   static PipelineCache new_cache(size_t size) { return PipelineCache(size); }
@@ -377,6 +378,7 @@ class Pipeline {
     d.fuse_rotatecrop = fuse_rotatecrop ? 1 : 0;
     d.fuse_scaledown = fuse_scaledown ? 1 : 0;
     if (fuse_four_colour && d.allow_fused) d.allow_fused |= IPK_FUSED_FOUR_COLOUR;
+    if (window_regions && d.allow_fused) d.allow_fused |= IPK_FUSED_WINDOW_REGIONS;
     return d;
   }
   // does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop; no GPU needed)?  out_type: IPK_OUT_*
