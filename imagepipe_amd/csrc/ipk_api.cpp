@@ -992,6 +992,39 @@ int ipk_output16bit(const float *src, size_t n, uint16_t *dst, void *stream) {
 // ------------------------------------------------------------------------------------------
 // fused raw -> sRGB
 // ------------------------------------------------------------------------------------------
+namespace {
+// what tolab..gamma need besides the pixels: normalised multipliers, the matrix, the curve, the tables -- and whether all of it
+// is ordinary enough for the fast point-wise form (pointwise4_fast; otherwise the kernels evaluate the literal form)
+struct PointwisePrep {
+  float mul[4], cm[12];
+  ipk::Spline sp;
+  ipk::FusedLaunch f;                    // zeroed here, so a caller may fill in its own fields before or after prepare()
+  PointwisePrep() { std::memset(&f, 0, sizeof(f)); }
+  int prepare(int monochrome, const float *wb_coeffs, const float *cam_to_xyz_normalized, float exposure, const float *points, int npoints, int linear) {
+    if (npoints < 0 || npoints > 64 || (npoints > 0 && !points)) return fail(IPK_ERR_INVALID, "npoints out of range");
+    if (monochrome) { ipk::srgb_d65_43(cm); mul[0] = mul[1] = mul[2] = mul[3] = 1.0f; }                     // colorspaces.rs:90-101
+    else { std::memcpy(cm, cam_to_xyz_normalized, sizeof(cm)); ipk::normalize_wbs(wb_coeffs, mul); }
+    f.mul4 = mul; f.cm12 = cm; f.rgbm9 = g_host.xyz_d65_33;
+    auto sane = [](float v) { return std::fabs(v) <= 0x1p20f; };
+    bool ok = true;
+    for (int i = 0; i < 4; ++i) ok = ok && sane(mul[i]);
+    for (int i = 0; i < 12; ++i) ok = ok && sane(cm[i]);
+    f.fast_ok = ok ? 1 : 0;
+    f.has_curve = !curve_is_noop(exposure, npoints);
+    if (f.has_curve) {
+      int rc = build_curve(exposure, points, npoints, sp); if (rc) return rc;
+      for (int i = 0; i < sp.npoints; ++i) if (!(std::fabs(sp.px[i]) <= 0x1p20f && std::fabs(sp.py[i]) <= 0x1p20f && std::fabs(sp.c1[i]) <= 0x1p40f)) f.fast_ok = 0;
+      for (int i = 0; i < sp.nseg; ++i) if (!(std::fabs(sp.c2[i]) <= 0x1p40f && std::fabs(sp.c3[i]) <= 0x1p40f)) f.fast_ok = 0;
+    }
+    f.spline = &sp;
+    f.linear = linear;
+    f.lab_table = cx().lut_plain[ipk::kLutXyzLab]; f.gam_table = cx().lut_plain[ipk::kLutGamma]; f.lab_pairs = cx().lut_pairs[ipk::kLutXyzLab]; f.gam_pairs = cx().lut_pairs[ipk::kLutGamma];
+    f.num_cus = cx().num_cus; f.gam_q8 = cx().lut_q8;
+    return IPK_OK;
+  }
+};
+}  // namespace
+
 // Generic-CFA cell records for a launch in rotated space: the record of rotated-space pixel (y', x') is the record of the sensor
 // pixel it came from (its taps stay in the sensor's order; the kernel renames the window).  The rotated pattern has the sensor
 // pattern's dimensions swapped (transposing orientations) and a phase that depends on the frame size through the flips.
@@ -1057,7 +1090,8 @@ static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, voi
                                                                      : "CFA \"%s\" has a fourth colour; run the staged ops", p->cfa);
   if (!bayer && !dev.gen_cells) return fail(IPK_ERR_UNSUPPORTED, "CFA \"%s\": no cell records; run the staged ops", p->cfa);
 
-  ipk::FusedLaunch f;
+  PointwisePrep pp;
+  ipk::FusedLaunch &f = pp.f;
   const size_t esz = p->src_type == IPK_SRC_U16 ? 2 : 4;
   const bool band = p->band_out_rows != 0;
   f.row_off = band ? p->band_src_row0 : 0;
@@ -1131,38 +1165,21 @@ static int fused_impl(const ipk_fused_params *p, const void *src, void *dst, voi
   // when the levels allow one outside [2^-60, 2^60] (f32 kernels always check)
   f.gen_check = (!bayer && f.src_is_u16 && !gen_levels_ok_u16(p->black0, p->white0 - p->black0)) ? 1 : 0;
   f.four = four ? 1 : 0;                                   // a fourth colour: literal demosaic with a fourth bin, literal point-wise form (launch_fused_bayer)
-  float mul[4];
-  ipk::normalize_wbs(p->wb_coeffs, mul);                                                                   // colorspaces.rs:100
-  f.mul4 = mul; f.cm12 = p->cam_to_xyz_normalized; f.rgbm9 = g_host.xyz_d65_33;
-  // the fast point-wise form assumes finite, ordinary parameters (see pointwise4_fast): |value| <= 2^20, no NaN/inf
+  // the point-wise stages' share -- multipliers, matrix, curve, fast_ok, tables -- as every other launch of the chain prepares it
+  { int rc = pp.prepare(0, p->wb_coeffs, p->cam_to_xyz_normalized, p->exposure, p->points, p->npoints, p->linear); if (rc) return rc; }
   {
-    auto sane = [](float v) { return std::fabs(v) <= 0x1p20f; };        // false for NaN and inf
-    bool ok = true;
-    for (int i = 0; i < 4; ++i) ok = ok && sane(mul[i]);
-    for (int i = 0; i < 12; ++i) ok = ok && sane(p->cam_to_xyz_normalized[i]);
-    f.fast_ok = ok ? 1 : 0;
     // when the samples (u16: all 65 536 walked here; f32: bounded below through the black level), the multipliers and the matrix
     // are ordinary (see pointwise4_fast in ipk_kernels.hip), the kernel variant without per-pixel input guards is legal
     const float range = p->white0 - p->black0;
-    bool plain = ok && bayer && range > 0.0f;
+    bool plain = bayer && range > 0.0f && std::fabs(pp.mul[3]) <= 0x1p20f;                               // (the fourth multiplier: finite and ordinary is enough)
     if (f.src_is_u16) plain = plain && gen_levels_ok_u16(p->black0, range);                       // every nonzero sample >= 2^-20 in magnitude
     else plain = plain && std::fabs(p->black0) >= range * 0x1p-6f && std::fabs(p->black0) <= 0x1p70f;   // every nonzero sample >= 2^-31
-    for (int i = 0; i < 3; ++i) plain = plain && mul[i] >= 0x1p-4f && mul[i] <= 0x1p10f;
-    for (int i = 0; i < 12; ++i) { const float c = std::fabs(p->cam_to_xyz_normalized[i]); plain = plain && (c == 0.0f || (c >= 0x1p-12f && c <= 0x1p20f)); }
+    for (int i = 0; i < 3; ++i) plain = plain && pp.mul[i] >= 0x1p-4f && pp.mul[i] <= 0x1p10f;
+    for (int i = 0; i < 12; ++i) { const float c = std::fabs(pp.cm[i]); plain = plain && (c == 0.0f || (c >= 0x1p-12f && c <= 0x1p20f)); }
     f.px_guard = plain ? 0 : 1;
   }
-  ipk::Spline sp;
-  f.has_curve = !curve_is_noop(p->exposure, p->npoints);
-  if (f.has_curve) {
-    int rc = build_curve(p->exposure, p->points, p->npoints, sp); if (rc) return rc;
-    for (int i = 0; i < sp.npoints; ++i) if (!(std::fabs(sp.px[i]) <= 0x1p20f && std::fabs(sp.py[i]) <= 0x1p20f && std::fabs(sp.c1[i]) <= 0x1p40f)) f.fast_ok = 0;
-    for (int i = 0; i < sp.nseg; ++i) if (!(std::fabs(sp.c2[i]) <= 0x1p40f && std::fabs(sp.c3[i]) <= 0x1p40f)) f.fast_ok = 0;
-  }
-  f.spline = &sp;
-  f.linear = p->linear;
   f.out_type = probe ? 4 : p->out_type;
-  f.lab_table = cx().lut_plain[ipk::kLutXyzLab]; f.gam_table = cx().lut_plain[ipk::kLutGamma]; f.lab_pairs = cx().lut_pairs[ipk::kLutXyzLab]; f.gam_pairs = cx().lut_pairs[ipk::kLutGamma];
-  f.num_cus = cx().num_cus; f.queues = cx().queues; f.gam_q8 = cx().lut_q8;
+  f.queues = cx().queues;
   if (p->schedule != IPK_SCHED_AUTO && p->schedule != IPK_SCHED_SPLIT) return fail(IPK_ERR_INVALID, "bad schedule");
   f.schedule = p->schedule;
   if (win_c1 != 0 && (ori != 0 || nbatch || probe || win_c0 >= win_c1 || win_c1 > p->width)) return fail(IPK_ERR_INVALID, "bad column window");
@@ -1207,38 +1224,6 @@ int ipk_raw_to_srgb_oriented(const ipk_fused_params *p, const void *src, int ori
 // OpToLab::run + OpBaseCurve::run + OpFromLab::run + OpGamma::run (colorspaces.rs:89-112, curves.rs:33-49, colorspaces.rs:127-137,
 // gamma.rs:16-26) in one pass: what Pipeline::run computes between rotatecrop and transform when no cache needs the
 // intermediate buffers.
-namespace {
-// what tolab..gamma need besides the pixels: normalised multipliers, the matrix, the curve, the tables -- and whether all of it
-// is ordinary enough for the fast point-wise form (pointwise4_fast; otherwise the kernels evaluate the literal form)
-struct PointwisePrep {
-  float mul[4], cm[12];
-  ipk::Spline sp;
-  ipk::FusedLaunch f;
-  int prepare(int monochrome, const float *wb_coeffs, const float *cam_to_xyz_normalized, float exposure, const float *points, int npoints, int linear) {
-    if (npoints < 0 || npoints > 64 || (npoints > 0 && !points)) return fail(IPK_ERR_INVALID, "npoints out of range");
-    if (monochrome) { ipk::srgb_d65_43(cm); mul[0] = mul[1] = mul[2] = mul[3] = 1.0f; }                     // colorspaces.rs:90-101
-    else { std::memcpy(cm, cam_to_xyz_normalized, sizeof(cm)); ipk::normalize_wbs(wb_coeffs, mul); }
-    std::memset(&f, 0, sizeof(f));
-    f.mul4 = mul; f.cm12 = cm; f.rgbm9 = g_host.xyz_d65_33;
-    auto sane = [](float v) { return std::fabs(v) <= 0x1p20f; };
-    bool ok = true;
-    for (int i = 0; i < 4; ++i) ok = ok && sane(mul[i]);
-    for (int i = 0; i < 12; ++i) ok = ok && sane(cm[i]);
-    f.fast_ok = ok ? 1 : 0;
-    f.has_curve = !curve_is_noop(exposure, npoints);
-    if (f.has_curve) {
-      int rc = build_curve(exposure, points, npoints, sp); if (rc) return rc;
-      for (int i = 0; i < sp.npoints; ++i) if (!(std::fabs(sp.px[i]) <= 0x1p20f && std::fabs(sp.py[i]) <= 0x1p20f && std::fabs(sp.c1[i]) <= 0x1p40f)) f.fast_ok = 0;
-      for (int i = 0; i < sp.nseg; ++i) if (!(std::fabs(sp.c2[i]) <= 0x1p40f && std::fabs(sp.c3[i]) <= 0x1p40f)) f.fast_ok = 0;
-    }
-    f.spline = &sp;
-    f.linear = linear;
-    f.lab_table = cx().lut_plain[ipk::kLutXyzLab]; f.gam_table = cx().lut_plain[ipk::kLutGamma]; f.lab_pairs = cx().lut_pairs[ipk::kLutXyzLab]; f.gam_pairs = cx().lut_pairs[ipk::kLutGamma];
-    f.num_cus = cx().num_cus; f.gam_q8 = cx().lut_q8;
-    return IPK_OK;
-  }
-};
-}  // namespace
 
 int ipk_pointwise_chain(const float *src4, size_t width, size_t height, int monochrome, const float *wb_coeffs, const float *cam_to_xyz_normalized,
                         float exposure, const float *points, int npoints, int linear, float *dst3, void *stream) {
@@ -1617,11 +1602,19 @@ struct Negotiated {
   bool raw, cfa_branch;                  // a raw source, and one OpGoFloat treats as a CFA mosaic (gofloat.rs:95,109,121)
   float scale;                           // OpDemosaic's scale: the cropped source against the demosaic size
 };
-int negotiate(const ipk_pipeline_desc *d, int out_type, Negotiated &n) {
+// The descriptor fields every driver checks before it reads them: out_type always, the two fuse flags and / or the curve's point count where the
+// driver asks (a driver that leaves the curve to the launch that builds it -- ipk_pipeline_run -- does not ask for it)
+enum { kCheckFuse = 1, kCheckCurve = 2 };
+int validate_desc(const ipk_pipeline_desc *d, int out_type, int checks) {
   if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
-  if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
-  if (d->fuse_scaledown != 0 && d->fuse_scaledown != 1) return fail(IPK_ERR_INVALID, "fuse_scaledown must be 0 or 1 (got %d)", d->fuse_scaledown);
+  if ((checks & kCheckCurve) && (d->npoints < 0 || d->npoints > 64)) return fail(IPK_ERR_INVALID, "npoints out of range");
+  if ((checks & kCheckFuse) && d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
+  if ((checks & kCheckFuse) && d->fuse_scaledown != 0 && d->fuse_scaledown != 1) return fail(IPK_ERR_INVALID, "fuse_scaledown must be 0 or 1 (got %d)", d->fuse_scaledown);
+  return IPK_OK;
+}
+int negotiate(const ipk_pipeline_desc *d, int out_type, Negotiated &n) {
+  { const int vrc = validate_desc(d, out_type, kCheckFuse); if (vrc) return vrc; }
   // one negotiation: the sizes and the rotatecrop state both come from pipeline_sizes_impl's folds (the reverse fold is seeded
   // with scaling_size of the forward result, pipeline.rs:328-335 -- not with the size run() produces)
   int rc = pipeline_sizes_impl(d, &n.dw, &n.dh, &n.fw, &n.fh, &n.rc); if (rc) return rc;
@@ -1643,8 +1636,7 @@ int check_produced(const Negotiated &n, size_t w, size_t h, size_t colors = 0) {
 }
 size_t out_elem_size(int t) { return t == IPK_OUT_F32 ? 4 : t == IPK_OUT_U8 ? 1 : 2; }
 
-// ---- fused raw path: legal when every op between gofloat and gamma is point-wise or demosaic::full.  Does this descriptor run gofloat..gamma
-// as the one fused raw->sRGB launch?  Then fp holds its parameters.  OpTransform does not enter: ipk_pipeline_run folds any orientation in ----
+// the parameters of a one-launch route's launch (ipk_fused_params), from the descriptor and its negotiation
 void fused_params_of(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp) {
   std::memset(&fp, 0, sizeof(fp));
   fp.struct_size = (uint32_t)sizeof(fp);
@@ -1656,52 +1648,67 @@ void fused_params_of(const ipk_pipeline_desc *d, const Negotiated &n, int out_ty
   fp.exposure = d->exposure; fp.npoints = d->npoints; std::memcpy(fp.points, d->points, sizeof(fp.points));
   fp.linear = n.linear; fp.out_type = out_type; fp.schedule = d->schedule;
 }
-// A filter with a fourth colour (RGBE ...) takes the route only where the caller opted in: allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR); the launch then
-// runs with fp.four_colour = 1.  `four` (optional) reports whether that is the case.
-bool fused_raw_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp, bool *four = nullptr) {
-  ipk::Cfa cfa; int xo, yo;
-  if (four) *four = false;
-  if (!(d->allow_fused && n.cfa_branch && d->cpp == 1 && n.rc.noop() && n.scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) && cfa.valid()))
-    return false;
-  const bool three = cfa.bayer_phase(xo, yo) || cfa.three_colour();
-  if (!three && !(d->allow_fused & IPK_FUSED_FOUR_COLOUR)) return false;
-  fused_params_of(d, n, out_type, fp);
-  fp.four_colour = three ? 0 : 1;
-  if (four) *four = !three;
-  return true;
-}
-// ---- the same with an ACTIVE OpRotateCrop between demosaic::full and OpToLab (ipk_raw_to_srgb_resampled): opted into with fuse_rotatecrop.  Then fp
-// holds the launch's parameters and rcp what OpRotateCrop::run hands to transform_buffer.  corners() fails for crops outside the image, where the op
-// returns its input -- and the frame stays staged, as it does when OpDemosaic scales (with an angle the reverse size fold often negotiates a demosaic
-// size one pixel short of the source) or the transform is not one the launch admits (resample_plan) ----
+
+// ---- The route of one frame, decided once (choose_route) and read by every driver and report.  fp: the launch's parameters (every one-launch kind; the
+// raster kind reads the source type, the size and the point-wise parameters from it); rcp: what OpRotateCrop::run hands to transform_buffer (kFusedResample);
+// pw x ph: the image the launch produces before OpTransform; four: kFusedRaw with a fourth colour in the launch (fp.four_colour = 1); label /
+// region_label: the stage run_timed shows for a whole frame / a windowed region ----
+enum RouteKind { kFastPath, kFusedRaw, kFusedResample, kFusedScaledown, kFusedRaster, kStaged };
 struct RotateCropPoints { int64_t pts[6]; size_t nw, nh; };
-bool fused_resample_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp, RotateCropPoints &rcp) {
-  ipk::Cfa cfa; ipk::ResamplePlan plan;
-  if (!(d->fuse_rotatecrop == 1 && d->allow_fused && n.cfa_branch && d->cpp == 1 && !n.rc.noop() && n.scale <= 1.0f && ipk::Cfa::parse(d->cfa, cfa) &&
-        cfa.three_colour()))
-    return false;
-  if (!rotatecrop_of(d).corners(n.r.width, n.r.height, rcp.pts, rcp.nw, rcp.nh)) return false;
-  if (!ipk::resample_plan(n.r.width, n.r.height, rcp.pts[0], rcp.pts[1], rcp.pts[2], rcp.pts[3], rcp.pts[4], rcp.pts[5], rcp.nw, rcp.nh, plan)) return false;
-  fused_params_of(d, n, out_type, fp);
-  return true;
-}
-// ---- OpDemosaic's `full` + scale_down_opbuf branch (demosaic.rs:51-59: 1 < scale < minscale, the near-full-size preview) inside the same launch
-// (ipk_raw_to_srgb_scaled): opted into with fuse_scaledown.  Then fp holds the launch's parameters; the launch resamples the cropped frame to the
-// negotiated n.dw x n.dh.  An active OpRotateCrop behind a scaling OpDemosaic would be a second resampling: such frames stay staged ----
-bool fused_scaledown_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, ipk_fused_params &fp) {
-  ipk::Cfa cfa; ipk::ResamplePlan plan;
-  if (!(d->fuse_scaledown == 1 && d->allow_fused && n.cfa_branch && d->cpp == 1 && n.rc.noop() && n.scale > 1.0f && ipk::Cfa::parse(d->cfa, cfa) &&
-        cfa.three_colour() && n.scale < ipk::demosaic_minscale(cfa.width)))
-    return false;
-  if (!ipk::scaledown_plan(n.r.width, n.r.height, n.dw, n.dh, plan)) return false;
-  fused_params_of(d, n, out_type, fp);
-  return true;
-}
-// ---- raster sources, same idea: run_other + tolab..gamma (+ quantisation) as one launch when OpDemosaic (a 4-channel buffer at
-// scale <= 1: pass-through, demosaic.rs:39-44) and OpRotateCrop are no-ops ----
-bool fused_raster_route(const ipk_pipeline_desc *d, const Negotiated &n) {
-  return d->allow_fused && !n.raw && n.rc.noop() && n.r.x == 0 && n.r.y == 0 && n.r.width == d->width && n.r.height == d->height &&
-         n.r.width * n.r.height >= 256 && n.scale <= 1.0f;
+struct Route {
+  RouteKind kind; ipk_fused_params fp; RotateCropPoints rcp; size_t pw, ph; bool four;
+  const char *label, *region_label;
+};
+// The chain, in order: fast path, raw, resample, scaledown, raster, staged -- the first link that holds names the route.
+//   raw        gofloat..gamma as the one raw->sRGB launch: a CFA mosaic, every op in between point-wise or demosaic::full (OpRotateCrop a no-op, OpDemosaic
+//              not scaling).  A filter with a fourth colour (RGBE ...) only where the caller opted in: allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR)
+//   resample   the same with an ACTIVE OpRotateCrop between demosaic::full and OpToLab (ipk_raw_to_srgb_resampled), opted into with fuse_rotatecrop.
+//              corners() fails for crops outside the image, where the op returns its input -- and the frame stays staged, as it does when OpDemosaic
+//              scales (with an angle the reverse size fold often negotiates a demosaic size one pixel short of the source) or the transform is not one
+//              the launch admits (resample_plan)
+//   scaledown  OpDemosaic's `full` + scale_down_opbuf branch (demosaic.rs:51-59: 1 < scale < minscale, the near-full-size preview) inside the launch
+//              (ipk_raw_to_srgb_scaled, to the negotiated n.dw x n.dh), opted into with fuse_scaledown.  An active OpRotateCrop behind a scaling
+//              OpDemosaic would be a second resampling: such frames stay staged
+//   raster     run_other + tolab..gamma (+ quantisation) as one launch when OpDemosaic (a 4-channel buffer at scale <= 1: pass-through,
+//              demosaic.rs:39-44) and OpRotateCrop are no-ops
+// OpTransform does not enter: run_route folds any orientation in.  The order matters less than it looks, because the links exclude each other, and the
+// callers that ask for one link only (the ipk_pipeline_fuses_* reports, the batch driver, the region plan) rely on exactly that:
+//   - the fast path needs a raster source (default_ops_other), the three raw links need n.cfa_branch, which implies a raw source, and the raster link
+//     needs !n.raw: a fast-path frame fails every raw link and a raw frame never takes the fast path or the raster link;
+//   - raw and scaledown need n.rc.noop(), resample needs !n.rc.noop();
+//   - raw and resample need n.scale <= 1, scaledown needs n.scale > 1.
+// So at most one raw link holds for a descriptor, wherever the fast-path test sits.  Fast path against raster is the one pair the order decides.
+// out_type enters through the fast path and fp.out_type alone: the cached driver, which produces f32 whatever the caller asked for, asks with
+// IPK_OUT_F32 after it has tested the fast path on the caller's type itself.
+void choose_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Route &rt) {
+  rt.kind = kStaged; rt.four = false; rt.pw = n.r.width; rt.ph = n.r.height; rt.label = rt.region_label = "";
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) { rt.kind = kFastPath; return; }
+  ipk::Cfa cfa; ipk::ResamplePlan plan; int xo, yo;
+  const bool mosaic = d->allow_fused && n.cfa_branch && d->cpp == 1 && ipk::Cfa::parse(d->cfa, cfa);
+  const bool three = mosaic && cfa.three_colour(), still = n.rc.noop();
+  RotateCropPoints &r = rt.rcp;
+  if (mosaic && still && n.scale <= 1.0f && cfa.valid() && (three || cfa.bayer_phase(xo, yo) || (d->allow_fused & IPK_FUSED_FOUR_COLOUR))) {
+    rt.kind = kFusedRaw; rt.four = !(three || cfa.bayer_phase(xo, yo));
+    rt.label = "fused gofloat+demosaic+to_lab+basecurve+from_lab+gamma(+transform)";
+    rt.region_label = "fused region gofloat+demosaic+to_lab+basecurve+from_lab+gamma(+transform)";
+  } else if (three && !still && n.scale <= 1.0f && d->fuse_rotatecrop == 1 && rotatecrop_of(d).corners(n.r.width, n.r.height, r.pts, r.nw, r.nh) &&
+             ipk::resample_plan(n.r.width, n.r.height, r.pts[0], r.pts[1], r.pts[2], r.pts[3], r.pts[4], r.pts[5], r.nw, r.nh, plan)) {
+    rt.kind = kFusedResample; rt.pw = r.nw; rt.ph = r.nh;
+    rt.label = "fused gofloat+demosaic+rotatecrop+to_lab+basecurve+from_lab+gamma(+transform)";
+    rt.region_label = "fused region gofloat+demosaic+rotatecrop+to_lab+basecurve+from_lab+gamma(+transform)";
+  } else if (three && still && n.scale > 1.0f && d->fuse_scaledown == 1 && n.scale < ipk::demosaic_minscale(cfa.width) &&
+             ipk::scaledown_plan(n.r.width, n.r.height, n.dw, n.dh, plan)) {
+    rt.kind = kFusedScaledown; rt.pw = n.dw; rt.ph = n.dh;
+    rt.label = "fused gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma";          // a whole frame marks "transform" as a stage of its own (run_route)
+    rt.region_label = "fused region gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma(+transform)";
+  } else if (d->allow_fused && !n.raw && still && n.r.x == 0 && n.r.y == 0 && n.r.width == d->width && n.r.height == d->height &&
+             n.r.width * n.r.height >= 256 && n.scale <= 1.0f) {
+    rt.kind = kFusedRaster;
+    rt.label = "fused gofloat+to_lab+basecurve+from_lab+gamma(+transform)";
+  }
+  if (rt.kind == kStaged) return;
+  fused_params_of(d, n, out_type, rt.fp);
+  rt.fp.four_colour = rt.four ? 1 : 0;
 }
 
 // output8bit / output16bit (pipeline.rs:408-414 / :455-461): cnt f32 samples into the quantised output type
@@ -1716,45 +1723,12 @@ int orient(const void *src, size_t w, size_t h, int orientation, int out_type, v
   if (out_type == IPK_OUT_U8) return ipk_rotate_image_u8(static_cast<const uint8_t *>(src), w, h, orientation, static_cast<uint8_t *>(dst), ow, oh, stream);
   return ipk_rotate_image_u16(static_cast<const uint16_t *>(src), w, h, orientation, static_cast<uint16_t *>(dst), ow, oh, stream);
 }
-// One fused launch of the cropped frame -- the raw->sRGB kernel with fp, the raster chain without -- then OpTransform: the launch writes the
-// image of the output type into dst itself when the orientation is Normal, else into a scratch image that the permutation moves into dst
-int fused_then_orient(const ipk_pipeline_desc *d, const Negotiated &n, const ipk_fused_params *fp, int out_type, const void *src, void *dst, void *stream) {
-  auto launch = [&](void *o) {
-    return fp ? ipk_raw_to_srgb(fp, src, o, stream)
-              : ipk_raster_to_srgb(src, d->src_type, n.r.width, n.r.height, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
-                                   n.linear, out_type, o, stream);
-  };
-  if (n.transform_noop) return launch(dst);
-  Scratch sc(S(stream));
-  void *tmp = nullptr;
-  size_t ow = 0, oh = 0;
-  int rc = sc.get(n.r.width * n.r.height * 3 * out_elem_size(out_type), &tmp); if (rc) return rc;
-  rc = launch(tmp); if (rc < 0) return rc;
-  rc = orient(tmp, n.r.width, n.r.height, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-  return check_produced(n, ow, oh);
-}
-int run_fused_raw(const ipk_pipeline_desc *d, const Negotiated &n, const ipk_fused_params &fp, const void *src, void *dst, StageTimer &tm, void *stream) {
-  tm.rest = "fused gofloat+demosaic+to_lab+basecurve+from_lab+gamma(+transform)";
-  if (!n.transform_noop) {
-    // An orientation other than Normal (every portrait shot): OpTransform is the last op and a pure permutation of pixels, so gofloat..gamma
-    // still run as the one fused launch -- 2 or 3 launches instead of 7.  Rotate90 / Rotate270 of a Bayer frame (the portrait shot): permute
-    // the 1-channel mosaic and run the fused kernel in rotated space -- no pass over the 3-channel result at all.  Otherwise the fused kernel
-    // quantises on the way out into scratch, and the permutation runs on the 3- or 6-byte pixels.
-    size_t ow = 0, oh = 0;
-    const int rc = ipk_raw_to_srgb_oriented(&fp, src, n.orientation, dst, &ow, &oh, stream);
-    if (rc == IPK_OK) return check_produced(n, ow, oh);
-    if (rc != IPK_ERR_UNSUPPORTED) return rc;
-  }
-  return fused_then_orient(d, n, &fp, fp.out_type, src, dst, stream);
-}
-// fused_resample_route's run: the one launch writes the image of the output type into dst, or into a scratch image that OpTransform's permutation
-// moves into dst (as fused_then_orient does)
 // Crop-only shortcut.  Without an angle the corner points are integers, both skips are exactly 1.0 and the cross terms 0, so the
 // window of output pixel (row, col) is the 2x2 block at (x + col, y + row) with the weights {1, 0, 0, 0}: the result is the demosaiced pixel
 // itself PROVIDED its three zero-weight neighbours are finite (0 * inf is NaN) and it is not -0.0 ((-0) + (+0) is +0).  For a u16 source whose
 // every normalised sample is zero or ordinary (gen_levels_ok_u16 walks all 65 536) both hold: the samples are finite and never -0.0, and a
-// demosaic output is a sum that starts at +0.0 over a positive count.  The launch is then the fused kernel's window form over the rectangle,
-// exactly as ipk_pipeline_run_region calls it.  f32 sources can hold -inf and always take k_fused_resample.
+// demosaic output is a sum that starts at +0.0 over a positive count.  The launch is then the fused kernel's window form over the rectangle
+// (launch_route).  f32 sources can hold -inf and always take k_fused_resample.
 bool crop_only_shortcut(const ipk_fused_params &fp, const RotateCropPoints &r) {
   const float range = fp.white0 - fp.black0;
   const size_t lim = size_t(1) << 22;                          // x + col + 0.5 is exact in f32 far beyond any frame this holds for
@@ -1764,45 +1738,71 @@ bool crop_only_shortcut(const ipk_fused_params &fp, const RotateCropPoints &r) {
   return r.pts[2] == x + (int64_t)r.nw - 1 && r.pts[3] == y && r.pts[4] == x && r.pts[5] == y + (int64_t)r.nh - 1 &&    // skips 1, 0, 0, 1
          (size_t)x + r.nw <= fp.width && (size_t)y + r.nh <= fp.height;                                                 // the rectangle lies inside the frame
 }
-int run_fused_resample(const Negotiated &n, const ipk_fused_params &fp, const RotateCropPoints &rcp, const void *src, void *dst, StageTimer &tm, void *stream) {
-  tm.rest = "fused gofloat+demosaic+rotatecrop+to_lab+basecurve+from_lab+gamma(+transform)";
-  auto launch = [&](void *o) {
-    if (crop_only_shortcut(fp, rcp)) {
-      ipk_fused_params b = fp;                                 // the rows as a band of the whole cropped frame, the columns as the launch's window
-      b.band_src_row0 = 0; b.band_src_rows = fp.height; b.band_out_row0 = (size_t)rcp.pts[1]; b.band_out_rows = rcp.nh;
-      const void *top = static_cast<const char *>(src) + fp.y * fp.owidth * 2;
-      { FusedOpts fo; fo.win_c0 = (size_t)rcp.pts[0]; fo.win_c1 = (size_t)rcp.pts[0] + rcp.nw; return fused_impl(&b, top, o, stream, 0, fo); }
-    }
-    return ipk_raw_to_srgb_resampled(&fp, src, rcp.pts[0], rcp.pts[1], rcp.pts[2], rcp.pts[3], rcp.pts[4], rcp.pts[5], rcp.nw, rcp.nh, o, stream);
+// The one launch of a route into `out`.  win == null: the whole pw x ph image, by the whole-frame entry point.  win: that rectangle of it, packed, by
+// the window form of the same launch (the raster kind has none: its regions are cut from the whole result).  Whole frames never go through the
+// window forms -- those are other kernel variants -- except on the crop-only shortcut, which IS the window form: written once, the whole frame
+// being the window (0, 0, nw, nh).
+int launch_route(const Route &rt, const void *src, const ipk::ResampleWindow *win, void *out, void *stream) {
+  const ipk_fused_params &fp = rt.fp;
+  const RotateCropPoints &r = rt.rcp;
+  // k_fused_bayer's window form: the rows are a band whose source is the whole cropped frame (src then starts at the crop's first row), the columns
+  // the launch's window; both are the cropped frame's
+  auto fused_window = [&](size_t col0, size_t row0, size_t cols, size_t rows, bool four_ok) {
+    ipk_fused_params b = fp;
+    b.band_src_row0 = 0; b.band_src_rows = fp.height; b.band_out_row0 = row0; b.band_out_rows = rows;
+    const void *top = static_cast<const char *>(src) + fp.y * fp.owidth * (fp.src_type == IPK_SRC_U16 ? 2 : 4);
+    FusedOpts fo; fo.win_c0 = col0; fo.win_c1 = col0 + cols; fo.four_ok = four_ok;
+    return fused_impl(&b, top, out, stream, 0, fo);
   };
-  if (n.transform_noop) {
-    int rc = check_produced(n, rcp.nw, rcp.nh); if (rc) return rc;
-    return launch(dst);
+  switch (rt.kind) {
+    case kFusedRaw:
+      return win ? fused_window(win->col0, win->row0, win->cols, win->rows, true) : ipk_raw_to_srgb(&fp, src, out, stream);
+    case kFusedResample: {
+      const ipk::ResampleWindow whole = {0, 0, r.nh, r.nw};
+      const ipk::ResampleWindow &w = win ? *win : whole;
+      if (crop_only_shortcut(fp, r)) return fused_window((size_t)r.pts[0] + w.col0, (size_t)r.pts[1] + w.row0, w.cols, w.rows, false);
+      return win ? ipk_raw_to_srgb_resampled_window(&fp, src, r.pts[0], r.pts[1], r.pts[2], r.pts[3], r.pts[4], r.pts[5], r.nw, r.nh, w.col0, w.row0, w.cols, w.rows, out, stream)
+                 : ipk_raw_to_srgb_resampled(&fp, src, r.pts[0], r.pts[1], r.pts[2], r.pts[3], r.pts[4], r.pts[5], r.nw, r.nh, out, stream);
+    }
+    case kFusedScaledown:
+      return win ? ipk_raw_to_srgb_scaled_window(&fp, src, rt.pw, rt.ph, win->col0, win->row0, win->cols, win->rows, out, stream)
+                 : ipk_raw_to_srgb_scaled(&fp, src, rt.pw, rt.ph, out, stream);
+    case kFusedRaster:
+      if (!win) return ipk_raster_to_srgb(src, fp.src_type, fp.width, fp.height, fp.wb_coeffs, fp.cam_to_xyz_normalized, fp.exposure, fp.points, fp.npoints,
+                                          fp.linear, fp.out_type, out, stream);
+      break;
+    default: break;
   }
-  Scratch sc(S(stream));
-  void *tmp = nullptr;
-  size_t ow = 0, oh = 0;
-  int rc = sc.get(rcp.nw * rcp.nh * 3 * out_elem_size(fp.out_type), &tmp); if (rc) return rc;
-  rc = launch(tmp); if (rc < 0) return rc;
-  rc = orient(tmp, rcp.nw, rcp.nh, n.orientation, fp.out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-  return check_produced(n, ow, oh);
+  return fail(IPK_ERR_INVALID, "internal: no such launch for this route");
 }
-
-// fused_scaledown_route's run, the same shape: the launch writes the n.dw x n.dh image of the output type into dst, or into scratch for orient()
-int run_fused_scaledown(const Negotiated &n, const ipk_fused_params &fp, const void *src, void *dst, StageTimer &tm, void *stream) {
-  tm.rest = "fused gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma";
-  if (n.transform_noop) {
-    int rc = check_produced(n, n.dw, n.dh); if (rc) return rc;
-    return ipk_raw_to_srgb_scaled(&fp, src, n.dw, n.dh, dst, stream);
+// A one-launch route, then OpTransform: the launch writes the image of the output type (fp.out_type) into dst itself when the orientation is Normal,
+// else into a scratch image that the permutation moves into dst -- after the quantisation, so it moves 3 or 6 bytes per pixel instead of 12.
+// win: a region (launch_route); want_w x want_h: the size the caller's dst holds, checked against what launch and permutation produce before
+// anything is enqueued.
+int run_route(const Route &rt, const Negotiated &n, const void *src, const ipk::ResampleWindow *win, size_t want_w, size_t want_h, void *dst, void *stream) {
+  StageTimer tm(S(stream));
+  tm.rest = win ? rt.region_label : rt.label;
+  const size_t pw = win ? win->cols : rt.pw, ph = win ? win->rows : rt.ph;
+  bool t = false, fx = false, fy = false;
+  if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
+  if ((t ? ph : pw) != want_w || (t ? pw : ph) != want_h)
+    return fail(IPK_ERR_INVALID, "internal: the launch produces %zux%zu (orientation %d), wanted %zux%zu", pw, ph, n.orientation, want_w, want_h);
+  if (n.transform_noop) return launch_route(rt, src, win, dst, stream);
+  if (rt.kind == kFusedRaw && !win) {
+    // Whole frames of the raw route (every portrait shot): Rotate90 / Rotate270 of a Bayer frame permute the 1-channel mosaic and run the fused
+    // kernel in rotated space -- no pass over the 3-channel result at all.  Where no such variant exists the launch below takes over.
+    size_t ow = 0, oh = 0;
+    const int rc = ipk_raw_to_srgb_oriented(&rt.fp, src, n.orientation, dst, &ow, &oh, stream);
+    if (rc != IPK_ERR_UNSUPPORTED) return rc;
   }
   Scratch sc(S(stream));
   void *tmp = nullptr;
   size_t ow = 0, oh = 0;
-  int rc = sc.get(n.dw * n.dh * 3 * out_elem_size(fp.out_type), &tmp); if (rc) return rc;
-  rc = ipk_raw_to_srgb_scaled(&fp, src, n.dw, n.dh, tmp, stream); if (rc < 0) return rc;
-  tm.mark(tm.rest); tm.rest = "transform";
-  rc = orient(tmp, n.dw, n.dh, n.orientation, fp.out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-  return check_produced(n, ow, oh);
+  int rc = sc.get(pw * ph * 3 * out_elem_size(rt.fp.out_type), &tmp); if (rc) return rc;
+  rc = launch_route(rt, src, win, tmp, stream); if (rc < 0) return rc;
+  if (rt.kind == kFusedScaledown && !win) { tm.mark(tm.rest); tm.rest = "transform"; }
+  rc = orient(tmp, pw, ph, n.orientation, rt.fp.out_type, dst, &ow, &oh, stream);
+  return rc < 0 ? rc : IPK_OK;
 }
 
 // ---- OpGoFloat (gofloat.rs:95-130): what it produces for a descriptor, and the launch that writes it ----
@@ -1977,93 +1977,74 @@ int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, co
 int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int out_type, int *used_fused, void *stream) {
   REQUIRE_INIT();
   if (!d || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
-  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
-  if (d->fuse_scaledown != 0 && d->fuse_scaledown != 1) return fail(IPK_ERR_INVALID, "fuse_scaledown must be 0 or 1 (got %d)", d->fuse_scaledown);
+  int rc = validate_desc(d, out_type, kCheckFuse); if (rc) return rc;      // (the curve's point count is left to the launch that builds the curve)
+  // the fast path is tested before the negotiation, not through choose_route: it takes frames the negotiation refuses (a side under 10 pixels)
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {
     if (used_fused) *used_fused = 0;
     if (d->width < 1 || d->height < 1) return fail(IPK_ERR_INVALID, "empty source");
     StageTimer tmf(S(stream)); tmf.rest = "fastpath";
     return run_fastpath(d, src, dst, out_type, stream);
   }
-  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
-  StageTimer tm(S(stream));
+  Negotiated n; rc = negotiate(d, out_type, n); if (rc) return rc;
   if (used_fused) *used_fused = 0;
-  ipk_fused_params fp; RotateCropPoints rcp;
-  if (fused_raw_route(d, n, out_type, fp)) {
-    rc = run_fused_raw(d, n, fp, src, dst, tm, stream);
-  } else if (fused_resample_route(d, n, out_type, fp, rcp)) {
-    rc = run_fused_resample(n, fp, rcp, src, dst, tm, stream);
-  } else if (fused_scaledown_route(d, n, out_type, fp)) {
-    rc = run_fused_scaledown(n, fp, src, dst, tm, stream);
-  } else if (fused_raster_route(d, n)) {
-    tm.rest = "fused gofloat+to_lab+basecurve+from_lab+gamma(+transform)";
-    rc = fused_then_orient(d, n, nullptr, out_type, src, dst, stream);
-  } else {
-    return run_staged(d, n, out_type, src, dst, tm, stream);
-  }
+  Route rt; choose_route(d, n, out_type, rt);
+  if (rt.kind == kStaged) { StageTimer tm(S(stream)); return run_staged(d, n, out_type, src, dst, tm, stream); }
+  rc = run_route(rt, n, src, nullptr, n.fw, n.fh, dst, stream);
   if (rc == IPK_OK && used_fused) *used_fused = 1;
   return rc;
 }
-// which route an active rotatecrop takes, for callers and CPU tests: the drivers' own predicate on the drivers' own negotiation (no GPU)
+// Which route a descriptor takes, for callers and CPU tests: the drivers' own choose_route on the drivers' own negotiation (no GPU)
+static int report_route(const ipk_pipeline_desc *d, int out_type, Route &rt) {
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; const int rc = negotiate(d, out_type, n); if (rc) return rc;
+  choose_route(d, n, out_type, rt);
+  return IPK_OK;
+}
+// does an active rotatecrop run inside the one launch (fuse_rotatecrop)?
 int ipk_pipeline_fuses_rotatecrop(const ipk_pipeline_desc *d, int out_type) {
-  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
-  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return 0;
-  ipk_fused_params fp; RotateCropPoints rcp;
-  return fused_resample_route(d, n, out_type, fp, rcp) ? 1 : 0;
+  Route rt; const int rc = report_route(d, out_type, rt);
+  return rc ? rc : rt.kind == kFusedResample;
 }
-// the same report for allow_fused's IPK_FUSED_FOUR_COLOUR bit: does a frame whose filter has a fourth colour run as the one raw->sRGB launch?
+// allow_fused's IPK_FUSED_FOUR_COLOUR bit: does a frame whose filter has a fourth colour run as the one raw->sRGB launch?
 int ipk_pipeline_fuses_four_colour(const ipk_pipeline_desc *d, int out_type) {
-  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
-  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return 0;
-  ipk_fused_params fp; bool four = false;
-  return fused_raw_route(d, n, out_type, fp, &four) && four ? 1 : 0;
+  Route rt; const int rc = report_route(d, out_type, rt);
+  return rc ? rc : rt.kind == kFusedRaw && rt.four;
 }
-// the same report for fuse_scaledown: does OpDemosaic's full + scale_down_opbuf branch run inside the one launch?
+// fuse_scaledown: does OpDemosaic's full + scale_down_opbuf branch run inside the one launch?
 int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type) {
-  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
-  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return 0;
-  ipk_fused_params fp;
-  return fused_scaledown_route(d, n, out_type, fp) ? 1 : 0;
+  Route rt; const int rc = report_route(d, out_type, rt);
+  return rc ? rc : rt.kind == kFusedScaledown;
 }
 
 // ------------------------------------------------------------------------------------------
 // A region of ipk_pipeline_run's result (a viewer's viewport, one tile of a tiled render)
 // ------------------------------------------------------------------------------------------
 namespace {
-// windowed = 1 (the run is the one fused raw launch, fused_raw_route): the region comes from the unrotated rectangle [c0, c1) x [r0, r1) of the
-// cropped frame, which the window launch computes and OpTransform's permutation (dihedral: rectangles map to rectangles) turns into the region
-// kind 1 / 2 (allow_fused has IPK_FUSED_WINDOW_REGIONS and the run is fused_resample_route's / fused_scaledown_route's one launch): the same with the
-// rectangle taken of the resampled pw x ph image that launch produces (rcp.nw x rcp.nh, n.dw x n.dh); the window launch of k_fused_resample computes it
-struct RegionPlan { int windowed; size_t c0, c1, r0, r1; int kind; RotateCropPoints rcp; size_t pw, ph; };
-int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n, ipk_fused_params &fp, RegionPlan &pl) {
+// windowed = 1 on kFusedRaw: the region comes from the unrotated rectangle `win` of the cropped frame, which the window launch computes and
+// OpTransform's permutation (dihedral: rectangles map to rectangles) turns into the region.  On kFusedResample / kFusedScaledown where allow_fused
+// has IPK_FUSED_WINDOW_REGIONS: the same with the rectangle taken of the resampled rt.pw x rt.ph image that launch produces; the window launch of
+// k_fused_resample computes it.  Every other route: windowed = 0, the region is cut from the whole result
+struct RegionPlan { int windowed; ipk::ResampleWindow win; };
+int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n, Route &rt, RegionPlan &pl) {
   int rc = negotiate(d, out_type, n); if (rc) return rc;
-  if (d->npoints < 0 || d->npoints > 64) return fail(IPK_ERR_INVALID, "npoints out of range");
+  rc = validate_desc(d, out_type, kCheckCurve); if (rc) return rc;
   if (n.fw == 0 || n.fh == 0) return fail(IPK_ERR_INVALID, "the result is empty");
   if (w == 0 || h == 0 || x > n.fw || w > n.fw - x || y > n.fh || h > n.fh - y)
     return fail(IPK_ERR_INVALID, "region (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", x, y, w, h, n.fw, n.fh);
-  pl.windowed = fused_raw_route(d, n, out_type, fp) ? 1 : 0;
-  pl.kind = 0; pl.pw = n.r.width; pl.ph = n.r.height;
-  if (!pl.windowed && (d->allow_fused & IPK_FUSED_WINDOW_REGIONS) && ipk_pipeline_takes_fastpath(d, out_type) != 1) {
-    if (fused_resample_route(d, n, out_type, fp, pl.rcp)) { pl.windowed = 1; pl.kind = 1; pl.pw = pl.rcp.nw; pl.ph = pl.rcp.nh; }
-    else if (fused_scaledown_route(d, n, out_type, fp)) { pl.windowed = 1; pl.kind = 2; pl.pw = n.dw; pl.ph = n.dh; }
-  }
+  choose_route(d, n, out_type, rt);
+  const bool opted = (d->allow_fused & IPK_FUSED_WINDOW_REGIONS) != 0;
+  pl.windowed = (rt.kind == kFusedRaw || (opted && (rt.kind == kFusedResample || rt.kind == kFusedScaledown))) ? 1 : 0;
   if (!pl.windowed) return IPK_OK;
   bool t = false, fx = false, fy = false;
   if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
-  const size_t W = pl.pw, H = pl.ph;
+  const size_t W = rt.pw, H = rt.ph;
   if ((t ? H : W) != n.fw || (t ? W : H) != n.fh) return fail(IPK_ERR_INVALID, "internal: fused result %zux%zu, negotiated %zux%zu", W, H, n.fw, n.fh);
   // rotate_buffer's walk (transform.rs:102-128): result pixel (ox, oy) is source pixel (fx ? W-1-u : u, fy ? H-1-v : v) with (u, v) = t ? (oy, ox) : (ox, oy)
   const size_t u0 = t ? y : x, un = t ? h : w, v0 = t ? x : y, vn = t ? w : h;
-  pl.c0 = fx ? W - u0 - un : u0; pl.c1 = pl.c0 + un;
-  pl.r0 = fy ? H - v0 - vn : v0; pl.r1 = pl.r0 + vn;
+  pl.win.col0 = fx ? W - u0 - un : u0; pl.win.cols = un;
+  pl.win.row0 = fy ? H - v0 - vn : v0; pl.win.rows = vn;
   return IPK_OK;
 }
 }  // namespace
@@ -2072,21 +2053,24 @@ int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size
                         size_t *src_h) {
   if (!d || !src_x || !src_y || !src_w || !src_h) return fail(IPK_ERR_INVALID, "null argument");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; ipk_fused_params fp; RegionPlan pl;
-  const int rc = plan_region(d, out_type, x, y, w, h, n, fp, pl); if (rc) return rc;
+  Negotiated n; Route rt; RegionPlan pl;
+  const int rc = plan_region(d, out_type, x, y, w, h, n, rt, pl); if (rc) return rc;
   if (!pl.windowed) { *src_x = n.r.x; *src_y = n.r.y; *src_w = n.r.width; *src_h = n.r.height; return 0; }
-  if (pl.kind != 0) {
+  const ipk::ResampleWindow &win = pl.win;
+  if (rt.kind != kFusedRaw) {
     // the window launch's footprint (ipk_transform_window_footprint) in sensor coordinates; empty where no pixel of the rectangle has a tap
+    const int64_t *pts = rt.rcp.pts;
     ipk::ResamplePlan plan;
-    const bool ok = pl.kind == 1 ? ipk::resample_plan(n.r.width, n.r.height, pl.rcp.pts[0], pl.rcp.pts[1], pl.rcp.pts[2], pl.rcp.pts[3], pl.rcp.pts[4], pl.rcp.pts[5], pl.pw, pl.ph, plan)
-                                 : ipk::scaledown_plan(n.r.width, n.r.height, pl.pw, pl.ph, plan);
+    const bool ok = rt.kind == kFusedResample ? ipk::resample_plan(n.r.width, n.r.height, pts[0], pts[1], pts[2], pts[3], pts[4], pts[5], rt.pw, rt.ph, plan)
+                                              : ipk::scaledown_plan(n.r.width, n.r.height, rt.pw, rt.ph, plan);
     if (!ok) return fail(IPK_ERR_INVALID, "internal: the route's plan was refused");
-    const ipk::ResampleFootprint f = ipk::resample_footprint(plan, n.r.width, n.r.height, pl.r0, pl.c0, pl.r1 - pl.r0, pl.c1 - pl.c0);
+    const ipk::ResampleFootprint f = ipk::resample_footprint(plan, n.r.width, n.r.height, win.row0, win.col0, win.rows, win.cols);
     *src_x = n.r.x + f.x; *src_y = n.r.y + f.y; *src_w = f.w; *src_h = f.h;
     return 1;
   }
   // demosaic::full's one-pixel halo, clipped to the crop window, in sensor coordinates
-  const size_t c0 = pl.c0 > 0 ? pl.c0 - 1 : 0, c1 = std::min(n.r.width, pl.c1 + 1), r0 = pl.r0 > 0 ? pl.r0 - 1 : 0, r1 = std::min(n.r.height, pl.r1 + 1);
+  const size_t c0 = win.col0 > 0 ? win.col0 - 1 : 0, c1 = std::min(n.r.width, win.col0 + win.cols + 1);
+  const size_t r0 = win.row0 > 0 ? win.row0 - 1 : 0, r1 = std::min(n.r.height, win.row0 + win.rows + 1);
   *src_x = n.r.x + c0; *src_y = n.r.y + r0; *src_w = c1 - c0; *src_h = r1 - r0;
   return 1;
 }
@@ -2095,13 +2079,12 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
                             void *stream) {
   REQUIRE_INIT();
   if (!d || !src || !dst) return fail(IPK_ERR_INVALID, "null argument");
-  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; ipk_fused_params fp; RegionPlan pl;
-  int rc = plan_region(d, out_type, x, y, w, h, n, fp, pl); if (rc) return rc;
+  Negotiated n; Route rt; RegionPlan pl;
+  int rc = plan_region(d, out_type, x, y, w, h, n, rt, pl); if (rc) return rc;
   if (windowed) *windowed = pl.windowed;
-  const size_t esz = out_elem_size(out_type);
   if (!pl.windowed) {
+    const size_t esz = out_elem_size(out_type);
     // every other route: the whole result into scratch, then the region's rows in one 2-D copy
     Scratch sc(S(stream));
     void *full = nullptr;
@@ -2112,49 +2095,8 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
                             hipMemcpyDeviceToDevice, S(stream)));
     return IPK_OK;
   }
-  StageTimer tm(S(stream));
-  if (pl.kind != 0) {
-    // the one-launch rotatecrop / scaledown routes: the window launch writes the rectangle into dst, or into scratch for orient()
-    tm.rest = pl.kind == 1 ? "fused region gofloat+demosaic+rotatecrop+to_lab+basecurve+from_lab+gamma(+transform)"
-                           : "fused region gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma(+transform)";
-    const size_t cw = pl.c1 - pl.c0, ch = pl.r1 - pl.r0;
-    const RotateCropPoints &r = pl.rcp;
-    auto launch = [&](void *o) {
-      if (pl.kind == 2) return ipk_raw_to_srgb_scaled_window(&fp, src, pl.pw, pl.ph, pl.c0, pl.r0, cw, ch, o, stream);
-      if (crop_only_shortcut(fp, r)) {                         // run_fused_resample's shortcut: the intersection of the two rectangles
-        ipk_fused_params b = fp;
-        b.band_src_row0 = 0; b.band_src_rows = fp.height; b.band_out_row0 = (size_t)r.pts[1] + pl.r0; b.band_out_rows = ch;
-        const void *top = static_cast<const char *>(src) + fp.y * fp.owidth * 2;
-        FusedOpts fo; fo.win_c0 = (size_t)r.pts[0] + pl.c0; fo.win_c1 = fo.win_c0 + cw;
-        return fused_impl(&b, top, o, stream, 0, fo);
-      }
-      return ipk_raw_to_srgb_resampled_window(&fp, src, r.pts[0], r.pts[1], r.pts[2], r.pts[3], r.pts[4], r.pts[5], pl.pw, pl.ph, pl.c0, pl.r0, cw, ch, o, stream);
-    };
-    if (n.transform_noop) return launch(dst);
-    Scratch sc(S(stream));
-    void *tmp = nullptr;
-    rc = sc.get(cw * ch * 3 * esz, &tmp); if (rc) return rc;
-    rc = launch(tmp); if (rc < 0) return rc;
-    size_t ow = 0, oh = 0;
-    rc = orient(tmp, cw, ch, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-    if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: oriented region %zux%zu, asked for %zux%zu", ow, oh, w, h);
-    return IPK_OK;
-  }
-  tm.rest = "fused region gofloat+demosaic+to_lab+basecurve+from_lab+gamma(+transform)";
-  // the rows are a band whose source is the whole cropped frame (src then starts at the crop's first row); the columns are the launch's window
-  fp.band_src_row0 = 0; fp.band_src_rows = n.r.height; fp.band_out_row0 = pl.r0; fp.band_out_rows = pl.r1 - pl.r0;
-  const void *top = static_cast<const char *>(src) + n.r.y * d->width * (d->src_type == IPK_SRC_U16 ? 2 : 4);
-  FusedOpts fo; fo.win_c0 = pl.c0; fo.win_c1 = pl.c1; fo.four_ok = true;
-  if (n.transform_noop) return fused_impl(&fp, top, dst, stream, 0, fo);
-  Scratch sc(S(stream));
-  void *tmp = nullptr;
-  const size_t cw = pl.c1 - pl.c0, ch = pl.r1 - pl.r0;
-  rc = sc.get(cw * ch * 3 * esz, &tmp); if (rc) return rc;
-  rc = fused_impl(&fp, top, tmp, stream, 0, fo); if (rc < 0) return rc;
-  size_t ow = 0, oh = 0;
-  rc = orient(tmp, cw, ch, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-  if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: oriented region %zux%zu, asked for %zux%zu", ow, oh, w, h);
-  return IPK_OK;
+  // the one-launch routes: the window launch writes the rectangle into dst, or into scratch for OpTransform's permutation
+  return run_route(rt, n, src, &pl.win, w, h, dst, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2195,7 +2137,7 @@ int ipk_pipeline_hashes(const ipk_pipeline_desc *d, int out_type, uint64_t sourc
   if (!out256) return fail(IPK_ERR_INVALID, "null output");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
   Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
-  if (d->npoints < 0 || d->npoints > 64) return fail(IPK_ERR_INVALID, "npoints out of range");
+  rc = validate_desc(d, out_type, kCheckCurve); if (rc) return rc;
   ipk::BufHash hs[8]; hash_chain(d, n, source_id, hs);
   for (int i = 0; i < 8; ++i) std::memcpy(out256 + 32 * i, hs[i].data(), 32);
   return IPK_OK;
@@ -2259,15 +2201,13 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   if (!cache->owner) cache->owner = ipk_ctx_current();                   // a cache made before ipk_init belongs to the first context that fills it
   if (cache->owner != ipk_ctx_current()) return fail(IPK_ERR_INVALID, "the cache belongs to another context (its buffers live on that context's device)");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  if (d->npoints < 0 || d->npoints > 64) return fail(IPK_ERR_INVALID, "npoints out of range");
-  if (d->fuse_rotatecrop != 0 && d->fuse_rotatecrop != 1) return fail(IPK_ERR_INVALID, "fuse_rotatecrop must be 0 or 1 (got %d)", d->fuse_rotatecrop);
-  if (d->fuse_scaledown != 0 && d->fuse_scaledown != 1) return fail(IPK_ERR_INVALID, "fuse_scaledown must be 0 or 1 (got %d)", d->fuse_scaledown);
-  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // returns before the cache is consulted (pipeline.rs:381-402)
+  int rc = validate_desc(d, out_type, kCheckCurve | kCheckFuse); if (rc) return rc;
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // returns before the cache is consulted (pipeline.rs:381-402), and before the negotiation
     if (ops_run) *ops_run = 0;
     if (used_fused) *used_fused = 0;
     return run_fastpath(d, src, dst, out_type, stream);
   }
-  Negotiated n; int rc = negotiate(d, out_type, n); if (rc) return rc;
+  Negotiated n; rc = negotiate(d, out_type, n); if (rc) return rc;
   ipk::BufHash hs[8]; hash_chain(d, n, source_id, hs);
   if (ops_run) *ops_run = 0;
   if (used_fused) *used_fused = 0;
@@ -2278,29 +2218,14 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   for (int i = 0; i < 8; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
   int mask = 0;
 
-  // Nothing memoised and the whole chain is one fused launch: cheaper on this machine than materialising seven
-  // intermediates; only the final buffer enters the cache.
-  ipk_fused_params fp;
-  if (startpos == 0 && fused_raw_route(d, n, IPK_OUT_F32, fp)) {          // any orientation: the fused route folds OpTransform in
+  // Nothing memoised and gofloat..transform is one launch on a raw source (any orientation: run_route folds OpTransform in): cheaper on this machine
+  // than materialising seven intermediates; only the final buffer enters the cache.  The buffer is f32 whatever the caller wants,
+  // so the route is asked for IPK_OUT_F32; a raster source's one launch is not taken here (its staged ops fill the cache)
+  Route rt;
+  if (startpos == 0) choose_route(d, n, IPK_OUT_F32, rt);
+  if (startpos == 0 && (rt.kind == kFusedRaw || rt.kind == kFusedResample || rt.kind == kFusedScaledown)) {
     CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
-    { StageTimer tm(st); rc = run_fused_raw(d, n, fp, src, o->p, tm, stream); }
-    if (rc < 0) return rc;
-    cache->lru.put(hs[7], o, o->bytes());
-    buf = o; startpos = 8; mask = 0xFF;
-    if (used_fused) *used_fused = rc == IPK_OK;
-  }
-  RotateCropPoints rcp;
-  if (startpos == 0 && fused_resample_route(d, n, IPK_OUT_F32, fp, rcp)) {   // the same with an active rotatecrop inside the launch
-    CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
-    { StageTimer tm(st); rc = run_fused_resample(n, fp, rcp, src, o->p, tm, stream); }
-    if (rc < 0) return rc;
-    cache->lru.put(hs[7], o, o->bytes());
-    buf = o; startpos = 8; mask = 0xFF;
-    if (used_fused) *used_fused = rc == IPK_OK;
-  }
-  if (startpos == 0 && fused_scaledown_route(d, n, IPK_OUT_F32, fp)) {       // the same for OpDemosaic's full + scale_down_opbuf branch
-    CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
-    { StageTimer tm(st); rc = run_fused_scaledown(n, fp, src, o->p, tm, stream); }
+    rc = run_route(rt, n, src, nullptr, n.fw, n.fh, o->p, stream);
     if (rc < 0) return rc;
     cache->lru.put(hs[7], o, o->bytes());
     buf = o; startpos = 8; mask = 0xFF;
@@ -2446,17 +2371,16 @@ void HostLanes::release() {
 int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *srcs, void *const *dsts, size_t n, int out_type, int *used_fused, void *stream) {
   REQUIRE_INIT();
   if (!d || (n && (!srcs || !dsts))) return fail(IPK_ERR_INVALID, "null argument");
-  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  if (d->npoints < 0 || d->npoints > 64) return fail(IPK_ERR_INVALID, "npoints out of range");
+  { const int rc = validate_desc(d, out_type, kCheckCurve); if (rc) return rc; }      // (the fuse flags: where a frame is run, so an empty batch passes)
   for (size_t i = 0; i < n; ++i) if (!srcs[i] || !dsts[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
   if (used_fused) *used_fused = 0;
   if (n == 0) return IPK_OK;
   // Is Pipeline::run for each frame exactly the fused raw launch with nothing behind it (OpTransform a no-op)?  Then the batch is one
   // persistent launch per 64 frames (ipk_raw_to_srgb_batch).
-  Negotiated ng; ipk_fused_params fp;
-  if (n > 1 && negotiate(d, out_type, ng) == IPK_OK && ng.transform_noop && fused_raw_route(d, ng, out_type, fp)) {
-    const int rc = ipk_raw_to_srgb_batch(&fp, srcs, dsts, n, stream);
+  Negotiated ng; Route rt;
+  if (n > 1 && negotiate(d, out_type, ng) == IPK_OK && ng.transform_noop && (choose_route(d, ng, out_type, rt), rt.kind == kFusedRaw)) {
+    const int rc = ipk_raw_to_srgb_batch(&rt.fp, srcs, dsts, n, stream);
     if (rc == IPK_OK && used_fused) *used_fused = 1;
     return rc;
   }
