@@ -222,8 +222,9 @@ class RawImage:
     def cropped_cfa(self):
         if not self.cfa:
             return ""
-        out = C.create_string_buffer(200)
-        _lib.check(lib().ipk_cfa_shift(self.cfa.encode(), int(self.crops[3]), int(self.crops[0]), out), "ipk_cfa_shift")
+        pat = self.cfa.encode()
+        out = C.create_string_buffer(len(pat) + 1)           # the result is at most strlen(pattern) characters (a stated 48x48 tile has 2310)
+        _lib.check(lib().ipk_cfa_shift(pat, int(self.crops[3]), int(self.crops[0]), out), "ipk_cfa_shift")
         return out.value.decode()
 
 

@@ -612,7 +612,7 @@ int ipk_deal_frames(size_t n_frames, int n_devices, int index, size_t *first, si
   const size_t nd = (size_t)n_devices, ix = (size_t)index;
   if (first) *first = ix;
   if (stride) *stride = nd;
-  if (count) *count = n_frames > ix ? (n_frames - ix + nd - 1) / nd : 0;
+  if (count) *count = n_frames > ix ? (n_frames - ix - 1) / nd + 1 : 0;   // ceil((n_frames - ix) / nd) without the sum that wraps near 2^64
   return IPK_OK;
 }
 

@@ -125,7 +125,8 @@ int ipk_band_plan(size_t height, int nranks, int cfa_period, ipk_band *bands) {
 int ipk_band_plan_scaled(size_t height, size_t nheight, int nranks, ipk_band *bands) {
   if (!bands || nranks < 1 || height < 1 || nheight < 2) return internal_fail(IPK_ERR_INVALID, "bad band_plan_scaled arguments");
   // scale_down_buffer's corners (scaling.rs:35-48): topleft (0,0), bottomleft (0, height-1) -> skip_y_y = (height-1)/(nheight-1) in f32
-  const float skip = ((float)((int64_t)height - 1) - 0.0f) / ((float)(nheight - 1));
+  // height - 1 stays unsigned: (int64_t)height - 1 overflows for a height of 2^63, and below that the two conversions give the same f32
+  const float skip = ((float)(height - 1) - 0.0f) / ((float)(nheight - 1));
   size_t r = 0;
   for (int k = 0; k < nranks; ++k) {
     const size_t n = nheight / (size_t)nranks + ((size_t)k < nheight % (size_t)nranks ? 1 : 0);

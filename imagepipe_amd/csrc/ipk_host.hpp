@@ -145,13 +145,20 @@ struct Cfa {
   }
   // whether a plain string of width*height letters would be read back with this shape
   bool shape_is_inferred() const { return width == height && (width == 2 || width == 6 || width == 12); }
-  // CFA::shift(x, y) as used by cropped_cfa()
+  // CFA::shift(x, y) as used by cropped_cfa().  The empty pattern (no filter) shifts to itself.  rawloader's shift takes usize; a negative
+  // shift is reduced here as a mathematical modulus of the 48 x 48 tiling (every accepted width and height divides 48), so shifting by -1 is
+  // shifting by width - 1 -- never size_t(r + y) of a negative sum, whose wrap at 2^64 is no multiple of 6 or 12.
+  // The name is never longer than the string parse() took it from: the prefix is written without leading zeros, and dropped where the
+  // letter count implies the shape.
+  static int shift_mod48(int v) { const int m = v % 48; return m < 0 ? m + 48 : m; }
   std::string shifted_name(int x, int y) const {
     static const char names[4] = {'R', 'G', 'B', 'E'};
     std::string s;
+    if (!valid()) return s;
+    const int mx = shift_mod48(x), my = shift_mod48(y);
     if (!shape_is_inferred()) s = std::to_string(width) + "x" + std::to_string(height) + ":";
     for (int r = 0; r < height; ++r)
-      for (int c = 0; c < width; ++c) s.push_back(names[color_at(size_t(r + y), size_t(c + x))]);
+      for (int c = 0; c < width; ++c) s.push_back(names[color_at(size_t(r + my), size_t(c + mx))]);
     return s;
   }
   // The per-pixel tap colours of demosaic::full (src/ops/demosaic.rs:77-90), 3 bits per tap packed

@@ -162,8 +162,12 @@ IPK_API int ipk_rotatecrop_calc_size(const float *params5, float input_ratio, si
  * dividing 48 -- the reference tiles every pattern into 48x48): "2x8:RGBGRGBG..." -- the caller's CFA object knows its width and height
  * (src/ops/demosaic.rs:33).  16 letters WITHOUT a stated shape return IPK_ERR_UNSUPPORTED: rawloader's shape for them (8 wide x 2 high as
  * imagepipe's minscale arm suggests, or dcraw's 2 x 8) cannot be verified without its source, and a wrong guess would pass every test.
- * The shifted pattern comes back in the same notation (with the prefix unless the shape is one the letter count implies). */
-IPK_API int ipk_cfa_shift(const char *pattern, int x, int y, char *out /* >= strlen+1 */);
+ * The shifted pattern comes back in the same notation (with the prefix unless the shape is one the letter count implies).
+ * The result is at most strlen(pattern) characters, so `out` of strlen(pattern) + 1 bytes always suffices: the prefix comes back without leading
+ * zeros ("02x08:" -> "2x8:"), is dropped where the letter count implies the shape ("2x2:RGGB" -> "RGGB"), and the empty pattern (no filter) shifts to
+ * the empty pattern.  x and y may be negative: rawloader's shift takes usize and leaves that undefined; here a shift counts as a mathematical modulus
+ * of the 48 x 48 tiling, so -1 is the same shift as width - 1 (or 47).  On failure `out` is not written. */
+IPK_API int ipk_cfa_shift(const char *pattern, int x, int y, char *out /* >= strlen(pattern) + 1 bytes */);
 /* Orientation::to_flips / from_flips (call sites src/ops/transform.rs:58-66,106);
  * flips3 = transpose, flip_x, flip_y */
 IPK_API int ipk_orientation_to_flips(int orientation, int *flips3);
@@ -596,7 +600,10 @@ IPK_API void ipk_host_free(void *p);
 IPK_API int ipk_pipeline_hashes(const ipk_pipeline_desc *d, int out_type, uint64_t source_id, uint8_t *out256);
 
 /* Pipeline::new_cache(size): a byte-budgeted LRU of device OpBuffers.  `get` refreshes recency; `put` evicts
- * least-recently-used entries until the newcomer fits.  Use one stream per cache. */
+ * least-recently-used entries until the newcomer fits.  Use one stream per cache.
+ * Threads: the bookkeeping is internally locked -- contains, stats, get, clear and the puts (ipk_pipeline_run_cached, ipk_selftest_cache_put) may be
+ * called on one cache from several threads at once (tests/cpp/host_threads.cpp does, under ThreadSanitizer).  ipk_cache_free must not run while
+ * another call on the same cache is in flight, and a pointer borrowed with ipk_cache_get lives only until another thread's put evicts its entry. */
 typedef struct ipk_cache ipk_cache;
 IPK_API int ipk_cache_new(size_t max_bytes, ipk_cache **out);
 IPK_API int ipk_cache_free(ipk_cache *cache);

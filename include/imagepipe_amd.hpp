@@ -84,7 +84,9 @@ struct ImageSource {
   DeviceArray data;                                    // sensor / raster samples on the device
   std::string cropped_cfa() const {
     if (cfa.empty()) return "";
-    char out[200]; check(ipk_cfa_shift(cfa.c_str(), (int)crops[3], (int)crops[0], out), "ipk_cfa_shift"); return out;
+    std::string out(cfa.size() + 1, '\0');               // the result is at most strlen(pattern) characters (a stated 48x48 tile has 2310)
+    check(ipk_cfa_shift(cfa.c_str(), (int)crops[3], (int)crops[0], &out[0]), "ipk_cfa_shift");
+    out.resize(std::strlen(out.c_str())); return out;
   }
 };
 

@@ -239,7 +239,7 @@ def lab_to_rgb(rgbmatrix, pix3):
 
 
 def cfa_shift(pat, x, y):
-    out = C.create_string_buffer(160)
+    out = C.create_string_buffer(len(pat.encode()) + 1)      # the shifted name is at most as long as the pattern
     if lib().orc_cfa_shift(pat.encode(), x, y, out):
         raise ValueError("invalid CFA pattern %r" % pat)
     return out.value.decode()

@@ -344,15 +344,18 @@ static inline int cfa_color_at(const orc_cfa *c, size_t row, size_t col) {
   return c->pattern[(row + 48) % 48][(col + 48) % 48];
 }
 /* RawImage::cropped_cfa() == cfa.shift(crop_left, crop_top) (call site demosaic.rs:13):
- * new pattern[row][col] = old color_at(row + y, col + x). Writes the shifted name string. */
+ * new pattern[row][col] = old color_at(row + y, col + x). Writes the shifted name string, at most strlen(pat) characters.
+ * The empty pattern shifts to itself; a negative shift (rawloader's takes usize) counts modulo the 48 x 48 tiling, like the product's. */
 ORC_API int orc_cfa_shift(const char *pat, int x, int y, char *out) {
   orc_cfa c; if (cfa_new(pat, &c)) return -1;
   static const char names[4] = {'R', 'G', 'B', 'E'};
   int n = 0;
+  if (c.width == 0) { out[0] = 0; return 0; }
+  const int mx = ((x % 48) + 48) % 48, my = ((y % 48) + 48) % 48;
   if (!(c.width == c.height && (c.width == 2 || c.width == 6 || c.width == 12))) n = sprintf(out, "%dx%d:", c.width, c.height);
   for (int row = 0; row < c.height; row++)
     for (int col = 0; col < c.width; col++)
-      out[n++] = names[cfa_color_at(&c, (size_t)(row + y), (size_t)(col + x))];
+      out[n++] = names[cfa_color_at(&c, (size_t)(row + my), (size_t)(col + mx))];
   out[n] = 0;
   return 0;
 }

@@ -148,6 +148,20 @@ def test_cfa_shift_and_orientation(L, orc):
             for y in range(9):
                 assert L.ipk_cfa_shift(pat.encode(), x, y, out) == 0, pat
                 assert out.value.decode() == orc.cfa_shift(pat, x, y)
+    # negative shifts count modulo the 48 x 48 tiling (rawloader's shift takes usize and leaves them undefined): -1 is width - 1, in product and oracle
+    w12 = (xt[:6] * 2 + xt[6:12] * 2) * 6
+    for pat, period in [("RGGB", 2), (xt, 6), (w12, 12), ("8x2:RGBGRBGGGBGRGRBG", 8), ("2x8:RGBGRBGGGBGRGRBG", 2), ("3x1:RGB", 3)]:
+        ph = {"8x2:RGBGRBGGGBGRGRBG": 2, "2x8:RGBGRBGGGBGRGRBG": 8, "3x1:RGB": 1}.get(pat, period)
+        for x, y in [(-1, 0), (0, -1), (-1, -1), (-5, -7), (-48, -96), (-49, 3), (-2 ** 31, 2 ** 31 - 1)]:
+            assert L.ipk_cfa_shift(pat.encode(), x, y, out) == 0, (pat, x, y)
+            got = out.value.decode()
+            assert got == orc.cfa_shift(pat, x, y) == orc.cfa_shift(pat, x % period, y % ph), (pat, x, y, got)
+    assert orc.cfa_shift("RGGB", -1, 0) == "GRBG" and orc.cfa_shift(xt, -1, 0) == orc.cfa_shift(xt, 5, 0) != orc.cfa_shift(xt, 3, 0)
+    # the result is at most strlen(pattern) characters: the empty pattern shifts to itself, into a buffer of exactly one byte
+    one = C.create_string_buffer(b"\x55", 1)
+    assert L.ipk_cfa_shift(b"", 3, -2, one) == 0 and one.raw == b"\x00" and orc.cfa_shift("", 3, -2) == ""
+    exact = C.create_string_buffer(len(b"02x08:RGBGRBGGGBGRGRBG") + 1)
+    assert L.ipk_cfa_shift(b"02x08:RGBGRBGGGBGRGRBG", 0, 0, exact) == 0 and exact.value == b"2x8:RGBGRBGGGBGRGRBG"
     for bad in [b"5x2:RGBGRGBGRG", b"2x8:RGGB", b"x8:RGGBGRBGGBRGBGGR", b"2x:RGGB", b"2x8RGGB", b"0x4:", b"2x8:RGBGRBGGGBGRGRBX"]:
         assert L.ipk_cfa_shift(bad, 0, 0, out) == -2, bad
     f = (C.c_int * 3)()
