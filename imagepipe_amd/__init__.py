@@ -22,7 +22,7 @@ from ._lib import (IpkError, FusedParams, PipelineDesc, OUT_F32, OUT_U8, OUT_U16
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
            "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "raw_to_srgb_resampled_window", "raw_to_srgb_scaled_window",
-           "transform_window_footprint", "FusedPlan", "IpkError"]
+           "transform_window_footprint", "raw_scaled_demosaic_window", "raster_scale_down_window", "scaled_window_footprint", "FusedPlan", "IpkError"]
 
 _initialized_device = None
 
@@ -604,6 +604,7 @@ class Pipeline:
         self.fuse_scaledown = False           # ipk_pipeline_desc.fuse_scaledown: OpDemosaic's full + scale_down_opbuf branch inside the one launch where fuses_scaledown() says so
         self.fuse_four_colour = False         # ipk_pipeline_desc.allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR): a filter with a fourth colour (RGBE ...) on the one-launch route where fuses_four_colour() says so
         self.window_regions = False           # ipk_pipeline_desc.allow_fused bit 2 (IPK_FUSED_WINDOW_REGIONS): regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch
+        self.window_previews = False          # ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
 
     @staticmethod
     def new_from_source(img):
@@ -668,6 +669,8 @@ class Pipeline:
             d.allow_fused |= _lib.FUSED_FOUR_COLOUR
         if self.window_regions and d.allow_fused:
             d.allow_fused |= _lib.FUSED_WINDOW_REGIONS
+        if self.window_previews and d.allow_fused:
+            d.allow_fused |= _lib.FUSED_WINDOW_PREVIEWS
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -688,6 +691,11 @@ class Pipeline:
         """Does the run take the one-launch route with its four-colour filter (ipk_pipeline_fuses_four_colour, host-only)?"""
         d = self.desc()
         return bool(_lib.check(lib().ipk_pipeline_fuses_four_colour(C.byref(d), out_type), "ipk_pipeline_fuses_four_colour"))
+
+    def windows_preview(self, out_type=OUT_F32) -> bool:
+        """Does a region of this downscaled preview run as a window of its scaling pass (ipk_pipeline_windows_preview, host-only)?"""
+        d = self.desc()
+        return bool(_lib.check(lib().ipk_pipeline_windows_preview(C.byref(d), out_type), "ipk_pipeline_windows_preview"))
 
     def sizes(self):
         d = self.desc()
@@ -914,4 +922,38 @@ def transform_window_footprint(width, height, corners, nwidth, nheight, window):
     wx, wy, ww, wh = [int(v) for v in window]
     _lib.check(lib().ipk_transform_window_footprint(width, height, *[int(c) for c in corners], nwidth, nheight, wx, wy, ww, wh, out4),
                "ipk_transform_window_footprint")
+    return tuple(int(v) for v in out4)
+
+
+def raw_scaled_demosaic_window(src: torch.Tensor, owidth, x, y, width, height, black0, white0, cfa, nwidth, nheight, window, *,
+                               out: Optional[torch.Tensor] = None):
+    """ipk_raw_scaled_demosaic_window: the columns [wx, wx+ww) and rows [wy, wy+wh) of gofloat + scaled_demosaic of the sensor window (x, y, width,
+    height) of an owidth-pitched u16 (int16 / uint16 tensor) or f32 frame, window = (wx, wy, ww, wh), by the whole-frame kernel laid over the window.
+    Returns the wh*ww*4 f32 device tensor."""
+    wx, wy, ww, wh = _check_window(nwidth, nheight, window)
+    if out is None:
+        out = torch.empty(wh * ww * 4, dtype=torch.float32, device="cuda")
+    _lib.check(lib().ipk_raw_scaled_demosaic_window(src.data_ptr(), SRC_F32 if src.dtype == torch.float32 else SRC_U16, owidth, x, y, width, height,
+                                                    black0, white0, cfa.encode(), nwidth, nheight, wx, wy, ww, wh, out.data_ptr(), _stream()),
+               "ipk_raw_scaled_demosaic_window")
+    return out
+
+
+def raster_scale_down_window(src: torch.Tensor, owidth, x, y, width, height, nwidth, nheight, window, *, out: Optional[torch.Tensor] = None):
+    """ipk_raster_scale_down_window: the same for run_other + scale_down_opbuf of an RGB8 (uint8 tensor) or RGB16 raster.  Returns the wh*ww*4 f32
+    device tensor (E = 0)."""
+    wx, wy, ww, wh = _check_window(nwidth, nheight, window)
+    if out is None:
+        out = torch.empty(wh * ww * 4, dtype=torch.float32, device="cuda")
+    _lib.check(lib().ipk_raster_scale_down_window(src.data_ptr(), SRC_RGB8 if src.dtype == torch.uint8 else SRC_RGB16, owidth, x, y, width, height,
+                                                  nwidth, nheight, wx, wy, ww, wh, out.data_ptr(), _stream()), "ipk_raster_scale_down_window")
+    return out
+
+
+def scaled_window_footprint(width, height, nwidth, nheight, window):
+    """ipk_scaled_window_footprint (host-only): (x, y, w, h) of the width x height cropped frame that the window (wx, wy, ww, wh) of the
+    nwidth x nheight preview reads in raw_scaled_demosaic_window / raster_scale_down_window: its taps plus the 8-sample row loads."""
+    out4 = (C.c_size_t * 4)()
+    wx, wy, ww, wh = [int(v) for v in window]
+    _lib.check(lib().ipk_scaled_window_footprint(width, height, nwidth, nheight, wx, wy, ww, wh, out4), "ipk_scaled_window_footprint")
     return tuple(int(v) for v in out4)

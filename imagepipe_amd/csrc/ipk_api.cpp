@@ -810,17 +810,49 @@ int ipk_scale_down_opbuf(const float *src4, size_t width, size_t height, size_t 
 
 // OpGoFloat (CFA branch) + scaled_demosaic in one pass over the raw frame (used by ipk_pipeline_run when OpDemosaic::run
 // would take its scaled_demosaic branch: the 1-channel f32 intermediate never exists)
-int ipk_raw_scaled_demosaic(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
-                            float black0, float white0, const char *cfa_pat, size_t nwidth, size_t nheight, float *dst4, void *stream) {
+namespace {
+// a window of an nwidth x nheight result: non-empty and inside it
+bool window_ok(size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh) {
+  return ww != 0 && wh != 0 && wx <= nwidth && ww <= nwidth - wx && wy <= nheight && wh <= nheight - wy;
+}
+// the whole-frame form (win == null) and the window form: one admission, one launcher
+int raw_scaled_demosaic_impl(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
+                             const char *cfa_pat, size_t nwidth, size_t nheight, const ipk::ResampleWindow *win, float *dst4, void *stream) {
   REQUIRE_INIT();
   if (!src || !dst4 || !cfa_pat || !dims_ok(width, height) || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32))
     return fail(IPK_ERR_INVALID, "bad raw_scaled_demosaic arguments");
+  if (win && !window_ok(nwidth, nheight, win->col0, win->row0, win->cols, win->rows))
+    return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", win->col0, win->row0, win->cols, win->rows, nwidth, nheight);
   ipk::Cfa cfa; DevCfa dev; int rc = get_cfa(cfa_pat, cfa, dev); if (rc) return rc;
   const int norm_fast = validate_cdiv_for_range(black0, white0 - black0, src_type == IPK_SRC_U16) ? 1 : 0;
-  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(static_cast<const uint16_t *>(src), owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0);
-  else ipk::launch_raw_scaled_demosaic<float>(static_cast<const float *>(src), owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0);
+  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(static_cast<const uint16_t *>(src), owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0, win);
+  else ipk::launch_raw_scaled_demosaic<float>(static_cast<const float *>(src), owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0, win);
   HIPCHK(hipGetLastError());
   return IPK_OK;
+}
+int raster_scale_down_impl(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, size_t nwidth, size_t nheight,
+                           const ipk::ResampleWindow *win, float *dst4, void *stream) {
+  REQUIRE_INIT();
+  if (!src || !dst4 || !dims_ok(width, height) || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_RGB8 && src_type != IPK_SRC_RGB16))
+    return fail(IPK_ERR_INVALID, "bad raster_scale_down arguments");
+  if (x + width > owidth) return fail(IPK_ERR_INVALID, "raster_scale_down: window wider than the source pitch");
+  if (win && !window_ok(nwidth, nheight, win->col0, win->row0, win->cols, win->rows))
+    return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", win->col0, win->row0, win->cols, win->rows, nwidth, nheight);
+  ipk::launch_raster_scale_down(src, src_type == IPK_SRC_RGB16, owidth, x, y, width, height, nwidth, nheight, cx().lut_pairs[ipk::kLutGammaReverse],
+                                dst4, S(stream), win);
+  HIPCHK(hipGetLastError());
+  return IPK_OK;
+}
+}  // namespace
+int ipk_raw_scaled_demosaic(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                            float black0, float white0, const char *cfa_pat, size_t nwidth, size_t nheight, float *dst4, void *stream) {
+  return raw_scaled_demosaic_impl(src, src_type, owidth, x, y, width, height, black0, white0, cfa_pat, nwidth, nheight, nullptr, dst4, stream);
+}
+// the columns [wx, wx + ww) and rows [wy, wy + wh) of the same result: the same kernel, its grid laid over the window
+int ipk_raw_scaled_demosaic_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
+                                   const char *cfa_pat, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream) {
+  const ipk::ResampleWindow win = {wy, wx, wh, ww};
+  return raw_scaled_demosaic_impl(src, src_type, owidth, x, y, width, height, black0, white0, cfa_pat, nwidth, nheight, &win, dst4, stream);
 }
 // one output-row band of the same (ipk_band_plan_scaled): multi-GPU sharding of a frame that OpDemosaic scales
 int ipk_raw_scaled_demosaic_band(const void *src, int src_type, size_t owidth, size_t x, size_t width, size_t height, float black0, float white0,
@@ -852,13 +884,21 @@ int ipk_raw_scaled_demosaic_band(const void *src, int src_type, size_t owidth, s
 // scale_down_opbuf branch for a raster source: the full-size 4-channel f32 buffer never exists)
 int ipk_raster_scale_down(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
                           size_t nwidth, size_t nheight, float *dst4, void *stream) {
-  REQUIRE_INIT();
-  if (!src || !dst4 || !dims_ok(width, height) || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_RGB8 && src_type != IPK_SRC_RGB16))
-    return fail(IPK_ERR_INVALID, "bad raster_scale_down arguments");
-  if (x + width > owidth) return fail(IPK_ERR_INVALID, "raster_scale_down: window wider than the source pitch");
-  ipk::launch_raster_scale_down(src, src_type == IPK_SRC_RGB16, owidth, x, y, width, height, nwidth, nheight, cx().lut_pairs[ipk::kLutGammaReverse],
-                                dst4, S(stream));
-  HIPCHK(hipGetLastError());
+  return raster_scale_down_impl(src, src_type, owidth, x, y, width, height, nwidth, nheight, nullptr, dst4, stream);
+}
+int ipk_raster_scale_down_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, size_t nwidth, size_t nheight,
+                                 size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream) {
+  const ipk::ResampleWindow win = {wy, wx, wh, ww};
+  return raster_scale_down_impl(src, src_type, owidth, x, y, width, height, nwidth, nheight, &win, dst4, stream);
+}
+// What such a window launch reads of the width x height cropped frame (host only): ipk::scaled_window_footprint
+int ipk_scaled_window_footprint(size_t width, size_t height, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, size_t *out4) {
+  if (!out4) return fail(IPK_ERR_INVALID, "null output");
+  if (!dims_ok(width, height) || !dims_ok(nwidth, nheight)) return fail(IPK_ERR_INVALID, "bad scaled_window_footprint sizes");
+  if (!window_ok(nwidth, nheight, wx, wy, ww, wh))
+    return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", wx, wy, ww, wh, nwidth, nheight);
+  const ipk::ResampleFootprint f = ipk::scaled_window_footprint(width, height, nwidth, nheight, wy, wx, wh, ww);
+  out4[0] = f.x; out4[1] = f.y; out4[2] = f.w; out4[3] = f.h;
   return IPK_OK;
 }
 
@@ -1839,11 +1879,14 @@ bool gofloat_demosaic_one_pass(const ipk_pipeline_desc *d, const Negotiated &n) 
   ipk::Cfa cfa;
   return n.cfa_branch && d->cpp == 1 && ipk::Cfa::parse(d->cfa, cfa) && cfa.valid() && n.scale >= ipk::demosaic_minscale(cfa.width);
 }
-int launch_gofloat_demosaic(const ipk_pipeline_desc *d, const Negotiated &n, const void *src, float *dst, void *stream) {
-  if (!n.raw) return ipk_raster_scale_down(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, n.dw, n.dh, dst, stream);
-  return ipk_raw_scaled_demosaic(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, d->blacklevels[0], d->whitelevels[0], d->cfa,
-                                 n.dw, n.dh, dst, stream);
+// win: that rectangle of the n.dw x n.dh buffer alone, packed (regions under IPK_FUSED_WINDOW_PREVIEWS); null: the whole buffer
+int launch_gofloat_demosaic(const ipk_pipeline_desc *d, const Negotiated &n, const void *src, const ipk::ResampleWindow *win, float *dst, void *stream) {
+  if (!n.raw) return raster_scale_down_impl(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, n.dw, n.dh, win, dst, stream);
+  return raw_scaled_demosaic_impl(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, d->blacklevels[0], d->whitelevels[0], d->cfa,
+                                  n.dw, n.dh, win, dst, stream);
 }
+int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scratch &sc, void *buf, size_t w, size_t h, size_t colors, int monochrome,
+             size_t want_w, size_t want_h, void *dst, StageTimer &tm, void *stream);
 
 // ---- staged path: the eight ops in the reference's order (pipeline.rs:155-164) ----
 int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, const void *src, void *dst, StageTimer &tm, void *stream) {
@@ -1856,7 +1899,7 @@ int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, co
   if (demosaic_done) {
     colors = 4; monochrome = 0;
     rc = sc.get(n.dw * n.dh * 4 * sizeof(float), &buf); if (rc) return rc;
-    rc = launch_gofloat_demosaic(d, n, src, static_cast<float *>(buf), stream);
+    rc = launch_gofloat_demosaic(d, n, src, nullptr, static_cast<float *>(buf), stream);
     w = n.dw; h = n.dh;
   } else {
     rc = gofloat_shape(d, n, colors, monochrome); if (rc) return rc;
@@ -1888,12 +1931,23 @@ int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, co
     }
     tm.mark("rotatecrop");
   }
+  return run_tail(d, n, out_type, sc, buf, w, h, colors, monochrome, n.fw, n.fh, dst, tm, stream);
+}
+// What follows OpRotateCrop: tolab..gamma, OpTransform and the quantisation of the w x h buffer `buf` (colors samples per pixel, owned by sc), into dst,
+// which holds want_w x want_h pixels of out_type -- the negotiated result behind run_staged, the region behind a window launch (ipk_pipeline_run_region
+// under IPK_FUSED_WINDOW_PREVIEWS).  Every op here is point-wise or a permutation, so a rectangle of the buffer gives that rectangle of the result
+int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scratch &sc, void *buf, size_t w, size_t h, size_t colors, int monochrome,
+             size_t want_w, size_t want_h, void *dst, StageTimer &tm, void *stream) {
+  int rc;
+  auto produced = [&](size_t pw, size_t ph) {
+    return pw == want_w && ph == want_h ? IPK_OK : fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", pw, ph, want_w, want_h);
+  };
   const size_t n3 = w * h * 3 * sizeof(float);
   const bool f32_out = out_type == IPK_OUT_F32;
   bool chained = false;
   if (d->allow_fused && colors == 4 && !f32_out && n.transform_noop && w * h >= 256) {
     // ... and with output8bit / output16bit in the same pass when the caller wants 8 or 16 bits and nothing follows: the f32 image never exists
-    rc = check_produced(n, w, h); if (rc) return rc;
+    rc = produced(w, h); if (rc) return rc;
     rc = ipk_pointwise_chain_out(static_cast<const float *>(buf), w, h, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
                                  n.linear, out_type, dst, stream);
     if (rc < 0) return rc;
@@ -1958,7 +2012,7 @@ int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, co
     rc = sc.get(w * h * 3 * out_elem_size(out_type), &q); if (rc) return rc;
     rc = quantise(buf, w * h * 3, out_type, q, stream); if (rc < 0) return rc;
     rc = orient(q, w, h, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-    return check_produced(n, ow, oh);
+    return produced(ow, oh);
   }
   if (!n.transform_noop) {
     void *o = nullptr; size_t ow, oh;
@@ -1968,7 +2022,7 @@ int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, co
     sc.release(buf); buf = o; w = ow; h = oh;
     tm.mark("transform");
   }
-  rc = check_produced(n, w, h); if (rc) return rc;
+  rc = produced(w, h); if (rc) return rc;
   if (out_type != IPK_OUT_F32) { tm.rest = "quantise"; rc = quantise(buf, w * h * 3, out_type, dst, stream); }
   return rc < 0 ? rc : IPK_OK;
 }
@@ -2025,8 +2079,15 @@ namespace {
 // windowed = 1 on kFusedRaw: the region comes from the unrotated rectangle `win` of the cropped frame, which the window launch computes and
 // OpTransform's permutation (dihedral: rectangles map to rectangles) turns into the region.  On kFusedResample / kFusedScaledown where allow_fused
 // has IPK_FUSED_WINDOW_REGIONS: the same with the rectangle taken of the resampled rt.pw x rt.ph image that launch produces; the window launch of
-// k_fused_resample computes it.  Every other route: windowed = 0, the region is cut from the whole result
-struct RegionPlan { int windowed; ipk::ResampleWindow win; };
+// k_fused_resample computes it.  preview = 1 (windowed too), where allow_fused has IPK_FUSED_WINDOW_PREVIEWS beside IPK_FUSED_ON: a staged frame whose
+// gofloat + demosaic is the one scaling pass (gofloat_demosaic_one_pass) and whose OpRotateCrop is a no-op -- everything behind that pass is point-wise
+// or OpTransform's permutation, so the rectangle is taken of the n.dw x n.dh preview, the pass runs as a window launch and run_tail finishes the
+// rectangle.  Every other route: windowed = 0, the region is cut from the whole result
+struct RegionPlan { int windowed, preview; ipk::ResampleWindow win; };
+bool windows_preview(const ipk_pipeline_desc *d, const Negotiated &n, const Route &rt) {
+  const int both = IPK_FUSED_ON | IPK_FUSED_WINDOW_PREVIEWS;
+  return (d->allow_fused & both) == both && rt.kind == kStaged && gofloat_demosaic_one_pass(d, n) && n.rc.noop();
+}
 int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n, Route &rt, RegionPlan &pl) {
   int rc = negotiate(d, out_type, n); if (rc) return rc;
   rc = validate_desc(d, out_type, kCheckCurve); if (rc) return rc;
@@ -2035,11 +2096,12 @@ int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, si
     return fail(IPK_ERR_INVALID, "region (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", x, y, w, h, n.fw, n.fh);
   choose_route(d, n, out_type, rt);
   const bool opted = (d->allow_fused & IPK_FUSED_WINDOW_REGIONS) != 0;
-  pl.windowed = (rt.kind == kFusedRaw || (opted && (rt.kind == kFusedResample || rt.kind == kFusedScaledown))) ? 1 : 0;
+  pl.preview = windows_preview(d, n, rt) ? 1 : 0;
+  pl.windowed = (pl.preview || rt.kind == kFusedRaw || (opted && (rt.kind == kFusedResample || rt.kind == kFusedScaledown))) ? 1 : 0;
   if (!pl.windowed) return IPK_OK;
   bool t = false, fx = false, fy = false;
   if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
-  const size_t W = rt.pw, H = rt.ph;
+  const size_t W = pl.preview ? n.dw : rt.pw, H = pl.preview ? n.dh : rt.ph;
   if ((t ? H : W) != n.fw || (t ? W : H) != n.fh) return fail(IPK_ERR_INVALID, "internal: fused result %zux%zu, negotiated %zux%zu", W, H, n.fw, n.fh);
   // rotate_buffer's walk (transform.rs:102-128): result pixel (ox, oy) is source pixel (fx ? W-1-u : u, fy ? H-1-v : v) with (u, v) = t ? (oy, ox) : (ox, oy)
   const size_t u0 = t ? y : x, un = t ? h : w, v0 = t ? x : y, vn = t ? w : h;
@@ -2049,6 +2111,16 @@ int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, si
 }
 }  // namespace
 
+// IPK_FUSED_WINDOW_PREVIEWS: does a region of this descriptor run as a window of its scaling gofloat + demosaic pass?
+int ipk_pipeline_windows_preview(const ipk_pipeline_desc *d, int out_type) {
+  Route rt;
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; const int rc = negotiate(d, out_type, n); if (rc) return rc;
+  choose_route(d, n, out_type, rt);
+  return windows_preview(d, n, rt) ? 1 : 0;
+}
+
 int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, size_t *src_x, size_t *src_y, size_t *src_w,
                         size_t *src_h) {
   if (!d || !src_x || !src_y || !src_w || !src_h) return fail(IPK_ERR_INVALID, "null argument");
@@ -2057,6 +2129,11 @@ int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size
   const int rc = plan_region(d, out_type, x, y, w, h, n, rt, pl); if (rc) return rc;
   if (!pl.windowed) { *src_x = n.r.x; *src_y = n.r.y; *src_w = n.r.width; *src_h = n.r.height; return 0; }
   const ipk::ResampleWindow &win = pl.win;
+  if (pl.preview) {
+    const ipk::ResampleFootprint f = ipk::scaled_window_footprint(n.r.width, n.r.height, n.dw, n.dh, win.row0, win.col0, win.rows, win.cols);
+    *src_x = n.r.x + f.x; *src_y = n.r.y + f.y; *src_w = f.w; *src_h = f.h;
+    return 1;
+  }
   if (rt.kind != kFusedRaw) {
     // the window launch's footprint (ipk_transform_window_footprint) in sensor coordinates; empty where no pixel of the rectangle has a tap
     const int64_t *pts = rt.rcp.pts;
@@ -2094,6 +2171,16 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
     HIPCHK(hipMemcpy2DAsync(dst, w * 3 * esz, static_cast<const char *>(full) + (y * n.fw + x) * 3 * esz, n.fw * 3 * esz, w * 3 * esz, h,
                             hipMemcpyDeviceToDevice, S(stream)));
     return IPK_OK;
+  }
+  if (pl.preview) {
+    // the scaling pass over the rectangle of the preview, then what run_staged runs behind it, on the rectangle
+    StageTimer tm(S(stream));
+    Scratch sc(S(stream));
+    void *buf = nullptr;
+    rc = sc.get(pl.win.cols * pl.win.rows * 4 * sizeof(float), &buf); if (rc) return rc;
+    rc = launch_gofloat_demosaic(d, n, src, &pl.win, static_cast<float *>(buf), stream); if (rc < 0) return rc;
+    tm.mark("region gofloat+demosaic");
+    return run_tail(d, n, out_type, sc, buf, pl.win.cols, pl.win.rows, 4, 0, w, h, dst, tm, stream);
   }
   // the one-launch routes: the window launch writes the rectangle into dst, or into scratch for OpTransform's permutation
   return run_route(rt, n, src, &pl.win, w, h, dst, stream);
@@ -2238,7 +2325,7 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
       case 0: {                                                          // gofloat
         if (gofloat_demosaic_one_pass(d, n) && !cache->lru.contains(hs[1])) {   // + demosaic in the same pass when it would scale
           rc = cbuf_new(n.dw, n.dh, 4, 0, o); if (rc) return rc;
-          rc = launch_gofloat_demosaic(d, n, src, static_cast<float *>(o->p), stream); if (rc < 0) return rc;
+          rc = launch_gofloat_demosaic(d, n, src, nullptr, static_cast<float *>(o->p), stream); if (rc < 0) return rc;
           mask |= 3; buf = o; cache->lru.put(hs[1], o, o->bytes()); i = 1;   // op 1's output; op 0's is never materialised
           continue;
         }

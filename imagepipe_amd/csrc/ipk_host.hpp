@@ -585,6 +585,25 @@ inline ResampleFootprint resample_footprint(const ResamplePlan &p, size_t width,
   f.x = mx0; f.y = my0; f.w = mx1 - mx0 + 1u; f.h = my1 - my0 + 1u;
   return f;
 }
+// What a window launch of the scale-in-one-pass kernels (launch_raw_scaled_demosaic / launch_raster_scale_down with a ResampleWindow) reads of the
+// width x height cropped frame.  The taps: scaling.rs:84-87 with scale_down_buffer's corners -- tl = (0, 0), no cross terms -- in f32 as the kernels
+// compute them; from and to are weakly monotone in row and in col, so the box of the window's taps runs from the first pixel's `from` to the last
+// pixel's `to` on each axis.  Columns are then widened by the 8-sample row loads of the window-8 kernels: a lane loads [lx, lx + 8) with
+// lx = min(from_x, width - 8), lx is monotone in col too, and lanes past the window shadow its last column, so the loads span lx(first column) ..
+// lx(last column) + 7.  lx >= from_x - 7 and lx + 7 <= from_x + 7 <= to_x + 7: at most 7 columns more per side than the taps, inside the frame, and no
+// row more.  Frames under 8 columns never take those kernels (launcher) and get the tap box.  A superset of every read, whichever kernel is chosen.
+inline ResampleFootprint scaled_window_footprint(size_t width, size_t height, size_t nwidth, size_t nheight, size_t row0, size_t col0, size_t rows, size_t cols) {
+  const uint32_t W = (uint32_t)width, H = (uint32_t)height;
+  const float skip_x = ((float)((int64_t)width - 1) - 0.0f) / ((float)(nwidth - 1));
+  const float skip_y = ((float)((int64_t)height - 1) - 0.0f) / ((float)(nheight - 1));
+  auto at = [](float skip, uint32_t i, uint32_t lim) { return std::min(lim - 1, f32_as_u32_sat_host(std::floor(0.0f + (skip * (float)i)))); };
+  const uint32_t c1 = (uint32_t)(col0 + cols - 1), r1 = (uint32_t)(row0 + rows - 1);
+  uint32_t x0 = at(skip_x, (uint32_t)col0, W), x1 = at(skip_x, c1 + 1, W);
+  const uint32_t y0 = at(skip_y, (uint32_t)row0, H), y1 = at(skip_y, r1 + 1, H);
+  if (W >= 8) { x1 = std::max(x1, std::min(at(skip_x, c1, W), W - 8) + 7); x0 = std::min(x0, W - 8); }
+  ResampleFootprint f = {x0, y0, (size_t)x1 - x0 + 1, (size_t)y1 - y0 + 1};
+  return f;
+}
 // the corner and the skips of scaling.rs:68-72 alone, for the footprint of either form (the scaled form's corners are (0, 0), (width - 1, 0),
 // (0, height - 1), for which these are scaledown_plan's expressions): sizes the launches could take and finite values, no admission by window size
 inline bool resample_skips(size_t width, size_t height, int64_t tlx, int64_t tly, int64_t trx, int64_t try_, int64_t blx, int64_t bly,

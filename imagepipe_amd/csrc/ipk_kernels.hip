@@ -397,6 +397,10 @@ struct TransformArgs {
   // output-row band [out_r0, out_r1) of the fused gofloat + scaled_demosaic kernels (multi-GPU sharding of one frame):
   // dst row 0 = output row out_r0; the source slab's first row is folded into src_y (which may wrap: pointer arithmetic mod 2^64)
   uint32_t out_r0, out_r1;
+  // output-column window [out_c0, out_c1) of the same kernels and of k_raster_scale_down (regions of a preview): dst holds out_c1 - out_c0 pixels per
+  // row, dst column 0 = output column out_c0.  Whole frames: 0, nwidth.  Only the grid and the store address see the window: every value that enters
+  // a pixel comes from its absolute row and column, and the skips from the whole nwidth x nheight
+  uint32_t out_c0, out_c1;
   // k_raw_scaled_demosaic_w8m: a one-dimensional launch of xcd_gx x xcd_gy blocks (xcd_gy a multiple of 8) laid out so that each XCD works on one
   // contiguous eighth of the block rows (see the kernel); 0 = the plain two-dimensional grid
   uint32_t xcd_gx, xcd_gy, xcd_group;
@@ -591,9 +595,11 @@ __global__ void k_raster_scale_down(const SrcT *__restrict__ src, TransformArgs 
     for (int i = threadIdx.x; i < 256; i += blockDim.x) s_expand[i] = lut_interp(gamma_reverse, input8bit((uint8_t)i));
     __syncthreads();
   }
-  const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= a.nwidth) return;
-  for (uint32_t row = blockIdx.y; row < a.nheight; row += gridDim.y) {
+  const uint32_t col = a.out_c0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= a.out_c1) return;
+  const uint32_t pitch = a.out_c1 - a.out_c0;
+  dst -= a.out_c0;                                                           // dst column 0 is output column out_c0 (the address below never leaves dst)
+  for (uint32_t row = a.out_r0 + blockIdx.y; row < a.out_r1; row += gridDim.y) {
     const float from_x_r = a.tlx + a.skip_y_x * (float)row;
     const float to_x_r = a.tlx + a.skip_y_x * (float)(row + 1);
     const float from_y_r = a.tly + a.skip_y_y * (float)row;
@@ -634,12 +640,12 @@ __global__ void k_raster_scale_down(const SrcT *__restrict__ src, TransformArgs 
     }
     float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);                          // scaling.rs:122-126: no weight, zero fill
     if (n > 0.0f) { o.x = s0 / n; o.y = s1 / n; o.z = s2 / n; }
-    dst[(size_t)row * a.nwidth + col] = o;
+    dst[(size_t)(row - a.out_r0) * pitch + col] = o;
   }
 }
 static int cdiv_host_ok(float c);
 void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, size_t x, size_t y, size_t width, size_t height,
-                              size_t nwidth, size_t nheight, const void *gamma_reverse_pairs, float *dst4, hipStream_t s) {
+                              size_t nwidth, size_t nheight, const void *gamma_reverse_pairs, float *dst4, hipStream_t s, const ResampleWindow *win) {
   TransformArgs a{};
   a.width = (uint32_t)width; a.height = (uint32_t)height; a.nwidth = (uint32_t)nwidth; a.nheight = (uint32_t)nheight; a.components = 4;
   a.tlx = 0.0f; a.tly = 0.0f;                                               // scale_down_buffer's corners (scaling.rs:35-48)
@@ -650,9 +656,14 @@ void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, si
   a.inv_skip_x_x = 1.0f / a.skip_x_x; a.inv_skip_y_y = 1.0f / a.skip_y_y;
   a.fast_x = cdiv_host_ok(a.skip_x_x); a.fast_y = cdiv_host_ok(a.skip_y_y);
   a.src_pitch = owidth; a.src_x = x; a.src_y = y;
+  // the whole nwidth x nheight result, or its window (rows and columns of the result; the grid is laid over the window)
+  a.out_r0 = 0; a.out_r1 = (uint32_t)nheight; a.out_c0 = 0; a.out_c1 = (uint32_t)nwidth;
+  if (win) { a.out_r0 = (uint32_t)win->row0; a.out_r1 = (uint32_t)(win->row0 + win->rows); a.out_c0 = (uint32_t)win->col0; a.out_c1 = (uint32_t)(win->col0 + win->cols); }
+  const dim3 grid = grid_rows_few(a.out_c1 - a.out_c0, a.out_r1 - a.out_r0, 128, 8192);
+  const char *t = win ? "win=1" : nullptr;
   const LutPair *gr = reinterpret_cast<const LutPair *>(gamma_reverse_pairs);
-  if (src_is_u16) IPK_LAUNCH(k_raster_scale_down<uint16_t>, grid_rows_few(nwidth, nheight, 128, 8192), dim3(128), 0, s, static_cast<const uint16_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
-  else IPK_LAUNCH(k_raster_scale_down<uint8_t>, grid_rows_few(nwidth, nheight, 128, 8192), dim3(128), 0, s, static_cast<const uint8_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
+  if (src_is_u16) IPK_LAUNCH_TAG(t, k_raster_scale_down<uint16_t>, grid, dim3(128), 0, s, static_cast<const uint16_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
+  else IPK_LAUNCH_TAG(t, k_raster_scale_down<uint8_t>, grid, dim3(128), 0, s, static_cast<const uint8_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
 }
 
 // OpGoFloat (CFA branch) + scaling::scaled_demosaic in one pass over the raw sensor frame: dst4 = scaled_demosaic(gofloat(src)).
@@ -662,8 +673,10 @@ __global__ void k_raw_scaled_demosaic(const T *__restrict__ src, TransformArgs a
   __shared__ uint8_t s_cfa[48 * 48];
   for (int i = threadIdx.x; i < 48 * 48; i += blockDim.x) s_cfa[i] = cfa48[i];
   __syncthreads();
-  const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= a.nwidth) return;
+  const uint32_t col = a.out_c0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= a.out_c1) return;
+  const uint32_t pitch = a.out_c1 - a.out_c0;
+  float4 *const dstw = reinterpret_cast<float4 *>(dst) - a.out_c0;          // dst column 0 is output column out_c0 (the address below never leaves dst)
   for (uint32_t row = a.out_r0 + blockIdx.y; row < a.out_r1; row += gridDim.y) {
     const float from_x_r = a.tlx + a.skip_y_x * (float)row;
     const float to_x_r = a.tlx + a.skip_y_x * (float)(row + 1);
@@ -704,7 +717,7 @@ __global__ void k_raw_scaled_demosaic(const T *__restrict__ src, TransformArgs a
     }
     float4 o;
     o.x = (n0 > 0.0f) ? s0 / n0 : 0.0f; o.y = (n1 > 0.0f) ? s1 / n1 : 0.0f; o.z = (n2 > 0.0f) ? s2 / n2 : 0.0f; o.w = (n3 > 0.0f) ? s3 / n3 : 0.0f;
-    reinterpret_cast<float4 *>(dst)[(size_t)(row - a.out_r0) * a.nwidth + col] = o;
+    dstw[(size_t)(row - a.out_r0) * pitch + col] = o;
   }
 }
 // The same for windows of at most 8 x 8 source samples (every scale up to 7, i.e. all previews larger than 1/7 size).
@@ -754,9 +767,11 @@ __global__ __launch_bounds__(256) void k_raw_scaled_demosaic_w8(const T *__restr
     s_bits[i] = (uint16_t)bits;
   }
   __syncthreads();
-  const uint32_t col_raw = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool lane_in = col_raw < a.nwidth;
-  const uint32_t col = min(col_raw, a.nwidth - 1);       // lanes past the row shadow its last pixel: every lane stays active
+  const uint32_t col_raw = a.out_c0 + blockIdx.x * blockDim.x + threadIdx.x;
+  const bool lane_in = col_raw < a.out_c1;
+  const uint32_t col = min(col_raw, a.out_c1 - 1);       // lanes past the row (the column window) shadow its last pixel: every lane stays active
+  const uint32_t pitch = a.out_c1 - a.out_c0;
+  float4 *const dstw = reinterpret_cast<float4 *>(dst) - a.out_c0;   // dst column 0 is output column out_c0 (the address below never leaves dst)
   // column window (scaling.rs:84-89 with skip_x_y = skip_y_x = 0, tlx = tly = 0 as scale_down_buffer sets them); the host
   // launches this kernel only when no window is wider or taller than 8
   const uint32_t from_x = min(a.width - 1, f32_as_u32_sat(floorf(a.tlx + (a.skip_x_x * (float)col))));
@@ -824,7 +839,7 @@ __global__ __launch_bounds__(256) void k_raw_scaled_demosaic_w8(const T *__restr
     }
     float4 o;
     o.x = (n0 > 0.0f) ? s0 / n0 : 0.0f; o.y = (n1 > 0.0f) ? s1 / n1 : 0.0f; o.z = (n2 > 0.0f) ? s2 / n2 : 0.0f; o.w = (n3 > 0.0f) ? s3 / n3 : 0.0f;
-    if (lane_in) reinterpret_cast<float4 *>(dst)[(size_t)(row - a.out_r0) * a.nwidth + col] = o;
+    if (lane_in) dstw[(size_t)(row - a.out_r0) * pitch + col] = o;
   }
 }
 // The same again for filters with a short period (pw x ph cells, pw * ph <= kW8MaxCells: Bayer, X-Trans, 12x12 ...): the
@@ -894,9 +909,13 @@ __global__ __launch_bounds__(256, C4 ? 6 : 7) void k_raw_scaled_demosaic_w8m(con
     blk_y = (gi * 8u + xcd) * a.xcd_group + rem / a.xcd_gx;
     rows_step = a.xcd_gy;
   }
-  const uint32_t col_raw = blk_x * blockDim.x + threadIdx.x;
-  const bool lane_in = col_raw < a.nwidth;
-  const uint32_t col = min(col_raw, a.nwidth - 1);
+  // the column window [out_c0, out_c1) (whole frames: 0, nwidth) moves the block's first column and the uniform base of the store; `col` stays the
+  // absolute column, so nothing a lane keeps changes
+  const uint32_t col_raw = a.out_c0 + blk_x * blockDim.x + threadIdx.x;
+  const bool lane_in = col_raw < a.out_c1;
+  const uint32_t col = min(col_raw, a.out_c1 - 1);
+  const uint32_t pitch = a.out_c1 - a.out_c0;
+  float4 *const dstw = reinterpret_cast<float4 *>(dst) - a.out_c0;
   const uint32_t from_x = min(a.width - 1, f32_as_u32_sat(floorf(a.tlx + (a.skip_x_x * (float)col))));
   const uint32_t to_x = min(a.width - 1, f32_as_u32_sat(floorf(a.tlx + (a.skip_x_x * (float)(col + 1)))));
   const float center_x = a.tlx + (a.skip_y_x / 2.0f) - 0.5f + (a.skip_x_x * (float)col) + (a.skip_x_x / 2.0f);
@@ -1036,7 +1055,7 @@ __global__ __launch_bounds__(256, C4 ? 6 : 7) void k_raw_scaled_demosaic_w8m(con
       o.x = (n0 > 0.0f) ? s0 / n0 : 0.0f; o.y = (n1 > 0.0f) ? s1 / n1 : 0.0f; o.z = (n2 > 0.0f) ? s2 / n2 : 0.0f; o.w = (n3 > 0.0f) ? s3 / n3 : 0.0f;
       // lanes past the row shadow its last pixel (same value to the same address): the store needs no predicate
       (void)lane_in;
-      reinterpret_cast<float4 *>(dst)[(size_t)(c0.row - a.out_r0) * a.nwidth + col] = o;
+      dstw[(size_t)(c0.row - a.out_r0) * pitch + col] = o;
       s0 = s1 = s2 = s3 = n0 = n1 = n2 = n3 = 0.0f;
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1055,7 +1074,7 @@ __global__ __launch_bounds__(256, C4 ? 6 : 7) void k_raw_scaled_demosaic_w8m(con
 template <typename T>
 void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
                                 int norm_fast, int has_fourth_colour, size_t nwidth, size_t nheight, const uint8_t *cfa48_dev, int pw, int ph, float *dst4, hipStream_t s,
-                                size_t band_src_row0, size_t band_out_row0, size_t band_out_rows) {
+                                size_t band_src_row0, size_t band_out_row0, size_t band_out_rows, const ResampleWindow *win) {
   TransformArgs a{};
   a.width = (uint32_t)width; a.height = (uint32_t)height; a.nwidth = (uint32_t)nwidth; a.nheight = (uint32_t)nheight; a.components = 4;
   a.tlx = 0.0f; a.tly = 0.0f;                                               // scale_down_buffer's corners (scaling.rs:35-48)
@@ -1072,27 +1091,31 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
   // row y + band_src_row0 (the slab's first row), which is folded into src_y; window bounds still clamp against the full height
   a.out_r0 = 0; a.out_r1 = (uint32_t)nheight;
   if (band_out_rows) { a.out_r0 = (uint32_t)band_out_row0; a.out_r1 = (uint32_t)(band_out_row0 + band_out_rows); a.src_y = (uint64_t)0 - (uint64_t)band_src_row0; }
-  const size_t out_rows = a.out_r1 - a.out_r0;
+  // or the window `win` of the result: rows as a band whose source is the whole frame (src_y stays), columns through out_c0 / out_c1; the grid below
+  // is laid over out_rows x out_cols, the kernel is chosen as for the whole frame
+  a.out_c0 = 0; a.out_c1 = (uint32_t)nwidth;
+  if (win) { a.out_r0 = (uint32_t)win->row0; a.out_r1 = (uint32_t)(win->row0 + win->rows); a.out_c0 = (uint32_t)win->col0; a.out_c1 = (uint32_t)(win->col0 + win->cols); }
+  const size_t out_rows = a.out_r1 - a.out_r0, out_cols = a.out_c1 - a.out_c0;
   a.xcd_gx = 0; a.xcd_gy = 0; a.xcd_group = 0;
   // launch-log tag: the host-known switches the kernels branch on, "norm_fast=.,norm_light=.,fast_x=.,fast_y=.,xcd=." (xcd: 0 plain grid, 1 XCD row
-  // grouping with no leftover rows, 2 grouping with leftover rows)
+  // grouping with no leftover rows, 2 grouping with leftover rows); window launches, and only they, append ",win=1"
   auto tag = [&](int xcd) -> const char * {
     if (!g_log_on.load(std::memory_order_relaxed)) return nullptr;         // the table is built, and read, only while the log is on
     static const std::vector<std::string> tags = [] {
       std::vector<std::string> t;
-      for (int i = 0; i < 48; ++i) {
-        char b[80]; snprintf(b, sizeof(b), "norm_fast=%d,norm_light=%d,fast_x=%d,fast_y=%d,xcd=%d", i & 1, (i >> 1) & 1, (i >> 2) & 1, (i >> 3) & 1, i >> 4);
+      for (int i = 0; i < 96; ++i) {
+        char b[80]; snprintf(b, sizeof(b), "norm_fast=%d,norm_light=%d,fast_x=%d,fast_y=%d,xcd=%d%s", i & 1, (i >> 1) & 1, (i >> 2) & 1, (i >> 3) & 1, (i % 48) >> 4, i >= 48 ? ",win=1" : "");
         t.push_back(b);
       }
       return t;
     }();
-    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4))].c_str();
+    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4)) + (win ? 48 : 0)].c_str();
   };
   a.components = has_fourth_colour ? 4 : 3;               // the w8 kernel skips the fourth bin for three-colour filters (it stays 0.0)
   // windows of at most 8 x 8 samples: floor(skip*(c+1)) - floor(skip*c) + 1 <= ceil(skip) + 1
   if (a.skip_x_x >= 1.0f && a.skip_x_x <= 7.0f && a.skip_y_y >= 1.0f && a.skip_y_y <= 7.0f && width >= 8 &&
       (reinterpret_cast<uintptr_t>(dst4) & 15) == 0) {
-    const unsigned gx = (unsigned)((nwidth + 255) / 256);
+    const unsigned gx = (unsigned)((out_cols + 255) / 256);
     // 21 blocks per CU = 3 full rounds of the 7 resident ones.  Round 4 sweep (50 MP X-Trans -> 2160x1440, one box, ms): 1620 / 1792 / 2688 / 3584 / 5376 /
     // 7168 blocks 0.064 / 0.059 / 0.058 / 0.0565 / 0.0563 / 0.0565 with the plain grid, 0.064 / 0.061 / 0.060 / 0.057 / 0.059 / 0.058 with runs of two
     // block rows per XCD; equal row counts per block (every block the same 3, 4, 6 or 8 rows) 0.064 / 0.064 / 0.061 / 0.058 / 0.057 / 0.059: fewer, longer-lived
@@ -1128,10 +1151,10 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
     IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic_w8<T>, grid, dim3(256), 0, s, src, a, cfa48_dev, dst4);
     return;
   }
-  IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(nwidth, out_rows, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst4);
+  IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(out_cols, out_rows, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst4);
 }
-template void launch_raw_scaled_demosaic<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t);
-template void launch_raw_scaled_demosaic<float>(const float *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t);
+template void launch_raw_scaled_demosaic<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *);
+template void launch_raw_scaled_demosaic<float>(const float *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *);
 template void launch_transform_buffer<float>(const float *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, float *, hipStream_t);
 template void launch_transform_buffer<uint8_t>(const uint8_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint8_t *, hipStream_t);
 template void launch_transform_buffer<uint16_t>(const uint16_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint16_t *, hipStream_t);

@@ -42,7 +42,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // The symbol is the code object's (hipKernelNameRefByPtr, resolved when the log is READ, never at launch).  The bracketed tag is attached by
 // launchers whose kernel also branches on a value the host knows: k_gamma [vec4=,wrap=], k_output8 / k_output16 [vec4=] (16-byte groups or sample by
 // sample; wrap: the grid cap holds), k_gofloat_cfa_v4 [rowwrap=] (more rows than grid rows), the ipk_raw_scaled_demosaic kernels
-// [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows),
+// [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows; their window launches,
+// ipk_raw_scaled_demosaic_window, append win=1: [norm_fast=,...,xcd=,win=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form);
 // k_fused_resample's axis-aligned mode (ipk_raw_to_srgb_scaled) [fast_ok=,axis=1]; k_fused_resample's window launches (launch_fused_resample with a
 // ResampleWindow: ipk_raw_to_srgb_resampled_window / _scaled_window, regions under IPK_FUSED_WINDOW_REGIONS) append win=1: [fast_ok=,win=1] /
@@ -56,13 +57,19 @@ void launch_transform_buffer(const T *src, size_t width, size_t height, int64_t 
                              int64_t blx, int64_t bly, size_t nwidth, size_t nheight, size_t components,
                              const uint8_t *cfa48_dev, T *dst, hipStream_t s);
 
+// A rectangle of a launch's nwidth x nheight result (launch_raster_scale_down, launch_raw_scaled_demosaic, launch_fused_resample): non-empty and inside it
+struct ResampleWindow { size_t row0, col0, rows, cols; };
 // run_other + scale_down_opbuf in one pass over an RGB8 / RGB16 raster (gofloat.rs:171-201 + scaling.rs:147-160)
+// win (optional, here and in launch_raw_scaled_demosaic): only that rectangle of the result is computed and dst4 holds rows * cols packed pixels; the
+// grid is sized from the window, the kernel chosen as for the whole frame, and every pixel's bits are those of the whole-frame launch (the kernels
+// work from absolute rows and columns).  Null: the whole frame, whose log entries are unchanged
 void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, size_t x, size_t y, size_t width, size_t height,
-                              size_t nwidth, size_t nheight, const void *gamma_reverse_pairs, float *dst4, hipStream_t s);
+                              size_t nwidth, size_t nheight, const void *gamma_reverse_pairs, float *dst4, hipStream_t s, const ResampleWindow *win = nullptr);
 template <typename T>
 void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0, int norm_fast, int has_fourth_colour,
                                 size_t nwidth, size_t nheight, const uint8_t *cfa48_dev, int pattern_width, int pattern_height, float *dst4, hipStream_t s,
-                                size_t band_src_row0 = 0, size_t band_out_row0 = 0, size_t band_out_rows = 0);   // band_out_rows == 0: the whole frame
+                                size_t band_src_row0 = 0, size_t band_out_row0 = 0, size_t band_out_rows = 0,    // band_out_rows == 0: the whole frame
+                                const ResampleWindow *win = nullptr);                                            // not together with a band
 
 void launch_tolab(const float *src4, size_t npix, const float *mul4, const float *cm12, const void *lab_pairs, float *dst3,
                   int num_cus, hipStream_t s);
@@ -120,7 +127,6 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s);
 // win (optional): only the rows [row0, row0 + rows) and columns [col0, col0 + cols) of the nwidth x nheight result are computed, and f.dst holds exactly
 // rows * cols * 3 packed samples (tiles are laid over the window from its origin; every pixel's bits are those of the whole-frame launch); it must be
 // non-empty and lie inside the result.  Null: the whole frame, whose log entries are unchanged; a window launch adds the key win=1
-struct ResampleWindow { size_t row0, col0, rows, cols; };
 int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s,
                           const ResampleWindow *win = nullptr);
 // rotate_buffer's permutation on a 1-channel image through an arbitrary source pitch / window (steps in source elements): |x_step| == 1 (flips, 180

@@ -239,6 +239,25 @@ IPK_API int ipk_raw_scaled_demosaic(const void *src, int src_type, size_t owidth
  * nwidth*nheight*4 f32 (E = 0). */
 IPK_API int ipk_raster_scale_down(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
                                   size_t nwidth, size_t nheight, float *dst4, void *stream);
+/* The window forms of the two: only the columns [wx, wx + ww) and rows [wy, wy + wh) of the nwidth x nheight result are computed, by the same kernel
+ * the whole-frame form selects, its grid laid over the window instead of the frame.  Admission is exactly that of the whole-frame forms; an empty
+ * window or one that leaves nwidth x nheight is IPK_ERR_INVALID (nothing written).  dst4 receives ww * wh * 4 packed f32, bit-identical to that
+ * rectangle of the whole-frame call -- every pixel is computed from its absolute row and column, and the skips from the whole nwidth x nheight, so
+ * nothing depends on the window -- and nothing outside those samples is written.  src is still the whole sensor frame's first sample, but the launch
+ * reads only the window's footprint (ipk_scaled_window_footprint, offset by x, y). */
+IPK_API int ipk_raw_scaled_demosaic_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                           float black0, float white0, const char *cfa, size_t nwidth, size_t nheight,
+                                           size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
+IPK_API int ipk_raster_scale_down_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                         size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
+/* What such a window reads of the width x height cropped frame, host-only (no GPU needed): out4 = {x, y, w, h} in cropped-frame coordinates.  The
+ * bounding box of the taps of the window's pixels (src/scaling.rs:84-87 with scale_down_buffer's corners (0, 0), (width - 1, 0), (0, height - 1), in
+ * f32 as the kernels compute them), its columns widened by the 8-sample row loads of the window-8 kernels (a lane loads [lx, lx + 8) with
+ * lx = min(from_x, width - 8); frames under 8 columns never take those kernels).  It therefore contains every read whichever kernel the launch
+ * selects, lies inside the frame, is never empty, and exceeds the exact tap box by at most 7 columns per side and by no row.  IPK_ERR_INVALID for an
+ * empty window or one that leaves nwidth x nheight. */
+IPK_API int ipk_scaled_window_footprint(size_t width, size_t height, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh,
+                                        size_t *out4);
 /* OpDemosaic::run dispatch (src/ops/demosaic.rs:27-61).  colors = 1 or 4.  dst4 must hold
  * max(width*height, demosaic_width*demosaic_height)*4 floats.  IPK_NOOP = pass-through.
  * out_width / out_height receive the result size. */
@@ -460,7 +479,13 @@ typedef struct {
                                       Bit 2 (IPK_FUSED_WINDOW_REGIONS = 4) concerns regions only (ipk_pipeline_region / _run_region / ipk_host_pipeline_run_region):
                                       with it, a descriptor for which ipk_pipeline_fuses_rotatecrop or ipk_pipeline_fuses_scaledown answers 1 renders a region
                                       as a window of that one launch instead of computing the whole result.  Same contract: no hash, no result, and no other
-                                      driver or report depends on it. */
+                                      driver or report depends on it.
+                                      Bit 3 (IPK_FUSED_WINDOW_PREVIEWS = 8) concerns regions only as well: with it, beside IPK_FUSED_ON, a descriptor for which
+                                      ipk_pipeline_windows_preview answers 1 -- the downscaled previews, scale >= minscale -- renders a region as a window of its
+                                      gofloat + demosaic pass (ipk_raw_scaled_demosaic_window / ipk_raster_scale_down_window) followed by the point-wise ops on
+                                      that rectangle.  Same contract again.  The bit acts only together with bit 0: allow_fused = 8 still means "on" for every
+                                      whole-frame route (any non-zero value does), but regions of previews are then cut from the whole result, as without the
+                                      bit.  Bit 2 does not window these frames, with or without bit 3. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -479,7 +504,14 @@ typedef struct {
 typedef enum {
   IPK_FUSED_ON = 1,                /* the one-launch routes where legal (any non-zero value means this) */
   IPK_FUSED_FOUR_COLOUR = 2,       /* bit 1: four-colour filters take the one-launch route too */
-  IPK_FUSED_WINDOW_REGIONS = 4     /* bit 2: regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch */
+  IPK_FUSED_WINDOW_REGIONS = 4,    /* bit 2: regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch */
+  IPK_FUSED_WINDOW_PREVIEWS = 8    /* bit 3 (beside bit 0): regions of downscaled previews (OpDemosaic's scaled_demosaic branch, scale >= minscale, and rasters
+                                      under a size limit) run as a window of the scaling pass, where ipk_pipeline_windows_preview says so.
+                                      Measured (profiles/r13_preview_regions.txt; 50 MP X-Trans -> 2160x1440 | 24 MP RGGB -> 1500x1000, u8, without -> with
+                                      the bit): device form, 1/16 of the area 0.096 -> 0.032 | 0.063 -> 0.029 ms, 1/4 0.095 -> 0.045 | 0.068 -> 0.034 ms, the
+                                      whole area 0.098 -> 0.090 | 0.068 -> 0.059 ms (the copy is saved); host form, 1/16 1.86 -> 0.17 ms (99.5 -> 6.3 MB
+                                      uploaded) | 0.92 -> 0.11 ms (48 -> 3.1 MB), 1/4 1.89 -> 0.55 | 0.94 -> 0.29 ms.  NOT faster: a whole-area region
+                                      through the host form uploads the whole frame either way, 2.016 -> 2.019 | 1.002 -> 1.001 ms */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -526,6 +558,13 @@ IPK_API int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_typ
  * does not scale (scale <= 1).  0 otherwise -- three-colour filters included: their one-launch route does not depend on the bit --; a negative error
  * code for a descriptor ipk_pipeline_sizes refuses.  No GPU needed. */
 IPK_API int ipk_pipeline_fuses_four_colour(const ipk_pipeline_desc *d, int out_type);
+/* Does a region of this descriptor (ipk_pipeline_region / _run_region / ipk_host_pipeline_run_region) run as a window of its scaling gofloat + demosaic
+ * pass?  1 when d->allow_fused has IPK_FUSED_ON and IPK_FUSED_WINDOW_PREVIEWS set, OpRotateCrop is a no-op, and the staged drivers run OpGoFloat and
+ * OpDemosaic as the one scaling pass: a one-sample-per-pixel CFA mosaic with a valid filter (three or four colours) at scale >= minscale
+ * (src/ops/demosaic.rs:33-50), or an RGB8 / RGB16 raster at scale > 1 that does not take the fast path.  0 otherwise -- mono and three-sample raws, an
+ * active rotatecrop behind a scaling demosaic, 1 < scale < minscale (IPK_FUSED_WINDOW_REGIONS' ground), full-size frames (windowed whatever the
+ * bits); a negative error code for a descriptor ipk_pipeline_sizes refuses.  Whole-frame drivers do not depend on the bit.  No GPU needed. */
+IPK_API int ipk_pipeline_windows_preview(const ipk_pipeline_desc *d, int out_type);
 /* do_timing! (src/pipeline.rs:68-80: the reference logs the wall time of every op of Pipeline::run): ipk_timing_begin arms the calling
  * thread, the following ipk_pipeline_run call(s) on it bracket every stage they enqueue with hipEvents on their stream, ipk_timing_end
  * waits for the last one and returns the stages in execution order under the reference's op names ("gofloat", "demosaic", "rotatecrop",
@@ -547,7 +586,11 @@ IPK_API int ipk_host_pipeline_run(const ipk_pipeline_desc *d, const void *src, v
  * With IPK_FUSED_WINDOW_REGIONS in allow_fused the one-launch rotatecrop and scaledown routes (ipk_pipeline_fuses_rotatecrop / _scaledown answer 1)
  * are windowed too: the region is mapped back through OpTransform to a rectangle of the resampled image, the launch runs over that rectangle only,
  * and the window reported is its footprint (ipk_transform_window_footprint plus the crop offset; it can be empty, w = h = 0, where no pixel of the
- * region has a tap).  Without the bit those routes answer 0, as they always did. */
+ * region has a tap).  Without the bit those routes answer 0, as they always did.
+ * With IPK_FUSED_WINDOW_PREVIEWS (and IPK_FUSED_ON) in allow_fused the downscaled previews (ipk_pipeline_windows_preview answers 1) are windowed too:
+ * the region is mapped back through OpTransform to a rectangle of the demosaic_w x demosaic_h preview, the scaling gofloat + demosaic pass runs over
+ * that rectangle only, the point-wise ops, the quantisation and OpTransform's permutation follow on the rectangle, and the window reported is
+ * ipk_scaled_window_footprint plus the crop offset (never empty).  Without the bit they answer 0. */
 IPK_API int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h,
                                 size_t *src_x, size_t *src_y, size_t *src_w, size_t *src_h);
 /* The region from the DEVICE source ipk_pipeline_run takes (the whole sensor frame) into the DEVICE buffer dst, enqueued on `stream`.
