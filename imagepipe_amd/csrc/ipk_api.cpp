@@ -1310,6 +1310,36 @@ int ipk_raster_to_srgb(const void *src, int src_type, size_t width, size_t heigh
   return IPK_OK;
 }
 
+// The same launch over a rectangle of any source whose OpDemosaic is a pass-through: rasters, three-sample and monochrome u16 raws (runtime modes of
+// k_raster_chain<uint8_t | uint16_t>; no kernel of its own, and none for f32 raws, which stay staged)
+int ipk_plain_to_srgb(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                      const float *black4, const float *white4, const float *wb_coeffs, const float *cam_to_xyz_normalized,
+                      float exposure, const float *points, int npoints, int linear, int out_type, void *dst, void *stream) {
+  REQUIRE_INIT();
+  if (!src || !dst || !wb_coeffs || !cam_to_xyz_normalized || !dims_ok(width, height) || !dims_ok(owidth, 1) || y >= (1ull << 31))
+    return fail(IPK_ERR_INVALID, "bad plain_to_srgb arguments");
+  if (kind != IPK_PLAIN_RASTER && kind != IPK_PLAIN_RGB && kind != IPK_PLAIN_MONO) return fail(IPK_ERR_INVALID, "bad plain kind");
+  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
+  if (x > owidth || width > owidth - x) return fail(IPK_ERR_INVALID, "the rectangle's columns [%zu, %zu) leave the %zu-wide source", x, x + width, owidth);
+  if (src_type == IPK_SRC_F32) return fail(IPK_ERR_UNSUPPORTED, "plain_to_srgb has no f32 form (run the staged ops)");
+  if (kind == IPK_PLAIN_RASTER ? (src_type != IPK_SRC_RGB8 && src_type != IPK_SRC_RGB16) : src_type != IPK_SRC_U16)
+    return fail(IPK_ERR_INVALID, "plain_to_srgb takes RGB8 / RGB16 rasters and u16 three-sample / monochrome raws");
+  if (kind != IPK_PLAIN_RASTER && (!black4 || !white4)) return fail(IPK_ERR_INVALID, "plain_to_srgb: a raw source needs its levels");
+  if (width * height < 256) return fail(IPK_ERR_UNSUPPORTED, "plain_to_srgb needs at least 256 pixels (use the staged ops)");
+  PointwisePrep pp;
+  int rc = pp.prepare(kind == IPK_PLAIN_MONO, wb_coeffs, cam_to_xyz_normalized, exposure, points, npoints, linear); if (rc) return rc;
+  const size_t spp = kind == IPK_PLAIN_MONO ? 1 : 3, esz = src_type == IPK_SRC_RGB8 ? 1 : 2;
+  pp.f.src = static_cast<const char *>(src) + (y * owidth + x) * spp * esz;         // the rectangle's first sample
+  pp.f.dst = dst; pp.f.out_type = out_type;
+  ipk::PlainSource ps;
+  ps.levels = kind; ps.owidth = owidth; ps.width = width;
+  for (int c = 0; c < 3; ++c) { ps.black[c] = kind == IPK_PLAIN_RASTER ? 0.0f : black4[c]; ps.white[c] = kind == IPK_PLAIN_RASTER ? 0.0f : white4[c]; }
+  if (ipk::launch_raster_chain(pp.f, width * height, src_type != IPK_SRC_RGB8, cx().lut_pairs[ipk::kLutGammaReverse], S(stream), &ps) != 0)
+    return fail(IPK_ERR_UNSUPPORTED, "plain_to_srgb: the launch refused this rectangle");
+  HIPCHK(hipGetLastError());
+  return IPK_OK;
+}
+
 // The launch behind ipk_raw_to_srgb_resampled (corners: its six corner coordinates) and ipk_raw_to_srgb_scaled (corners == NULL: scale_down_opbuf's
 // transform), k_fused_resample: the checks both share, then the plan from the cropped frame's sides, or the refusal (nothing is enqueued then)
 // win (the window forms): the rectangle of the nwidth x nheight result the launch is laid over; dst then holds exactly its pixels
@@ -1698,6 +1728,9 @@ struct RotateCropPoints { int64_t pts[6]; size_t nw, nh; };
 struct Route {
   RouteKind kind; ipk_fused_params fp; RotateCropPoints rcp; size_t pw, ph; bool four;
   const char *label, *region_label;
+  // kFusedRaster: plain = the frame is on the link because of IPK_FUSED_PLAIN (a cropped raster, a u16 three-sample or monochrome raw) and its launch is
+  // ipk_plain_to_srgb of plain_kind (ipk_plain_kind) over the crop rectangle with these levels; an uncropped raster has plain = false, plain_kind 0
+  bool plain; int plain_kind; float black4[4], white4[4];
 };
 // The chain, in order: fast path, raw, resample, scaledown, raster, staged -- the first link that holds names the route.
 //   raw        gofloat..gamma as the one raw->sRGB launch: a CFA mosaic, every op in between point-wise or demosaic::full (OpRotateCrop a no-op, OpDemosaic
@@ -1710,18 +1743,26 @@ struct Route {
 //              (ipk_raw_to_srgb_scaled, to the negotiated n.dw x n.dh), opted into with fuse_scaledown.  An active OpRotateCrop behind a scaling
 //              OpDemosaic would be a second resampling: such frames stay staged
 //   raster     run_other + tolab..gamma (+ quantisation) as one launch when OpDemosaic (a 4-channel buffer at scale <= 1: pass-through,
-//              demosaic.rs:39-44) and OpRotateCrop are no-ops
+//              demosaic.rs:39-44) and OpRotateCrop are no-ops: an uncropped RGB8 / RGB16 raster.  With IPK_FUSED_PLAIN beside IPK_FUSED_ON the link also
+//              takes the other frames whose OpGoFloat writes that 4-channel buffer -- rasters with OpGoFloat crops, u16 raws with cpp == 3 and u16
+//              monochrome raws (cpp == 1 without a filter) -- as ipk_plain_to_srgb over the crop rectangle.  Their f32 forms stay staged: the launch is
+//              a mode of the RGB8 / RGB16 kernels and has no f32 instantiation
 // OpTransform does not enter: run_route folds any orientation in.  The order matters less than it looks, because the links exclude each other, and the
 // callers that ask for one link only (the ipk_pipeline_fuses_* reports, the batch driver, the region plan) rely on exactly that:
 //   - the fast path needs a raster source (default_ops_other), the three raw links need n.cfa_branch, which implies a raw source, and the raster link
-//     needs !n.raw: a fast-path frame fails every raw link and a raw frame never takes the fast path or the raster link;
+//     needs !n.cfa_branch (a raster, or under IPK_FUSED_PLAIN a raw OpGoFloat does not treat as a mosaic): a fast-path frame fails every raw link and
+//     a frame on a raw link never takes the fast path or the raster link;
 //   - raw and scaledown need n.rc.noop(), resample needs !n.rc.noop();
 //   - raw and resample need n.scale <= 1, scaledown needs n.scale > 1.
 // So at most one raw link holds for a descriptor, wherever the fast-path test sits.  Fast path against raster is the one pair the order decides.
 // out_type enters through the fast path and fp.out_type alone: the cached driver, which produces f32 whatever the caller asked for, asks with
 // IPK_OUT_F32 after it has tested the fast path on the caller's type itself.
+bool plain_opted(const ipk_pipeline_desc *d) { const int both = IPK_FUSED_ON | IPK_FUSED_PLAIN; return (d->allow_fused & both) == both; }
 void choose_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Route &rt) {
   rt.kind = kStaged; rt.four = false; rt.pw = n.r.width; rt.ph = n.r.height; rt.label = rt.region_label = "";
+  rt.plain = false; rt.plain_kind = IPK_PLAIN_RASTER;
+  const bool uncropped = n.r.x == 0 && n.r.y == 0 && n.r.width == d->width && n.r.height == d->height;
+  const bool plain_raw = n.raw && !n.cfa_branch && d->src_type == IPK_SRC_U16;           // cpp == 3, or cpp == 1 without a filter (negotiate)
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) { rt.kind = kFastPath; return; }
   ipk::Cfa cfa; ipk::ResamplePlan plan; int xo, yo;
   const bool mosaic = d->allow_fused && n.cfa_branch && d->cpp == 1 && ipk::Cfa::parse(d->cfa, cfa);
@@ -1741,10 +1782,14 @@ void choose_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type,
     rt.kind = kFusedScaledown; rt.pw = n.dw; rt.ph = n.dh;
     rt.label = "fused gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma";          // a whole frame marks "transform" as a stage of its own (run_route)
     rt.region_label = "fused region gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma(+transform)";
-  } else if (d->allow_fused && !n.raw && still && n.r.x == 0 && n.r.y == 0 && n.r.width == d->width && n.r.height == d->height &&
-             n.r.width * n.r.height >= 256 && n.scale <= 1.0f) {
+  } else if (d->allow_fused && still && n.r.width * n.r.height >= 256 && n.scale <= 1.0f &&
+             ((!n.raw && uncropped) || (plain_opted(d) && (!n.raw || plain_raw)))) {
     rt.kind = kFusedRaster;
+    rt.plain = n.raw || !uncropped;
+    rt.plain_kind = !n.raw ? IPK_PLAIN_RASTER : d->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO;
+    std::memcpy(rt.black4, d->blacklevels, sizeof(rt.black4)); std::memcpy(rt.white4, d->whitelevels, sizeof(rt.white4));
     rt.label = "fused gofloat+to_lab+basecurve+from_lab+gamma(+transform)";
+    rt.region_label = "fused region gofloat+to_lab+basecurve+from_lab+gamma(+transform)";      // regions under IPK_FUSED_PLAIN (plan_region)
   }
   if (rt.kind == kStaged) return;
   fused_params_of(d, n, out_type, rt.fp);
@@ -1779,7 +1824,7 @@ bool crop_only_shortcut(const ipk_fused_params &fp, const RotateCropPoints &r) {
          (size_t)x + r.nw <= fp.width && (size_t)y + r.nh <= fp.height;                                                 // the rectangle lies inside the frame
 }
 // The one launch of a route into `out`.  win == null: the whole pw x ph image, by the whole-frame entry point.  win: that rectangle of it, packed, by
-// the window form of the same launch (the raster kind has none: its regions are cut from the whole result).  Whole frames never go through the
+// the window form of the same launch (the raster kind's is ipk_plain_to_srgb over the rectangle: plan_region asks for it under IPK_FUSED_PLAIN only).  Whole frames never go through the
 // window forms -- those are other kernel variants -- except on the crop-only shortcut, which IS the window form: written once, the whole frame
 // being the window (0, 0, nw, nh).
 int launch_route(const Route &rt, const void *src, const ipk::ResampleWindow *win, void *out, void *stream) {
@@ -1808,9 +1853,12 @@ int launch_route(const Route &rt, const void *src, const ipk::ResampleWindow *wi
       return win ? ipk_raw_to_srgb_scaled_window(&fp, src, rt.pw, rt.ph, win->col0, win->row0, win->cols, win->rows, out, stream)
                  : ipk_raw_to_srgb_scaled(&fp, src, rt.pw, rt.ph, out, stream);
     case kFusedRaster:
-      if (!win) return ipk_raster_to_srgb(src, fp.src_type, fp.width, fp.height, fp.wb_coeffs, fp.cam_to_xyz_normalized, fp.exposure, fp.points, fp.npoints,
-                                          fp.linear, fp.out_type, out, stream);
-      break;
+      if (!win && !rt.plain) return ipk_raster_to_srgb(src, fp.src_type, fp.width, fp.height, fp.wb_coeffs, fp.cam_to_xyz_normalized, fp.exposure, fp.points, fp.npoints,
+                                                       fp.linear, fp.out_type, out, stream);
+      // the point-wise ops have no halo: a window is the launch's rectangle moved and shrunk, the whole frame of a plain source the crop rectangle
+      return ipk_plain_to_srgb(src, fp.src_type, rt.plain_kind, fp.owidth, fp.x + (win ? win->col0 : 0), fp.y + (win ? win->row0 : 0), win ? win->cols : fp.width,
+                               win ? win->rows : fp.height, rt.black4, rt.white4, fp.wb_coeffs, fp.cam_to_xyz_normalized, fp.exposure, fp.points, fp.npoints,
+                               fp.linear, fp.out_type, out, stream);
     default: break;
   }
   return fail(IPK_ERR_INVALID, "internal: no such launch for this route");
@@ -2071,6 +2119,11 @@ int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type) {
   Route rt; const int rc = report_route(d, out_type, rt);
   return rc ? rc : rt.kind == kFusedScaledown;
 }
+// IPK_FUSED_PLAIN: does a cropped raster / a u16 three-sample or monochrome raw run as the one launch ipk_plain_to_srgb (the whole-frame half of the bit)?
+int ipk_pipeline_fuses_plain(const ipk_pipeline_desc *d, int out_type) {
+  Route rt; const int rc = report_route(d, out_type, rt);
+  return rc ? rc : rt.kind == kFusedRaster && rt.plain;
+}
 
 // ------------------------------------------------------------------------------------------
 // A region of ipk_pipeline_run's result (a viewer's viewport, one tile of a tiled render)
@@ -2082,7 +2135,9 @@ namespace {
 // k_fused_resample computes it.  preview = 1 (windowed too), where allow_fused has IPK_FUSED_WINDOW_PREVIEWS beside IPK_FUSED_ON: a staged frame whose
 // gofloat + demosaic is the one scaling pass (gofloat_demosaic_one_pass) and whose OpRotateCrop is a no-op -- everything behind that pass is point-wise
 // or OpTransform's permutation, so the rectangle is taken of the n.dw x n.dh preview, the pass runs as a window launch and run_tail finishes the
-// rectangle.  Every other route: windowed = 0, the region is cut from the whole result
+// rectangle.  On kFusedRaster where allow_fused has IPK_FUSED_PLAIN beside IPK_FUSED_ON and the region has at least 256 pixels (the launch's floor): the
+// rectangle of the cropped frame, which ipk_plain_to_srgb computes from its own samples alone (point-wise: no halo).  Every other route: windowed = 0, the
+// region is cut from the whole result
 struct RegionPlan { int windowed, preview; ipk::ResampleWindow win; };
 bool windows_preview(const ipk_pipeline_desc *d, const Negotiated &n, const Route &rt) {
   const int both = IPK_FUSED_ON | IPK_FUSED_WINDOW_PREVIEWS;
@@ -2097,7 +2152,8 @@ int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, si
   choose_route(d, n, out_type, rt);
   const bool opted = (d->allow_fused & IPK_FUSED_WINDOW_REGIONS) != 0;
   pl.preview = windows_preview(d, n, rt) ? 1 : 0;
-  pl.windowed = (pl.preview || rt.kind == kFusedRaw || (opted && (rt.kind == kFusedResample || rt.kind == kFusedScaledown))) ? 1 : 0;
+  pl.windowed = (pl.preview || rt.kind == kFusedRaw || (opted && (rt.kind == kFusedResample || rt.kind == kFusedScaledown)) ||
+                 (rt.kind == kFusedRaster && plain_opted(d) && w * h >= 256)) ? 1 : 0;
   if (!pl.windowed) return IPK_OK;
   bool t = false, fx = false, fy = false;
   if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
@@ -2132,6 +2188,10 @@ int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size
   if (pl.preview) {
     const ipk::ResampleFootprint f = ipk::scaled_window_footprint(n.r.width, n.r.height, n.dw, n.dh, win.row0, win.col0, win.rows, win.cols);
     *src_x = n.r.x + f.x; *src_y = n.r.y + f.y; *src_w = f.w; *src_h = f.h;
+    return 1;
+  }
+  if (rt.kind == kFusedRaster) {                                  // point-wise from the sensor samples: the rectangle itself, in sensor coordinates
+    *src_x = n.r.x + win.col0; *src_y = n.r.y + win.row0; *src_w = win.cols; *src_h = win.rows;
     return 1;
   }
   if (rt.kind != kFusedRaw) {

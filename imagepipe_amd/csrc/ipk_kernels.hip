@@ -1564,11 +1564,24 @@ struct FusedArgs {
   const Q8Entry *gam_q8;      // gamma + output8bit as 8192 {k, threshold} steps (ipk_device.hpp Q8Entry): the 8-bit-output variants' LDS image
   const float *gen_cells;     // generic-CFA mode: gen_pw*gen_ph cells of 36 floats (ipk_host.hpp Cfa::gen_cells), else null
   uint32_t gen_pw, gen_ph;    // pattern width / height (both divide 48)
+  union {
   int gen_check;              // generic-CFA mode, u16 sources: 1 when the host could not show that every normalised sample is ordinary
+  int plain_levels;           // k_raster_chain<uint16_t> alone, which reads none of the mosaic fields (ipk_plain_to_srgb; wave-uniform, host-set, 0 on every other
+                              // launch): the sample mode -- 0 raster (input16bit), 1 three-sample raw, 2 monochrome raw: min((s - min) / range, 1) on min0 / range0
+                              // (channel 0, and the monochrome sample) and plain_lv (channels 1, 2)
+  };
   int px_guard;               // 0: u16 source with host-checked levels and parameters -> the variant without per-pixel input guards
+  union {
   int ori;                    // ROT variants: the orientation (ipk_orientation) whose rotated space this launch works in
+  int plain_rect;             // k_raster_chain<uint8_t | uint16_t> alone (as plain_levels): 1 = rectangle mode -- src is the first sample of a W-pixel-wide rectangle
+                              // inside an image whose rows are owidth pixels of 3 (plain_levels 2: 1) samples apart; the walk stays flat over the packed output,
+                              // only a pixel's source address changes
+  };
+  union {
   int roles[4];               // ROT variants: demosaic role (0 R, 1 G on the R row, 2 G on the B row, 3 B) of the rotated-space pixel with
                               // parities (row & 1, column & 1) -> roles[2 * (row & 1) + (column & 1)]
+  float plain_lv[4];          // plain_levels 1: {blacklevels[1], whitelevels[1] - blacklevels[1], blacklevels[2], whitelevels[2] - blacklevels[2]}
+  };
   SplineDev spline;
   int four;                   // generic-CFA mode, the CM = 0 whole-frame and window variants: 1 = the filter has a fourth colour (RGBE ...): every pixel's
                               // demosaic takes the literal form with a fourth bin and its point-wise stages the literal form, which keeps E.  Wave-uniform,
@@ -3302,6 +3315,64 @@ struct __attribute__((packed, aligned(1))) rgb8x4 { uint32_t w[3]; };
 struct __attribute__((packed, aligned(2))) rgb16x4 { uint32_t w[6]; };
 struct Rgbe32 { float4 v; };            // SrcT tag: the source is a 4-channel f32 OpBuffer (demosaic's / gofloat's RGBE pixels), not raster bytes -- the staged
                                         // pipeline's tolab..gamma + quantisation in one pass when the caller wants 8 or 16 bits (ipk_pointwise_chain_out)
+// The two runtime modes of the uint8_t / uint16_t kernels (FusedArgs::plain_rect, ::plain_levels), for the four pixels i0 .. i0 + 3 of the packed output:
+//   rectangle  pixel i lies in row i / W, column i - row * W of the rectangle, whose first sample is src and whose rows are owidth pixels apart.  A
+//              lane's four pixels can lie in four rows (W = 1, 2, 3), so each is addressed and loaded on its own, with element-aligned loads that
+//              touch the pixel's own samples and nothing else.  Flat (plain_rect 0) the pixel index is the source index
+//   levels     1: a three-sample raw's pixel, min((s[c] - min[c]) / range[c], 1) per channel (gofloat.rs:109-120, k_gofloat_rgb's expression);
+//              2: a monochrome raw's, one sample per pixel, (v, v, v) with v = min((s - min[0]) / range[0], 1) (gofloat.rs:95-108, k_gofloat_mono's).
+//              The divisions are true divisions, values below black stay negative, and the fourth channel is +0.0 as both staged kernels write it --
+//              which is what the fast point-wise form asks of its producers.  0: the raster's samples (s_expand / input16bit)
+template <typename SrcT>
+__device__ __forceinline__ void plain_load4(const FusedArgs &a, const SrcT *__restrict__ src, const float *__restrict__ s_expand, uint64_t i0, float4 (&px)[4]) {
+  [[maybe_unused]] const float lv_min[3] = {a.min0, a.plain_lv[0], a.plain_lv[2]};
+  [[maybe_unused]] const float lv_range[3] = {a.range0, a.plain_lv[1], a.plain_lv[3]};                 // (the raw modes read the two)
+  if constexpr (sizeof(SrcT) == 2) {
+    if (!a.plain_rect) {                                               // flat raw levels: the lane's 4 (mono) or 12 samples as one element-aligned grouped load
+      float e[12];
+      if (a.plain_levels == 2) {
+        const us4u t = *reinterpret_cast<const us4u *>(src + i0);
+        const float m = a.min0, r = a.range0;
+        e[0] = rs_min(((float)t.x - m) / r, 1.0f); e[1] = rs_min(((float)t.y - m) / r, 1.0f);
+        e[2] = rs_min(((float)t.z - m) / r, 1.0f); e[3] = rs_min(((float)t.w - m) / r, 1.0f);
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) px[j] = make_float4(e[j], e[j], e[j], 0.0f);
+      } else {
+        const rgb16x4 t = *reinterpret_cast<const rgb16x4 *>(src + i0 * 3);
+        #pragma unroll
+        for (int k = 0; k < 12; ++k) e[k] = rs_min(((float)(uint16_t)((t.w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu) - lv_min[k % 3]) / lv_range[k % 3], 1.0f);
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) px[j] = make_float4(e[3 * j], e[3 * j + 1], e[3 * j + 2], 0.0f);
+      }
+      return;
+    }
+  }
+  const uint32_t w = a.W;                                              // rectangle mode from here on (a flat launch without levels is not `plain`)
+  uint64_t row = i0 / w;
+  uint32_t col = (uint32_t)(i0 - row * w);
+  #pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint64_t p = row * a.owidth + col;                           // the pixel's index in the source image, counted from src
+    if constexpr (sizeof(SrcT) == 1) {
+      const uint8_t *s = reinterpret_cast<const uint8_t *>(src) + p * 3;
+      px[j] = make_float4(s_expand[s[0]], s_expand[s[1]], s_expand[s[2]], 0.0f);
+    } else {
+      const uint16_t *s = reinterpret_cast<const uint16_t *>(src);
+      if (a.plain_levels == 2) {
+        const float v = rs_min(((float)s[p] - a.min0) / a.range0, 1.0f);
+        px[j] = make_float4(v, v, v, 0.0f);
+      } else if (a.plain_levels == 1) {
+        s += p * 3;
+        px[j] = make_float4(rs_min(((float)s[0] - lv_min[0]) / lv_range[0], 1.0f), rs_min(((float)s[1] - lv_min[1]) / lv_range[1], 1.0f),
+                            rs_min(((float)s[2] - lv_min[2]) / lv_range[2], 1.0f), 0.0f);
+      } else {
+        s += p * 3;
+        px[j] = make_float4(input16bit(s[0]), input16bit(s[1]), input16bit(s[2]), 0.0f);
+      }
+    }
+    if (++col == w) { col = 0; ++row; }
+  }
+}
 template <typename SrcT, int OUT>
 __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npix, const LutPair *__restrict__ gamma_reverse) {
   constexpr bool RGBE = std::is_same<SrcT, Rgbe32>::value;
@@ -3330,6 +3401,7 @@ __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npi
   const uint64_t nchunks = (npix + 255) / 256;
   uint32_t *stg = s_stage + (threadIdx.x >> 6) * STG;
   const SrcT *src = reinterpret_cast<const SrcT *>(a.src);
+  const bool plain = !RGBE && (a.plain_rect | a.plain_levels) != 0;   // ipk_plain_to_srgb's modes: off on every launch of ipk_raster_to_srgb / ipk_pointwise_chain_out
   for (uint64_t chunk = wave; chunk < nchunks; chunk += nwaves) {
     const uint64_t base = min(chunk * 256, npix - 256);                // the last chunk ends at the last pixel
     float4 px[4];
@@ -3337,6 +3409,9 @@ __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npi
       const float *p4 = reinterpret_cast<const float *>(a.src) + (base + 4u * lane) * 4;
       #pragma unroll
       for (int j = 0; j < 4; ++j) px[j] = ld_stream4(p4 + 4 * j);
+    } else
+    if (IPK_RARE(plain)) {                                             // rectangle and / or raw levels (wave-uniform): the lane's four pixels one by one
+      plain_load4(a, src, s_expand, base + 4u * lane, px);
     } else
     if (sizeof(SrcT) == 1) {
       const rgb8x4 t = *reinterpret_cast<const rgb8x4 *>(src + (base + 4u * lane) * 3);
@@ -3375,12 +3450,20 @@ __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npi
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
 }
+// the log tag of a k_raster_chain<uint8_t | uint16_t> launch: fast_ok alone, as ever, on launches that use neither mode (the log keeps the pointer: literals only)
+static const char *raster_tag(const FusedArgs &a) {
+  static const char *const tags[2][2][3] = {
+    {{"fast_ok=0", "fast_ok=0,levels=1", "fast_ok=0,levels=2"}, {"fast_ok=0,rect=1", "fast_ok=0,rect=1,levels=1", "fast_ok=0,rect=1,levels=2"}},
+    {{"fast_ok=1", "fast_ok=1,levels=1", "fast_ok=1,levels=2"}, {"fast_ok=1,rect=1", "fast_ok=1,rect=1,levels=1", "fast_ok=1,rect=1,levels=2"}}};
+  return tags[a.fast_ok ? 1 : 0][a.plain_rect ? 1 : 0][a.plain_levels];
+}
 template <typename SrcT>
 static void launch_raster_t(const FusedArgs &a, size_t npix, int out_type, const void *gamma_reverse, unsigned blocks, hipStream_t s) {
   const LutPair *gr = reinterpret_cast<const LutPair *>(gamma_reverse);
-  if (out_type == 0) IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<SrcT, 0>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
-  else if (out_type == 1) IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<SrcT, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
-  else IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<SrcT, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
+  const char *tag = raster_tag(a);
+  if (out_type == 0) IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 0>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
+  else if (out_type == 1) IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
+  else IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
 }
 // OpToLab..OpGamma + output8bit / output16bit over a 4-channel f32 OpBuffer in one pass (f.out_type 1 or 2; npix >= 256)
 int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s) {
@@ -3394,10 +3477,19 @@ int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s) {
   else IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<Rgbe32, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
   return 0;
 }
-int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const void *gamma_reverse_pairs, hipStream_t s) {
+int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const void *gamma_reverse_pairs, hipStream_t s, const PlainSource *plain) {
   if (npix < 256) return -1;
   FusedArgs a = chain_args(f);
   a.gam_q8 = reinterpret_cast<const Q8Entry *>(f.gam_q8);
+  if (plain) {
+    if (plain->levels < 0 || plain->levels > 2 || (plain->levels != 0 && !src_is_u16) || plain->width == 0 || plain->width > plain->owidth ||
+        plain->width > 0xFFFFFFFFull || npix % plain->width != 0) return -1;
+    a.plain_levels = plain->levels;
+    a.plain_rect = plain->width != plain->owidth;                          // full-width rows follow each other in memory: the flat walk from f.src
+    a.W = (uint32_t)plain->width; a.owidth = plain->owidth;
+    a.min0 = plain->black[0]; a.range0 = plain->white[0] - plain->black[0];                                                 // gofloat.rs:86-89
+    for (int c = 1; c < 3; ++c) { a.plain_lv[2 * c - 2] = plain->black[c]; a.plain_lv[2 * c - 1] = plain->white[c] - plain->black[c]; }
+  }
   const size_t chunks = (npix + 255) / 256;
   const unsigned cap = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = std::max(1u, (unsigned)std::min<size_t>(cap, (chunks + 15) / 16));

@@ -45,6 +45,9 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows; their window launches,
 // ipk_raw_scaled_demosaic_window, append win=1: [norm_fast=,...,xcd=,win=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form);
+// k_raster_chain's launches by ipk_plain_to_srgb append rect=1 in rectangle mode (a rectangle narrower than the source's pitch) and levels=1 / levels=2
+// in the three-sample / monochrome raw sample modes, in that order: [fast_ok=,rect=1], [fast_ok=,levels=2], [fast_ok=,rect=1,levels=1] -- launches
+// that use neither mode (ipk_raster_to_srgb, ipk_pointwise_chain_out, a full-width raster rectangle) carry [fast_ok=] and nothing else;
 // k_fused_resample's axis-aligned mode (ipk_raw_to_srgb_scaled) [fast_ok=,axis=1]; k_fused_resample's window launches (launch_fused_resample with a
 // ResampleWindow: ipk_raw_to_srgb_resampled_window / _scaled_window, regions under IPK_FUSED_WINDOW_REGIONS) append win=1: [fast_ok=,win=1] /
 // [fast_ok=,axis=1,win=1] -- whole-frame launches never carry the key; the generic-CFA runtime-flag variants of k_fused_bayer /
@@ -140,7 +143,13 @@ int launch_tolab_fast(const FusedLaunch &f, size_t npix, hipStream_t s);   // Op
 // OpToLab..OpGamma + output8bit / output16bit in one pass over a 4-channel f32 buffer (f.out_type 1 / 2, f.gam_q8 set; npix >= 256): -1 otherwise
 int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s);
 // run_other + OpToLab..OpGamma + quantisation in one pass over an RGB8 / RGB16 raster (npix >= 256; f.out_type selects the output)
-int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const void *gamma_reverse_pairs, hipStream_t s);
+// plain (optional; ipk_plain_to_srgb): the launch covers a width-pixel-wide rectangle of npix pixels whose first sample is f.src, inside an image whose rows
+// are owidth pixels apart, and f.dst holds its npix * 3 packed samples.  levels: 0 the raster's samples; 1 a three-sample u16 raw, each channel
+// min((s - black[c]) / (white[c] - black[c]), 1); 2 a monochrome u16 raw, ONE sample per pixel (owidth and width still count pixels) on black[0] /
+// white[0], the pixel (v, v, v, +0.0).  width == owidth is the flat walk from f.src.  Both are runtime modes of the same six kernels; f32 raws have no
+// instantiation to ride on and stay on the staged kernels.  -1 (nothing launched) for levels on a u8 source, npix no multiple of width, width > owidth
+struct PlainSource { int levels; size_t owidth, width; float black[3], white[3]; };
+int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const void *gamma_reverse_pairs, hipStream_t s, const PlainSource *plain = nullptr);
 
 // exhaustive on-device checks of the arithmetic shortcuts (see ipk_kernels.hip "Self-test kernels")
 int launch_selftest_cdiv(float c, int variant, unsigned lo_bits, unsigned hi_bits, int include_special, void *out_dev, hipStream_t s);

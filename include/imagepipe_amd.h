@@ -447,6 +447,23 @@ IPK_API int ipk_pointwise_chain_out(const float *src4, size_t width, size_t heig
 IPK_API int ipk_raster_to_srgb(const void *src, int src_type, size_t width, size_t height, const float *wb_coeffs,
                                const float *cam_to_xyz_normalized, float exposure, const float *points, int npoints, int linear,
                                int out_type, void *dst, void *stream);
+/* The same launch for every source whose OpDemosaic is a pass-through (a 4-channel buffer, src/ops/demosaic.rs:41-43), over a rectangle of it.
+ * kind says how OpGoFloat reads a pixel: IPK_PLAIN_RASTER, run_other on an RGB8 / RGB16 raster as above (black4 / white4 are ignored and may be NULL);
+ * IPK_PLAIN_RGB, a three-sample raw (cpp == 3: linear DNG, sRAW), min((s[c] - black4[c]) / (white4[c] - black4[c]), 1) per channel; IPK_PLAIN_MONO, a
+ * monochrome raw (cpp == 1 without a filter), ONE sample per pixel on black4[0] / white4[0], the pixel (v, v, v) and the point-wise parameters those
+ * of a monochrome buffer (the sRGB matrix, unit multipliers: wb_coeffs and cam_to_xyz_normalized must be given but are not read).  The divisions are
+ * true divisions, values below black stay negative and the fourth channel is +0.0: bit for bit what ipk_gofloat_rgb_u16 / ipk_gofloat_mono_u16
+ * followed by ipk_pointwise_chain (+ ipk_output8bit / 16bit) give.  RGB and MONO take IPK_SRC_U16 sources only.  IPK_SRC_F32 is refused with
+ * IPK_ERR_UNSUPPORTED and nothing written: the launch is a runtime mode of the RGB8 / RGB16 raster kernels (k_raster_chain<uint8_t | uint16_t>),
+ * there is no f32 instantiation for it to ride on, and f32 mono / three-sample raws therefore stay on the staged ops, bit for bit as they were.
+ * The source is owidth pixels wide (3 samples per pixel, 1 for MONO); the launch covers columns [x, x + width) and rows [y, y + height) of it
+ * (x + width <= owidth; the caller vouches for the rows) and reads no sample outside that rectangle; dst receives width*height*3 packed samples of
+ * out_type and nothing else is written.  src and dst need the alignment of their element type only.  At least 256 pixels in the rectangle
+ * (IPK_ERR_UNSUPPORTED below, as ipk_raster_to_srgb).  A rectangle as wide as the source (any y) runs exactly ipk_raster_to_srgb's flat walk. */
+typedef enum { IPK_PLAIN_RASTER = 0, IPK_PLAIN_RGB = 1, IPK_PLAIN_MONO = 2 } ipk_plain_kind;
+IPK_API int ipk_plain_to_srgb(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                              const float *black4, const float *white4, const float *wb_coeffs, const float *cam_to_xyz_normalized,
+                              float exposure, const float *points, int npoints, int linear, int out_type, void *dst, void *stream);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Pipeline driver: Pipeline::run / output_8bit / output_16bit for one source                */
@@ -485,7 +502,11 @@ typedef struct {
                                       gofloat + demosaic pass (ipk_raw_scaled_demosaic_window / ipk_raster_scale_down_window) followed by the point-wise ops on
                                       that rectangle.  Same contract again.  The bit acts only together with bit 0: allow_fused = 8 still means "on" for every
                                       whole-frame route (any non-zero value does), but regions of previews are then cut from the whole result, as without the
-                                      bit.  Bit 2 does not window these frames, with or without bit 3. */
+                                      bit.  Bit 2 does not window these frames, with or without bit 3.
+                                      Bit 4 (IPK_FUSED_PLAIN = 16), beside IPK_FUSED_ON as well: the frames whose OpDemosaic is a pass-through -- RGB8 / RGB16
+                                      rasters with OpGoFloat crops, u16 monochrome and u16 three-sample raws -- run as the one launch ipk_plain_to_srgb where
+                                      ipk_pipeline_fuses_plain says so, and regions of every frame on that launch (the uncropped rasters it always took
+                                      included) are windowed.  Same contract: no hash, no result.  Without bit 0 it does nothing. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -505,13 +526,24 @@ typedef enum {
   IPK_FUSED_ON = 1,                /* the one-launch routes where legal (any non-zero value means this) */
   IPK_FUSED_FOUR_COLOUR = 2,       /* bit 1: four-colour filters take the one-launch route too */
   IPK_FUSED_WINDOW_REGIONS = 4,    /* bit 2: regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch */
-  IPK_FUSED_WINDOW_PREVIEWS = 8    /* bit 3 (beside bit 0): regions of downscaled previews (OpDemosaic's scaled_demosaic branch, scale >= minscale, and rasters
+  IPK_FUSED_WINDOW_PREVIEWS = 8,   /* bit 3 (beside bit 0): regions of downscaled previews (OpDemosaic's scaled_demosaic branch, scale >= minscale, and rasters
                                       under a size limit) run as a window of the scaling pass, where ipk_pipeline_windows_preview says so.
                                       Measured (profiles/r13_preview_regions.txt; 50 MP X-Trans -> 2160x1440 | 24 MP RGGB -> 1500x1000, u8, without -> with
                                       the bit): device form, 1/16 of the area 0.096 -> 0.032 | 0.063 -> 0.029 ms, 1/4 0.095 -> 0.045 | 0.068 -> 0.034 ms, the
                                       whole area 0.098 -> 0.090 | 0.068 -> 0.059 ms (the copy is saved); host form, 1/16 1.86 -> 0.17 ms (99.5 -> 6.3 MB
                                       uploaded) | 0.92 -> 0.11 ms (48 -> 3.1 MB), 1/4 1.89 -> 0.55 | 0.94 -> 0.29 ms.  NOT faster: a whole-area region
                                       through the host form uploads the whole frame either way, 2.016 -> 2.019 | 1.002 -> 1.001 ms */
+  IPK_FUSED_PLAIN = 16             /* bit 4 (beside bit 0): cropped RGB8 / RGB16 rasters and u16 monochrome / three-sample raws run as one launch
+                                      (ipk_plain_to_srgb) where ipk_pipeline_fuses_plain says so, and regions of every frame on the raster launch are
+                                      windowed.  f32 monochrome / three-sample raws stay staged (no kernel instantiation carries them).
+                                      Measured (profiles/r14_plain_route.txt; 6000x4000 noise, without -> with the bit): whole frames, mono u16 -> u8
+                                      0.253 -> 0.138 ms, -> f32 0.225 -> 0.144 ms; cpp3 u16 -> u8 0.268 -> 0.175 ms, -> f32 0.260 -> 0.175 ms; RGB8 with 5 %
+                                      crops per side -> u8 0.229 -> 0.092 ms.  Regions to u8 (RGB8 | mono u16), device form: 1/16 of the area 0.123 -> 0.017 |
+                                      0.272 -> 0.020 ms, 1/4 0.124 -> 0.036 | 0.273 -> 0.047 ms, the whole area 0.139 -> 0.108 | 0.292 -> 0.140 ms; host form:
+                                      1/16 1.49 -> 0.20 ms (72 -> 4.5 MB uploaded) | 1.21 -> 0.18 ms (48 -> 3.1 MB), 1/4 1.72 -> 0.70 | 1.45 -> 0.60 ms.  NOT
+                                      faster beyond the noise: a whole-area region through the host form uploads the whole frame either way, 2.77 -> 2.66 |
+                                      2.41 -> 2.27 ms.  The cost to launches that use neither mode (the kernels test for them once per 256-pixel chunk):
+                                      ipk_raster_to_srgb, RGB8 -> u8 at 24 MP, parent 0.1269 ms (its spread 0.0033) -> 0.1283 ms */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -565,6 +597,13 @@ IPK_API int ipk_pipeline_fuses_four_colour(const ipk_pipeline_desc *d, int out_t
  * active rotatecrop behind a scaling demosaic, 1 < scale < minscale (IPK_FUSED_WINDOW_REGIONS' ground), full-size frames (windowed whatever the
  * bits); a negative error code for a descriptor ipk_pipeline_sizes refuses.  Whole-frame drivers do not depend on the bit.  No GPU needed. */
 IPK_API int ipk_pipeline_windows_preview(const ipk_pipeline_desc *d, int out_type);
+/* Does ipk_pipeline_run (and the batch, host and multi-device drivers; the cached driver fills its cache from the staged ops) run this descriptor's
+ * whole frame as the one launch ipk_plain_to_srgb BECAUSE of IPK_FUSED_PLAIN?  1 when d->allow_fused has IPK_FUSED_ON and IPK_FUSED_PLAIN set, the frame
+ * does not take the fast path, OpRotateCrop is a no-op, OpDemosaic does not scale (scale <= 1), the cropped rectangle has at least 256 pixels, and the
+ * source is an RGB8 / RGB16 raster WITH OpGoFloat crops, a u16 raw with cpp == 3, or a u16 raw with cpp == 1 and no filter (is_cfa == 0).  0 otherwise
+ * -- uncropped rasters included: their one launch does not depend on the bit (only their regions do) --, f32 monochrome / three-sample raws
+ * (staged: the launch has no f32 form), mosaics; a negative error code for a descriptor ipk_pipeline_sizes refuses.  No GPU needed. */
+IPK_API int ipk_pipeline_fuses_plain(const ipk_pipeline_desc *d, int out_type);
 /* do_timing! (src/pipeline.rs:68-80: the reference logs the wall time of every op of Pipeline::run): ipk_timing_begin arms the calling
  * thread, the following ipk_pipeline_run call(s) on it bracket every stage they enqueue with hipEvents on their stream, ipk_timing_end
  * waits for the last one and returns the stages in execution order under the reference's op names ("gofloat", "demosaic", "rotatecrop",
@@ -590,7 +629,11 @@ IPK_API int ipk_host_pipeline_run(const ipk_pipeline_desc *d, const void *src, v
  * With IPK_FUSED_WINDOW_PREVIEWS (and IPK_FUSED_ON) in allow_fused the downscaled previews (ipk_pipeline_windows_preview answers 1) are windowed too:
  * the region is mapped back through OpTransform to a rectangle of the demosaic_w x demosaic_h preview, the scaling gofloat + demosaic pass runs over
  * that rectangle only, the point-wise ops, the quantisation and OpTransform's permutation follow on the rectangle, and the window reported is
- * ipk_scaled_window_footprint plus the crop offset (never empty).  Without the bit they answer 0. */
+ * ipk_scaled_window_footprint plus the crop offset (never empty).  Without the bit they answer 0.
+ * With IPK_FUSED_PLAIN (and IPK_FUSED_ON) in allow_fused every frame on the raster launch -- uncropped and cropped RGB8 / RGB16 rasters off the fast
+ * path, u16 monochrome and three-sample raws; OpRotateCrop a no-op, scale <= 1 -- is windowed: the region is mapped back through OpTransform to a rectangle of
+ * the cropped frame, ipk_plain_to_srgb runs over that rectangle, and the window reported is the rectangle itself in sensor coordinates (the ops are
+ * point-wise: no halo, never empty).  A region of fewer than 256 pixels answers 0 and is cut from the whole result.  Without the bit they answer 0. */
 IPK_API int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h,
                                 size_t *src_x, size_t *src_y, size_t *src_w, size_t *src_h);
 /* The region from the DEVICE source ipk_pipeline_run takes (the whole sensor frame) into the DEVICE buffer dst, enqueued on `stream`.

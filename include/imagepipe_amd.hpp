@@ -301,6 +301,7 @@ class Pipeline {
   bool fuse_scaledown = false;             // ipk_pipeline_desc.fuse_scaledown: OpDemosaic's full + scale_down_opbuf branch inside the one launch where fuses_scaledown() says so
   bool fuse_four_colour = false;           // ipk_pipeline_desc.allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR): a filter with a fourth colour (RGBE ...) on the one-launch route where fuses_four_colour() says so
   bool window_regions = false;             // ipk_pipeline_desc.allow_fused bit 2 (IPK_FUSED_WINDOW_REGIONS): regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch
+  bool fuse_plain = false;                 // ipk_pipeline_desc.allow_fused bit 4 (IPK_FUSED_PLAIN): cropped RGB8 / RGB16 rasters and u16 monochrome / three-sample raws as one launch where fuses_plain() says so; regions of every frame on the raster launch windowed
   bool window_previews = false;            // ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
   int last_ops_run = 0xFF;                 // bit i: op i executed in the last run (0 = served from the cache)
   uint64_t source_id = 0;                  // identifies the frame inside a shared PipelineCache (extension, see the C header)
@@ -383,6 +384,7 @@ class Pipeline {
     if (fuse_four_colour && d.allow_fused) d.allow_fused |= IPK_FUSED_FOUR_COLOUR;
     if (window_regions && d.allow_fused) d.allow_fused |= IPK_FUSED_WINDOW_REGIONS;
     if (window_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_WINDOW_PREVIEWS;
+    if (fuse_plain && d.allow_fused) d.allow_fused |= IPK_FUSED_PLAIN;
     return d;
   }
   // does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop; no GPU needed)?  out_type: IPK_OUT_*
@@ -393,6 +395,8 @@ class Pipeline {
   bool fuses_four_colour(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_fuses_four_colour(&d, out_type) == 1; }
   // does a region of this downscaled preview run as a window of its scaling pass (ipk_pipeline_windows_preview)?
   bool windows_preview(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_windows_preview(&d, out_type) == 1; }
+  // does this cropped raster / u16 monochrome or three-sample raw run as the one launch ipk_plain_to_srgb (ipk_pipeline_fuses_plain)?
+  bool fuses_plain(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_fuses_plain(&d, out_type) == 1; }
  private:
   explicit Pipeline(ImageSource img) : globals{std::move(img), PipelineSettings()}, ops(globals.image) {}
   std::pair<size_t, size_t> final_size() const {
