@@ -747,16 +747,34 @@ class Pipeline:
                         "ipk_pipeline_region")
         return rc, (sx.value, sy.value, sw.value, sh.value)
 
-    def run_region(self, x, y, w, h, out_type=OUT_F32, out: Optional[torch.Tensor] = None):
+    def region_gather(self, x, y, w, h, out_type=OUT_F32):
+        """Where the region (x, y, w, h) of the result lies in the buffer OpRotateCrop hands to OpToLab (ipk_pipeline_region_gather, host-only):
+        ((buf_w, buf_h), base, x_step, y_step) -- region pixel (column i, row j) is pixel base + i * x_step + j * y_step of that buffer."""
+        d = self.desc()
+        bw, bh = C.c_size_t(), C.c_size_t()
+        base, xs, ys = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(lib().ipk_pipeline_region_gather(C.byref(d), out_type, x, y, w, h, C.byref(bw), C.byref(bh), C.byref(base), C.byref(xs), C.byref(ys)),
+                   "ipk_pipeline_region_gather")
+        return (bw.value, bh.value), base.value, xs.value, ys.value
+
+    def run_region(self, x, y, w, h, out_type=OUT_F32, out: Optional[torch.Tensor] = None, cache: Optional[PipelineCache] = None):
         """Columns [x, x+w) and rows [y, y+h) of what run() / output_8bit() / output_16bit() return, without the rest of the frame
-        (ipk_pipeline_run_region): an h*w*3 device tensor of the output type; sets last_region_windowed."""
+        (ipk_pipeline_run_region): an h*w*3 device tensor of the output type; sets last_region_windowed.
+        With a cache (ipk_pipeline_run_cached_region): the cache is brought up to the buffer behind OpRotateCrop and one launch over the region
+        computes the rest, so an edit of the exposure, the curve, the white balance or the orientation costs that launch alone; sets last_ops_run too."""
         d = self.desc()
         dt = {OUT_F32: torch.float32, OUT_U8: torch.uint8, OUT_U16: torch.int16}[out_type]
         if out is None:
             out = torch.empty(w * h * 3, dtype=dt, device="cuda")
         win = C.c_int(0)
-        _lib.check(lib().ipk_pipeline_run_region(C.byref(d), _ptr(self.globals.image.data), x, y, w, h, _ptr(out), out_type, C.byref(win), _stream()),
-                   "ipk_pipeline_run_region")
+        if cache is None:
+            _lib.check(lib().ipk_pipeline_run_region(C.byref(d), _ptr(self.globals.image.data), x, y, w, h, _ptr(out), out_type, C.byref(win), _stream()),
+                       "ipk_pipeline_run_region")
+        else:
+            mask = C.c_int(0)
+            _lib.check(lib().ipk_pipeline_run_cached_region(C.byref(d), _ptr(self.globals.image.data), int(self.source_id), cache.handle, x, y, w, h,
+                                                            _ptr(out), out_type, C.byref(mask), C.byref(win), _stream()), "ipk_pipeline_run_cached_region")
+            self.last_ops_run = mask.value
         self.last_region_windowed = bool(win.value)
         return out
 

@@ -240,6 +240,10 @@ SIGNATURES = {
     "ipk_comm_wait": (C.c_int, [_vp, _vp]),
     "ipk_comm_selftest": (C.c_int, [_vp]),
     "ipk_pipeline_run_cached": (C.c_int, [C.POINTER(PipelineDesc), _vp, C.c_uint64, _vp, C.c_int, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
+    "ipk_pipeline_region_gather": (C.c_int, [C.POINTER(PipelineDesc), C.c_int, _sz, _sz, _sz, _sz, _szp, _szp,
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ipk_pipeline_run_cached_region": (C.c_int, [C.POINTER(PipelineDesc), _vp, C.c_uint64, _vp, _sz, _sz, _sz, _sz, _vp, C.c_int,
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
 }
 
 _lib = None

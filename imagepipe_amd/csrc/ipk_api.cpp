@@ -2143,26 +2143,58 @@ bool windows_preview(const ipk_pipeline_desc *d, const Negotiated &n, const Rout
   const int both = IPK_FUSED_ON | IPK_FUSED_WINDOW_PREVIEWS;
   return (d->allow_fused & both) == both && rt.kind == kStaged && gofloat_demosaic_one_pass(d, n) && n.rc.noop();
 }
-int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n, Route &rt, RegionPlan &pl) {
+// the descriptor's negotiation and the region against its result: what every region entry point checks first
+int negotiate_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n) {
   int rc = negotiate(d, out_type, n); if (rc) return rc;
   rc = validate_desc(d, out_type, kCheckCurve); if (rc) return rc;
   if (n.fw == 0 || n.fh == 0) return fail(IPK_ERR_INVALID, "the result is empty");
   if (w == 0 || h == 0 || x > n.fw || w > n.fw - x || y > n.fh || h > n.fh - y)
     return fail(IPK_ERR_INVALID, "region (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", x, y, w, h, n.fw, n.fh);
+  return IPK_OK;
+}
+// The rectangle of the W x H image in front of OpTransform that region (x, y, w, h) of the result comes from, and the flips that take one to the other.
+// rotate_buffer's walk (transform.rs:102-128): result pixel (ox, oy) is source pixel (fx ? W-1-u : u, fy ? H-1-v : v) with (u, v) = t ? (oy, ox) : (ox, oy)
+int region_window(const Negotiated &n, size_t W, size_t H, size_t x, size_t y, size_t w, size_t h, ipk::ResampleWindow &win, bool &t, bool &fx, bool &fy) {
+  t = fx = fy = false;
+  if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
+  if ((t ? H : W) != n.fw || (t ? W : H) != n.fh) return fail(IPK_ERR_INVALID, "internal: fused result %zux%zu, negotiated %zux%zu", W, H, n.fw, n.fh);
+  const size_t u0 = t ? y : x, un = t ? h : w, v0 = t ? x : y, vn = t ? w : h;
+  win.col0 = fx ? W - u0 - un : u0; win.cols = un;
+  win.row0 = fy ? H - v0 - vn : v0; win.rows = vn;
+  return IPK_OK;
+}
+int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n, Route &rt, RegionPlan &pl) {
+  int rc = negotiate_region(d, out_type, x, y, w, h, n); if (rc) return rc;
   choose_route(d, n, out_type, rt);
   const bool opted = (d->allow_fused & IPK_FUSED_WINDOW_REGIONS) != 0;
   pl.preview = windows_preview(d, n, rt) ? 1 : 0;
   pl.windowed = (pl.preview || rt.kind == kFusedRaw || (opted && (rt.kind == kFusedResample || rt.kind == kFusedScaledown)) ||
                  (rt.kind == kFusedRaster && plain_opted(d) && w * h >= 256)) ? 1 : 0;
   if (!pl.windowed) return IPK_OK;
+  bool t, fx, fy;
+  return region_window(n, pl.preview ? n.dw : rt.pw, pl.preview ? n.dh : rt.ph, x, y, w, h, pl.win, t, fx, fy);
+}
+// Where region (x, y, w, h) of the result lies in the bw x bh buffer Pipeline::run hands from OpRotateCrop to OpToLab: region pixel (i, j) is the buffer's
+// pixel g.base + i * g.x_step + j * g.y_step.  The buffer's size is the one whose transform is the negotiated result (check_produced's rule: what the
+// ops produce is held against n.fw x n.fh), not the forward fold's
+// win: the unrotated rectangle of the buffer the region comes from; transposed: the orientation swaps rows and columns (g.x_step is then +-bw)
+struct RegionGather { size_t bw, bh; ipk::GatherSource g; ipk::ResampleWindow win; bool transposed; };
+int region_gather(const Negotiated &n, size_t x, size_t y, size_t w, size_t h, RegionGather &rg) {
   bool t = false, fx = false, fy = false;
   if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
-  const size_t W = pl.preview ? n.dw : rt.pw, H = pl.preview ? n.dh : rt.ph;
-  if ((t ? H : W) != n.fw || (t ? W : H) != n.fh) return fail(IPK_ERR_INVALID, "internal: fused result %zux%zu, negotiated %zux%zu", W, H, n.fw, n.fh);
-  // rotate_buffer's walk (transform.rs:102-128): result pixel (ox, oy) is source pixel (fx ? W-1-u : u, fy ? H-1-v : v) with (u, v) = t ? (oy, ox) : (ox, oy)
-  const size_t u0 = t ? y : x, un = t ? h : w, v0 = t ? x : y, vn = t ? w : h;
-  pl.win.col0 = fx ? W - u0 - un : u0; pl.win.cols = un;
-  pl.win.row0 = fy ? H - v0 - vn : v0; pl.win.rows = vn;
+  rg.bw = t ? n.fh : n.fw; rg.bh = t ? n.fw : n.fh;
+  ipk::ResampleWindow &win = rg.win;
+  const int rc = region_window(n, rg.bw, rg.bh, x, y, w, h, win, t, fx, fy); if (rc) return rc;
+  rg.transposed = t;
+  // the region's pixel (0, 0) is the window's corner the flips name; a step along u moves one column, along v one row of the buffer
+  const int64_t W = (int64_t)rg.bw, du = fx ? -1 : 1, dv = fy ? -W : W;
+  const int64_t col = (int64_t)(fx ? win.col0 + win.cols - 1 : win.col0), row = (int64_t)(fy ? win.row0 + win.rows - 1 : win.row0);
+  rg.g.base = row * W + col;
+  rg.g.x_step = t ? dv : du; rg.g.y_step = t ? du : dv;
+  rg.g.width = w;
+  const int64_t far = rg.g.base + (int64_t)(w - 1) * rg.g.x_step + (int64_t)(h - 1) * rg.g.y_step, cnt = W * (int64_t)rg.bh;
+  const int64_t cx1 = rg.g.base + (int64_t)(w - 1) * rg.g.x_step, cy1 = rg.g.base + (int64_t)(h - 1) * rg.g.y_step;
+  for (int64_t c : {rg.g.base, far, cx1, cy1}) if (c < 0 || c >= cnt) return fail(IPK_ERR_INVALID, "internal: the region's gather leaves the %zux%zu buffer", rg.bw, rg.bh);
   return IPK_OK;
 }
 }  // namespace
@@ -2341,45 +2373,14 @@ int ipk_selftest_sha256(const void *data, size_t n, uint8_t *out32) {
   ipk::Sha256 s; s.update(data, n); const auto r = s.result(); std::memcpy(out32, r.data(), 32); return IPK_OK;
 }
 
-int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache, int out_type, void *dst,
-                            int *ops_run, int *used_fused, void *stream) {
-  REQUIRE_INIT();
-  if (!d || !src || !dst || !cache) return fail(IPK_ERR_INVALID, "null argument");
-  if (!cache->owner) cache->owner = ipk_ctx_current();                   // a cache made before ipk_init belongs to the first context that fills it
-  if (cache->owner != ipk_ctx_current()) return fail(IPK_ERR_INVALID, "the cache belongs to another context (its buffers live on that context's device)");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  int rc = validate_desc(d, out_type, kCheckCurve | kCheckFuse); if (rc) return rc;
-  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // returns before the cache is consulted (pipeline.rs:381-402), and before the negotiation
-    if (ops_run) *ops_run = 0;
-    if (used_fused) *used_fused = 0;
-    return run_fastpath(d, src, dst, out_type, stream);
-  }
-  Negotiated n; rc = negotiate(d, out_type, n); if (rc) return rc;
-  ipk::BufHash hs[8]; hash_chain(d, n, source_id, hs);
-  if (ops_run) *ops_run = 0;
-  if (used_fused) *used_fused = 0;
-  hipStream_t st = S(stream);
-
-  // the latest op whose output is memoised (pipeline.rs:352-361: every hash is looked up, the last hit wins)
-  CBufP buf; int startpos = 0;
-  for (int i = 0; i < 8; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
-  int mask = 0;
-
-  // Nothing memoised and gofloat..transform is one launch on a raw source (any orientation: run_route folds OpTransform in): cheaper on this machine
-  // than materialising seven intermediates (DESIGN.md section 3); only the final buffer enters the cache.  The buffer is f32 whatever the caller wants,
-  // so the route is asked for IPK_OUT_F32; a raster source's one launch is not taken here (its staged ops fill the cache)
-  Route rt;
-  if (startpos == 0) choose_route(d, n, IPK_OUT_F32, rt);
-  if (startpos == 0 && (rt.kind == kFusedRaw || rt.kind == kFusedResample || rt.kind == kFusedScaledown)) {
-    CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
-    rc = run_route(rt, n, src, nullptr, n.fw, n.fh, o->p, stream);
-    if (rc < 0) return rc;
-    cache->lru.put(hs[7], o, o->bytes());
-    buf = o; startpos = 8; mask = 0xFF;
-    if (used_fused) *used_fused = rc == IPK_OK;
-  }
-
-  for (int i = startpos; i < 8; ++i) {
+namespace {
+// Ops [from, to) of Pipeline::run(Some(cache)) from `buf` (op from - 1's buffer; unused for from == 0): every buffer materialised enters the cache under
+// its op's hash, a no-op stores its input under its own key, `mask` gains bit i for every op executed and `buf` ends as op to - 1's buffer.  Shared by
+// ipk_pipeline_run_cached (to = 8) and ipk_pipeline_run_cached_region (to = 3: the RGBE buffer its gather launch reads)
+int run_cached_ops(const ipk_pipeline_desc *d, const Negotiated &n, const ipk::BufHash hs[8], const void *src, ipk_cache *cache, int from, int to,
+                   CBufP &buf, int &mask, void *stream) {
+  int rc = IPK_OK;
+  for (int i = from; i < to; ++i) {
     CBufP o;
     switch (i) {
       case 0: {                                                          // gofloat
@@ -2442,6 +2443,49 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
     mask |= 1 << i;
     cache->lru.put(hs[i], buf, buf->bytes());
   }
+  return IPK_OK;
+}
+}  // namespace
+
+int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache, int out_type, void *dst,
+                            int *ops_run, int *used_fused, void *stream) {
+  REQUIRE_INIT();
+  if (!d || !src || !dst || !cache) return fail(IPK_ERR_INVALID, "null argument");
+  if (!cache->owner) cache->owner = ipk_ctx_current();                   // a cache made before ipk_init belongs to the first context that fills it
+  if (cache->owner != ipk_ctx_current()) return fail(IPK_ERR_INVALID, "the cache belongs to another context (its buffers live on that context's device)");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  int rc = validate_desc(d, out_type, kCheckCurve | kCheckFuse); if (rc) return rc;
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // returns before the cache is consulted (pipeline.rs:381-402), and before the negotiation
+    if (ops_run) *ops_run = 0;
+    if (used_fused) *used_fused = 0;
+    return run_fastpath(d, src, dst, out_type, stream);
+  }
+  Negotiated n; rc = negotiate(d, out_type, n); if (rc) return rc;
+  ipk::BufHash hs[8]; hash_chain(d, n, source_id, hs);
+  if (ops_run) *ops_run = 0;
+  if (used_fused) *used_fused = 0;
+  hipStream_t st = S(stream);
+
+  // the latest op whose output is memoised (pipeline.rs:352-361: every hash is looked up, the last hit wins)
+  CBufP buf; int startpos = 0;
+  for (int i = 0; i < 8; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
+  int mask = 0;
+
+  // Nothing memoised and gofloat..transform is one launch on a raw source (any orientation: run_route folds OpTransform in): cheaper on this machine
+  // than materialising seven intermediates (DESIGN.md section 3); only the final buffer enters the cache.  The buffer is f32 whatever the caller wants,
+  // so the route is asked for IPK_OUT_F32; a raster source's one launch is not taken here (its staged ops fill the cache)
+  Route rt;
+  if (startpos == 0) choose_route(d, n, IPK_OUT_F32, rt);
+  if (startpos == 0 && (rt.kind == kFusedRaw || rt.kind == kFusedResample || rt.kind == kFusedScaledown)) {
+    CBufP o; rc = cbuf_new(n.fw, n.fh, 3, 0, o); if (rc) return rc;
+    rc = run_route(rt, n, src, nullptr, n.fw, n.fh, o->p, stream);
+    if (rc < 0) return rc;
+    cache->lru.put(hs[7], o, o->bytes());
+    buf = o; startpos = 8; mask = 0xFF;
+    if (used_fused) *used_fused = rc == IPK_OK;
+  }
+
+  rc = run_cached_ops(d, n, hs, src, cache, startpos, 8, buf, mask, stream); if (rc < 0) return rc;
   if (ops_run) *ops_run = mask;
   rc = check_produced(n, buf->w, buf->h, buf->colors); if (rc) return rc;
   const size_t cnt = buf->w * buf->h * 3;
@@ -2449,6 +2493,111 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   else { HIPCHK(hipMemcpyAsync(dst, buf->p, cnt * sizeof(float), hipMemcpyDeviceToDevice, st)); rc = IPK_OK; }
   if (rc < 0) return rc;
   // `buf` may be evicted (and its memory freed) as soon as we return; hipFree waits for the device, so the copy above is safe
+  return IPK_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// A region from the cache: the buffer behind OpRotateCrop is all a region needs (everything after it is point-wise or OpTransform's permutation)
+// ------------------------------------------------------------------------------------------
+int ipk_pipeline_region_gather(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, size_t *buf_w, size_t *buf_h,
+                               int64_t *base, int64_t *x_step, int64_t *y_step) {
+  if (!d || !buf_w || !buf_h || !base || !x_step || !y_step) return fail(IPK_ERR_INVALID, "null argument");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; RegionGather rg;
+  int rc = negotiate_region(d, out_type, x, y, w, h, n); if (rc) return rc;
+  rc = region_gather(n, x, y, w, h, rg); if (rc) return rc;
+  *buf_w = rg.bw; *buf_h = rg.bh; *base = rg.g.base; *x_step = rg.g.x_step; *y_step = rg.g.y_step;
+  return IPK_OK;
+}
+
+int ipk_pipeline_run_cached_region(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache, size_t x, size_t y, size_t w, size_t h,
+                                   void *dst, int out_type, int *ops_run, int *windowed, void *stream) {
+  if (!d || !src || !dst || !cache) return fail(IPK_ERR_INVALID, "null argument");
+  REQUIRE_INIT();
+  if (!cache->owner) cache->owner = ipk_ctx_current();
+  if (cache->owner != ipk_ctx_current()) return fail(IPK_ERR_INVALID, "the cache belongs to another context (its buffers live on that context's device)");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  int rc = validate_desc(d, out_type, kCheckCurve | kCheckFuse); if (rc) return rc;
+  Negotiated n; RegionGather rg;
+  rc = negotiate_region(d, out_type, x, y, w, h, n); if (rc) return rc;
+  rc = region_gather(n, x, y, w, h, rg); if (rc) return rc;
+  if (ops_run) *ops_run = 0;
+  if (windowed) *windowed = 0;
+  hipStream_t st = S(stream);
+  const size_t esz = out_elem_size(out_type);
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // the reference returns before it consults the cache: the whole result, then the rectangle
+    Scratch sc(st);
+    void *full = nullptr;
+    rc = sc.get(n.fw * n.fh * 3 * esz, &full); if (rc) return rc;
+    rc = run_fastpath(d, src, full, out_type, stream); if (rc < 0) return rc;
+    HIPCHK(hipMemcpy2DAsync(dst, w * 3 * esz, static_cast<const char *>(full) + (y * n.fw + x) * 3 * esz, n.fw * 3 * esz, w * 3 * esz, h, hipMemcpyDeviceToDevice, st));
+    return IPK_OK;
+  }
+  ipk::BufHash hs[8]; hash_chain(d, n, source_id, hs);
+  StageTimer tm(st);
+
+  // the final buffer is memoised: the region is cut from it
+  if (CBufP fin = cache->lru.get(hs[7])) {
+    rc = check_produced(n, fin->w, fin->h, fin->colors); if (rc) return rc;
+    const char *from = static_cast<const char *>(fin->p) + (y * n.fw + x) * 3 * sizeof(float);
+    const size_t row = w * 3 * sizeof(float);
+    tm.rest = "region copy";
+    if (out_type == IPK_OUT_F32) { HIPCHK(hipMemcpy2DAsync(dst, row, from, n.fw * 3 * sizeof(float), row, h, hipMemcpyDeviceToDevice, st)); return IPK_OK; }
+    Scratch sc(st);
+    void *rect = nullptr;
+    rc = sc.get(row * h, &rect); if (rc) return rc;
+    HIPCHK(hipMemcpy2DAsync(rect, row, from, n.fw * 3 * sizeof(float), row, h, hipMemcpyDeviceToDevice, st));
+    tm.mark(tm.rest); tm.rest = "quantise";
+    rc = quantise(rect, w * h * 3, out_type, dst, stream);
+    return rc < 0 ? rc : IPK_OK;
+  }
+
+  // Bring the cache up to op 2: the latest hit among gofloat, demosaic and rotatecrop, then the missing ones as ipk_pipeline_run_cached runs them.  Its
+  // whole-frame one-launch shortcut is not taken (the next edit is to find the RGBE buffer), and hits behind op 2 are not used: entering at the RGBE
+  // buffer is one launch either way
+  CBufP buf; int startpos = 0, mask = 0;
+  for (int i = 0; i < 3; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
+  rc = run_cached_ops(d, n, hs, src, cache, startpos, 3, buf, mask, stream); if (rc < 0) return rc;
+  if (buf->w != rg.bw || buf->h != rg.bh || buf->colors != 4)
+    return fail(IPK_ERR_INVALID, "internal: produced %zux%zux%zu in front of to_lab, negotiated %zux%zu", buf->w, buf->h, buf->colors, rg.bw, rg.bh);
+  if (mask) tm.mark("gofloat..rotatecrop");
+
+  // ONE launch over the rectangle: to_lab..gamma with OpTransform folded into the load (and the quantisation where the region has the launch's 256 pixels).
+  // The transposing orientations are the exception from 256 pixels up: there a wave's 64 loads of the folded form lie a buffer row apart, one cache line
+  // each, and the launch measured 3.3x the plain rectangle's time at 24 MP (0.68 against 0.20 ms, profiles/r15_cached_region.txt) -- more than orient()
+  // costs on the rectangle.  They take the plain-rectangle gather launch into scratch and orient() behind it, the two-launch form run_tail uses
+  PointwisePrep pp;
+  rc = pp.prepare(buf->mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
+  const size_t npix = w * h;
+  const bool direct = out_type == IPK_OUT_F32 || npix >= 256;
+  const bool two = rg.transposed && npix >= 256;
+  ipk::GatherSource g = rg.g;
+  if (two) g = ipk::GatherSource{(int64_t)(rg.win.row0 * rg.bw + rg.win.col0), 1, (int64_t)rg.bw, rg.win.cols};
+  Scratch sc(st);
+  void *o = dst;
+  if (two) { rc = sc.get(npix * 3 * esz, &o); if (rc) return rc; }
+  else if (!direct) { rc = sc.get(npix * 3 * sizeof(float), &o); if (rc) return rc; }
+  pp.f.src = buf->p; pp.f.dst = o; pp.f.out_type = direct ? out_type : IPK_OUT_F32;
+  const int lrc = pp.f.out_type == IPK_OUT_F32 ? ipk::launch_pointwise_chain(pp.f, npix, st, &g) : ipk::launch_chain_quantised(pp.f, npix, st, &g);
+  if (lrc != 0) return fail(IPK_ERR_INVALID, "internal: the gather launch refused a %zux%zu region", w, h);
+  HIPCHK(hipGetLastError());
+  if (two) {
+    tm.mark("region to_lab+basecurve+from_lab+gamma");
+    tm.rest = "transform";
+    size_t ow = 0, oh = 0;
+    rc = orient(o, rg.win.cols, rg.win.rows, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
+    if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", ow, oh, w, h);
+  } else {
+    tm.mark("region to_lab+basecurve+from_lab+gamma+transform");
+    if (!direct) { tm.rest = "quantise"; rc = quantise(o, npix * 3, out_type, dst, stream); if (rc < 0) return rc; }
+  }
+  mask |= (1 << 3) | (1 << 5);
+  if (pp.f.has_curve) mask |= 1 << 4;
+  if (!n.linear) mask |= 1 << 6;
+  if (!n.transform_noop) mask |= 1 << 7;
+  if (ops_run) *ops_run = mask;
+  if (windowed) *windowed = 1;
+  // `buf` may be evicted (and its memory freed) as soon as we return; hipFree waits for the device, so the launch above is safe
   return IPK_OK;
 }
 

@@ -1541,13 +1541,19 @@ struct FusedArgs {
   const void *src;            // element (row 0 of the slab, sensor column x) -- see row_off
   void *dst;                  // first output row (image row out_r0)
   uint32_t W, H;              // cropped image size
+  union {
   uint64_t owidth;            // source row pitch (elements)
+  int64_t gather_base;        // gather mode (below): the source pixel of the rectangle's pixel (0, 0), counted from src
+  };
   uint32_t row_off;           // image row held by slab row 0
   uint32_t out_r0, out_r1;    // output rows [out_r0, out_r1)
   uint32_t n_frames;          // batch launches (k_fused_bayer_batch): frames behind the BatchPtrs argument
+  union {
+  int64_t gather_x_step;      // gather mode: source pixels from one column of the rectangle to the next (signed: +-1, or +-pitch where the load transposes)
   uint32_t *task_ctr;         // the launch stream's task queue: tasks n_waves + *task_ctr, ... are still to be drawn; kQueueStride words behind it the
                               // arrival counter of the leaving waves.  Both zero when a launch starts and when it ends.  Null = no queue: one task per
                               // wave (task_counters_for, fused_task_grid)
+  };
   float min0, range0;         // blacklevels[0], whitelevels[0]-blacklevels[0]
   float inv_range0;           // RN(1/range0) for the 4-instruction division
   int exact_norm;             // 1: normalise with true divisions (host could not validate the fast form for range0)
@@ -1562,7 +1568,10 @@ struct FusedArgs {
   const float *gam_table;     // SRGB_GAMMA_TRANSFORM, 8193 plain floats
   const LutPair *lab_pairs, *gam_pairs;   // the two tables as 8192 {v, dv} pairs (the LDS image of the pair form)
   const Q8Entry *gam_q8;      // gamma + output8bit as 8192 {k, threshold} steps (ipk_device.hpp Q8Entry): the 8-bit-output variants' LDS image
+  union {
   const float *gen_cells;     // generic-CFA mode: gen_pw*gen_ph cells of 36 floats (ipk_host.hpp Cfa::gen_cells), else null
+  int64_t gather_y_step;      // gather mode: source pixels from one row of the rectangle to the next (signed: +-pitch, or +-1 where the load transposes)
+  };
   uint32_t gen_pw, gen_ph;    // pattern width / height (both divide 48)
   union {
   int gen_check;              // generic-CFA mode, u16 sources: 1 when the host could not show that every normalised sample is ordinary
@@ -1576,6 +1585,10 @@ struct FusedArgs {
   int plain_rect;             // k_raster_chain<uint8_t | uint16_t> alone (as plain_levels): 1 = rectangle mode -- src is the first sample of a W-pixel-wide rectangle
                               // inside an image whose rows are owidth pixels of 3 (plain_levels 2: 1) samples apart; the walk stays flat over the packed output,
                               // only a pixel's source address changes
+  int gather;                 // the kernels over a 4-channel f32 buffer alone (k_pointwise_chain<false>, k_pointwise_chain_small, k_raster_chain<Rgbe32, 1 | 2>), which
+                              // read none of the mosaic fields (wave-uniform, host-set, 0 on every other launch): 1 = gather mode -- the launch covers the npix = W * H
+                              // packed pixels of a rectangle, and pixel i (row = i / W, col = i - row * W) is the 16-byte pixel gather_base + col * gather_x_step +
+                              // row * gather_y_step of src: a rectangle of a pitched buffer, flipped and / or transposed (rotate_buffer's walk, as k_rotate takes it)
   };
   union {
   int roles[4];               // ROT variants: demosaic role (0 R, 1 G on the R row, 2 G on the B row, 3 B) of the rotated-space pixel with
@@ -3191,6 +3204,42 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s) {
 // NPV = pixel PAIRS per lane of the full chain: 2 (256-pixel chunks), or 1 for small frames -- a preview of 3 MP is three chunks per wave, and its time is the
 // launch, the table fill and the first and last round trips rather than the pixels: with six shorter chunks per wave the four waves of a SIMD fill and drain
 // their pipeline in half the time (config 5's 2160x1440: 21.0 -> 20.3 us; at 24 and 100 MP the long chunks win by 1-3 %, gpurun_out ab_r06_chainnp1.txt).
+// Gather mode (FusedArgs::gather; the full chain here and k_raster_chain<Rgbe32, 1 | 2>): the launch covers the W * H packed pixels of a rectangle of the
+// result, and OpTransform's permutation is folded into the load -- pixel i reads the source pixel gather_base + col * gather_x_step + row * gather_y_step.
+// One division per lane and chunk (32-bit where the index allows), then the walk steps col / row; each pixel is one 16-byte load of its own samples.
+__device__ __forceinline__ void gather_split(uint64_t i, uint32_t w, uint64_t &row, uint32_t &col) {
+  if (i <= 0xFFFFFFFFull) { const uint32_t r = (uint32_t)i / w; row = r; col = (uint32_t)i - r * w; }
+  else { row = i / w; col = (uint32_t)(i - row * w); }
+}
+__device__ __forceinline__ const float *gather_at(const FusedArgs &a, uint64_t row, uint32_t col) {
+  return reinterpret_cast<const float *>(a.src) + (a.gather_base + (int64_t)col * a.gather_x_step + (int64_t)row * a.gather_y_step) * 4;
+}
+// a lane's PPL pixels i0, i0 + 64, ... of the clamped-tail walk (pointwise_chain_body): the step of 64 pixels is 64 / W rows and 64 % W columns
+template <int PPL>
+__device__ __forceinline__ void gather_load_strided(const FusedArgs &a, uint64_t i0, uint64_t npix, float4 (&px)[PPL]) {
+  const uint32_t w = a.W, q64 = 64u / w, r64 = 64u - q64 * w;
+  uint64_t row; uint32_t col;
+  gather_split(i0 < npix ? i0 : npix - 1, w, row, col);
+  const uint64_t last_row = (npix - 1) / w;                            // (scalar: npix and W are uniform)
+  #pragma unroll
+  for (int j = 0; j < PPL; ++j) {
+    const bool in = i0 + 64u * j < npix;                               // the tail lanes recompute the last pixel, as in the flat walk
+    px[j] = ld_stream4(gather_at(a, in ? row : last_row, in ? col : w - 1u));
+    row += q64; col += r64;
+    if (col >= w) { col -= w; ++row; }
+  }
+}
+// a lane's four consecutive pixels i0 .. i0 + 3 (k_raster_chain: plain_load4's walk)
+__device__ __forceinline__ void gather_load4(const FusedArgs &a, uint64_t i0, float4 (&px)[4]) {
+  const uint32_t w = a.W;
+  uint64_t row; uint32_t col;
+  gather_split(i0, w, row, col);
+  #pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    px[j] = ld_stream4(gather_at(a, row, col));
+    if (++col == w) { col = 0; ++row; }
+  }
+}
 template <bool TOLAB_ONLY, int NPV = 2>
 __device__ __forceinline__ void pointwise_chain_body(const FusedArgs &a, uint64_t npix) {
   constexpr int NP = TOLAB_ONLY ? 1 : NPV, PPL = 2 * NP;                // pixel pairs / pixels per lane
@@ -3223,10 +3272,16 @@ __device__ __forceinline__ void pointwise_chain_body(const FusedArgs &a, uint64_
   for (uint64_t chunk = wave; chunk < nchunks; chunk += nwaves) {
     const uint64_t base = chunk * CH + lane;
     float4 px[PPL];
-    #pragma unroll
-    for (int j = 0; j < PPL; ++j) {
-      const uint64_t i = base + 64u * j;
-      px[j] = ld_stream4(reinterpret_cast<const float *>(src + (i < npix ? i : npix - 1)));   // clamped, unpredicated: the tail lanes recompute the last pixel
+    // (measured: the mode naming only the indices, with one shared set of loads behind the branch, is no faster on the flat launches -- 0.638 against
+    // 0.640 ms at 100 MP, parent 0.632; the 24 MP launch to 8 bits 0.152 against 0.151, parent 0.151 -- profiles/r15_cached_region.txt)
+    if (!TOLAB_ONLY && IPK_RARE(a.gather != 0)) {                       // wave-uniform, host-set: a region from the cache (compiled out of TOLAB_ONLY)
+      gather_load_strided<PPL>(a, base, npix, px);
+    } else {
+      #pragma unroll
+      for (int j = 0; j < PPL; ++j) {
+        const uint64_t i = base + 64u * j;
+        px[j] = ld_stream4(reinterpret_cast<const float *>(src + (i < npix ? i : npix - 1)));   // clamped, unpredicated: the tail lanes recompute the last pixel
+      }
     }
     if (!arrived) { sync_after_lds_direct(); arrived = true; }          // the block's one barrier, behind the first chunk's loads
     PixOut o[PPL];
@@ -3276,18 +3331,32 @@ static FusedArgs chain_args(const FusedLaunch &f) {
   a.lab_pairs = reinterpret_cast<const LutPair *>(f.lab_pairs); a.gam_pairs = reinterpret_cast<const LutPair *>(f.gam_pairs);
   return a;
 }
-int launch_pointwise_chain(const FusedLaunch &f, size_t npix, hipStream_t s) {
+// the log tag of a launch over a 4-channel f32 buffer: fast_ok alone, as ever, on flat launches (the log keeps the pointer: literals only)
+static const char *chain_tag(const FusedArgs &a) {
+  static const char *const tags[2][2] = {{"fast_ok=0", "fast_ok=0,gather=1"}, {"fast_ok=1", "fast_ok=1,gather=1"}};
+  return tags[a.fast_ok ? 1 : 0][a.gather ? 1 : 0];
+}
+// gather mode's arguments; false (nothing to launch) for a rectangle the kernels cannot walk
+static bool set_gather(FusedArgs &a, const GatherSource *g, size_t npix) {
+  if (!g) return true;
+  if (g->width == 0 || g->width > 0xFFFFFFFFull || npix == 0 || npix % g->width != 0) return false;
+  a.gather = 1; a.W = (uint32_t)g->width;
+  a.gather_base = g->base; a.gather_x_step = g->x_step; a.gather_y_step = g->y_step;
+  return true;
+}
+int launch_pointwise_chain(const FusedLaunch &f, size_t npix, hipStream_t s, const GatherSource *gather) {
   FusedArgs a = chain_args(f);
+  if (!set_gather(a, gather, npix)) return -1;
   const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   if (npix < (size_t)cus * 16u * 256u * 6u) {                              // fewer than six long chunks per wave (6.3 MP on 256 CUs): the two-pixel form
     const size_t chunks = (npix + 127) / 128;
-    IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), k_pointwise_chain_small, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(cus, (chunks + 15) / 16))), dim3(1024), 0, s, a, (uint64_t)npix);
+    IPK_LAUNCH_TAG(chain_tag(a), k_pointwise_chain_small, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(cus, (chunks + 15) / 16))), dim3(1024), 0, s, a, (uint64_t)npix);
     return 0;
   }
   const size_t chunks = (npix + 255) / 256;
   const unsigned cap = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);                      // (more blocks measured: 1 / 2 / 4 / 8 / 16 per CU 0.663 / 0.665 / 0.677 / 0.673 / 0.704 ms at 100 MP)
   const unsigned blocks = (unsigned)std::min<size_t>(cap, (chunks + 15) / 16);
-  IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), k_pointwise_chain<false>, dim3(blocks ? blocks : 1), dim3(1024), 0, s, a, (uint64_t)npix);
+  IPK_LAUNCH_TAG(chain_tag(a), k_pointwise_chain<false>, dim3(blocks ? blocks : 1), dim3(1024), 0, s, a, (uint64_t)npix);
   return 0;
 }
 // OpToLab::run on the fast form (the staged op): f.fast_ok / f.mul4 / f.cm12 / f.lab_table as for the chain
@@ -3406,9 +3475,13 @@ __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npi
     const uint64_t base = min(chunk * 256, npix - 256);                // the last chunk ends at the last pixel
     float4 px[4];
     if constexpr (RGBE) {
-      const float *p4 = reinterpret_cast<const float *>(a.src) + (base + 4u * lane) * 4;
-      #pragma unroll
-      for (int j = 0; j < 4; ++j) px[j] = ld_stream4(p4 + 4 * j);
+      if (IPK_RARE(a.gather != 0)) {                                   // wave-uniform, host-set: a region from the cache (the 8- and 16-bit outputs)
+        gather_load4(a, base + 4u * lane, px);
+      } else {
+        const float *p4 = reinterpret_cast<const float *>(a.src) + (base + 4u * lane) * 4;
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) px[j] = ld_stream4(p4 + 4 * j);
+      }
     } else
     if (IPK_RARE(plain)) {                                             // rectangle and / or raw levels (wave-uniform): the lane's four pixels one by one
       plain_load4(a, src, s_expand, base + 4u * lane, px);
@@ -3466,15 +3539,16 @@ static void launch_raster_t(const FusedArgs &a, size_t npix, int out_type, const
   else IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
 }
 // OpToLab..OpGamma + output8bit / output16bit over a 4-channel f32 OpBuffer in one pass (f.out_type 1 or 2; npix >= 256)
-int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s) {
+int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s, const GatherSource *gather) {
   if (npix < 256 || (f.out_type != 1 && f.out_type != 2)) return -1;
   FusedArgs a = chain_args(f);
+  if (!set_gather(a, gather, npix)) return -1;
   a.gam_q8 = reinterpret_cast<const Q8Entry *>(f.gam_q8);
   const size_t chunks = (npix + 255) / 256;
   const unsigned cap = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = std::max(1u, (unsigned)std::min<size_t>(cap, (chunks + 15) / 16));
-  if (f.out_type == 1) IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<Rgbe32, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
-  else IPK_LAUNCH_TAG((a.fast_ok ? "fast_ok=1" : "fast_ok=0"), (k_raster_chain<Rgbe32, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
+  if (f.out_type == 1) IPK_LAUNCH_TAG(chain_tag(a), (k_raster_chain<Rgbe32, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
+  else IPK_LAUNCH_TAG(chain_tag(a), (k_raster_chain<Rgbe32, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
   return 0;
 }
 int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const void *gamma_reverse_pairs, hipStream_t s, const PlainSource *plain) {

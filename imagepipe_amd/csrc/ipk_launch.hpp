@@ -44,7 +44,9 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // sample; wrap: the grid cap holds), k_gofloat_cfa_v4 [rowwrap=] (more rows than grid rows), the ipk_raw_scaled_demosaic kernels
 // [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows; their window launches,
 // ipk_raw_scaled_demosaic_window, append win=1: [norm_fast=,...,xcd=,win=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
-// k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form);
+// k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form); the gather
+// launches of k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2> (a GatherSource: ipk_pipeline_run_cached_region) append
+// gather=1: [fast_ok=,gather=1] -- flat launches never carry the key;
 // k_raster_chain's launches by ipk_plain_to_srgb append rect=1 in rectangle mode (a rectangle narrower than the source's pitch) and levels=1 / levels=2
 // in the three-sample / monochrome raw sample modes, in that order: [fast_ok=,rect=1], [fast_ok=,levels=2], [fast_ok=,rect=1,levels=1] -- launches
 // that use neither mode (ipk_raster_to_srgb, ipk_pointwise_chain_out, a full-width raster rectangle) carry [fast_ok=] and nothing else;
@@ -137,11 +139,18 @@ int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t
 constexpr size_t kRotate1MaxTransposedRows = 65535u * 64u;
 template <typename T>
 void launch_rotate1(const T *src, size_t owidth, size_t oheight, int64_t base_offset, int64_t x_step, int64_t y_step, T *dst, hipStream_t s);
+// Gather mode of the launches over a 4-channel f32 buffer (launch_pointwise_chain, launch_chain_quantised): the launch covers the npix = width * height
+// packed pixels of a rectangle, and its pixel (col, row) is the 16-byte pixel base + col * x_step + row * y_step of f.src (steps in pixels, signed): a
+// rectangle of a pitched buffer (x_step 1, y_step pitch), flipped (x_step -1 and / or y_step -pitch) or transposed (x_step +-pitch, y_step +-1) --
+// rotate_buffer's walk as launch_rotate takes it, restricted to the rectangle, so OpTransform needs no pass of its own.  The caller keeps every such
+// index inside the buffer; the kernels read each pixel's own 16 bytes and nothing else.  Null: the flat launch, whose log entries are unchanged.
+// -1 (nothing launched) for width == 0, width >= 2^32 or npix no multiple of width
+struct GatherSource { int64_t base, x_step, y_step; size_t width; };
 // OpToLab..OpGamma in one pass over a 4-channel f32 buffer (src/dst, mul4, cm12, rgbm9, curve, linear, tables, fast_ok are read)
-int launch_pointwise_chain(const FusedLaunch &f, size_t npix, hipStream_t s);
+int launch_pointwise_chain(const FusedLaunch &f, size_t npix, hipStream_t s, const GatherSource *gather = nullptr);
 int launch_tolab_fast(const FusedLaunch &f, size_t npix, hipStream_t s);   // OpToLab alone on the chain's fast form
 // OpToLab..OpGamma + output8bit / output16bit in one pass over a 4-channel f32 buffer (f.out_type 1 / 2, f.gam_q8 set; npix >= 256): -1 otherwise
-int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s);
+int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s, const GatherSource *gather = nullptr);
 // run_other + OpToLab..OpGamma + quantisation in one pass over an RGB8 / RGB16 raster (npix >= 256; f.out_type selects the output)
 // plain (optional; ipk_plain_to_srgb): the launch covers a width-pixel-wide rectangle of npix pixels whose first sample is f.src, inside an image whose rows
 // are owidth pixels apart, and f.dst holds its npix * 3 packed samples.  levels: 0 the raster's samples; 1 a three-sample u16 raw, each channel

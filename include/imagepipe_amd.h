@@ -707,6 +707,49 @@ IPK_API int ipk_cache_get(ipk_cache *cache, const uint8_t *key32, const float **
 IPK_API int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache,
                                     int out_type, void *dst, int *ops_run, int *used_fused, void *stream);
 
+/* A region from the cache (an editor's loop: a slider moves, the viewport is redrawn).  Everything behind OpRotateCrop is point-wise or OpTransform's
+ * dihedral permutation, so the buffer memoised under the rotatecrop hash (op 2: the 4-channel image Pipeline::run hands to OpToLab; a no-op rotatecrop
+ * stores its input under that key) is all a region needs: the region is a strided rectangle of it.
+ * ipk_pipeline_region_gather (host-only, no GPU) says where: region pixel (i, j) -- column i, row j of region (x, y, w, h) of the final result -- is pixel
+ * base + i * x_step + j * y_step of that buf_w x buf_h buffer (steps in pixels, signed: a plain rectangle has x_step 1 and y_step buf_w, the flips
+ * negate one or both, the transposing orientations swap them).  Empty or outside regions and refused descriptors fail with IPK_ERR_INVALID as in
+ * ipk_pipeline_region. */
+IPK_API int ipk_pipeline_region_gather(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h,
+                                       size_t *buf_w, size_t *buf_h, int64_t *base, int64_t *x_step, int64_t *y_step);
+/* Writes the region's w*h*3 packed samples of out_type to the DEVICE buffer dst, bit-identical to that rectangle of ipk_pipeline_run_cached's result for
+ * the same descriptor.  Checks and hash chain as in ipk_pipeline_run_cached.
+ *   - fast path (ipk_pipeline_takes_fastpath = 1): the fast-path result is computed and the rectangle copied out; *windowed = 0, *ops_run = 0, the cache
+ *     is not consulted.
+ *   - the final buffer (hash 7) is memoised: the rectangle is cut from it (one 2-D copy; for 8 / 16 bits the copy, then the quantisation of the
+ *     rectangle); *windowed = 0, *ops_run = 0.
+ *   - otherwise the cache is brought up to op 2 -- the latest hit among hashes 0..2, then the missing ones of gofloat, demosaic and rotatecrop over the
+ *     whole frame, exactly as ipk_pipeline_run_cached runs and stores them -- and ONE launch over the region computes to_lab..gamma with OpTransform folded
+ *     into its loads (and output8bit / output16bit in the same launch; a region of fewer than 256 pixels takes the f32 launch plus the quantisation of the
+ *     rectangle).  The transposing orientations (Transpose, Rotate90, Rotate270, Transverse) take two launches from 256 pixels up -- the same launch over
+ *     the unrotated rectangle, then OpTransform's permutation of the rectangle: folded into the loads, a transposing walk reads one cache line per
+ *     lane and measured 3.3x the plain rectangle's time.  *windowed = 1; *ops_run has bit i set for every op executed, whole-frame (0..2) or on the rectangle (3..7 without the reference's no-ops:
+ *     a no-op curve, linear gamma, a no-op transform).  Nothing computed on the rectangle enters the cache.
+ * The whole-frame one-launch shortcut ipk_pipeline_run_cached takes with nothing memoised is NOT taken here: the point of this call is that the next edit
+ * finds the RGBE buffer.  Hits at hashes 3..6 are not used either: entering at the RGBE buffer is one launch whatever lies behind it.
+ * The borrowed buffer may be evicted once the call has returned; freeing it waits for the device, so the enqueued launch is safe.
+ * ipk_timing_begin/end see "region to_lab+basecurve+from_lab+gamma+transform" (and "quantise" where it is separate; the two-launch form: "region
+ * to_lab+basecurve+from_lab+gamma", then "transform").  No host-pointer or batch form.
+ * Measured (profiles/r15_cached_region.txt; one exposure edit and the region redrawn, wall clock, 1/16 / 1/4 / the whole area) against what the parent
+ * build offers for the same edit -- A: ipk_pipeline_run_cached + a 2-D copy, B: ipk_pipeline_run_region without a cache:
+ *   24 MP RGGB u16 -> f32, Normal     0.041 / 0.075 / 0.207 ms    A 0.99 / 1.04 / 1.11     B 0.046 / 0.061 / 0.143
+ *   24 MP RGGB u16 -> f32, Rotate180  0.041 / 0.080 / 0.210       A 1.33 / 1.36 / 1.44     B 0.055 / 0.086 / 0.258
+ *   24 MP RGGB u16 -> f32, Rotate90   0.051 / 0.106 / 0.319       A 1.3 - 17 (allocations) B 0.056 / 0.091 / 0.263
+ *   50 MP X-Trans -> 2160x1440 f32    0.031 / 0.035 / 0.049       A 0.111 / 0.113 / 0.117  B 0.045 / 0.059 / 0.101
+ *   the same, Rotate90 (2160x3240)    0.037 / 0.052 / 0.107       A 0.21 / 0.95 / 8.1      B 1.06 / 1.07 / 1.10
+ * (u8: within 10 % of these.)  Always faster than A (2.2x - 160x).  NOT faster than B where B is the one raw->sRGB window launch of a full-resolution
+ * Bayer frame, which reads 2 bytes per pixel where this call reads 16: Normal and Rotate90 from a quarter of the area up (0.69 - 0.90 of B's speed);
+ * such a caller is better served by ipk_pipeline_run_region.  On the staged routes (previews, and everything at an angle) it is 1.4x - 28x B.
+ * The flat launches of the touched kernels (ipk_pointwise_chain, ipk_pointwise_chain_out) stayed within the parent's run-to-run spread, 0 - 3 % behind it.
+ * Not measured: 16-bit outputs, the other flips and transposing orientations, regions below 256 pixels, photo-like data. */
+IPK_API int ipk_pipeline_run_cached_region(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache,
+                                           size_t x, size_t y, size_t w, size_t h, void *dst, int out_type,
+                                           int *ops_run, int *windowed, void *stream);
+
 /* ---------------------------------------------------------------------------------------- */
 /* Multi-GPU: one process per GPU; a frame batch shards with no exchange (frame i -> rank i mod N, */
 /* src/pipeline.rs:246-249), ONE frame shards by row bands                */

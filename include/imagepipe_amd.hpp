@@ -342,6 +342,17 @@ class Pipeline {
     last_region_windowed = win != 0;
     return o;
   }
+  // The same from the cache (ipk_pipeline_run_cached_region): the cache is brought up to the buffer behind OpRotateCrop, then one launch over the
+  // region computes the rest; an edit behind OpRotateCrop costs that launch alone.  Sets last_ops_run as well
+  DeviceArray run_region(const PipelineCache &cache, size_t x, size_t y, size_t w, size_t h, int out_type = IPK_OUT_F32) {
+    ipk_pipeline_desc d = desc(); int win = 0;
+    DeviceArray o(w * h * 3 * (out_type == IPK_OUT_F32 ? 4 : out_type == IPK_OUT_U8 ? 1 : 2));
+    check(ipk_pipeline_run_cached_region(&d, globals.image.data.get(), source_id, cache.get(), x, y, w, h, o.get(), out_type, &last_ops_run, &win, nullptr),
+          "pipeline_run_cached_region");
+    check(ipk_stream_sync(nullptr), "sync");
+    last_region_windowed = win != 0;
+    return o;
+  }
   bool last_region_windowed = false;
   // ophashes of pipeline.rs:342-361
   std::vector<std::array<uint8_t, 32>> hashes(int out_type = IPK_OUT_F32) const {
