@@ -605,6 +605,7 @@ class Pipeline:
         self.fuse_four_colour = False         # ipk_pipeline_desc.allow_fused bit 1 (IPK_FUSED_FOUR_COLOUR): a filter with a fourth colour (RGBE ...) on the one-launch route where fuses_four_colour() says so
         self.window_regions = False           # ipk_pipeline_desc.allow_fused bit 2 (IPK_FUSED_WINDOW_REGIONS): regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch
         self.fuse_plain = False               # ipk_pipeline_desc.allow_fused bit 4 (IPK_FUSED_PLAIN): cropped RGB8 / RGB16 rasters and u16 monochrome / three-sample raws as one launch where fuses_plain() says so; regions of every frame on the raster launch windowed
+        self.resample_cached = False          # ipk_pipeline_desc.allow_fused bit 5 (IPK_FUSED_CACHED_RESAMPLE): run_region with a cache resamples the region from the cached demosaic buffer when the rotatecrop buffer is missing, where resamples_cached_region() says so; that call then never fills the rotatecrop hash
         self.window_previews = False          # ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
 
     @staticmethod
@@ -674,6 +675,8 @@ class Pipeline:
             d.allow_fused |= _lib.FUSED_WINDOW_PREVIEWS
         if self.fuse_plain and d.allow_fused:
             d.allow_fused |= _lib.FUSED_PLAIN
+        if self.resample_cached and d.allow_fused:
+            d.allow_fused |= _lib.FUSED_CACHED_RESAMPLE
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -704,6 +707,11 @@ class Pipeline:
         """Does this cropped raster / u16 monochrome or three-sample raw run as the one launch ipk_plain_to_srgb (ipk_pipeline_fuses_plain, host-only)?"""
         d = self.desc()
         return bool(_lib.check(lib().ipk_pipeline_fuses_plain(C.byref(d), out_type), "ipk_pipeline_fuses_plain"))
+
+    def resamples_cached_region(self, out_type=OUT_F32) -> bool:
+        """Would run_region with a cache resample the region straight from the cached demosaic buffer (ipk_pipeline_resamples_cached_region, host-only)?"""
+        d = self.desc()
+        return bool(_lib.check(lib().ipk_pipeline_resamples_cached_region(C.byref(d), out_type), "ipk_pipeline_resamples_cached_region"))
 
     def sizes(self):
         d = self.desc()

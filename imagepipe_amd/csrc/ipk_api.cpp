@@ -1518,6 +1518,9 @@ int ipk_selftest_cbrtf(const float *in, float *out, size_t n, int variant, void 
 // ------------------------------------------------------------------------------------------
 // Pipeline::run (src/pipeline.rs:311-375) for one source, cache == None
 // ------------------------------------------------------------------------------------------
+// allow_fused as the switch it began as: any non-zero value means "on" -- except IPK_FUSED_CACHED_RESAMPLE standing alone, a bit younger than that rule,
+// which no route, report or region plan may see (with it or without it they answer the same, for every mask)
+static bool fused_on(const ipk_pipeline_desc *d) { return (d->allow_fused & ~IPK_FUSED_CACHED_RESAMPLE) != 0; }
 // the descriptor's OpRotateCrop in its reset() state (pipeline.rs:314-316)
 static ipk::RotateCrop rotatecrop_of(const ipk_pipeline_desc *d) {
   ipk::RotateCrop rc;
@@ -1765,7 +1768,7 @@ void choose_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type,
   const bool plain_raw = n.raw && !n.cfa_branch && d->src_type == IPK_SRC_U16;           // cpp == 3, or cpp == 1 without a filter (negotiate)
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) { rt.kind = kFastPath; return; }
   ipk::Cfa cfa; ipk::ResamplePlan plan; int xo, yo;
-  const bool mosaic = d->allow_fused && n.cfa_branch && d->cpp == 1 && ipk::Cfa::parse(d->cfa, cfa);
+  const bool mosaic = fused_on(d) && n.cfa_branch && d->cpp == 1 && ipk::Cfa::parse(d->cfa, cfa);
   const bool three = mosaic && cfa.three_colour(), still = n.rc.noop();
   RotateCropPoints &r = rt.rcp;
   if (mosaic && still && n.scale <= 1.0f && cfa.valid() && (three || cfa.bayer_phase(xo, yo) || (d->allow_fused & IPK_FUSED_FOUR_COLOUR))) {
@@ -1782,7 +1785,7 @@ void choose_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type,
     rt.kind = kFusedScaledown; rt.pw = n.dw; rt.ph = n.dh;
     rt.label = "fused gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma";          // a whole frame marks "transform" as a stage of its own (run_route)
     rt.region_label = "fused region gofloat+demosaic(scaled)+to_lab+basecurve+from_lab+gamma(+transform)";
-  } else if (d->allow_fused && still && n.r.width * n.r.height >= 256 && n.scale <= 1.0f &&
+  } else if (fused_on(d) && still && n.r.width * n.r.height >= 256 && n.scale <= 1.0f &&
              ((!n.raw && uncropped) || (plain_opted(d) && (!n.raw || plain_raw)))) {
     rt.kind = kFusedRaster;
     rt.plain = n.raw || !uncropped;
@@ -1922,7 +1925,7 @@ int launch_gofloat(const ipk_pipeline_desc *d, const Negotiated &n, const void *
 // OpGoFloat + OpDemosaic in one pass, into a dw x dh 4-channel buffer, when OpDemosaic::run would scale: its scaled_demosaic branch for a
 // mosaic (demosaic.rs:47-50), its scale_down_opbuf branch for a raster source under a size limit (demosaic.rs:44-46)
 bool gofloat_demosaic_one_pass(const ipk_pipeline_desc *d, const Negotiated &n) {
-  if (!d->allow_fused) return false;
+  if (!fused_on(d)) return false;
   if (!n.raw) return n.scale > 1.0f;
   ipk::Cfa cfa;
   return n.cfa_branch && d->cpp == 1 && ipk::Cfa::parse(d->cfa, cfa) && cfa.valid() && n.scale >= ipk::demosaic_minscale(cfa.width);
@@ -1993,7 +1996,7 @@ int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scra
   const size_t n3 = w * h * 3 * sizeof(float);
   const bool f32_out = out_type == IPK_OUT_F32;
   bool chained = false;
-  if (d->allow_fused && colors == 4 && !f32_out && n.transform_noop && w * h >= 256) {
+  if (fused_on(d) && colors == 4 && !f32_out && n.transform_noop && w * h >= 256) {
     // ... and with output8bit / output16bit in the same pass when the caller wants 8 or 16 bits and nothing follows: the f32 image never exists
     rc = produced(w, h); if (rc) return rc;
     rc = ipk_pointwise_chain_out(static_cast<const float *>(buf), w, h, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
@@ -2003,7 +2006,7 @@ int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scra
     tm.mark("to_lab+basecurve+from_lab+gamma+quantise");
     return IPK_OK;
   }
-  if (d->allow_fused && colors == 4) {
+  if (fused_on(d) && colors == 4) {
     // tolab + basecurve + fromlab + gamma in one pass (no cache wants the three intermediates)
     void *o = nullptr;
     if (f32_out && n.transform_noop) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
@@ -2499,6 +2502,28 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
 // ------------------------------------------------------------------------------------------
 // A region from the cache: the buffer behind OpRotateCrop is all a region needs (everything after it is point-wise or OpTransform's permutation)
 // ------------------------------------------------------------------------------------------
+namespace {
+// IPK_FUSED_CACHED_RESAMPLE: may a region be resampled straight from the demosaic buffer (hash 1)?  The bit beside IPK_FUSED_ON, off the fast path, an
+// OpRotateCrop that is active and accepts its crops on the sw x sh buffer OpDemosaic hands it (pipeline_sizes_impl's rule: the negotiated size where it
+// scales, else the cropped source), no fourth colour -- the one 4-channel buffer whose E is not +0.0 everywhere --, and a transform the launch admits
+struct CachedResample { size_t sw, sh; RotateCropPoints r; ipk::ResamplePlan plan; };
+bool cached_resample(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, CachedResample &c) {
+  const int both = IPK_FUSED_ON | IPK_FUSED_CACHED_RESAMPLE;
+  if ((d->allow_fused & both) != both || ipk_pipeline_takes_fastpath(d, out_type) == 1) return false;
+  if (n.cfa_branch) { ipk::Cfa cfa; if (!ipk::Cfa::parse(d->cfa, cfa) || !cfa.valid() || !cfa.three_colour()) return false; }
+  c.sw = n.scale > 1.0f ? n.dw : n.r.width; c.sh = n.scale > 1.0f ? n.dh : n.r.height;
+  if (n.rc.noop() || !rotatecrop_of(d).corners(c.sw, c.sh, c.r.pts, c.r.nw, c.r.nh)) return false;
+  return ipk::resample_plan(c.sw, c.sh, c.r.pts[0], c.r.pts[1], c.r.pts[2], c.r.pts[3], c.r.pts[4], c.r.pts[5], c.r.nw, c.r.nh, c.plan);
+}
+}  // namespace
+int ipk_pipeline_resamples_cached_region(const ipk_pipeline_desc *d, int out_type) {
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; const int rc = negotiate(d, out_type, n); if (rc) return rc;
+  CachedResample c;
+  return cached_resample(d, n, out_type, c) ? 1 : 0;
+}
+
 int ipk_pipeline_region_gather(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, size_t *buf_w, size_t *buf_h,
                                int64_t *base, int64_t *x_step, int64_t *y_step) {
   if (!d || !buf_w || !buf_h || !base || !x_step || !y_step) return fail(IPK_ERR_INVALID, "null argument");
@@ -2550,6 +2575,47 @@ int ipk_pipeline_run_cached_region(const ipk_pipeline_desc *d, const void *src, 
     tm.mark(tm.rest); tm.rest = "quantise";
     rc = quantise(rect, w * h * 3, out_type, dst, stream);
     return rc < 0 ? rc : IPK_OK;
+  }
+
+  // IPK_FUSED_CACHED_RESAMPLE with the rotatecrop buffer missing (a crop or straighten edit): the cache is brought up to op 1 only, and ONE launch resamples
+  // the region's rectangle of OpRotateCrop's rg.bw x rg.bh result from that buffer, chain and quantiser behind it (k_fused_resample's cached-buffer
+  // source mode).  Nothing enters the cache under hash 2.  Every orientation but Normal: the plain rectangle into scratch, then orient()
+  CachedResample cr;
+  if (cached_resample(d, n, out_type, cr) && !cache->lru.contains(hs[2])) {
+    CBufP buf; int startpos = 0, mask = 0;
+    for (int i = 0; i < 2; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
+    rc = run_cached_ops(d, n, hs, src, cache, startpos, 2, buf, mask, stream); if (rc < 0) return rc;
+    if (buf->w != cr.sw || buf->h != cr.sh || buf->colors != 4 || cr.r.nw != rg.bw || cr.r.nh != rg.bh)
+      return fail(IPK_ERR_INVALID, "internal: produced %zux%zux%zu in front of rotatecrop (negotiated %zux%zu), rotatecrop to %zux%zu (negotiated %zux%zu)",
+                  buf->w, buf->h, buf->colors, cr.sw, cr.sh, cr.r.nw, cr.r.nh, rg.bw, rg.bh);
+    if (mask) tm.mark("gofloat..demosaic");
+    PointwisePrep pp;
+    rc = pp.prepare(buf->mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
+    const size_t npix = w * h;
+    Scratch sc(st);
+    void *o = dst;
+    if (!n.transform_noop) { rc = sc.get(npix * 3 * esz, &o); if (rc) return rc; }
+    pp.f.src = buf->p; pp.f.dst = o; pp.f.src_is_u16 = false; pp.f.out_type = out_type;
+    pp.f.width = buf->w; pp.f.height = buf->h; pp.f.owidth = buf->w;
+    pp.f.black0 = 0.0f; pp.f.white0 = 1.0f;                                // not read in this mode
+    if (ipk::launch_fused_resample(pp.f, cr.plan, rg.bw, rg.bh, nullptr, st, &rg.win, 1) != 0)
+      return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
+    HIPCHK(hipGetLastError());
+    tm.mark("region rotatecrop+to_lab+basecurve+from_lab+gamma");
+    if (!n.transform_noop) {
+      tm.rest = "transform";
+      size_t ow = 0, oh = 0;
+      rc = orient(o, rg.win.cols, rg.win.rows, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
+      if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", ow, oh, w, h);
+    }
+    mask |= (1 << 2) | (1 << 3) | (1 << 5);
+    if (pp.f.has_curve) mask |= 1 << 4;
+    if (!n.linear) mask |= 1 << 6;
+    if (!n.transform_noop) mask |= 1 << 7;
+    if (ops_run) *ops_run = mask;
+    if (windowed) *windowed = 1;
+    // `buf` may be evicted (and its memory freed) as soon as we return; hipFree waits for the device, so the launch above is safe
+    return IPK_OK;
   }
 
   // Bring the cache up to op 2: the latest hit among gofloat, demosaic and rotatecrop, then the missing ones as ipk_pipeline_run_cached runs them.  Its

@@ -3604,6 +3604,9 @@ struct ResampleArgs {
   float tlx, tly, skip_x_x, skip_x_y, skip_y_x, skip_y_y, inv_skip_x_x, inv_skip_y_y;
   int fast_x, fast_y;
   int axis;                              // 1: scale_down_opbuf's transform (scaledown_plan): corner (0, 0), cross skips exactly +0.0, windows of up to 4x4
+                                         // 2: the general walk, as 0, over the source mode below (rs_fill_rgb): a.src is the demosaiced frame itself, dense
+                                         //    4-channel f32 of W x H pixels (f32 instantiations only; lookups unused).  One field for both: the kernel has no
+                                         //    scalar register to spare, and a second flag kept across the tile loop spilled four vector registers to scratch
   const uint32_t *lookups;
 };
 struct RsWin { uint32_t fx, tx, fy, ty; };
@@ -3675,6 +3678,45 @@ __device__ __forceinline__ void rs_store_mosaic(const FusedArgs &a, const RsBox 
       s_mos[i] = rs_min(ieee ? d / a.range0 : cdiv_fast(d, a.range0, a.inv_range0), 1.0f);
     }
   }
+}
+
+// The source mode ResampleArgs::axis == 2 (launch_fused_resample's src_rgbe: ipk_pipeline_run_cached_region under IPK_FUSED_CACHED_RESAMPLE): a.src is what
+// stages 1 and 2 rebuild -- the 4-channel f32 frame in front of OpRotateCrop, a.owidth pixels per row -- so stage 1 copies the box's pixels straight into
+// s_rgb (R, G, B of each 16-byte pixel: no halo, no s_mos, no normalisation) and stage 2 is skipped.  E is dropped where the header above argues it: it is
+// +0.0 in every pixel of such a frame (three-colour mosaics, monochrome and three-sample raws, rasters), and stage 3 writes E = 0.0 itself.
+// A box holds up to kResampleRgbCap pixels, kRsRgbPerThread per thread.  The kernel runs a few registers under its limit of 128 (a mode flag of its own
+// was enough to spill four of them to scratch in the f32 instantiations: the mode is a value of ResampleArgs::axis instead), so of the NEXT tile only
+// the thread's first pixel is in flight behind stage 3, in the four registers the mosaic mode keeps its samples in (rs_load_rgb0 / rs_store_rgb0); the
+// rest of the box follows behind the barrier that ends stage 3's reads of s_rgb (rs_fill_rgb<1>), all of a thread's loads issued before its first store.
+constexpr int kRsRgbPerThread = (int)((kResampleRgbCap + 1023u) / 1024u);
+static_assert(kRsMosPerThread >= 3, "rs_load_rgb0 keeps one pixel's R, G, B in the mosaic mode's registers");
+__device__ __forceinline__ float4 rs_load_px(const FusedArgs &a, const RsBox &b, const RsDiv &dv, uint32_t i) {
+  const uint32_t r = rs_div(dv, i), c = i - r * b.w;
+  return reinterpret_cast<const float4 *>(a.src)[(size_t)(b.y0 + r) * a.owidth + b.x0 + c];
+}
+template <int K0>
+__device__ __forceinline__ void rs_fill_rgb(const FusedArgs &a, const RsBox &b, float *__restrict__ s_rgb) {
+  const RsDiv dv = rs_div_make(b.w);
+  const uint32_t n = b.w * b.h;
+  float4 v[kRsRgbPerThread];
+  #pragma unroll
+  for (int k = K0; k < kRsRgbPerThread; ++k) {
+    const uint32_t i = threadIdx.x + 1024u * k;
+    v[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (i < n) v[k] = rs_load_px(a, b, dv, i);
+  }
+  #pragma unroll
+  for (int k = K0; k < kRsRgbPerThread; ++k) {
+    const uint32_t i = threadIdx.x + 1024u * k;
+    if (i < n) { s_rgb[3u * i] = v[k].x; s_rgb[3u * i + 1u] = v[k].y; s_rgb[3u * i + 2u] = v[k].z; }
+  }
+}
+__device__ __forceinline__ void rs_load_rgb0(const FusedArgs &a, const RsBox &b, float v[kRsMosPerThread]) {
+  v[0] = 0.0f; v[1] = 0.0f; v[2] = 0.0f;
+  if (threadIdx.x < b.w * b.h) { const float4 p = rs_load_px(a, b, rs_div_make(b.w), threadIdx.x); v[0] = p.x; v[1] = p.y; v[2] = p.z; }
+}
+__device__ __forceinline__ void rs_store_rgb0(const RsBox &b, const float v[kRsMosPerThread], float *__restrict__ s_rgb) {
+  if (threadIdx.x < b.w * b.h) { s_rgb[3u * threadIdx.x] = v[0]; s_rgb[3u * threadIdx.x + 1u] = v[1]; s_rgb[3u * threadIdx.x + 2u] = v[2]; }
 }
 
 // Stage 3's window walk for the axis-aligned transform of scale_down_opbuf (t.axis; scaling.rs:46 hands transform_buffer the corners (0, 0), (w - 1, 0),
@@ -3765,7 +3807,9 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
   const uint32_t trow = p0 / t.tw, tcol = p0 - trow * t.tw;
   const uint32_t arow = t.wr0 + trow, acol = t.wc0 + tcol;
   RsBox box = rs_box(t, a.W, a.H, tile, arow - trow, acol - tcol);
-  {
+  const bool rgbe = std::is_same<SrcT, float>::value && t.axis == 2;   // block-uniform: the launch's source mode (rs_fill_rgb)
+  if (rgbe) rs_fill_rgb<0>(a, box, s_rgb);
+  else {
     float mv[kRsMosPerThread];
     rs_load_mosaic<SrcT>(a, box, mv);
     rs_store_mosaic<SrcT>(a, box, mv, s_mos);
@@ -3773,7 +3817,7 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
   sync_after_lds_direct();                                              // the tables and the first tile's mosaic
   for (;;) {
     // ---- stage 2: demosaic::full over the box ----
-    {
+    if (!rgbe) {
       const RsDiv dv = rs_div_make(box.w);
       const uint32_t n = box.w * box.h;
       for (uint32_t i = threadIdx.x; i < n; i += 1024u) {
@@ -3803,7 +3847,10 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
     const bool more = next < t.n_tiles;
     RsBox nbox = box;
     float mv[kRsMosPerThread];
-    if (more) { nbox = rs_box(t, a.W, a.H, next, arow - trow, acol - tcol); rs_load_mosaic<SrcT>(a, nbox, mv); }
+    if (more) {
+      nbox = rs_box(t, a.W, a.H, next, arow - trow, acol - tcol);
+      if (rgbe) rs_load_rgb0(a, nbox, mv); else rs_load_mosaic<SrcT>(a, nbox, mv);
+    }
     // ---- stage 3: resample, chain, store ----
     {
       const uint32_t tyi = tile / t.tiles_x, txi = tile - tyi * t.tiles_x;
@@ -3816,7 +3863,7 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
       const float center_y_r = t.tly + (t.skip_y_y * (float)row) + (t.skip_y_y / 2.0f) - 0.5f;
       float4 px[2];
       bool ok[2];
-      if (t.axis) {                                                     // block-uniform: the launch's mode
+      if (t.axis == 1) {                                                // block-uniform: the launch's mode
         rs_walk_axis(t, box, a.W, a.H, s_rgb, row, col0, wcol0, row_ok, center_x_r, center_y_r, px, ok);
       } else {
         #pragma unroll
@@ -3890,14 +3937,21 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
       }
     }
     if (!more) break;
-    rs_store_mosaic<SrcT>(a, nbox, mv, s_mos);
-    __syncthreads();
+    if (rgbe) {                                                           // s_rgb is stage 3's source: every wave has to be through with it first
+      __syncthreads();
+      rs_store_rgb0(nbox, mv, s_rgb);
+      rs_fill_rgb<1>(a, nbox, s_rgb);
+    } else {
+      rs_store_mosaic<SrcT>(a, nbox, mv, s_mos);
+      __syncthreads();
+    }
     box = nbox; tile = next;
   }
 }
 
 int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s,
-                          const ResampleWindow *win) {
+                          const ResampleWindow *win, int src_rgbe) {
+  if (src_rgbe && (f.src_is_u16 || plan.axis || !win)) return -1;          // a mode of the f32 instantiations' general window launches alone
   FusedArgs a = chain_args(f);
   a.W = (uint32_t)f.width; a.H = (uint32_t)f.height; a.owidth = f.owidth;
   a.min0 = f.black0; a.range0 = f.white0 - f.black0;                       // gofloat.rs:86-89
@@ -3916,14 +3970,15 @@ int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t
   t.skip_x_x = plan.skip_x_x; t.skip_x_y = plan.skip_x_y; t.skip_y_x = plan.skip_y_x; t.skip_y_y = plan.skip_y_y;
   t.inv_skip_x_x = 1.0f / t.skip_x_x; t.inv_skip_y_y = 1.0f / t.skip_y_y;
   t.fast_x = cdiv_host_ok(t.skip_x_x); t.fast_y = cdiv_host_ok(t.skip_y_y);
-  t.axis = plan.axis ? 1 : 0;
+  t.axis = src_rgbe ? 2 : plan.axis ? 1 : 0;
   t.lookups = lookups_dev;
   const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = (unsigned)std::min<uint64_t>(cus, tiles);
   // the general mode's tags stay as they were; the axis-aligned mode (scaledown_plan) adds its own key
-  // and a window launch (win) its own next to them
-  const char *tag = win ? (t.axis ? (a.fast_ok ? "fast_ok=1,axis=1,win=1" : "fast_ok=0,axis=1,win=1") : (a.fast_ok ? "fast_ok=1,win=1" : "fast_ok=0,win=1"))
-                        : (t.axis ? (a.fast_ok ? "fast_ok=1,axis=1" : "fast_ok=0,axis=1") : (a.fast_ok ? "fast_ok=1" : "fast_ok=0"));
+  // and a window launch (win) its own next to them; the cached-buffer source mode (src_rgbe: window launches only) appends rgbe=1
+  const char *tag = src_rgbe ? (a.fast_ok ? "fast_ok=1,win=1,rgbe=1" : "fast_ok=0,win=1,rgbe=1") :
+                    win ? (plan.axis ? (a.fast_ok ? "fast_ok=1,axis=1,win=1" : "fast_ok=0,axis=1,win=1") : (a.fast_ok ? "fast_ok=1,win=1" : "fast_ok=0,win=1"))
+                        : (plan.axis ? (a.fast_ok ? "fast_ok=1,axis=1" : "fast_ok=0,axis=1") : (a.fast_ok ? "fast_ok=1" : "fast_ok=0"));
   #define IPK_RS_LAUNCH(T, O) IPK_LAUNCH_TAG(tag, (k_fused_resample<T, O>), dim3(blocks), dim3(1024), 0, s, a, t)
   if (f.src_is_u16) { if (f.out_type == 0) IPK_RS_LAUNCH(uint16_t, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(uint16_t, 1); else IPK_RS_LAUNCH(uint16_t, 2); }
   else { if (f.out_type == 0) IPK_RS_LAUNCH(float, 0); else if (f.out_type == 1) IPK_RS_LAUNCH(float, 1); else IPK_RS_LAUNCH(float, 2); }

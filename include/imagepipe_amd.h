@@ -506,7 +506,12 @@ typedef struct {
                                       Bit 4 (IPK_FUSED_PLAIN = 16), beside IPK_FUSED_ON as well: the frames whose OpDemosaic is a pass-through -- RGB8 / RGB16
                                       rasters with OpGoFloat crops, u16 monochrome and u16 three-sample raws -- run as the one launch ipk_plain_to_srgb where
                                       ipk_pipeline_fuses_plain says so, and regions of every frame on that launch (the uncropped rasters it always took
-                                      included) are windowed.  Same contract: no hash, no result.  Without bit 0 it does nothing. */
+                                      included) are windowed.  Same contract: no hash, no result.  Without bit 0 it does nothing.
+                                      Bit 5 (IPK_FUSED_CACHED_RESAMPLE = 32), beside IPK_FUSED_ON as well, concerns ipk_pipeline_run_cached_region alone: where
+                                      ipk_pipeline_resamples_cached_region says so and the rotatecrop buffer (hash 2) is not memoised, the region is resampled
+                                      from the cached demosaic buffer (hash 1) in one launch instead of running OpRotateCrop over the whole frame first.  Same
+                                      contract: no hash, no result, no region report.  Without bit 0 it does nothing -- not even what "any non-zero value"
+                                      does: allow_fused = 32 is 0 to every route and report. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -533,7 +538,7 @@ typedef enum {
                                       whole area 0.098 -> 0.090 | 0.068 -> 0.059 ms (the copy is saved); host form, 1/16 1.86 -> 0.17 ms (99.5 -> 6.3 MB
                                       uploaded) | 0.92 -> 0.11 ms (48 -> 3.1 MB), 1/4 1.89 -> 0.55 | 0.94 -> 0.29 ms.  NOT faster: a whole-area region
                                       through the host form uploads the whole frame either way, 2.016 -> 2.019 | 1.002 -> 1.001 ms */
-  IPK_FUSED_PLAIN = 16             /* bit 4 (beside bit 0): cropped RGB8 / RGB16 rasters and u16 monochrome / three-sample raws run as one launch
+  IPK_FUSED_PLAIN = 16,            /* bit 4 (beside bit 0): cropped RGB8 / RGB16 rasters and u16 monochrome / three-sample raws run as one launch
                                       (ipk_plain_to_srgb) where ipk_pipeline_fuses_plain says so, and regions of every frame on the raster launch are
                                       windowed.  f32 monochrome / three-sample raws stay staged (no kernel instantiation carries them).
                                       Measured (profiles/r14_plain_route.txt; 6000x4000 noise, without -> with the bit): whole frames, mono u16 -> u8
@@ -544,6 +549,11 @@ typedef enum {
                                       faster beyond the noise: a whole-area region through the host form uploads the whole frame either way, 2.77 -> 2.66 |
                                       2.41 -> 2.27 ms.  The cost to launches that use neither mode (the kernels test for them once per 256-pixel chunk):
                                       ipk_raster_to_srgb, RGB8 -> u8 at 24 MP, parent 0.1269 ms (its spread 0.0033) -> 0.1283 ms */
+  IPK_FUSED_CACHED_RESAMPLE = 32   /* bit 5 (beside bit 0): ipk_pipeline_run_cached_region resamples a region straight from the cached demosaic buffer when the
+                                      rotatecrop buffer is missing (a crop or straighten edit), where ipk_pipeline_resamples_cached_region says so: one launch
+                                      of k_fused_resample's cached-buffer source mode over the rectangle instead of OpRotateCrop over the whole frame plus the
+                                      gather launch.  The trade-off: while the bit is set that call never fills hash 2 (see ipk_pipeline_run_cached_region).
+                                      Measurements: profiles/r16_cached_resample.txt */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -749,6 +759,42 @@ IPK_API int ipk_pipeline_region_gather(const ipk_pipeline_desc *d, int out_type,
 IPK_API int ipk_pipeline_run_cached_region(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache,
                                            size_t x, size_t y, size_t w, size_t h, void *dst, int out_type,
                                            int *ops_run, int *windowed, void *stream);
+/* IPK_FUSED_CACHED_RESAMPLE: a crop or straighten edit changes hash 2, and the call above then runs OpRotateCrop over the WHOLE frame (16 bytes read and
+ * written per pixel) before it gathers the rectangle -- and stores a buffer the next step of the slider invalidates.  With the bit (beside IPK_FUSED_ON)
+ * the call takes another route, behind its fast-path and hash-7 branches, when hash 2 is NOT memoised and ipk_pipeline_resamples_cached_region answers 1:
+ *   - the cache is brought up to op 1 only (the latest hit among hashes 0..1, then the missing ones of gofloat and demosaic over the whole frame, run and
+ *     stored as ipk_pipeline_run_cached does, the one-pass gofloat + demosaic of scaled previews included);
+ *   - ONE launch computes the region's unrotated rectangle of OpRotateCrop's result straight from that buffer and runs to_lab..gamma and the
+ *     quantisation on it: k_fused_resample's cached-buffer source mode (launch log: k_fused_resample<float, OUT>[fast_ok=,win=1,rgbe=1]), the window walk
+ *     of transform_buffer tap for tap, zero-weight taps accumulated (0 * inf stays NaN), bit-identical to the staged result;
+ *   - every orientation but Normal computes the plain rectangle into scratch and runs OpTransform's permutation on it (two launches);
+ *   - *windowed = 1; *ops_run = the whole-frame ops executed (bits 0..1), bit 2, and bits 3..7 as on the gather route; nothing computed on the rectangle
+ *     enters the cache, so hash 2 stays absent.
+ * With hash 2 memoised the gather launch above runs as ever: one tap per pixel instead of up to nine.
+ * THE TRADE-OFF: while the bit is set this call never fills hash 2, so every later point-wise edit (white balance, curve, exposure) pays the resample
+ * again.  A caller whose crop / straighten slider has come to rest fills it with ipk_pipeline_run_cached, or with one region call that leaves the bit out.
+ * ipk_timing_begin/end see "region rotatecrop+to_lab+basecurve+from_lab+gamma" (then "transform" for the other orientations).
+ * ipk_pipeline_resamples_cached_region (host-only, no GPU): would the call take that route with hash 2 absent?  1 when allow_fused has IPK_FUSED_ON and
+ * IPK_FUSED_CACHED_RESAMPLE set, the frame does not take the fast path, OpRotateCrop is not a no-op and accepts its crops on the buffer OpDemosaic hands
+ * it (the negotiated demosaic size where OpDemosaic scales, else the cropped source), the source is not a CFA mosaic whose filter has a fourth colour
+ * (E is +0.0 in every other 4-channel buffer in front of OpRotateCrop, which the launch relies on), and the launch admits the transform (windows of at most
+ * 3x3: |skip| sums below 2 per axis, sides below 2^24).  Three-colour mosaics of any pattern at any scale, monochrome and three-sample raws (u16 and f32)
+ * and RGB8 / RGB16 rasters are all admitted.  0 otherwise; a negative error code for a descriptor ipk_pipeline_sizes refuses.
+ * Measured (profiles/r16_cached_resample.txt; one straighten step that keeps hash 1 and the region redrawn, wall clock, the fastest run of 60, 1/16 / 1/4 /
+ * the whole area) against what the parent build offers for the same step -- A: this call without the bit, B: ipk_pipeline_run_region without a cache, every
+ * window bit on (at an angle B is never the one launch: the size fold lands a pixel short):
+ *   24 MP RGGB u16 -> f32             0.057 / 0.130 / 0.428 ms    A 0.824 / 0.835 / 0.942    B 1.432 / 1.488 / 1.643
+ *   24 MP RGGB u16 -> u8              0.057 / 0.123 / 0.396       A 0.833 / 0.869 / 0.983    B 1.452 / 1.489 / 1.618
+ *   50 MP X-Trans -> 2160x1440 u8     0.039 / 0.046 / 0.084       A 0.306 / 0.333 / 0.348    B 0.182 / 0.186 / 0.202
+ *   24 MP RGB8 raster -> u8           0.051 / 0.113 / 0.361       A 0.826 / 0.832 / 0.944    B 0.947 / 0.987 / 1.129
+ * 2.2x - 16x over A, 2.4x - 25x over B; no measured step was slower.  (Medians agree wherever no run of a case stalled; the file has both.)  NOT
+ * measured, and not expected to win: a crop-only edit of a full-size Bayer u16 frame, where B is the raw window launch reading 2 bytes per pixel (0.028 ms
+ * for 1920x1080, profiles/r12_region_windows.txt) and this call reads 16.  A step that moves the negotiated demosaic size by a pixel changes every hash
+ * (the settings are hashed): the whole chain runs again with the bit or without it; of the angles 0.02 + k * 0.00001 the first 256 kept hash 1 on the
+ * full-size frames, 43 of 20 000 on the preview.  The kernel's mosaic mode against the parent: whole frames and windows within the parent's spread except
+ * two readings, f32 -> f32 crop 5 % at 100 MP 1.740 -> 1.771 ms (spread 0.015) and the 256x256 window of the scale-1.5 preview to u8 0.0250 -> 0.0267 ms
+ * (spread 0.0014); the f32 whole frames are 1.0 - 1.8 % behind the parent, the u16 ones between 1.1 % ahead and 0.6 % behind. */
+IPK_API int ipk_pipeline_resamples_cached_region(const ipk_pipeline_desc *d, int out_type);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Multi-GPU: one process per GPU; a frame batch shards with no exchange (frame i -> rank i mod N, */
