@@ -1521,6 +1521,7 @@ int ipk_selftest_cbrtf(const float *in, float *out, size_t n, int variant, void 
 // allow_fused as the switch it began as: any non-zero value means "on" -- except IPK_FUSED_CACHED_RESAMPLE standing alone, a bit younger than that rule,
 // which no route, report or region plan may see (with it or without it they answer the same, for every mask)
 static bool fused_on(const ipk_pipeline_desc *d) { return (d->allow_fused & ~IPK_FUSED_CACHED_RESAMPLE) != 0; }
+static bool opted(const ipk_pipeline_desc *d, int bit) { return (d->allow_fused & (IPK_FUSED_ON | bit)) == (IPK_FUSED_ON | bit); }   // an opt-in bit counts beside IPK_FUSED_ON only
 // the descriptor's OpRotateCrop in its reset() state (pipeline.rs:314-316)
 static ipk::RotateCrop rotatecrop_of(const ipk_pipeline_desc *d) {
   ipk::RotateCrop rc;
@@ -1760,7 +1761,7 @@ struct Route {
 // So at most one raw link holds for a descriptor, wherever the fast-path test sits.  Fast path against raster is the one pair the order decides.
 // out_type enters through the fast path and fp.out_type alone: the cached driver, which produces f32 whatever the caller asked for, asks with
 // IPK_OUT_F32 after it has tested the fast path on the caller's type itself.
-bool plain_opted(const ipk_pipeline_desc *d) { const int both = IPK_FUSED_ON | IPK_FUSED_PLAIN; return (d->allow_fused & both) == both; }
+bool plain_opted(const ipk_pipeline_desc *d) { return opted(d, IPK_FUSED_PLAIN); }
 void choose_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Route &rt) {
   rt.kind = kStaged; rt.four = false; rt.pw = n.r.width; rt.ph = n.r.height; rt.label = rt.region_label = "";
   rt.plain = false; rt.plain_kind = IPK_PLAIN_RASTER;
@@ -1866,34 +1867,47 @@ int launch_route(const Route &rt, const void *src, const ipk::ResampleWindow *wi
   }
   return fail(IPK_ERR_INVALID, "internal: no such launch for this route");
 }
-// A one-launch route, then OpTransform: the launch writes the image of the output type (fp.out_type) into dst itself when the orientation is Normal,
-// else into a scratch image that the permutation moves into dst -- after the quantisation, so it moves 3 or 6 bytes per pixel instead of 12.
-// win: a region (launch_route); want_w x want_h: the size the caller's dst holds, checked against what launch and permutation produce before
-// anything is enqueued.
+// The launch-then-orient step of every driver: `launch` enqueues the 3-sample pw x ph image in front of OpTransform into the pointer it is handed -- dst
+// itself when there is nothing to permute (permute = false behind another orientation than Normal: the launch applies OpTransform itself), else a scratch
+// image of the output type that orient() moves into dst.  want_w x want_h: what dst holds, checked against the result before anything is enqueued
+extern "C++" template <typename Launch>
+int launch_then_orient(size_t pw, size_t ph, int out_type, bool permute, int orientation, size_t want_w, size_t want_h, void *dst, void *stream, Launch launch) {
+  bool t, fx, fy; ipk::orientation_to_flips(orientation, t, fx, fy);
+  if ((t ? ph : pw) != want_w || (t ? pw : ph) != want_h)
+    return fail(IPK_ERR_INVALID, "internal: the launch produces %zux%zu (orientation %d), wanted %zux%zu", pw, ph, orientation, want_w, want_h);
+  if (!permute) return launch(dst);
+  Scratch sc(S(stream));
+  void *tmp = nullptr; size_t ow = 0, oh = 0;
+  int rc = sc.get(pw * ph * 3 * out_elem_size(out_type), &tmp); if (rc) return rc;
+  rc = launch(tmp); if (rc < 0) return rc;
+  rc = orient(tmp, pw, ph, orientation, out_type, dst, &ow, &oh, stream);
+  return rc < 0 ? rc : IPK_OK;
+}
+// Rectangle (x, y, w, h) of a 3-sample image full_width pixels wide, packed into dst: one 2-D copy
+int cut_region(const void *full, size_t full_width, size_t elem_size, size_t x, size_t y, size_t w, size_t h, void *dst, void *stream) {
+  const size_t px = 3 * elem_size;
+  HIPCHK(hipMemcpy2DAsync(dst, w * px, static_cast<const char *>(full) + (y * full_width + x) * px, full_width * px, w * px, h, hipMemcpyDeviceToDevice, S(stream)));
+  return IPK_OK;
+}
+// A one-launch route, then OpTransform (launch_then_orient): the launch writes the image of the output type (fp.out_type).  win: a region
+// (launch_route); want_w x want_h: the size the caller's dst holds.
 int run_route(const Route &rt, const Negotiated &n, const void *src, const ipk::ResampleWindow *win, size_t want_w, size_t want_h, void *dst, void *stream) {
   StageTimer tm(S(stream));
   tm.rest = win ? rt.region_label : rt.label;
   const size_t pw = win ? win->cols : rt.pw, ph = win ? win->rows : rt.ph;
-  bool t = false, fx = false, fy = false;
-  if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
-  if ((t ? ph : pw) != want_w || (t ? pw : ph) != want_h)
-    return fail(IPK_ERR_INVALID, "internal: the launch produces %zux%zu (orientation %d), wanted %zux%zu", pw, ph, n.orientation, want_w, want_h);
-  if (n.transform_noop) return launch_route(rt, src, win, dst, stream);
-  if (rt.kind == kFusedRaw && !win) {
+  if (!n.transform_noop && rt.kind == kFusedRaw && !win) {
     // Whole frames of the raw route (every portrait shot): Rotate90 / Rotate270 of a Bayer frame permute the 1-channel mosaic and run the fused
     // kernel in rotated space -- no pass over the 3-channel result at all.  Where no such variant exists the launch below takes over.
     size_t ow = 0, oh = 0;
-    const int rc = ipk_raw_to_srgb_oriented(&rt.fp, src, n.orientation, dst, &ow, &oh, stream);
+    const int rc = launch_then_orient(pw, ph, rt.fp.out_type, false, n.orientation, want_w, want_h, dst, stream,
+                                      [&](void *out) { return ipk_raw_to_srgb_oriented(&rt.fp, src, n.orientation, out, &ow, &oh, stream); });
     if (rc != IPK_ERR_UNSUPPORTED) return rc;
   }
-  Scratch sc(S(stream));
-  void *tmp = nullptr;
-  size_t ow = 0, oh = 0;
-  int rc = sc.get(pw * ph * 3 * out_elem_size(rt.fp.out_type), &tmp); if (rc) return rc;
-  rc = launch_route(rt, src, win, tmp, stream); if (rc < 0) return rc;
-  if (rt.kind == kFusedScaledown && !win) { tm.mark(tm.rest); tm.rest = "transform"; }
-  rc = orient(tmp, pw, ph, n.orientation, rt.fp.out_type, dst, &ow, &oh, stream);
-  return rc < 0 ? rc : IPK_OK;
+  return launch_then_orient(pw, ph, rt.fp.out_type, !n.transform_noop, n.orientation, want_w, want_h, dst, stream, [&](void *out) {
+    const int rc = launch_route(rt, src, win, out, stream);
+    if (rc >= 0 && !n.transform_noop && rt.kind == kFusedScaledown && !win) { tm.mark(tm.rest); tm.rest = "transform"; }
+    return rc;
+  });
 }
 
 // ---- OpGoFloat (gofloat.rs:95-130): what it produces for a descriptor, and the launch that writes it ----
@@ -2059,11 +2073,7 @@ int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scra
   // transform -- for the 8- and 16-bit outputs after the quantise loop instead of before it (orient)
   if (!n.transform_noop && !f32_out) {
     tm.rest = "quantise+transform";
-    void *q = nullptr; size_t ow, oh;
-    rc = sc.get(w * h * 3 * out_elem_size(out_type), &q); if (rc) return rc;
-    rc = quantise(buf, w * h * 3, out_type, q, stream); if (rc < 0) return rc;
-    rc = orient(q, w, h, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-    return produced(ow, oh);
+    return launch_then_orient(w, h, out_type, true, n.orientation, want_w, want_h, dst, stream, [&](void *q) { return quantise(buf, w * h * 3, out_type, q, stream); });
   }
   if (!n.transform_noop) {
     void *o = nullptr; size_t ow, oh;
@@ -2143,8 +2153,7 @@ namespace {
 // region is cut from the whole result
 struct RegionPlan { int windowed, preview; ipk::ResampleWindow win; };
 bool windows_preview(const ipk_pipeline_desc *d, const Negotiated &n, const Route &rt) {
-  const int both = IPK_FUSED_ON | IPK_FUSED_WINDOW_PREVIEWS;
-  return (d->allow_fused & both) == both && rt.kind == kStaged && gofloat_demosaic_one_pass(d, n) && n.rc.noop();
+  return opted(d, IPK_FUSED_WINDOW_PREVIEWS) && rt.kind == kStaged && gofloat_demosaic_one_pass(d, n) && n.rc.noop();
 }
 // the descriptor's negotiation and the region against its result: what every region entry point checks first
 int negotiate_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, Negotiated &n) {
@@ -2263,9 +2272,7 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
     rc = sc.get(n.fw * n.fh * 3 * esz, &full); if (rc) return rc;
     rc = ipk_pipeline_run(d, src, full, out_type, nullptr, stream); if (rc < 0) return rc;
     StageTimer tc(S(stream)); tc.rest = "region copy";
-    HIPCHK(hipMemcpy2DAsync(dst, w * 3 * esz, static_cast<const char *>(full) + (y * n.fw + x) * 3 * esz, n.fw * 3 * esz, w * 3 * esz, h,
-                            hipMemcpyDeviceToDevice, S(stream)));
-    return IPK_OK;
+    return cut_region(full, n.fw, esz, x, y, w, h, dst, stream);
   }
   if (pl.preview) {
     // the scaling pass over the rectangle of the preview, then what run_staged runs behind it, on the rectangle
@@ -2377,6 +2384,19 @@ int ipk_selftest_sha256(const void *data, size_t n, uint8_t *out32) {
 }
 
 namespace {
+int claim_cache(ipk_cache *cache) {
+  if (!cache->owner) cache->owner = ipk_ctx_current();                   // a cache made before ipk_init belongs to the first context that fills it
+  if (cache->owner != ipk_ctx_current()) return fail(IPK_ERR_INVALID, "the cache belongs to another context (its buffers live on that context's device)");
+  return IPK_OK;
+}
+// the latest op among [0, upto) whose output is memoised (pipeline.rs:352-361: every hash is looked up, the last hit wins) into buf; the op to resume at
+int cache_resume(ipk_cache *cache, const ipk::BufHash hs[8], int upto, CBufP &buf) {
+  int startpos = 0;
+  for (int i = 0; i < upto; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
+  return startpos;
+}
+// ops_run bits 3..7 of a launch that runs the point-wise tail with OpTransform: to_lab and from_lab always, the no-ops of the reference not counted
+int pointwise_ops_mask(bool has_curve, const Negotiated &n) { return 0x28 | (has_curve ? 1 << 4 : 0) | (n.linear ? 0 : 1 << 6) | (n.transform_noop ? 0 : 1 << 7); }
 // Ops [from, to) of Pipeline::run(Some(cache)) from `buf` (op from - 1's buffer; unused for from == 0): every buffer materialised enters the cache under
 // its op's hash, a no-op stores its input under its own key, `mask` gains bit i for every op executed and `buf` ends as op to - 1's buffer.  Shared by
 // ipk_pipeline_run_cached (to = 8) and ipk_pipeline_run_cached_region (to = 3: the RGBE buffer its gather launch reads)
@@ -2454,10 +2474,9 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
                             int *ops_run, int *used_fused, void *stream) {
   REQUIRE_INIT();
   if (!d || !src || !dst || !cache) return fail(IPK_ERR_INVALID, "null argument");
-  if (!cache->owner) cache->owner = ipk_ctx_current();                   // a cache made before ipk_init belongs to the first context that fills it
-  if (cache->owner != ipk_ctx_current()) return fail(IPK_ERR_INVALID, "the cache belongs to another context (its buffers live on that context's device)");
+  int rc = claim_cache(cache); if (rc) return rc;
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  int rc = validate_desc(d, out_type, kCheckCurve | kCheckFuse); if (rc) return rc;
+  rc = validate_desc(d, out_type, kCheckCurve | kCheckFuse); if (rc) return rc;
   if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // returns before the cache is consulted (pipeline.rs:381-402), and before the negotiation
     if (ops_run) *ops_run = 0;
     if (used_fused) *used_fused = 0;
@@ -2469,10 +2488,8 @@ int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_
   if (used_fused) *used_fused = 0;
   hipStream_t st = S(stream);
 
-  // the latest op whose output is memoised (pipeline.rs:352-361: every hash is looked up, the last hit wins)
-  CBufP buf; int startpos = 0;
-  for (int i = 0; i < 8; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
-  int mask = 0;
+  CBufP buf;
+  int startpos = cache_resume(cache, hs, 8, buf), mask = 0;
 
   // Nothing memoised and gofloat..transform is one launch on a raw source (any orientation: run_route folds OpTransform in): cheaper on this machine
   // than materialising seven intermediates; only the final buffer enters the cache.  The buffer is f32 whatever the caller wants,
@@ -2508,8 +2525,7 @@ namespace {
 // scales, else the cropped source), no fourth colour -- the one 4-channel buffer whose E is not +0.0 everywhere --, and a transform the launch admits
 struct CachedResample { size_t sw, sh; RotateCropPoints r; ipk::ResamplePlan plan; };
 bool cached_resample(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, CachedResample &c) {
-  const int both = IPK_FUSED_ON | IPK_FUSED_CACHED_RESAMPLE;
-  if ((d->allow_fused & both) != both || ipk_pipeline_takes_fastpath(d, out_type) == 1) return false;
+  if (!opted(d, IPK_FUSED_CACHED_RESAMPLE) || ipk_pipeline_takes_fastpath(d, out_type) == 1) return false;
   if (n.cfa_branch) { ipk::Cfa cfa; if (!ipk::Cfa::parse(d->cfa, cfa) || !cfa.valid() || !cfa.three_colour()) return false; }
   c.sw = n.scale > 1.0f ? n.dw : n.r.width; c.sh = n.scale > 1.0f ? n.dh : n.r.height;
   if (n.rc.noop() || !rotatecrop_of(d).corners(c.sw, c.sh, c.r.pts, c.r.nw, c.r.nh)) return false;
@@ -2535,135 +2551,127 @@ int ipk_pipeline_region_gather(const ipk_pipeline_desc *d, int out_type, size_t 
   return IPK_OK;
 }
 
-int ipk_pipeline_run_cached_region(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache, size_t x, size_t y, size_t w, size_t h,
-                                   void *dst, int out_type, int *ops_run, int *windowed, void *stream) {
-  if (!d || !src || !dst || !cache) return fail(IPK_ERR_INVALID, "null argument");
-  REQUIRE_INIT();
-  if (!cache->owner) cache->owner = ipk_ctx_current();
-  if (cache->owner != ipk_ctx_current()) return fail(IPK_ERR_INVALID, "the cache belongs to another context (its buffers live on that context's device)");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  int rc = validate_desc(d, out_type, kCheckCurve | kCheckFuse); if (rc) return rc;
-  Negotiated n; RegionGather rg;
-  rc = negotiate_region(d, out_type, x, y, w, h, n); if (rc) return rc;
-  rc = region_gather(n, x, y, w, h, rg); if (rc) return rc;
-  if (ops_run) *ops_run = 0;
-  if (windowed) *windowed = 0;
-  hipStream_t st = S(stream);
-  const size_t esz = out_elem_size(out_type);
-  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) {                    // the reference returns before it consults the cache: the whole result, then the rectangle
-    Scratch sc(st);
+namespace {
+// One ipk_pipeline_run_cached_region call behind its checks -- arguments, negotiation, the region's place in the buffer behind OpRotateCrop, hash chain --
+// and the four forms that serve it, one per state of descriptor and cache.  `mask` gains the bit of every op a form executed
+struct CachedRegion {
+  const ipk_pipeline_desc *d; const void *src; ipk_cache *cache; size_t x, y, w, h; void *dst; int out_type; void *stream;
+  Negotiated n; RegionGather rg; ipk::BufHash hs[8];
+  // a fast-path descriptor: the reference returns before it consults the cache: the whole result, then the rectangle
+  int cut_fastpath() const {
+    const size_t esz = out_elem_size(out_type);
+    Scratch sc(S(stream));
     void *full = nullptr;
-    rc = sc.get(n.fw * n.fh * 3 * esz, &full); if (rc) return rc;
+    int rc = sc.get(n.fw * n.fh * 3 * esz, &full); if (rc) return rc;
     rc = run_fastpath(d, src, full, out_type, stream); if (rc < 0) return rc;
-    HIPCHK(hipMemcpy2DAsync(dst, w * 3 * esz, static_cast<const char *>(full) + (y * n.fw + x) * 3 * esz, n.fw * 3 * esz, w * 3 * esz, h, hipMemcpyDeviceToDevice, st));
-    return IPK_OK;
+    return cut_region(full, n.fw, esz, x, y, w, h, dst, stream);
   }
-  ipk::BufHash hs[8]; hash_chain(d, n, source_id, hs);
-  StageTimer tm(st);
-
-  // the final buffer is memoised: the region is cut from it
-  if (CBufP fin = cache->lru.get(hs[7])) {
-    rc = check_produced(n, fin->w, fin->h, fin->colors); if (rc) return rc;
-    const char *from = static_cast<const char *>(fin->p) + (y * n.fw + x) * 3 * sizeof(float);
-    const size_t row = w * 3 * sizeof(float);
+  // the final buffer is memoised: the region is cut from it (8- / 16-bit output: the f32 rectangle into scratch, then the quantiser)
+  int cut_final(const CBufP &fin) const {
+    StageTimer tm(S(stream));
+    int rc = check_produced(n, fin->w, fin->h, fin->colors); if (rc) return rc;
     tm.rest = "region copy";
-    if (out_type == IPK_OUT_F32) { HIPCHK(hipMemcpy2DAsync(dst, row, from, n.fw * 3 * sizeof(float), row, h, hipMemcpyDeviceToDevice, st)); return IPK_OK; }
-    Scratch sc(st);
-    void *rect = nullptr;
-    rc = sc.get(row * h, &rect); if (rc) return rc;
-    HIPCHK(hipMemcpy2DAsync(rect, row, from, n.fw * 3 * sizeof(float), row, h, hipMemcpyDeviceToDevice, st));
+    Scratch sc(S(stream));
+    void *rect = dst;
+    if (out_type != IPK_OUT_F32) { rc = sc.get(w * h * 3 * sizeof(float), &rect); if (rc) return rc; }
+    rc = cut_region(fin->p, n.fw, sizeof(float), x, y, w, h, rect, stream);
+    if (rc || out_type == IPK_OUT_F32) return rc;
     tm.mark(tm.rest); tm.rest = "quantise";
     rc = quantise(rect, w * h * 3, out_type, dst, stream);
     return rc < 0 ? rc : IPK_OK;
   }
-
   // IPK_FUSED_CACHED_RESAMPLE with the rotatecrop buffer missing (a crop or straighten edit): the cache is brought up to op 1 only, and ONE launch resamples
   // the region's rectangle of OpRotateCrop's rg.bw x rg.bh result from that buffer, chain and quantiser behind it (k_fused_resample's cached-buffer
   // source mode).  Nothing enters the cache under hash 2.  Every orientation but Normal: the plain rectangle into scratch, then orient()
-  CachedResample cr;
-  if (cached_resample(d, n, out_type, cr) && !cache->lru.contains(hs[2])) {
-    CBufP buf; int startpos = 0, mask = 0;
-    for (int i = 0; i < 2; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
-    rc = run_cached_ops(d, n, hs, src, cache, startpos, 2, buf, mask, stream); if (rc < 0) return rc;
+  int resample(const CachedResample &cr, int &mask) const {
+    StageTimer tm(S(stream));
+    CBufP buf;
+    const int startpos = cache_resume(cache, hs, 2, buf);
+    int rc = run_cached_ops(d, n, hs, src, cache, startpos, 2, buf, mask, stream); if (rc < 0) return rc;
     if (buf->w != cr.sw || buf->h != cr.sh || buf->colors != 4 || cr.r.nw != rg.bw || cr.r.nh != rg.bh)
       return fail(IPK_ERR_INVALID, "internal: produced %zux%zux%zu in front of rotatecrop (negotiated %zux%zu), rotatecrop to %zux%zu (negotiated %zux%zu)",
                   buf->w, buf->h, buf->colors, cr.sw, cr.sh, cr.r.nw, cr.r.nh, rg.bw, rg.bh);
     if (mask) tm.mark("gofloat..demosaic");
     PointwisePrep pp;
     rc = pp.prepare(buf->mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
-    const size_t npix = w * h;
-    Scratch sc(st);
-    void *o = dst;
-    if (!n.transform_noop) { rc = sc.get(npix * 3 * esz, &o); if (rc) return rc; }
-    pp.f.src = buf->p; pp.f.dst = o; pp.f.src_is_u16 = false; pp.f.out_type = out_type;
+    pp.f.src = buf->p; pp.f.src_is_u16 = false; pp.f.out_type = out_type;
     pp.f.width = buf->w; pp.f.height = buf->h; pp.f.owidth = buf->w;
     pp.f.black0 = 0.0f; pp.f.white0 = 1.0f;                                // not read in this mode
-    if (ipk::launch_fused_resample(pp.f, cr.plan, rg.bw, rg.bh, nullptr, st, &rg.win, 1) != 0)
-      return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
-    HIPCHK(hipGetLastError());
-    tm.mark("region rotatecrop+to_lab+basecurve+from_lab+gamma");
-    if (!n.transform_noop) {
-      tm.rest = "transform";
-      size_t ow = 0, oh = 0;
-      rc = orient(o, rg.win.cols, rg.win.rows, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-      if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", ow, oh, w, h);
-    }
-    mask |= (1 << 2) | (1 << 3) | (1 << 5);
-    if (pp.f.has_curve) mask |= 1 << 4;
-    if (!n.linear) mask |= 1 << 6;
-    if (!n.transform_noop) mask |= 1 << 7;
-    if (ops_run) *ops_run = mask;
-    if (windowed) *windowed = 1;
+    rc = launch_then_orient(rg.win.cols, rg.win.rows, out_type, !n.transform_noop, n.orientation, w, h, dst, stream, [&](void *out) -> int {
+      pp.f.dst = out;
+      if (ipk::launch_fused_resample(pp.f, cr.plan, rg.bw, rg.bh, nullptr, S(stream), &rg.win, 1) != 0)
+        return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
+      HIPCHK(hipGetLastError());
+      tm.mark("region rotatecrop+to_lab+basecurve+from_lab+gamma");
+      if (!n.transform_noop) tm.rest = "transform";
+      return IPK_OK;
+    });
+    mask |= (1 << 2) | pointwise_ops_mask(pp.f.has_curve, n);
     // `buf` may be evicted (and its memory freed) as soon as we return; hipFree waits for the device, so the launch above is safe
-    return IPK_OK;
+    return rc;
   }
-
   // Bring the cache up to op 2: the latest hit among gofloat, demosaic and rotatecrop, then the missing ones as ipk_pipeline_run_cached runs them.  Its
   // whole-frame one-launch shortcut is not taken (the next edit is to find the RGBE buffer), and hits behind op 2 are not used: entering at the RGBE
   // buffer is one launch either way
-  CBufP buf; int startpos = 0, mask = 0;
-  for (int i = 0; i < 3; ++i) { CBufP hit = cache->lru.get(hs[i]); if (hit) { buf = hit; startpos = i + 1; } }
-  rc = run_cached_ops(d, n, hs, src, cache, startpos, 3, buf, mask, stream); if (rc < 0) return rc;
-  if (buf->w != rg.bw || buf->h != rg.bh || buf->colors != 4)
-    return fail(IPK_ERR_INVALID, "internal: produced %zux%zux%zu in front of to_lab, negotiated %zux%zu", buf->w, buf->h, buf->colors, rg.bw, rg.bh);
-  if (mask) tm.mark("gofloat..rotatecrop");
-
-  // ONE launch over the rectangle: to_lab..gamma with OpTransform folded into the load (and the quantisation where the region has the launch's 256 pixels).
-  // The transposing orientations are the exception from 256 pixels up: there a wave's 64 loads of the folded form lie a buffer row apart, one cache line
-  // each, and the launch measured 3.3x the plain rectangle's time at 24 MP (0.68 against 0.20 ms, profiles/r15_cached_region.txt) -- more than orient()
-  // costs on the rectangle.  They take the plain-rectangle gather launch into scratch and orient() behind it, the two-launch form run_tail uses
-  PointwisePrep pp;
-  rc = pp.prepare(buf->mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
-  const size_t npix = w * h;
-  const bool direct = out_type == IPK_OUT_F32 || npix >= 256;
-  const bool two = rg.transposed && npix >= 256;
-  ipk::GatherSource g = rg.g;
-  if (two) g = ipk::GatherSource{(int64_t)(rg.win.row0 * rg.bw + rg.win.col0), 1, (int64_t)rg.bw, rg.win.cols};
-  Scratch sc(st);
-  void *o = dst;
-  if (two) { rc = sc.get(npix * 3 * esz, &o); if (rc) return rc; }
-  else if (!direct) { rc = sc.get(npix * 3 * sizeof(float), &o); if (rc) return rc; }
-  pp.f.src = buf->p; pp.f.dst = o; pp.f.out_type = direct ? out_type : IPK_OUT_F32;
-  const int lrc = pp.f.out_type == IPK_OUT_F32 ? ipk::launch_pointwise_chain(pp.f, npix, st, &g) : ipk::launch_chain_quantised(pp.f, npix, st, &g);
-  if (lrc != 0) return fail(IPK_ERR_INVALID, "internal: the gather launch refused a %zux%zu region", w, h);
-  HIPCHK(hipGetLastError());
-  if (two) {
-    tm.mark("region to_lab+basecurve+from_lab+gamma");
-    tm.rest = "transform";
-    size_t ow = 0, oh = 0;
-    rc = orient(o, rg.win.cols, rg.win.rows, n.orientation, out_type, dst, &ow, &oh, stream); if (rc < 0) return rc;
-    if (ow != w || oh != h) return fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", ow, oh, w, h);
-  } else {
-    tm.mark("region to_lab+basecurve+from_lab+gamma+transform");
-    if (!direct) { tm.rest = "quantise"; rc = quantise(o, npix * 3, out_type, dst, stream); if (rc < 0) return rc; }
+  int gather(int &mask) const {
+    StageTimer tm(S(stream));
+    CBufP buf;
+    const int startpos = cache_resume(cache, hs, 3, buf);
+    int rc = run_cached_ops(d, n, hs, src, cache, startpos, 3, buf, mask, stream); if (rc < 0) return rc;
+    if (buf->w != rg.bw || buf->h != rg.bh || buf->colors != 4)
+      return fail(IPK_ERR_INVALID, "internal: produced %zux%zux%zu in front of to_lab, negotiated %zux%zu", buf->w, buf->h, buf->colors, rg.bw, rg.bh);
+    if (mask) tm.mark("gofloat..rotatecrop");
+    // ONE launch over the rectangle: to_lab..gamma with OpTransform folded into the load (and the quantisation where the region has the launch's 256 pixels).
+    // The transposing orientations are the exception from 256 pixels up: there a wave's 64 loads of the folded form lie a buffer row apart, one cache line
+    // each, and the launch measured 3.3x the plain rectangle's time at 24 MP (0.68 against 0.20 ms, profiles/r15_cached_region.txt) -- more than orient()
+    // costs on the rectangle.  They take the plain-rectangle gather launch into scratch and orient() behind it, the two-launch form run_tail uses
+    PointwisePrep pp;
+    rc = pp.prepare(buf->mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
+    const size_t npix = w * h;
+    const bool direct = out_type == IPK_OUT_F32 || npix >= 256;
+    const bool two = rg.transposed && npix >= 256;
+    const ipk::GatherSource g = two ? ipk::GatherSource{(int64_t)(rg.win.row0 * rg.bw + rg.win.col0), 1, (int64_t)rg.bw, rg.win.cols} : rg.g;
+    pp.f.src = buf->p; pp.f.out_type = direct ? out_type : IPK_OUT_F32;
+    rc = launch_then_orient(rg.win.cols, rg.win.rows, out_type, two, n.orientation, w, h, dst, stream, [&](void *out) -> int {
+      Scratch sc(S(stream));                                               // under 256 pixels an 8- / 16-bit region is the f32 launch and the quantiser
+      void *o = out;
+      if (!direct) { const int grc = sc.get(npix * 3 * sizeof(float), &o); if (grc) return grc; }
+      pp.f.dst = o;
+      const int lrc = pp.f.out_type == IPK_OUT_F32 ? ipk::launch_pointwise_chain(pp.f, npix, S(stream), &g) : ipk::launch_chain_quantised(pp.f, npix, S(stream), &g);
+      if (lrc != 0) return fail(IPK_ERR_INVALID, "internal: the gather launch refused a %zux%zu region", w, h);
+      HIPCHK(hipGetLastError());
+      tm.mark(two ? "region to_lab+basecurve+from_lab+gamma" : "region to_lab+basecurve+from_lab+gamma+transform");
+      if (two) tm.rest = "transform";
+      if (direct) return IPK_OK;
+      tm.rest = "quantise";
+      return quantise(o, npix * 3, out_type, out, stream);
+    });
+    mask |= pointwise_ops_mask(pp.f.has_curve, n);
+    // `buf` may be evicted (and its memory freed) as soon as we return; hipFree waits for the device, so the launch above is safe
+    return rc;
   }
-  mask |= (1 << 3) | (1 << 5);
-  if (pp.f.has_curve) mask |= 1 << 4;
-  if (!n.linear) mask |= 1 << 6;
-  if (!n.transform_noop) mask |= 1 << 7;
-  if (ops_run) *ops_run = mask;
-  if (windowed) *windowed = 1;
-  // `buf` may be evicted (and its memory freed) as soon as we return; hipFree waits for the device, so the launch above is safe
+};
+}  // namespace
+
+int ipk_pipeline_run_cached_region(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache, size_t x, size_t y, size_t w, size_t h,
+                                   void *dst, int out_type, int *ops_run, int *windowed, void *stream) {
+  if (!d || !src || !dst || !cache) return fail(IPK_ERR_INVALID, "null argument");
+  REQUIRE_INIT();
+  int rc = claim_cache(cache); if (rc) return rc;
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  rc = validate_desc(d, out_type, kCheckCurve | kCheckFuse); if (rc) return rc;
+  CachedRegion c = {d, src, cache, x, y, w, h, dst, out_type, stream, {}, {}, {}};
+  rc = negotiate_region(d, out_type, x, y, w, h, c.n); if (rc) return rc;
+  rc = region_gather(c.n, x, y, w, h, c.rg); if (rc) return rc;
+  if (ops_run) *ops_run = 0; if (windowed) *windowed = 0;
+  // the form, in order of precedence: a fast-path descriptor, the final buffer memoised, IPK_FUSED_CACHED_RESAMPLE without the rotatecrop buffer, the gather
+  if (ipk_pipeline_takes_fastpath(d, out_type) == 1) return c.cut_fastpath();
+  hash_chain(d, c.n, source_id, c.hs);
+  if (CBufP fin = cache->lru.get(c.hs[7])) return c.cut_final(fin);
+  CachedResample cr; int mask = 0;
+  rc = cached_resample(d, c.n, out_type, cr) && !cache->lru.contains(c.hs[2]) ? c.resample(cr, mask) : c.gather(mask);
+  if (rc < 0) return rc;
+  if (ops_run) *ops_run = mask; if (windowed) *windowed = 1;
   return IPK_OK;
 }
 

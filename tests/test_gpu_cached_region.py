@@ -271,6 +271,28 @@ def test_final_buffer_memoised_is_cut_not_launched(ipa, orc, out_type):
     cache.close()
 
 
+@pytest.mark.parametrize("out_type", [U8, U16])
+def test_fast_path_descriptor_is_cut_from_the_fast_path_result(ipa, orc, out_type):
+    """an RGB8 raster with the default ops and use_fastpath: the reference returns before it consults the cache, so the region is the rectangle of the
+    integer fast path's result and nothing enters the cache"""
+    import torch
+    sw, sh = 91, 61
+    img = (util.noise_u16(util.SEED + 15010, sh, sw * 3) & 255).astype(np.uint8).reshape(sh, sw, 3)
+    pipe = ipa.Pipeline.new_from_source(ipa.OtherImage(sw, sh, torch.from_numpy(img.ravel()).cuda(), bits=8))
+    pipe.globals.settings.use_fastpath = True
+    assert ipa.lib().ipk_pipeline_takes_fastpath(pipe.desc(), out_type) == 1
+    want = _want(orc, orc.make_pipeline(img, use_fastpath=True), out_type)
+    assert want.shape == (sh, sw, 3)
+    cache = ipa.PipelineCache(1 << 28)
+    for x, y, w, h in [(0, 0, 1, 1), (7, 3, 41, 30), (sw - 1, sh - 1, 1, 1), (0, 0, sw, sh)]:
+        got = pipe.run_region(x, y, w, h, out_type, cache=cache)
+        torch.cuda.synchronize()
+        assert not pipe.last_region_windowed and pipe.last_ops_run == 0, (x, y, w, h)
+        _same(_host(got, out_type, h, w), want[y:y + h, x:x + w], out_type, "fast-path region %r out %d" % ((x, y, w, h), out_type))
+    assert cache.stats()["entries"] == 0
+    cache.close()
+
+
 def test_run_cached_after_regions_is_unchanged(ipa, orc):
     import torch
     pipe, desc = _build(ipa, orc, "xtrans_f32", seed=8, rotation=3)
