@@ -22,7 +22,7 @@ from ._lib import (IpkError, FusedParams, PipelineDesc, OUT_F32, OUT_U8, OUT_U16
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
            "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "raw_to_srgb_resampled_window", "raw_to_srgb_scaled_window",
-           "transform_window_footprint", "raw_scaled_demosaic_window", "raster_scale_down_window", "scaled_window_footprint", "FusedPlan", "IpkError"]
+           "transform_window_footprint", "raw_scaled_demosaic_window", "raw_demosaic_scaled", "raster_scale_down_window", "scaled_window_footprint", "FusedPlan", "IpkError"]
 
 _initialized_device = None
 
@@ -606,6 +606,7 @@ class Pipeline:
         self.window_regions = False           # ipk_pipeline_desc.allow_fused bit 2 (IPK_FUSED_WINDOW_REGIONS): regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch
         self.fuse_plain = False               # ipk_pipeline_desc.allow_fused bit 4 (IPK_FUSED_PLAIN): cropped RGB8 / RGB16 rasters and u16 monochrome / three-sample raws as one launch where fuses_plain() says so; regions of every frame on the raster launch windowed
         self.resample_cached = False          # ipk_pipeline_desc.allow_fused bit 5 (IPK_FUSED_CACHED_RESAMPLE): run_region with a cache resamples the region from the cached demosaic buffer when the rotatecrop buffer is missing, where resamples_cached_region() says so; that call then never fills the rotatecrop hash
+        self.fuse_scaled_rotatecrop = False   # ipk_pipeline_desc.allow_fused bit 6 (IPK_FUSED_SCALED_ROTATECROP): an active OpRotateCrop behind a scaling OpDemosaic as two launches where fuses_scaled_rotatecrop() says so; regions of such frames windowed
         self.window_previews = False          # ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
 
     @staticmethod
@@ -677,6 +678,8 @@ class Pipeline:
             d.allow_fused |= _lib.FUSED_PLAIN
         if self.resample_cached and d.allow_fused:
             d.allow_fused |= _lib.FUSED_CACHED_RESAMPLE
+        if self.fuse_scaled_rotatecrop and d.allow_fused:
+            d.allow_fused |= _lib.FUSED_SCALED_ROTATECROP
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -707,6 +710,11 @@ class Pipeline:
         """Does this cropped raster / u16 monochrome or three-sample raw run as the one launch ipk_plain_to_srgb (ipk_pipeline_fuses_plain, host-only)?"""
         d = self.desc()
         return bool(_lib.check(lib().ipk_pipeline_fuses_plain(C.byref(d), out_type), "ipk_pipeline_fuses_plain"))
+
+    def fuses_scaled_rotatecrop(self, out_type=OUT_F32) -> bool:
+        """Does the run take the two-launch route through a scaling OpDemosaic and an active OpRotateCrop (ipk_pipeline_fuses_scaled_rotatecrop, host-only)?"""
+        d = self.desc()
+        return bool(_lib.check(lib().ipk_pipeline_fuses_scaled_rotatecrop(C.byref(d), out_type), "ipk_pipeline_fuses_scaled_rotatecrop"))
 
     def resamples_cached_region(self, out_type=OUT_F32) -> bool:
         """Would run_region with a cache resample the region straight from the cached demosaic buffer (ipk_pipeline_resamples_cached_region, host-only)?"""
@@ -957,6 +965,26 @@ def transform_window_footprint(width, height, corners, nwidth, nheight, window):
     _lib.check(lib().ipk_transform_window_footprint(width, height, *[int(c) for c in corners], nwidth, nheight, wx, wy, ww, wh, out4),
                "ipk_transform_window_footprint")
     return tuple(int(v) for v in out4)
+
+
+def raw_demosaic_scaled(src: torch.Tensor, owidth, x, y, width, height, black0, white0, cfa, nwidth, nheight, window=None, *,
+                        out: Optional[torch.Tensor] = None):
+    """ipk_raw_demosaic_scaled (window = None) / ipk_raw_demosaic_scaled_window: gofloat + demosaic::full + scale_down_opbuf to nwidth x nheight of the
+    sensor window (x, y, width, height) of an owidth-pitched u16 (int16 / uint16 tensor) or f32 frame in one launch -- OpDemosaic's branch below minscale.
+    window = (wx, wy, ww, wh): that rectangle of the result alone.  Returns the packed 4-channel f32 device tensor (E = +0.0)."""
+    st = SRC_F32 if src.dtype == torch.float32 else SRC_U16
+    if window is None:
+        if out is None:
+            out = torch.empty(nheight * nwidth * 4, dtype=torch.float32, device="cuda")
+        _lib.check(lib().ipk_raw_demosaic_scaled(src.data_ptr(), st, owidth, x, y, width, height, black0, white0, cfa.encode(), nwidth, nheight,
+                                                 out.data_ptr(), _stream()), "ipk_raw_demosaic_scaled")
+        return out
+    wx, wy, ww, wh = _check_window(nwidth, nheight, window)
+    if out is None:
+        out = torch.empty(wh * ww * 4, dtype=torch.float32, device="cuda")
+    _lib.check(lib().ipk_raw_demosaic_scaled_window(src.data_ptr(), st, owidth, x, y, width, height, black0, white0, cfa.encode(), nwidth, nheight,
+                                                    wx, wy, ww, wh, out.data_ptr(), _stream()), "ipk_raw_demosaic_scaled_window")
+    return out
 
 
 def raw_scaled_demosaic_window(src: torch.Tensor, owidth, x, y, width, height, black0, white0, cfa, nwidth, nheight, window, *,

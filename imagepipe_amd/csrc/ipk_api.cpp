@@ -1405,6 +1405,46 @@ int ipk_raw_to_srgb_scaled_window(const ipk_fused_params *p, const void *src, si
   const ipk::ResampleWindow win = {wy, wx, wh, ww};
   return resampled_launch(p, src, nullptr, nwidth, nheight, dst, stream, "scaled", kScaledRefusal, &win);
 }
+// OpGoFloat (CFA branch) + OpDemosaic::run's `full` + scale_down_opbuf branch (demosaic.rs:51-59) in one launch, into the nwidth x nheight 4-channel f32
+// buffer ipk_gofloat_cfa_* -> ipk_demosaic_run write for such a frame, bit for bit: k_fused_resample's axis walk in its RGBE output mode (no chain, no
+// quantiser).  The sibling of ipk_raw_scaled_demosaic for the scales below minscale; win: that rectangle of the result alone, packed.  A filter with a
+// fourth colour (E is not +0.0 there) and geometry scaledown_plan refuses get IPK_ERR_UNSUPPORTED with nothing enqueued
+static int raw_demosaic_scaled_impl(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
+                                    const char *cfa_pat, size_t nwidth, size_t nheight, const ipk::ResampleWindow *win, float *dst4, void *stream) {
+  REQUIRE_INIT();
+  if (!src || !dst4 || !cfa_pat || !dims_ok(width, height) || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32) || owidth < x + width)
+    return fail(IPK_ERR_INVALID, "bad raw_demosaic_scaled arguments");
+  if (win && !window_ok(nwidth, nheight, win->col0, win->row0, win->cols, win->rows))
+    return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", win->col0, win->row0, win->cols, win->rows, nwidth, nheight);
+  ipk::Cfa cfa; DevCfa dev;
+  { int rc = get_cfa(cfa_pat, cfa, dev); if (rc) return rc; }
+  if (!cfa.three_colour()) return fail(IPK_ERR_UNSUPPORTED, "CFA \"%s\" has a fourth colour; run the staged ops", cfa_pat);
+  ipk::ResamplePlan plan;
+  if (!ipk::scaledown_plan(width, height, nwidth, nheight, plan)) return fail(IPK_ERR_UNSUPPORTED, "%s", kScaledRefusal);
+  PointwisePrep pp;                                                          // the mode reads none of the point-wise parameters: any ordinary set
+  { int rc = pp.prepare(1, nullptr, nullptr, 0.0f, nullptr, 0, 1); if (rc) return rc; }
+  const size_t esz = src_type == IPK_SRC_U16 ? 2 : 4;
+  pp.f.src = static_cast<const char *>(src) + (y * owidth + x) * esz;        // the cropped frame's first sample
+  pp.f.dst = dst4;
+  pp.f.src_is_u16 = src_type == IPK_SRC_U16;
+  pp.f.width = width; pp.f.height = height; pp.f.owidth = owidth;
+  pp.f.black0 = black0; pp.f.white0 = white0;
+  pp.f.exact_norm = validate_cdiv_for_range(black0, white0 - black0, pp.f.src_is_u16) ? 0 : 1;
+  pp.f.out_type = IPK_OUT_F32;
+  if (ipk::launch_fused_resample(pp.f, plan, nwidth, nheight, dev.lookups, S(stream), win, 0, 1) != 0)
+    return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
+  HIPCHK(hipGetLastError());
+  return IPK_OK;
+}
+int ipk_raw_demosaic_scaled(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
+                            const char *cfa_pat, size_t nwidth, size_t nheight, float *dst4, void *stream) {
+  return raw_demosaic_scaled_impl(src, src_type, owidth, x, y, width, height, black0, white0, cfa_pat, nwidth, nheight, nullptr, dst4, stream);
+}
+int ipk_raw_demosaic_scaled_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
+                                   const char *cfa_pat, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream) {
+  const ipk::ResampleWindow win = {wy, wx, wh, ww};
+  return raw_demosaic_scaled_impl(src, src_type, owidth, x, y, width, height, black0, white0, cfa_pat, nwidth, nheight, &win, dst4, stream);
+}
 // what such a window reads of the cropped frame (host only): ipk::resample_footprint on the skips of the corners
 int ipk_transform_window_footprint(size_t width, size_t height, int64_t tlx, int64_t tly, int64_t trx, int64_t try_, int64_t blx, int64_t bly,
                                    size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, size_t *out4) {
@@ -1519,8 +1559,9 @@ int ipk_selftest_cbrtf(const float *in, float *out, size_t n, int variant, void 
 // Pipeline::run (src/pipeline.rs:311-375) for one source, cache == None
 // ------------------------------------------------------------------------------------------
 // allow_fused as the switch it began as: any non-zero value means "on" -- except IPK_FUSED_CACHED_RESAMPLE standing alone, a bit younger than that rule,
-// which no route, report or region plan may see (with it or without it they answer the same, for every mask)
-static bool fused_on(const ipk_pipeline_desc *d) { return (d->allow_fused & ~IPK_FUSED_CACHED_RESAMPLE) != 0; }
+// which no route, report or region plan may see (with it or without it they answer the same, for every mask); IPK_FUSED_SCALED_ROTATECROP, younger still,
+// likewise counts beside IPK_FUSED_ON only and is nothing alone
+static bool fused_on(const ipk_pipeline_desc *d) { return (d->allow_fused & ~(IPK_FUSED_CACHED_RESAMPLE | IPK_FUSED_SCALED_ROTATECROP)) != 0; }
 static bool opted(const ipk_pipeline_desc *d, int bit) { return (d->allow_fused & (IPK_FUSED_ON | bit)) == (IPK_FUSED_ON | bit); }   // an opt-in bit counts beside IPK_FUSED_ON only
 // the descriptor's OpRotateCrop in its reset() state (pipeline.rs:314-316)
 static ipk::RotateCrop rotatecrop_of(const ipk_pipeline_desc *d) {
@@ -1727,10 +1768,13 @@ void fused_params_of(const ipk_pipeline_desc *d, const Negotiated &n, int out_ty
 // raster kind reads the source type, the size and the point-wise parameters from it); rcp: what OpRotateCrop::run hands to transform_buffer (kFusedResample);
 // pw x ph: the image the launch produces before OpTransform; four: kFusedRaw with a fourth colour in the launch (fp.four_colour = 1); label /
 // region_label: the stage run_timed shows for a whole frame / a windowed region ----
-enum RouteKind { kFastPath, kFusedRaw, kFusedResample, kFusedScaledown, kFusedRaster, kStaged };
+enum RouteKind { kFastPath, kFusedRaw, kFusedResample, kFusedScaledown, kFusedRaster, kScaledRotateCrop, kStaged };
+enum ScalingPass { kPassScaledDemosaic, kPassDemosaicScaled, kPassRasterScaleDown };   // raw_scaled_demosaic_impl, raw_demosaic_scaled_impl, raster_scale_down_impl
 struct RotateCropPoints { int64_t pts[6]; size_t nw, nh; };
 struct Route {
   RouteKind kind; ipk_fused_params fp; RotateCropPoints rcp; size_t pw, ph; bool four;
+  // kScaledRotateCrop: the launch that writes the n.dw x n.dh RGBE buffer, and the plan of the resampling launch over that buffer (rcp: its corners)
+  ScalingPass pass1; ipk::ResamplePlan plan2;
   const char *label, *region_label;
   // kFusedRaster: plain = the frame is on the link because of IPK_FUSED_PLAIN (a cropped raster, a u16 three-sample or monochrome raw) and its launch is
   // ipk_plain_to_srgb of plain_kind (ipk_plain_kind) over the crop rectangle with these levels; an uncropped raster has plain = false, plain_kind 0
@@ -1762,6 +1806,28 @@ struct Route {
 // out_type enters through the fast path and fp.out_type alone: the cached driver, which produces f32 whatever the caller asked for, asks with
 // IPK_OUT_F32 after it has tested the fast path on the caller's type itself.
 bool plain_opted(const ipk_pipeline_desc *d) { return opted(d, IPK_FUSED_PLAIN); }
+// An ACTIVE OpRotateCrop as one resampling launch over the sw x sh 4-channel buffer OpDemosaic hands it: the op accepts its crops there (corners) and the
+// transform is one k_fused_resample admits (resample_plan).  Shared by the cached region driver (cached_resample) and the two-launch route below
+bool rotatecrop_resamples(const ipk_pipeline_desc *d, const Negotiated &n, size_t sw, size_t sh, RotateCropPoints &r, ipk::ResamplePlan &plan) {
+  if (n.rc.noop() || !rotatecrop_of(d).corners(sw, sh, r.pts, r.nw, r.nh)) return false;
+  return ipk::resample_plan(sw, sh, r.pts[0], r.pts[1], r.pts[2], r.pts[3], r.pts[4], r.pts[5], r.nw, r.nh, plan);
+}
+// IPK_FUSED_SCALED_ROTATECROP (tried where the chain below ends staged): an active OpRotateCrop behind an OpDemosaic that scales, as TWO launches -- the
+// scaling gofloat + demosaic pass into the n.dw x n.dh RGBE buffer, then k_fused_resample's cached-buffer source mode over that buffer with the chain and
+// the quantiser behind it.  Pass 1 exists as one launch for a cpp == 1 mosaic with a valid three-colour filter (scale >= minscale: the scaled_demosaic
+// kernels; below it: k_fused_resample's RGBE output mode where scaledown_plan admits the geometry) and for an RGB8 / RGB16 raster.  A fourth colour (E is
+// not +0.0 there), monochrome and three-sample raws, scale <= 1 (fuse_rotatecrop's ground) and a no-op rotatecrop stay where they were
+bool scaled_rotatecrop(const ipk_pipeline_desc *d, const Negotiated &n, Route &rt) {
+  if (!opted(d, IPK_FUSED_SCALED_ROTATECROP) || n.rc.noop() || !(n.scale > 1.0f)) return false;
+  if (n.raw) {
+    ipk::Cfa cfa; ipk::ResamplePlan p1;
+    if (!n.cfa_branch || d->cpp != 1 || !ipk::Cfa::parse(d->cfa, cfa) || !cfa.valid() || !cfa.three_colour()) return false;
+    if (n.scale >= ipk::demosaic_minscale(cfa.width)) rt.pass1 = kPassScaledDemosaic;
+    else if (ipk::scaledown_plan(n.r.width, n.r.height, n.dw, n.dh, p1)) rt.pass1 = kPassDemosaicScaled;
+    else return false;
+  } else rt.pass1 = kPassRasterScaleDown;
+  return rotatecrop_resamples(d, n, n.dw, n.dh, rt.rcp, rt.plan2);
+}
 void choose_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Route &rt) {
   rt.kind = kStaged; rt.four = false; rt.pw = n.r.width; rt.ph = n.r.height; rt.label = rt.region_label = "";
   rt.plain = false; rt.plain_kind = IPK_PLAIN_RASTER;
@@ -1794,6 +1860,11 @@ void choose_route(const ipk_pipeline_desc *d, const Negotiated &n, int out_type,
     std::memcpy(rt.black4, d->blacklevels, sizeof(rt.black4)); std::memcpy(rt.white4, d->whitelevels, sizeof(rt.white4));
     rt.label = "fused gofloat+to_lab+basecurve+from_lab+gamma(+transform)";
     rt.region_label = "fused region gofloat+to_lab+basecurve+from_lab+gamma(+transform)";      // regions under IPK_FUSED_PLAIN (plan_region)
+  }
+  if (rt.kind == kStaged && scaled_rotatecrop(d, n, rt)) {
+    rt.kind = kScaledRotateCrop; rt.pw = r.nw; rt.ph = r.nh;
+    rt.label = "rotatecrop+to_lab+basecurve+from_lab+gamma";                                // behind "gofloat+demosaic" (run_scaled_rotatecrop)
+    rt.region_label = "region rotatecrop+to_lab+basecurve+from_lab+gamma";
   }
   if (rt.kind == kStaged) return;
   fused_params_of(d, n, out_type, rt.fp);
@@ -1953,6 +2024,73 @@ int launch_gofloat_demosaic(const ipk_pipeline_desc *d, const Negotiated &n, con
 int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scratch &sc, void *buf, size_t w, size_t h, size_t colors, int monochrome,
              size_t want_w, size_t want_h, void *dst, StageTimer &tm, void *stream);
 
+// ---- kScaledRotateCrop: the scaling pass into the n.dw x n.dh RGBE buffer, then the resampling launch over it (choose_route / scaled_rotatecrop) ----
+// Every tile box of the resampling launch over window w2 -- the kernel's rs_box: the extremes of the windows at the tile's four corner pixels -- lies
+// inside the rectangle F of the buffer (an empty F: every box is empty).  resample_footprint's header argues it; the launch below reads a scratch that
+// holds F alone, so the host checks it tile by tile before anything is enqueued
+bool tile_boxes_inside(const ipk::ResamplePlan &p, size_t W, size_t H, const ipk::ResampleWindow &w2, const ipk::ResampleFootprint &F) {
+  for (size_t q0 = 0; q0 < w2.rows; q0 += p.tile_h) {
+    for (size_t p0 = 0; p0 < w2.cols; p0 += p.tile_w) {
+      const uint32_t r[2] = {(uint32_t)(w2.row0 + q0), (uint32_t)(w2.row0 + std::min<size_t>(q0 + p.tile_h, w2.rows) - 1)};
+      const uint32_t c[2] = {(uint32_t)(w2.col0 + p0), (uint32_t)(w2.col0 + std::min<size_t>(p0 + p.tile_w, w2.cols) - 1)};
+      uint32_t x0 = 0xFFFFFFFFu, x1 = 0u, y0 = 0xFFFFFFFFu, y1 = 0u;
+      for (int i = 0; i < 4; ++i) {
+        uint32_t w[4];
+        ipk::resample_window_at(p, (uint32_t)W, (uint32_t)H, r[i >> 1], c[i & 1], w);
+        x0 = std::min(x0, w[0]); x1 = std::max(x1, w[1]); y0 = std::min(y0, w[2]); y1 = std::max(y1, w[3]);
+      }
+      if (x1 < x0 || y1 < y0) continue;                                     // the kernel reads nothing for this tile
+      if (F.w == 0 || x0 < F.x || y0 < F.y || x1 >= F.x + F.w || y1 >= F.y + F.h) return false;
+    }
+  }
+  return true;
+}
+// the rectangle of the n.dw x n.dh buffer that window w2 of OpRotateCrop's result reads (w == 0: no pixel of it has a tap)
+ipk::ResampleFootprint scaled_rotatecrop_footprint(const Route &rt, const Negotiated &n, const ipk::ResampleWindow &w2) {
+  return ipk::resample_footprint(rt.plan2, n.dw, n.dh, w2.row0, w2.col0, w2.rows, w2.cols);
+}
+// win: the rectangle of OpRotateCrop's rt.pw x rt.ph result a region comes from (plan_region); null: the whole frame.  want_w x want_h: what dst holds
+int run_scaled_rotatecrop(const ipk_pipeline_desc *d, const Negotiated &n, const Route &rt, const void *src, const ipk::ResampleWindow *win, size_t want_w,
+                          size_t want_h, void *dst, void *stream) {
+  StageTimer tm(S(stream));
+  const ipk::ResampleWindow whole = {0, 0, rt.rcp.nh, rt.rcp.nw};
+  const ipk::ResampleWindow &w2 = win ? *win : whole;
+  // pass 1 writes F packed: the whole buffer for a whole frame, the region's footprint in it otherwise
+  ipk::ResampleFootprint F = {0, 0, n.dw, n.dh};
+  if (win) F = scaled_rotatecrop_footprint(rt, n, w2);
+  if (!tile_boxes_inside(rt.plan2, n.dw, n.dh, w2, F)) return fail(IPK_ERR_INVALID, "internal: a tile of the resampling launch leaves the %zux%zu footprint", F.w, F.h);
+  Scratch sc(S(stream));
+  void *buf = nullptr;
+  int rc = sc.get(std::max<size_t>(F.w * F.h, 1) * 4 * sizeof(float), &buf); if (rc) return rc;
+  if (F.w != 0) {
+    const ipk::ResampleWindow w1 = {F.y, F.x, F.h, F.w};
+    const ipk::ResampleWindow *pw1 = win ? &w1 : nullptr;
+    rc = rt.pass1 == kPassDemosaicScaled
+             ? raw_demosaic_scaled_impl(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, d->blacklevels[0], d->whitelevels[0], d->cfa, n.dw, n.dh,
+                                        pw1, static_cast<float *>(buf), stream)
+             : launch_gofloat_demosaic(d, n, src, pw1, static_cast<float *>(buf), stream);
+    if (rc < 0) return rc;
+  }
+  tm.mark(win ? "region gofloat+demosaic" : "gofloat+demosaic");
+  // pass 2 addresses its source in the buffer's own coordinates: the pointer is moved back by F's origin and the pitch is F's width, so pixel (x, y) of
+  // the buffer is pixel (x - F.x, y - F.y) of the scratch; the kernel reads tile boxes only, all inside F (above)
+  PointwisePrep pp;
+  rc = pp.prepare(0, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
+  pp.f.src = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(buf) - (uintptr_t)(F.y * F.w + F.x) * 4 * sizeof(float));
+  pp.f.src_is_u16 = false; pp.f.out_type = rt.fp.out_type;
+  pp.f.width = n.dw; pp.f.height = n.dh; pp.f.owidth = F.w;
+  pp.f.black0 = 0.0f; pp.f.white0 = 1.0f;                                  // not read in this mode
+  return launch_then_orient(w2.cols, w2.rows, rt.fp.out_type, !n.transform_noop, n.orientation, want_w, want_h, dst, stream, [&](void *out) -> int {
+    pp.f.dst = out;
+    if (ipk::launch_fused_resample(pp.f, rt.plan2, rt.rcp.nw, rt.rcp.nh, nullptr, S(stream), &w2, 1) != 0)
+      return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
+    HIPCHK(hipGetLastError());
+    tm.mark(win ? rt.region_label : rt.label);
+    if (!n.transform_noop) tm.rest = "transform";
+    return IPK_OK;
+  });
+}
+
 // ---- staged path: the eight ops in the reference's order (pipeline.rs:155-164) ----
 int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, const void *src, void *dst, StageTimer &tm, void *stream) {
   Scratch sc(S(stream));
@@ -2105,7 +2243,8 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
   if (used_fused) *used_fused = 0;
   Route rt; choose_route(d, n, out_type, rt);
   if (rt.kind == kStaged) { StageTimer tm(S(stream)); return run_staged(d, n, out_type, src, dst, tm, stream); }
-  rc = run_route(rt, n, src, nullptr, n.fw, n.fh, dst, stream);
+  rc = rt.kind == kScaledRotateCrop ? run_scaled_rotatecrop(d, n, rt, src, nullptr, n.fw, n.fh, dst, stream)
+                                    : run_route(rt, n, src, nullptr, n.fw, n.fh, dst, stream);
   if (rc == IPK_OK && used_fused) *used_fused = 1;
   return rc;
 }
@@ -2131,6 +2270,11 @@ int ipk_pipeline_fuses_four_colour(const ipk_pipeline_desc *d, int out_type) {
 int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type) {
   Route rt; const int rc = report_route(d, out_type, rt);
   return rc ? rc : rt.kind == kFusedScaledown;
+}
+// IPK_FUSED_SCALED_ROTATECROP: does an active OpRotateCrop behind a scaling OpDemosaic run as the two launches of scaled_rotatecrop()?
+int ipk_pipeline_fuses_scaled_rotatecrop(const ipk_pipeline_desc *d, int out_type) {
+  Route rt; const int rc = report_route(d, out_type, rt);
+  return rc ? rc : rt.kind == kScaledRotateCrop;
 }
 // IPK_FUSED_PLAIN: does a cropped raster / a u16 three-sample or monochrome raw run as the one launch ipk_plain_to_srgb (the whole-frame half of the bit)?
 int ipk_pipeline_fuses_plain(const ipk_pipeline_desc *d, int out_type) {
@@ -2180,7 +2324,7 @@ int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, si
   choose_route(d, n, out_type, rt);
   const bool opted = (d->allow_fused & IPK_FUSED_WINDOW_REGIONS) != 0;
   pl.preview = windows_preview(d, n, rt) ? 1 : 0;
-  pl.windowed = (pl.preview || rt.kind == kFusedRaw || (opted && (rt.kind == kFusedResample || rt.kind == kFusedScaledown)) ||
+  pl.windowed = (pl.preview || rt.kind == kFusedRaw || rt.kind == kScaledRotateCrop || (opted && (rt.kind == kFusedResample || rt.kind == kFusedScaledown)) ||
                  (rt.kind == kFusedRaster && plain_opted(d) && w * h >= 256)) ? 1 : 0;
   if (!pl.windowed) return IPK_OK;
   bool t, fx, fy;
@@ -2231,6 +2375,18 @@ int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size
   const ipk::ResampleWindow &win = pl.win;
   if (pl.preview) {
     const ipk::ResampleFootprint f = ipk::scaled_window_footprint(n.r.width, n.r.height, n.dw, n.dh, win.row0, win.col0, win.rows, win.cols);
+    *src_x = n.r.x + f.x; *src_y = n.r.y + f.y; *src_w = f.w; *src_h = f.h;
+    return 1;
+  }
+  if (rt.kind == kScaledRotateCrop) {
+    // what pass 1's window launch over F -- the rectangle's footprint in the n.dw x n.dh buffer -- reads, in sensor coordinates; empty where F is
+    const ipk::ResampleFootprint F = scaled_rotatecrop_footprint(rt, n, win);
+    ipk::ResampleFootprint f = {0, 0, 0, 0};
+    ipk::ResamplePlan p1;
+    if (F.w != 0 && rt.pass1 == kPassDemosaicScaled) {
+      if (!ipk::scaledown_plan(n.r.width, n.r.height, n.dw, n.dh, p1)) return fail(IPK_ERR_INVALID, "internal: the route's plan was refused");
+      f = ipk::resample_footprint(p1, n.r.width, n.r.height, F.y, F.x, F.h, F.w);
+    } else if (F.w != 0) f = ipk::scaled_window_footprint(n.r.width, n.r.height, n.dw, n.dh, F.y, F.x, F.h, F.w);
     *src_x = n.r.x + f.x; *src_y = n.r.y + f.y; *src_w = f.w; *src_h = f.h;
     return 1;
   }
@@ -2285,6 +2441,7 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
     return run_tail(d, n, out_type, sc, buf, pl.win.cols, pl.win.rows, 4, 0, w, h, dst, tm, stream);
   }
   // the one-launch routes: the window launch writes the rectangle into dst, or into scratch for OpTransform's permutation
+  if (rt.kind == kScaledRotateCrop) return run_scaled_rotatecrop(d, n, rt, src, &pl.win, w, h, dst, stream);
   return run_route(rt, n, src, &pl.win, w, h, dst, stream);
 }
 
@@ -2528,8 +2685,7 @@ bool cached_resample(const ipk_pipeline_desc *d, const Negotiated &n, int out_ty
   if (!opted(d, IPK_FUSED_CACHED_RESAMPLE) || ipk_pipeline_takes_fastpath(d, out_type) == 1) return false;
   if (n.cfa_branch) { ipk::Cfa cfa; if (!ipk::Cfa::parse(d->cfa, cfa) || !cfa.valid() || !cfa.three_colour()) return false; }
   c.sw = n.scale > 1.0f ? n.dw : n.r.width; c.sh = n.scale > 1.0f ? n.dh : n.r.height;
-  if (n.rc.noop() || !rotatecrop_of(d).corners(c.sw, c.sh, c.r.pts, c.r.nw, c.r.nh)) return false;
-  return ipk::resample_plan(c.sw, c.sh, c.r.pts[0], c.r.pts[1], c.r.pts[2], c.r.pts[3], c.r.pts[4], c.r.pts[5], c.r.nw, c.r.nh, c.plan);
+  return rotatecrop_resamples(d, n, c.sw, c.sh, c.r, c.plan);
 }
 }  // namespace
 int ipk_pipeline_resamples_cached_region(const ipk_pipeline_desc *d, int out_type) {

@@ -3592,6 +3592,16 @@ int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const
 // hides behind the arithmetic: two barriers per tile.
 // A window launch (ResampleArgs::wr0 / wc0: regions, ipk_raw_to_srgb_*_window) walks the tiles of a rectangle of the output image instead: fewer tiles,
 // the same arithmetic per pixel.
+// The RGBE output mode (ResampleArgs::axis == 3, f32-output instantiations only: ipk_raw_demosaic_scaled, pass 1 under IPK_FUSED_SCALED_ROTATECROP): the
+// axis walk's two pixels per lane are stored as they are -- R, G, B and E = +0.0, 32 contiguous bytes per lane of a packed nw x nh x 4 image, the buffer
+// ipk_gofloat_cfa_* -> ipk_demosaic_run write -- and neither the chain nor a quantiser runs.  Two choices, both by measurement at 24 MP (5999 x 3999,
+// profiles/r17_scaled_rotatecrop.txt):
+//   the tables are NOT staged: the mode reads none of the 96 KB; staging them anyway measured the same (pass 1 alone 0.437 against 0.437 ms, whole frames
+//       and regions inside the spread), so the mode does the lesser work;
+//   plain stores, not non-temporal ones: non-temporal stores took 4 % off pass 1 alone (0.437 -> 0.418 ms) but the two launches of a whole frame
+//       moved inside the spread (1.085 -> 1.072 ms, spread 0.017) and a quarter-area region got slower (0.316 -> 0.320 ms): pass 2 reads the buffer
+//       straight back, and a region's footprint fits the last-level cache.
+// The mode costs the two f32-output instantiations one vector register and no scratch; the four quantising instantiations compile to the code they were.
 // ------------------------------------------------------------------------------------------
 struct ResampleArgs {
   // nw x nh: the output window this launch computes and stores packed into dst -- the whole result, or (launch_fused_resample's ResampleWindow) the
@@ -3607,6 +3617,8 @@ struct ResampleArgs {
                                          // 2: the general walk, as 0, over the source mode below (rs_fill_rgb): a.src is the demosaiced frame itself, dense
                                          //    4-channel f32 of W x H pixels (f32 instantiations only; lookups unused).  One field for both: the kernel has no
                                          //    scalar register to spare, and a second flag kept across the tile loop spilled four vector registers to scratch
+                                         // 3: the axis walk of 1 with the RGBE output mode (f32-output instantiations only; launch_fused_resample's rgbe_out):
+                                         //    stage 3 stores the walk's pixels as a packed nw x nh x 4 f32 image and runs neither the chain nor a quantiser
   const uint32_t *lookups;
 };
 struct RsWin { uint32_t fx, tx, fy, ty; };
@@ -3793,13 +3805,19 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
   __shared__ float s_par[32];
   __shared__ __attribute__((aligned(16))) float s_mos[kResampleMosCap];
   __shared__ __attribute__((aligned(16))) float s_rgb[3 * kResampleRgbCap];
-  stage_table_direct(s_lab, a.lab_table, a.lab_pairs);
-  stage_table_direct(s_gam, a.gam_table, a.gam_pairs);
-  if (threadIdx.x < 4) s_par[threadIdx.x] = a.tolab.mul[threadIdx.x];
-  else if (threadIdx.x < 16) s_par[threadIdx.x] = a.tolab.cm[threadIdx.x - 4];
-  else if (threadIdx.x < 25) s_par[threadIdx.x] = a.rgbm.m[threadIdx.x - 16];
-  if (threadIdx.x < kSplineMaxKnots) fill_knots(s_knots, a.spline, (int)threadIdx.x);
-  if (a.spline.grid_ok) fill_grid(s_grid, a.spline, (int)threadIdx.x);
+#ifdef IPK_RGBE_OUT_STAGE_TABLES                                          // development switch (tools/build_variant.sh): the mode stages the tables it never reads
+  {
+#else
+  if (!(OUT == 0 && t.axis == 3)) {                                     // the RGBE output mode reads no table and no point-wise parameter (header above)
+#endif
+    stage_table_direct(s_lab, a.lab_table, a.lab_pairs);
+    stage_table_direct(s_gam, a.gam_table, a.gam_pairs);
+    if (threadIdx.x < 4) s_par[threadIdx.x] = a.tolab.mul[threadIdx.x];
+    else if (threadIdx.x < 16) s_par[threadIdx.x] = a.tolab.cm[threadIdx.x - 4];
+    else if (threadIdx.x < 25) s_par[threadIdx.x] = a.rgbm.m[threadIdx.x - 16];
+    if (threadIdx.x < kSplineMaxKnots) fill_knots(s_knots, a.spline, (int)threadIdx.x);
+    if (a.spline.grid_ok) fill_grid(s_grid, a.spline, (int)threadIdx.x);
+  }
 
   uint32_t tile = blockIdx.x;                                           // the grid never exceeds the tile count
   // the lane's two pixels inside a tile: neighbours in one tile row (tile_w is even); the same two as positions in the result for the window's first tile
@@ -3863,7 +3881,7 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
       const float center_y_r = t.tly + (t.skip_y_y * (float)row) + (t.skip_y_y / 2.0f) - 0.5f;
       float4 px[2];
       bool ok[2];
-      if (t.axis == 1) {                                                // block-uniform: the launch's mode
+      if (t.axis == 1 || (OUT == 0 && t.axis == 3)) {                   // block-uniform: the launch's mode
         rs_walk_axis(t, box, a.W, a.H, s_rgb, row, col0, wcol0, row_ok, center_x_r, center_y_r, px, ok);
       } else {
         #pragma unroll
@@ -3897,6 +3915,23 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
           px[j] = make_float4(has ? s0 / n : 0.0f, has ? s1 / n : 0.0f, has ? s2 / n : 0.0f, 0.0f);
         }
       }
+      if (OUT == 0 && t.axis == 3) {
+        // the RGBE output mode: the walk's two pixels as they are, E = +0.0, 32 contiguous bytes per lane of the packed nw x nh x 4 image (a pixel of
+        // the packed image is 16 bytes from dst, which the allocator or the caller's element alignment gives no more than 4-byte alignment of)
+        typedef float f4a __attribute__((ext_vector_type(4), aligned(4)));
+        f4a *g = reinterpret_cast<f4a *>(reinterpret_cast<float *>(a.dst) + ((size_t)wrow * t.nw + wcol0) * 4u);
+        #pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          if (ok[j]) {
+            f4a v; v.x = px[j].x; v.y = px[j].y; v.z = px[j].z; v.w = px[j].w;
+#ifdef IPK_RGBE_OUT_NT                                                    // development switch (tools/build_variant.sh): non-temporal stores
+            __builtin_nontemporal_store(v, g + j);
+#else
+            g[j] = v;
+#endif
+          }
+        }
+      } else {
       PixOut o[2];
       bool bad = a.fast_ok == 0;
       if (a.fast_ok) bad |= pointwise4_fast<true, false, 1>(a, s_par, s_lab, s_gam, s_knots, px, o, a.has_curve != 0, a.linear != 0, 0, nullptr, s_grid);
@@ -3935,6 +3970,7 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
           __builtin_nontemporal_store(w0, gv); __builtin_nontemporal_store(w1, gv + 1); __builtin_nontemporal_store(w2, gv + 2);
         } else if (ok[0]) { g[0] = (uint16_t)w0; g[1] = (uint16_t)(w0 >> 16); g[2] = (uint16_t)w1; }
       }
+      }
     }
     if (!more) break;
     if (rgbe) {                                                           // s_rgb is stage 3's source: every wave has to be through with it first
@@ -3950,8 +3986,9 @@ __global__ __launch_bounds__(1024) void k_fused_resample(FusedArgs a, ResampleAr
 }
 
 int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s,
-                          const ResampleWindow *win, int src_rgbe) {
+                          const ResampleWindow *win, int src_rgbe, int rgbe_out) {
   if (src_rgbe && (f.src_is_u16 || plan.axis || !win)) return -1;          // a mode of the f32 instantiations' general window launches alone
+  if (rgbe_out && (f.out_type != 0 || !plan.axis || src_rgbe)) return -1;  // a mode of the f32-output instantiations' axis walk alone
   FusedArgs a = chain_args(f);
   a.W = (uint32_t)f.width; a.H = (uint32_t)f.height; a.owidth = f.owidth;
   a.min0 = f.black0; a.range0 = f.white0 - f.black0;                       // gofloat.rs:86-89
@@ -3970,13 +4007,16 @@ int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t
   t.skip_x_x = plan.skip_x_x; t.skip_x_y = plan.skip_x_y; t.skip_y_x = plan.skip_y_x; t.skip_y_y = plan.skip_y_y;
   t.inv_skip_x_x = 1.0f / t.skip_x_x; t.inv_skip_y_y = 1.0f / t.skip_y_y;
   t.fast_x = cdiv_host_ok(t.skip_x_x); t.fast_y = cdiv_host_ok(t.skip_y_y);
-  t.axis = src_rgbe ? 2 : plan.axis ? 1 : 0;
+  t.axis = src_rgbe ? 2 : rgbe_out ? 3 : plan.axis ? 1 : 0;
   t.lookups = lookups_dev;
   const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = (unsigned)std::min<uint64_t>(cus, tiles);
   // the general mode's tags stay as they were; the axis-aligned mode (scaledown_plan) adds its own key
   // and a window launch (win) its own next to them; the cached-buffer source mode (src_rgbe: window launches only) appends rgbe=1
+  // the RGBE output mode (rgbe_out: the axis walk alone) appends rgbe_out=1 behind axis=1, and win=1 behind that on window launches
   const char *tag = src_rgbe ? (a.fast_ok ? "fast_ok=1,win=1,rgbe=1" : "fast_ok=0,win=1,rgbe=1") :
+                    rgbe_out ? (win ? (a.fast_ok ? "fast_ok=1,axis=1,rgbe_out=1,win=1" : "fast_ok=0,axis=1,rgbe_out=1,win=1")
+                                    : (a.fast_ok ? "fast_ok=1,axis=1,rgbe_out=1" : "fast_ok=0,axis=1,rgbe_out=1")) :
                     win ? (plan.axis ? (a.fast_ok ? "fast_ok=1,axis=1,win=1" : "fast_ok=0,axis=1,win=1") : (a.fast_ok ? "fast_ok=1,win=1" : "fast_ok=0,win=1"))
                         : (plan.axis ? (a.fast_ok ? "fast_ok=1,axis=1" : "fast_ok=0,axis=1") : (a.fast_ok ? "fast_ok=1" : "fast_ok=0"));
   #define IPK_RS_LAUNCH(T, O) IPK_LAUNCH_TAG(tag, (k_fused_resample<T, O>), dim3(blocks), dim3(1024), 0, s, a, t)

@@ -53,7 +53,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // k_fused_resample's axis-aligned mode (ipk_raw_to_srgb_scaled) [fast_ok=,axis=1]; k_fused_resample's window launches (launch_fused_resample with a
 // ResampleWindow: ipk_raw_to_srgb_resampled_window / _scaled_window, regions under IPK_FUSED_WINDOW_REGIONS) append win=1: [fast_ok=,win=1] /
 // [fast_ok=,axis=1,win=1] -- whole-frame launches never carry the key; its window launches over a cached 4-channel buffer (src_rgbe:
-// ipk_pipeline_run_cached_region under IPK_FUSED_CACHED_RESAMPLE) append rgbe=1 behind that: [fast_ok=,win=1,rgbe=1]; the generic-CFA runtime-flag variants of k_fused_bayer /
+// ipk_pipeline_run_cached_region under IPK_FUSED_CACHED_RESAMPLE, both passes' second under IPK_FUSED_SCALED_ROTATECROP) append rgbe=1 behind that:
+// [fast_ok=,win=1,rgbe=1]; its RGBE output mode (ipk_raw_demosaic_scaled / _window) [fast_ok=,axis=1,rgbe_out=1] / [fast_ok=,axis=1,rgbe_out=1,win=1]; the generic-CFA runtime-flag variants of k_fused_bayer /
 // k_fused_bayer_window [four=1] on the launches of a filter with a fourth colour only (FusedLaunch::four) -- three-colour launches carry no tag.
 void launch_log_enable(bool on);                 // clears the log, then switches it on or off
 size_t launch_log_read(char *buf, size_t cap);   // entries sorted, newline-separated, NUL-terminated (truncated to cap); returns the bytes a full read needs
@@ -136,8 +137,11 @@ int launch_fused_bayer(const FusedLaunch &f, hipStream_t s);
 // src_rgbe (f32 instantiations, general plans, window launches only: -1 otherwise, nothing launched): f.src is the demosaiced frame itself -- the dense
 // 4-channel f32 buffer in front of OpRotateCrop, f.width x f.height pixels, f.owidth pixels per row, E = +0.0 in every pixel -- so the kernel loads each
 // tile's box straight from it and skips its gofloat and demosaic stages; levels and lookups_dev are not read.  The launch adds the key rgbe=1
+// rgbe_out (f.out_type 0 and plan.axis only, not with src_rgbe: -1 otherwise, nothing launched): the RGBE output mode -- f.dst holds the nwidth x nheight
+// (or the window's) result of gofloat + demosaic::full + scale_down_opbuf as packed 4-channel f32 pixels, E = +0.0, what ipk_demosaic_run writes for such a
+// frame; the point-wise parameters and tables of f are not read.  Whole frames and windows; the launch adds the key rgbe_out=1 behind axis=1
 int launch_fused_resample(const FusedLaunch &f, const ResamplePlan &plan, size_t nwidth, size_t nheight, const uint32_t *lookups_dev, hipStream_t s,
-                          const ResampleWindow *win = nullptr, int src_rgbe = 0);
+                          const ResampleWindow *win = nullptr, int src_rgbe = 0, int rgbe_out = 0);
 // rotate_buffer's permutation on a 1-channel image through an arbitrary source pitch / window (steps in source elements): |x_step| == 1 (flips, 180
 // degrees) or |y_step| == 1 (the transposing orientations, oheight <= kRotate1MaxTransposedRows)
 constexpr size_t kRotate1MaxTransposedRows = 65535u * 64u;

@@ -250,6 +250,19 @@ IPK_API int ipk_raw_scaled_demosaic_window(const void *src, int src_type, size_t
                                            size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
 IPK_API int ipk_raster_scale_down_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
                                          size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
+/* OpGoFloat::run_raw (CFA branch) followed by OpDemosaic::run's LAST branch -- demosaic::full, then scale_down_opbuf to nwidth x nheight
+ * (src/ops/demosaic.rs:51-59: 1 < scale < minscale) -- in one launch over the raw sensor frame: ipk_raw_scaled_demosaic's sibling below minscale.  dst4
+ * receives nwidth * nheight * 4 f32, bit for bit what ipk_gofloat_cfa_* -> ipk_demosaic_run write for such a frame (E = +0.0); the full-size 1- and
+ * 4-channel buffers never exist.  The launch is k_fused_resample's axis-aligned walk (ipk_raw_to_srgb_scaled) in its RGBE output mode: the resampled
+ * pixels are stored as they are, no point-wise chain, no quantiser.  src_type IPK_SRC_U16 or IPK_SRC_F32.  IPK_ERR_UNSUPPORTED with nothing enqueued for
+ * a filter with a fourth colour and for geometry ipk_raw_to_srgb_scaled refuses (output sides >= 2, both skips at least 1 and below 3, sides below
+ * 2^24).  The window form computes the columns [wx, wx + ww) and rows [wy, wy + wh) of that result alone, packed, bit-identical to the rectangle of the
+ * whole-frame call; what it reads is ipk_transform_window_footprint of scale_down_opbuf's corners (0, 0), (width - 1, 0), (0, height - 1). */
+IPK_API int ipk_raw_demosaic_scaled(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                    float black0, float white0, const char *cfa, size_t nwidth, size_t nheight, float *dst4, void *stream);
+IPK_API int ipk_raw_demosaic_scaled_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                           float black0, float white0, const char *cfa, size_t nwidth, size_t nheight,
+                                           size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
 /* What such a window reads of the width x height cropped frame, host-only (no GPU needed): out4 = {x, y, w, h} in cropped-frame coordinates.  The
  * bounding box of the taps of the window's pixels (src/scaling.rs:84-87 with scale_down_buffer's corners (0, 0), (width - 1, 0), (0, height - 1), in
  * f32 as the kernels compute them), its columns widened by the 8-sample row loads of the window-8 kernels (a lane loads [lx, lx + 8) with
@@ -511,7 +524,10 @@ typedef struct {
                                       ipk_pipeline_resamples_cached_region says so and the rotatecrop buffer (hash 2) is not memoised, the region is resampled
                                       from the cached demosaic buffer (hash 1) in one launch instead of running OpRotateCrop over the whole frame first.  Same
                                       contract: no hash, no result, no region report.  Without bit 0 it does nothing -- not even what "any non-zero value"
-                                      does: allow_fused = 32 is 0 to every route and report. */
+                                      does: allow_fused = 32 is 0 to every route and report.
+                                      Bit 6 (IPK_FUSED_SCALED_ROTATECROP = 64), beside IPK_FUSED_ON as well: an active OpRotateCrop behind an OpDemosaic that
+                                      scales runs as TWO launches where ipk_pipeline_fuses_scaled_rotatecrop says so, whole frames and (windowed) regions.
+                                      Same contract: no hash, no result.  Like bit 5 it is nothing alone: allow_fused = 64 is 0 to every route and report. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -549,11 +565,14 @@ typedef enum {
                                       faster beyond the noise: a whole-area region through the host form uploads the whole frame either way, 2.77 -> 2.66 |
                                       2.41 -> 2.27 ms.  The cost to launches that use neither mode (the kernels test for them once per 256-pixel chunk):
                                       ipk_raster_to_srgb, RGB8 -> u8 at 24 MP, parent 0.1269 ms (its spread 0.0033) -> 0.1283 ms */
-  IPK_FUSED_CACHED_RESAMPLE = 32   /* bit 5 (beside bit 0): ipk_pipeline_run_cached_region resamples a region straight from the cached demosaic buffer when the
+  IPK_FUSED_CACHED_RESAMPLE = 32,  /* bit 5 (beside bit 0): ipk_pipeline_run_cached_region resamples a region straight from the cached demosaic buffer when the
                                       rotatecrop buffer is missing (a crop or straighten edit), where ipk_pipeline_resamples_cached_region says so: one launch
                                       of k_fused_resample's cached-buffer source mode over the rectangle instead of OpRotateCrop over the whole frame plus the
                                       gather launch.  The trade-off: while the bit is set that call never fills hash 2 (see ipk_pipeline_run_cached_region).
                                       Measurements: profiles/r16_cached_resample.txt */
+  IPK_FUSED_SCALED_ROTATECROP = 64 /* bit 6 (beside bit 0): a straightened or cropped frame whose OpDemosaic scales (with an angle the reverse size fold usually
+                                      lands a pixel short, so this is the common straightened frame, and every straightened preview) runs as two launches
+                                      instead of the staged ops, where ipk_pipeline_fuses_scaled_rotatecrop says so; regions of such frames are windowed */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -614,6 +633,26 @@ IPK_API int ipk_pipeline_windows_preview(const ipk_pipeline_desc *d, int out_typ
  * -- uncropped rasters included: their one launch does not depend on the bit (only their regions do) --, f32 monochrome / three-sample raws
  * (staged: the launch has no f32 form), mosaics; a negative error code for a descriptor ipk_pipeline_sizes refuses.  No GPU needed. */
 IPK_API int ipk_pipeline_fuses_plain(const ipk_pipeline_desc *d, int out_type);
+/* Does ipk_pipeline_run (and the host, batch and multi-device drivers; the cached drivers are unchanged) run this descriptor's frame as TWO launches: the
+ * scaling gofloat + demosaic pass into the negotiated demosaic-size RGBE buffer, then ONE resampling launch over that buffer (k_fused_resample's 4-channel
+ * source mode: OpRotateCrop's transform_buffer, tolab..gamma and the quantiser), then OpTransform's permutation if there is one?  1 when d->allow_fused has
+ * IPK_FUSED_ON and IPK_FUSED_SCALED_ROTATECROP set, the frame does not take the fast path, OpRotateCrop is active and accepts its crops on the
+ * demosaic-size buffer, OpDemosaic scales (scale > 1), the resampling launch admits the transform (windows of at most 3x3), and pass 1 exists as one
+ * launch: a one-sample-per-pixel mosaic with a valid three-colour filter at scale >= minscale (ipk_raw_scaled_demosaic) or at 1 < scale < minscale with
+ * geometry ipk_raw_demosaic_scaled takes, or an RGB8 / RGB16 raster (ipk_raster_scale_down).  0 otherwise: filters with a fourth colour (E is not +0.0
+ * there), monochrome and three-sample raws, scale <= 1 (fuse_rotatecrop's ground), a no-op rotatecrop, the bit without IPK_FUSED_ON.  Regions of such a
+ * descriptor are windowed under the same bit: pass 1 runs over the footprint F of the region's rectangle in the demosaic-size buffer, pass 2 over the
+ * rectangle, and ipk_pipeline_region reports what pass 1 reads for F plus the crop offset.  ipk_timing names the stages "gofloat+demosaic",
+ * "rotatecrop+to_lab+basecurve+from_lab+gamma" and "transform".  A negative error code for a descriptor ipk_pipeline_sizes refuses.  No GPU needed.
+ * Traffic model for a 24 MP u16 mosaic at scale 1.00025 to u8: the staged ops move about 109 bytes per pixel in five launches, this route about 37 in
+ * two.  Measured (profiles/r17_scaled_rotatecrop.txt; noise frames at rotation 0.02, wall clock, medians, the parent build's run -> this route):
+ * 6000x4000 RGGB u16 (negotiates 5999x3999) to u8, whole frame 1.473 -> 1.079 ms, 1/16 of the area 1.483 -> 0.122 ms, 1/4 1.522 -> 0.315 ms (to f32:
+ * 1.480 -> 1.088, 1.492 -> 0.122, 1.536 -> 0.316); the same under maxwidth 4000 (scale 1.5) 0.872 -> 0.668, 0.865 -> 0.098, 0.882 -> 0.219 ms.  Where
+ * pass 1 is a launch the staged drivers already had, the regions are the gain and whole frames are level: 8640x5760 X-Trans under maxwidth 2160, whole
+ * frame 0.184 -> 0.180 ms (this build's own staged run in the same process: 0.179), 1/16 0.185 -> 0.055, 1/4 0.189 -> 0.080 ms; a 6000x4000 RGB8 raster
+ * under maxwidth 3000, 0.275 -> 0.266 ms (own staged run 0.264), 0.272 -> 0.048, 0.280 -> 0.094 ms.  No measured case was slower than the parent's run;
+ * none is excluded.  Not measured: 100 MP frames, 16-bit outputs, photo-like data. */
+IPK_API int ipk_pipeline_fuses_scaled_rotatecrop(const ipk_pipeline_desc *d, int out_type);
 /* do_timing! (src/pipeline.rs:68-80: the reference logs the wall time of every op of Pipeline::run): ipk_timing_begin arms the calling
  * thread, the following ipk_pipeline_run call(s) on it bracket every stage they enqueue with hipEvents on their stream, ipk_timing_end
  * waits for the last one and returns the stages in execution order under the reference's op names ("gofloat", "demosaic", "rotatecrop",
