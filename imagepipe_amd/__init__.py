@@ -17,12 +17,13 @@ import torch
 from . import _lib
 from ._lib import (IpkError, FusedParams, PipelineDesc, OUT_F32, OUT_U8, OUT_U16, SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16,
                    OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN,
-                   ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP)
+                   ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO)
 
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
            "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "raw_to_srgb_resampled_window", "raw_to_srgb_scaled_window",
-           "transform_window_footprint", "raw_scaled_demosaic_window", "raw_demosaic_scaled", "raster_scale_down_window", "scaled_window_footprint", "FusedPlan", "IpkError"]
+           "transform_window_footprint", "raw_scaled_demosaic_window", "raw_demosaic_scaled", "raster_scale_down_window", "scaled_window_footprint", "plain_scale_down",
+           "plain_scale_down_window", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FusedPlan", "IpkError"]
 
 _initialized_device = None
 
@@ -607,6 +608,7 @@ class Pipeline:
         self.fuse_plain = False               # ipk_pipeline_desc.allow_fused bit 4 (IPK_FUSED_PLAIN): cropped RGB8 / RGB16 rasters and u16 monochrome / three-sample raws as one launch where fuses_plain() says so; regions of every frame on the raster launch windowed
         self.resample_cached = False          # ipk_pipeline_desc.allow_fused bit 5 (IPK_FUSED_CACHED_RESAMPLE): run_region with a cache resamples the region from the cached demosaic buffer when the rotatecrop buffer is missing, where resamples_cached_region() says so; that call then never fills the rotatecrop hash
         self.fuse_scaled_rotatecrop = False   # ipk_pipeline_desc.allow_fused bit 6 (IPK_FUSED_SCALED_ROTATECROP): an active OpRotateCrop behind a scaling OpDemosaic as two launches where fuses_scaled_rotatecrop() says so; regions of such frames windowed
+        self.scale_plain = False              # ipk_pipeline_desc.allow_fused bit 7 (IPK_FUSED_PLAIN_PREVIEWS): downscaled previews of monochrome / three-sample raws (u16, f32) run gofloat + demosaic as the one launch ipk_plain_scale_down where scales_plain() says so; window_previews and fuse_scaled_rotatecrop then take them too
         self.window_previews = False          # ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
 
     @staticmethod
@@ -680,6 +682,8 @@ class Pipeline:
             d.allow_fused |= _lib.FUSED_CACHED_RESAMPLE
         if self.fuse_scaled_rotatecrop and d.allow_fused:
             d.allow_fused |= _lib.FUSED_SCALED_ROTATECROP
+        if self.scale_plain and d.allow_fused:
+            d.allow_fused |= _lib.FUSED_PLAIN_PREVIEWS
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -715,6 +719,11 @@ class Pipeline:
         """Does the run take the two-launch route through a scaling OpDemosaic and an active OpRotateCrop (ipk_pipeline_fuses_scaled_rotatecrop, host-only)?"""
         d = self.desc()
         return bool(_lib.check(lib().ipk_pipeline_fuses_scaled_rotatecrop(C.byref(d), out_type), "ipk_pipeline_fuses_scaled_rotatecrop"))
+
+    def scales_plain(self, out_type=OUT_F32) -> bool:
+        """Do OpGoFloat and the scaling OpDemosaic of this monochrome / three-sample raw run as the one launch ipk_plain_scale_down (ipk_pipeline_scales_plain, host-only)?"""
+        d = self.desc()
+        return bool(_lib.check(lib().ipk_pipeline_scales_plain(C.byref(d), out_type), "ipk_pipeline_scales_plain"))
 
     def resamples_cached_region(self, out_type=OUT_F32) -> bool:
         """Would run_region with a cache resample the region straight from the cached demosaic buffer (ipk_pipeline_resamples_cached_region, host-only)?"""
@@ -1009,6 +1018,39 @@ def raster_scale_down_window(src: torch.Tensor, owidth, x, y, width, height, nwi
         out = torch.empty(wh * ww * 4, dtype=torch.float32, device="cuda")
     _lib.check(lib().ipk_raster_scale_down_window(src.data_ptr(), SRC_RGB8 if src.dtype == torch.uint8 else SRC_RGB16, owidth, x, y, width, height,
                                                   nwidth, nheight, wx, wy, ww, wh, out.data_ptr(), _stream()), "ipk_raster_scale_down_window")
+    return out
+
+
+def _plain_levels(kind, black4, white4):
+    if kind == PLAIN_RASTER:
+        return None, None
+    return (C.c_float * 4)(*[float(v) for v in black4]), (C.c_float * 4)(*[float(v) for v in white4])
+
+
+def plain_scale_down(src: torch.Tensor, kind, owidth, x, y, width, height, black4, white4, nwidth, nheight, *, out: Optional[torch.Tensor] = None):
+    """ipk_plain_scale_down: OpGoFloat + scale_down_opbuf in one pass over the window (x, y, width, height) of an owidth-pitched source whose OpGoFloat
+    writes a 4-channel buffer.  kind PLAIN_MONO (one sample per pixel) / PLAIN_RGB (three): a u16 (int16 / uint16 tensor) or f32 raw with the level
+    pairs black4 / white4; PLAIN_RASTER: an RGB8 (uint8 tensor) or RGB16 raster (levels ignored).  Returns the nheight*nwidth*4 f32 device tensor (E = 0)."""
+    st = (SRC_RGB8 if src.dtype == torch.uint8 else SRC_RGB16) if kind == PLAIN_RASTER else (SRC_F32 if src.dtype == torch.float32 else SRC_U16)
+    b, w = _plain_levels(kind, black4, white4)
+    if out is None:
+        out = torch.empty(nheight * nwidth * 4, dtype=torch.float32, device="cuda")
+    _lib.check(lib().ipk_plain_scale_down(src.data_ptr(), st, kind, owidth, x, y, width, height, b, w, nwidth, nheight, out.data_ptr(), _stream()),
+               "ipk_plain_scale_down")
+    return out
+
+
+def plain_scale_down_window(src: torch.Tensor, kind, owidth, x, y, width, height, black4, white4, nwidth, nheight, window, *,
+                            out: Optional[torch.Tensor] = None):
+    """ipk_plain_scale_down_window: the columns [wx, wx+ww) and rows [wy, wy+wh) of plain_scale_down's result, window = (wx, wy, ww, wh), by the same
+    kernel laid over the window.  Returns the wh*ww*4 f32 device tensor."""
+    st = (SRC_RGB8 if src.dtype == torch.uint8 else SRC_RGB16) if kind == PLAIN_RASTER else (SRC_F32 if src.dtype == torch.float32 else SRC_U16)
+    b, w = _plain_levels(kind, black4, white4)
+    wx, wy, ww, wh = _check_window(nwidth, nheight, window)
+    if out is None:
+        out = torch.empty(wh * ww * 4, dtype=torch.float32, device="cuda")
+    _lib.check(lib().ipk_plain_scale_down_window(src.data_ptr(), st, kind, owidth, x, y, width, height, b, w, nwidth, nheight, wx, wy, ww, wh,
+                                                 out.data_ptr(), _stream()), "ipk_plain_scale_down_window")
     return out
 
 

@@ -843,7 +843,36 @@ int raster_scale_down_impl(const void *src, int src_type, size_t owidth, size_t 
   HIPCHK(hipGetLastError());
   return IPK_OK;
 }
+// gofloat_mono / gofloat_rgb + scale_down_opbuf in one pass: the monochrome and three-sample modes of k_raw_scaled_demosaic<T>.  IPK_PLAIN_RASTER forwards
+// to the raster kernel; admission is raster_scale_down_impl's
+int plain_scale_down_impl(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height, const float *black4,
+                          const float *white4, size_t nwidth, size_t nheight, const ipk::ResampleWindow *win, float *dst4, void *stream) {
+  if (kind == IPK_PLAIN_RASTER) return raster_scale_down_impl(src, src_type, owidth, x, y, width, height, nwidth, nheight, win, dst4, stream);
+  REQUIRE_INIT();
+  if (kind != IPK_PLAIN_RGB && kind != IPK_PLAIN_MONO) return fail(IPK_ERR_INVALID, "bad plain kind");
+  if (!src || !dst4 || !black4 || !white4 || !dims_ok(width, height) || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32))
+    return fail(IPK_ERR_INVALID, "bad plain_scale_down arguments");
+  if (x + width > owidth) return fail(IPK_ERR_INVALID, "plain_scale_down: window wider than the source pitch");
+  if (win && !window_ok(nwidth, nheight, win->col0, win->row0, win->cols, win->rows))
+    return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", win->col0, win->row0, win->cols, win->rows, nwidth, nheight);
+  ipk::PlainLevels pl;
+  pl.layout = kind == IPK_PLAIN_MONO ? 1 : 3;
+  for (int c = 0; c < 3; ++c) { pl.black[c] = black4[c]; pl.white[c] = white4[c]; }
+  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(static_cast<const uint16_t *>(src), owidth, x, y, width, height, 0.0f, 0.0f, 0, 0, nwidth, nheight, nullptr, 0, 0, dst4, S(stream), 0, 0, 0, win, &pl);
+  else ipk::launch_raw_scaled_demosaic<float>(static_cast<const float *>(src), owidth, x, y, width, height, 0.0f, 0.0f, 0, 0, nwidth, nheight, nullptr, 0, 0, dst4, S(stream), 0, 0, 0, win, &pl);
+  HIPCHK(hipGetLastError());
+  return IPK_OK;
+}
 }  // namespace
+int ipk_plain_scale_down(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height, const float *black4,
+                         const float *white4, size_t nwidth, size_t nheight, float *dst4, void *stream) {
+  return plain_scale_down_impl(src, src_type, kind, owidth, x, y, width, height, black4, white4, nwidth, nheight, nullptr, dst4, stream);
+}
+int ipk_plain_scale_down_window(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height, const float *black4,
+                                const float *white4, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream) {
+  const ipk::ResampleWindow win = {wy, wx, wh, ww};
+  return plain_scale_down_impl(src, src_type, kind, owidth, x, y, width, height, black4, white4, nwidth, nheight, &win, dst4, stream);
+}
 int ipk_raw_scaled_demosaic(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
                             float black0, float white0, const char *cfa_pat, size_t nwidth, size_t nheight, float *dst4, void *stream) {
   return raw_scaled_demosaic_impl(src, src_type, owidth, x, y, width, height, black0, white0, cfa_pat, nwidth, nheight, nullptr, dst4, stream);
@@ -1806,6 +1835,11 @@ struct Route {
 // out_type enters through the fast path and fp.out_type alone: the cached driver, which produces f32 whatever the caller asked for, asks with
 // IPK_OUT_F32 after it has tested the fast path on the caller's type itself.
 bool plain_opted(const ipk_pipeline_desc *d) { return opted(d, IPK_FUSED_PLAIN); }
+// IPK_FUSED_PLAIN_PREVIEWS: a monochrome or three-sample raw (u16 or f32: the raws OpGoFloat does not treat as a mosaic, negotiate) whose OpDemosaic
+// scales its 4-channel buffer (demosaic.rs:44-46) runs gofloat + demosaic as the one launch ipk_plain_scale_down
+bool scales_plain(const ipk_pipeline_desc *d, const Negotiated &n) {
+  return opted(d, IPK_FUSED_PLAIN_PREVIEWS) && n.raw && !n.cfa_branch && n.scale > 1.0f;
+}
 // An ACTIVE OpRotateCrop as one resampling launch over the sw x sh 4-channel buffer OpDemosaic hands it: the op accepts its crops there (corners) and the
 // transform is one k_fused_resample admits (resample_plan).  Shared by the cached region driver (cached_resample) and the two-launch route below
 bool rotatecrop_resamples(const ipk_pipeline_desc *d, const Negotiated &n, size_t sw, size_t sh, RotateCropPoints &r, ipk::ResamplePlan &plan) {
@@ -1815,13 +1849,19 @@ bool rotatecrop_resamples(const ipk_pipeline_desc *d, const Negotiated &n, size_
 // IPK_FUSED_SCALED_ROTATECROP (tried where the chain below ends staged): an active OpRotateCrop behind an OpDemosaic that scales, as TWO launches -- the
 // scaling gofloat + demosaic pass into the n.dw x n.dh RGBE buffer, then k_fused_resample's cached-buffer source mode over that buffer with the chain and
 // the quantiser behind it.  Pass 1 exists as one launch for a cpp == 1 mosaic with a valid three-colour filter (scale >= minscale: the scaled_demosaic
-// kernels; below it: k_fused_resample's RGBE output mode where scaledown_plan admits the geometry) and for an RGB8 / RGB16 raster.  A fourth colour (E is
-// not +0.0 there), monochrome and three-sample raws, scale <= 1 (fuse_rotatecrop's ground) and a no-op rotatecrop stay where they were
+// kernels; below it: k_fused_resample's RGBE output mode where scaledown_plan admits the geometry), for an RGB8 / RGB16 raster and, under
+// IPK_FUSED_PLAIN_PREVIEWS, for a monochrome or three-sample raw (ipk_plain_scale_down).  A fourth colour (E is not +0.0 there), monochrome and
+// three-sample raws without that bit, scale <= 1 (fuse_rotatecrop's ground) and a no-op rotatecrop stay where they were
 bool scaled_rotatecrop(const ipk_pipeline_desc *d, const Negotiated &n, Route &rt) {
   if (!opted(d, IPK_FUSED_SCALED_ROTATECROP) || n.rc.noop() || !(n.scale > 1.0f)) return false;
   if (n.raw) {
     ipk::Cfa cfa; ipk::ResamplePlan p1;
-    if (!n.cfa_branch || d->cpp != 1 || !ipk::Cfa::parse(d->cfa, cfa) || !cfa.valid() || !cfa.three_colour()) return false;
+    if (!n.cfa_branch) {                                                     // IPK_FUSED_PLAIN_PREVIEWS: ipk_plain_scale_down is pass 1 (E = +0.0)
+      if (!scales_plain(d, n)) return false;
+      rt.pass1 = kPassScaledDemosaic;
+      return rotatecrop_resamples(d, n, n.dw, n.dh, rt.rcp, rt.plan2);
+    }
+    if (d->cpp != 1 || !ipk::Cfa::parse(d->cfa, cfa) || !cfa.valid() || !cfa.three_colour()) return false;
     if (n.scale >= ipk::demosaic_minscale(cfa.width)) rt.pass1 = kPassScaledDemosaic;
     else if (ipk::scaledown_plan(n.r.width, n.r.height, n.dw, n.dh, p1)) rt.pass1 = kPassDemosaicScaled;
     else return false;
@@ -2007,17 +2047,25 @@ int launch_gofloat(const ipk_pipeline_desc *d, const Negotiated &n, const void *
   return u16 ? ipk_gofloat_cfa_u16(s16, d->width, x, y, w, h, d->blacklevels[0], d->whitelevels[0], dst, stream)
              : ipk_gofloat_cfa_f32(s32, d->width, x, y, w, h, d->blacklevels[0], d->whitelevels[0], dst, stream);
 }
+// the monochrome flag of the buffer the one pass writes: a monochrome raw's (gofloat.rs:95-108), which the tail reads with the sRGB matrix and unit
+// multipliers; every other source of the pass writes colour
+int one_pass_monochrome(const ipk_pipeline_desc *d, const Negotiated &n) { return (n.raw && !n.cfa_branch && d->cpp == 1) ? 1 : 0; }
 // OpGoFloat + OpDemosaic in one pass, into a dw x dh 4-channel buffer, when OpDemosaic::run would scale: its scaled_demosaic branch for a
-// mosaic (demosaic.rs:47-50), its scale_down_opbuf branch for a raster source under a size limit (demosaic.rs:44-46)
+// mosaic (demosaic.rs:47-50), its scale_down_opbuf branch for a raster source under a size limit and, under IPK_FUSED_PLAIN_PREVIEWS, for a
+// monochrome or three-sample raw (demosaic.rs:44-46)
 bool gofloat_demosaic_one_pass(const ipk_pipeline_desc *d, const Negotiated &n) {
   if (!fused_on(d)) return false;
   if (!n.raw) return n.scale > 1.0f;
+  if (!n.cfa_branch) return scales_plain(d, n);
   ipk::Cfa cfa;
   return n.cfa_branch && d->cpp == 1 && ipk::Cfa::parse(d->cfa, cfa) && cfa.valid() && n.scale >= ipk::demosaic_minscale(cfa.width);
 }
 // win: that rectangle of the n.dw x n.dh buffer alone, packed (regions under IPK_FUSED_WINDOW_PREVIEWS); null: the whole buffer
 int launch_gofloat_demosaic(const ipk_pipeline_desc *d, const Negotiated &n, const void *src, const ipk::ResampleWindow *win, float *dst, void *stream) {
   if (!n.raw) return raster_scale_down_impl(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, n.dw, n.dh, win, dst, stream);
+  if (!n.cfa_branch)
+    return plain_scale_down_impl(src, d->src_type, d->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO, d->width, n.r.x, n.r.y, n.r.width, n.r.height, d->blacklevels,
+                                 d->whitelevels, n.dw, n.dh, win, dst, stream);
   return raw_scaled_demosaic_impl(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, d->blacklevels[0], d->whitelevels[0], d->cfa,
                                   n.dw, n.dh, win, dst, stream);
 }
@@ -2075,7 +2123,7 @@ int run_scaled_rotatecrop(const ipk_pipeline_desc *d, const Negotiated &n, const
   // pass 2 addresses its source in the buffer's own coordinates: the pointer is moved back by F's origin and the pitch is F's width, so pixel (x, y) of
   // the buffer is pixel (x - F.x, y - F.y) of the scratch; the kernel reads tile boxes only, all inside F (above)
   PointwisePrep pp;
-  rc = pp.prepare(0, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
+  rc = pp.prepare(one_pass_monochrome(d, n), d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
   pp.f.src = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(buf) - (uintptr_t)(F.y * F.w + F.x) * 4 * sizeof(float));
   pp.f.src_is_u16 = false; pp.f.out_type = rt.fp.out_type;
   pp.f.width = n.dw; pp.f.height = n.dh; pp.f.owidth = F.w;
@@ -2100,7 +2148,7 @@ int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, co
   // gofloat (+ demosaic when OpDemosaic::run would scale: one pass over the source)
   const bool demosaic_done = gofloat_demosaic_one_pass(d, n);
   if (demosaic_done) {
-    colors = 4; monochrome = 0;
+    colors = 4; monochrome = one_pass_monochrome(d, n);
     rc = sc.get(n.dw * n.dh * 4 * sizeof(float), &buf); if (rc) return rc;
     rc = launch_gofloat_demosaic(d, n, src, nullptr, static_cast<float *>(buf), stream);
     w = n.dw; h = n.dh;
@@ -2276,6 +2324,13 @@ int ipk_pipeline_fuses_scaled_rotatecrop(const ipk_pipeline_desc *d, int out_typ
   Route rt; const int rc = report_route(d, out_type, rt);
   return rc ? rc : rt.kind == kScaledRotateCrop;
 }
+// IPK_FUSED_PLAIN_PREVIEWS: do OpGoFloat and a scaling OpDemosaic of a monochrome / three-sample raw run as the one launch ipk_plain_scale_down?
+int ipk_pipeline_scales_plain(const ipk_pipeline_desc *d, int out_type) {
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated n; const int rc = negotiate(d, out_type, n); if (rc) return rc;
+  return (ipk_pipeline_takes_fastpath(d, out_type) != 1 && scales_plain(d, n)) ? 1 : 0;
+}
 // IPK_FUSED_PLAIN: does a cropped raster / a u16 three-sample or monochrome raw run as the one launch ipk_plain_to_srgb (the whole-frame half of the bit)?
 int ipk_pipeline_fuses_plain(const ipk_pipeline_desc *d, int out_type) {
   Route rt; const int rc = report_route(d, out_type, rt);
@@ -2438,7 +2493,7 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
     rc = sc.get(pl.win.cols * pl.win.rows * 4 * sizeof(float), &buf); if (rc) return rc;
     rc = launch_gofloat_demosaic(d, n, src, &pl.win, static_cast<float *>(buf), stream); if (rc < 0) return rc;
     tm.mark("region gofloat+demosaic");
-    return run_tail(d, n, out_type, sc, buf, pl.win.cols, pl.win.rows, 4, 0, w, h, dst, tm, stream);
+    return run_tail(d, n, out_type, sc, buf, pl.win.cols, pl.win.rows, 4, one_pass_monochrome(d, n), w, h, dst, tm, stream);
   }
   // the one-launch routes: the window launch writes the rectangle into dst, or into scratch for OpTransform's permutation
   if (rt.kind == kScaledRotateCrop) return run_scaled_rotatecrop(d, n, rt, src, &pl.win, w, h, dst, stream);
@@ -2565,7 +2620,7 @@ int run_cached_ops(const ipk_pipeline_desc *d, const Negotiated &n, const ipk::B
     switch (i) {
       case 0: {                                                          // gofloat
         if (gofloat_demosaic_one_pass(d, n) && !cache->lru.contains(hs[1])) {   // + demosaic in the same pass when it would scale
-          rc = cbuf_new(n.dw, n.dh, 4, 0, o); if (rc) return rc;
+          rc = cbuf_new(n.dw, n.dh, 4, one_pass_monochrome(d, n), o); if (rc) return rc;
           rc = launch_gofloat_demosaic(d, n, src, nullptr, static_cast<float *>(o->p), stream); if (rc < 0) return rc;
           mask |= 3; buf = o; cache->lru.put(hs[1], o, o->bytes()); i = 1;   // op 1's output; op 0's is never materialised
           continue;

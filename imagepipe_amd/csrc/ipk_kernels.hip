@@ -408,6 +408,10 @@ struct TransformArgs {
   // centres are then sums of terms that are zero or multiples of 2^-24, so a nonzero difference lies in [2^-24, 2^25] -- inside the multiply-fma
   // division's proven zone without tb_div's per-tap exponent test and its divergent IEEE fallback
   int plain_axis;
+  // k_raw_scaled_demosaic: what a tap loads.  0: one sample of a mosaic, binned by the filter's colour at (y, x); 1: one sample of a monochrome raw
+  // (gofloat.rs:95-108), feeding R, G and B alike; 3: the three samples of a cpp == 3 raw (gofloat.rs:109-120), channel c normalised with its own
+  // level pair -- min0 / range0 for c = 0, the two pairs below for c = 1, 2.  Launch-uniform
+  int layout; float min1, range1, min2, range2;
 };
 // (v - center) / skip  (scaling.rs:104-105): cdiv_fast when the host validated the divisor and the dividend is in the proven
 // zone, the IEEE division otherwise (zero or negative skips of degenerate / rotated transforms, absurd centres)
@@ -671,12 +675,76 @@ void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, si
 template <typename T>
 __global__ void k_raw_scaled_demosaic(const T *__restrict__ src, TransformArgs a, const uint8_t *__restrict__ cfa48, float *__restrict__ dst) {
   __shared__ uint8_t s_cfa[48 * 48];
-  for (int i = threadIdx.x; i < 48 * 48; i += blockDim.x) s_cfa[i] = cfa48[i];
-  __syncthreads();
+  const bool mosaic = a.layout == 0;                                        // launch-uniform: so is the barrier
+  if (mosaic) {
+    for (int i = threadIdx.x; i < 48 * 48; i += blockDim.x) s_cfa[i] = cfa48[i];
+    __syncthreads();
+  }
   const uint32_t col = a.out_c0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (col >= a.out_c1) return;
   const uint32_t pitch = a.out_c1 - a.out_c0;
   float4 *const dstw = reinterpret_cast<float4 *>(dst) - a.out_c0;          // dst column 0 is output column out_c0 (the address below never leaves dst)
+  if (!mosaic) {
+    // Monochrome and three-sample raws: OpGoFloat::run_raw's 4-channel buffer (gofloat.rs:95-120) through scale_down_opbuf (demosaic.rs:44-46) without the
+    // buffer.  Same corner points, window, weights and tap order as the mosaic walk below (and as k_transform_buffer's 4-component walk over that buffer);
+    // a tap feeds every channel, so the channels share one count -- transform_buffer's four counts are sums of the same factors in the same order.  Taps of
+    // weight 0 still multiply their sample (0 * inf is NaN there and here)
+    const bool three = a.layout == 3;
+    for (uint32_t row = a.out_r0 + blockIdx.y; row < a.out_r1; row += gridDim.y) {
+      const float from_x_r = a.tlx + a.skip_y_x * (float)row;
+      const float to_x_r = a.tlx + a.skip_y_x * (float)(row + 1);
+      const float from_y_r = a.tly + a.skip_y_y * (float)row;
+      const float to_y_r = a.tly + a.skip_y_y * (float)(row + 1);
+      const float center_x_r = a.tlx + (a.skip_y_x * (float)row) + (a.skip_y_x / 2.0f) - 0.5f;
+      const float center_y_r = a.tly + (a.skip_y_y * (float)row) + (a.skip_y_y / 2.0f) - 0.5f;
+      const uint32_t from_x = min(a.width - 1, f32_as_u32_sat(floorf(from_x_r + (a.skip_x_x * (float)col))));
+      const uint32_t to_x = min(a.width - 1, f32_as_u32_sat(floorf(to_x_r + (a.skip_x_x * (float)(col + 1)))));
+      const uint32_t from_y = min(a.height - 1, f32_as_u32_sat(floorf(from_y_r + (a.skip_x_y * (float)col))));
+      const uint32_t to_y = min(a.height - 1, f32_as_u32_sat(floorf(to_y_r + (a.skip_x_y * (float)(col + 1)))));
+      const float center_x = center_x_r + (a.skip_x_x * (float)col) + (a.skip_x_x / 2.0f);
+      const float center_y = center_y_r + (a.skip_x_y * (float)col) + (a.skip_x_y / 2.0f);
+      float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, n = 0.0f;
+      for (uint32_t y = from_y; y <= to_y; ++y) {
+        const float delta_y = tb_div((float)y - center_y, a.skip_y_y, a.inv_skip_y_y, a.fast_y);
+        const float dy2 = delta_y * delta_y;
+        const size_t row0 = (size_t)((uint64_t)y + a.src_y) * a.src_pitch + a.src_x;
+        if (three) {
+          const T *rowp = src + row0 * 3;
+          for (uint32_t x = from_x; x <= to_x; ++x) {
+            const float delta_x = tb_div((float)x - center_x, a.skip_x_x, a.inv_skip_x_x, a.fast_x);
+            float factor = 1.0f - (delta_x * delta_x) - dy2;
+            factor = (factor < 0.0f) ? 0.0f : factor;
+            const T *p = rowp + (size_t)x * 3;
+            const float v0 = rs_min(((float)p[0] - a.min0) / a.range0, 1.0f);       // gofloat.rs:115-117
+            const float v1 = rs_min(((float)p[1] - a.min1) / a.range1, 1.0f);
+            const float v2 = rs_min(((float)p[2] - a.min2) / a.range2, 1.0f);
+            s0 += v0 * factor; s1 += v1 * factor; s2 += v2 * factor; n += factor;
+            if (x == 0xFFFFFFFFu) break;
+          }
+        } else {
+          const T *rowp = src + row0;
+          for (uint32_t x = from_x; x <= to_x; ++x) {
+            const float delta_x = tb_div((float)x - center_x, a.skip_x_x, a.inv_skip_x_x, a.fast_x);
+            float factor = 1.0f - (delta_x * delta_x) - dy2;
+            factor = (factor < 0.0f) ? 0.0f : factor;
+            const float v = rs_min(((float)rowp[x] - a.min0) / a.range0, 1.0f);     // gofloat.rs:100-104
+            s0 += v * factor; n += factor;
+            if (x == 0xFFFFFFFFu) break;
+          }
+        }
+        if (y == 0xFFFFFFFFu) break;
+      }
+      // E: the reference adds 0.0 * factor (factor finite and >= 0) to a sum that starts at +0.0 and divides it by a positive count, or leaves
+      // the zero fill -- +0.0 either way, so the constant is written
+      float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (n > 0.0f) {
+        o.x = s0 / n;
+        if (three) { o.y = s1 / n; o.z = s2 / n; } else { o.y = o.x; o.z = o.x; }
+      }
+      dstw[(size_t)(row - a.out_r0) * pitch + col] = o;
+    }
+    return;
+  }
   for (uint32_t row = a.out_r0 + blockIdx.y; row < a.out_r1; row += gridDim.y) {
     const float from_x_r = a.tlx + a.skip_y_x * (float)row;
     const float to_x_r = a.tlx + a.skip_y_x * (float)(row + 1);
@@ -1074,7 +1142,8 @@ __global__ __launch_bounds__(256, C4 ? 6 : 7) void k_raw_scaled_demosaic_w8m(con
 template <typename T>
 void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
                                 int norm_fast, int has_fourth_colour, size_t nwidth, size_t nheight, const uint8_t *cfa48_dev, int pw, int ph, float *dst4, hipStream_t s,
-                                size_t band_src_row0, size_t band_out_row0, size_t band_out_rows, const ResampleWindow *win) {
+                                size_t band_src_row0, size_t band_out_row0, size_t band_out_rows, const ResampleWindow *win, const PlainLevels *plain) {
+  if (plain) { black0 = plain->black[0]; white0 = plain->white[0]; norm_fast = 0; has_fourth_colour = 1; }
   TransformArgs a{};
   a.width = (uint32_t)width; a.height = (uint32_t)height; a.nwidth = (uint32_t)nwidth; a.nheight = (uint32_t)nheight; a.components = 4;
   a.tlx = 0.0f; a.tly = 0.0f;                                               // scale_down_buffer's corners (scaling.rs:35-48)
@@ -1087,6 +1156,10 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
   a.has_cfa = 1; a.norm = 1; a.min0 = black0; a.range0 = white0 - black0; a.src_pitch = owidth; a.src_x = x; a.src_y = y;
   a.norm_fast = norm_fast; a.inv_range0 = 1.0f / a.range0;
   a.norm_light = (std::fabs(black0) >= 0x1p-70f && std::fabs(black0) <= 0x1p70f) ? 1 : 0;
+  if (plain) {                                                              // true divisions only: neither shortcut of the mosaic kernels applies
+    a.layout = plain->layout; a.has_cfa = 0; a.norm_light = 0;
+    a.min1 = plain->black[1]; a.range1 = plain->white[1] - plain->black[1]; a.min2 = plain->black[2]; a.range2 = plain->white[2] - plain->black[2];
+  }
   // whole frame, or the output-row band [band_out_row0, +band_out_rows) of a frame sharded across GPUs: `src` then points at sensor
   // row y + band_src_row0 (the slab's first row), which is folded into src_y; window bounds still clamp against the full height
   a.out_r0 = 0; a.out_r1 = (uint32_t)nheight;
@@ -1098,22 +1171,25 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
   const size_t out_rows = a.out_r1 - a.out_r0, out_cols = a.out_c1 - a.out_c0;
   a.xcd_gx = 0; a.xcd_gy = 0; a.xcd_group = 0;
   // launch-log tag: the host-known switches the kernels branch on, "norm_fast=.,norm_light=.,fast_x=.,fast_y=.,xcd=." (xcd: 0 plain grid, 1 XCD row
-  // grouping with no leftover rows, 2 grouping with leftover rows); window launches, and only they, append ",win=1"
+  // grouping with no leftover rows, 2 grouping with leftover rows); window launches, and only they, append ",win=1"; the monochrome / three-sample
+  // launches, and only they, append ",plain=1" / ",plain=3" behind that (table entries 96..191 / 192..287)
   auto tag = [&](int xcd) -> const char * {
     if (!g_log_on.load(std::memory_order_relaxed)) return nullptr;         // the table is built, and read, only while the log is on
     static const std::vector<std::string> tags = [] {
       std::vector<std::string> t;
-      for (int i = 0; i < 96; ++i) {
-        char b[80]; snprintf(b, sizeof(b), "norm_fast=%d,norm_light=%d,fast_x=%d,fast_y=%d,xcd=%d%s", i & 1, (i >> 1) & 1, (i >> 2) & 1, (i >> 3) & 1, (i % 48) >> 4, i >= 48 ? ",win=1" : "");
+      for (int i = 0; i < 288; ++i) {
+        const int j = i % 96;
+        char b[96]; snprintf(b, sizeof(b), "norm_fast=%d,norm_light=%d,fast_x=%d,fast_y=%d,xcd=%d%s%s", j & 1, (j >> 1) & 1, (j >> 2) & 1, (j >> 3) & 1, (j % 48) >> 4, j >= 48 ? ",win=1" : "",
+                             i >= 192 ? ",plain=3" : i >= 96 ? ",plain=1" : "");
         t.push_back(b);
       }
       return t;
     }();
-    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4)) + (win ? 48 : 0)].c_str();
+    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4)) + (win ? 48 : 0) + (a.layout == 3 ? 192 : a.layout == 1 ? 96 : 0)].c_str();
   };
   a.components = has_fourth_colour ? 4 : 3;               // the w8 kernel skips the fourth bin for three-colour filters (it stays 0.0)
-  // windows of at most 8 x 8 samples: floor(skip*(c+1)) - floor(skip*c) + 1 <= ceil(skip) + 1
-  if (a.skip_x_x >= 1.0f && a.skip_x_x <= 7.0f && a.skip_y_y >= 1.0f && a.skip_y_y <= 7.0f && width >= 8 &&
+  // windows of at most 8 x 8 samples: floor(skip*(c+1)) - floor(skip*c) + 1 <= ceil(skip) + 1 (mosaics only: the 8-sample kernels have no plain mode)
+  if (!plain && a.skip_x_x >= 1.0f && a.skip_x_x <= 7.0f && a.skip_y_y >= 1.0f && a.skip_y_y <= 7.0f && width >= 8 &&
       (reinterpret_cast<uintptr_t>(dst4) & 15) == 0) {
     const unsigned gx = (unsigned)((out_cols + 255) / 256);
     // 21 blocks per CU = 3 full rounds of the 7 resident ones.  Round 4 sweep (50 MP X-Trans -> 2160x1440, one box, ms): 1620 / 1792 / 2688 / 3584 / 5376 /
@@ -1153,8 +1229,8 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
   }
   IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(out_cols, out_rows, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst4);
 }
-template void launch_raw_scaled_demosaic<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *);
-template void launch_raw_scaled_demosaic<float>(const float *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *);
+template void launch_raw_scaled_demosaic<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *, const PlainLevels *);
+template void launch_raw_scaled_demosaic<float>(const float *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *, const PlainLevels *);
 template void launch_transform_buffer<float>(const float *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, float *, hipStream_t);
 template void launch_transform_buffer<uint8_t>(const uint8_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint8_t *, hipStream_t);
 template void launch_transform_buffer<uint16_t>(const uint16_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint16_t *, hipStream_t);

@@ -43,7 +43,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // launchers whose kernel also branches on a value the host knows: k_gamma [vec4=,wrap=], k_output8 / k_output16 [vec4=] (16-byte groups or sample by
 // sample; wrap: the grid cap holds), k_gofloat_cfa_v4 [rowwrap=] (more rows than grid rows), the ipk_raw_scaled_demosaic kernels
 // [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows; their window launches,
-// ipk_raw_scaled_demosaic_window, append win=1: [norm_fast=,...,xcd=,win=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
+// ipk_raw_scaled_demosaic_window, append win=1: [norm_fast=,...,xcd=,win=1]; the monochrome / three-sample launches of k_raw_scaled_demosaic by
+// ipk_plain_scale_down append plain=1 / plain=3 behind that), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form); the gather
 // launches of k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2> (a GatherSource: ipk_pipeline_run_cached_region) append
 // gather=1: [fast_ok=,gather=1] -- flat launches never carry the key;
@@ -72,11 +73,17 @@ struct ResampleWindow { size_t row0, col0, rows, cols; };
 // work from absolute rows and columns).  Null: the whole frame, whose log entries are unchanged
 void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, size_t x, size_t y, size_t width, size_t height,
                               size_t nwidth, size_t nheight, const void *gamma_reverse_pairs, float *dst4, hipStream_t s, const ResampleWindow *win = nullptr);
+// plain (optional): the source is no mosaic but a monochrome (layout 1) or three-sample (layout 3) raw -- OpGoFloat::run_raw's 4-channel buffer through
+// scale_down_opbuf, E = +0.0 -- with the level pairs of its channels (layout 1 reads pair 0 alone).  Such launches always take the general kernel
+// k_raw_scaled_demosaic<T>, whatever the skips and dst4's alignment, read no filter (cfa48_dev may be null; black0 / white0, norm_fast and the pattern
+// size are ignored), and append plain=1 / plain=3 to the tag: [norm_fast=0,...,xcd=0,plain=1] / [...,xcd=0,win=1,plain=3]
+struct PlainLevels { int layout; float black[3], white[3]; };
 template <typename T>
 void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0, int norm_fast, int has_fourth_colour,
                                 size_t nwidth, size_t nheight, const uint8_t *cfa48_dev, int pattern_width, int pattern_height, float *dst4, hipStream_t s,
                                 size_t band_src_row0 = 0, size_t band_out_row0 = 0, size_t band_out_rows = 0,    // band_out_rows == 0: the whole frame
-                                const ResampleWindow *win = nullptr);                                            // not together with a band
+                                const ResampleWindow *win = nullptr,                                             // not together with a band
+                                const PlainLevels *plain = nullptr);
 
 void launch_tolab(const float *src4, size_t npix, const float *mul4, const float *cm12, const void *lab_pairs, float *dst3,
                   int num_cus, hipStream_t s);

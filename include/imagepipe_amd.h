@@ -250,6 +250,22 @@ IPK_API int ipk_raw_scaled_demosaic_window(const void *src, int src_type, size_t
                                            size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
 IPK_API int ipk_raster_scale_down_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
                                          size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
+/* The counterpart for every source whose OpGoFloat writes a 4-channel buffer: OpGoFloat + scaling::scale_down_opbuf (OpDemosaic's branch for such a
+ * buffer above the size limit, src/ops/demosaic.rs:44-46) in one pass.  kind is an ipk_plain_kind (declared with ipk_plain_to_srgb below; passed as
+ * int): IPK_PLAIN_RGB (1), a three-sample raw (cpp == 3: linear DNG, sRAW, pixel-shift and HDR merges), min((s[c] - black4[c]) / (white4[c] - black4[c]), 1)
+ * per channel (gofloat.rs:109-120); IPK_PLAIN_MONO (2), a monochrome raw, one sample per pixel, the same with black4[0] / white4[0] written to R, G and B
+ * (gofloat.rs:95-108) -- both with src_type IPK_SRC_U16 or IPK_SRC_F32, true divisions, values below black left negative, degenerate levels (a range of
+ * 0, an inverted range) accepted as the staged kernels accept them; IPK_PLAIN_RASTER (0) forwards to ipk_raster_scale_down(_window) (src_type
+ * IPK_SRC_RGB8 / IPK_SRC_RGB16; black4 / white4 are ignored and may be NULL).  src: owidth-pitched pixels (1 or 3 samples each), window (x, y, width,
+ * height); dst4 receives nwidth * nheight * 4 packed f32 (ww * wh * 4 for the window form), bit-identical to ipk_gofloat_mono_* / ipk_gofloat_rgb_*
+ * followed by ipk_scale_down_opbuf, E = +0.0, and nothing else is written.  src and dst4 need element alignment only.  The raw kinds are run-time modes of
+ * ipk_raw_scaled_demosaic's general kernel (one thread per output pixel, tap by tap), whatever the scale.  Admission, the window rules and the
+ * IPK_ERR_INVALID cases are exactly those of ipk_raster_scale_down(_window); a window launch reads only ipk_scaled_window_footprint, offset by x, y. */
+IPK_API int ipk_plain_scale_down(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                 const float *black4, const float *white4, size_t nwidth, size_t nheight, float *dst4, void *stream);
+IPK_API int ipk_plain_scale_down_window(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                        const float *black4, const float *white4, size_t nwidth, size_t nheight,
+                                        size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
 /* OpGoFloat::run_raw (CFA branch) followed by OpDemosaic::run's LAST branch -- demosaic::full, then scale_down_opbuf to nwidth x nheight
  * (src/ops/demosaic.rs:51-59: 1 < scale < minscale) -- in one launch over the raw sensor frame: ipk_raw_scaled_demosaic's sibling below minscale.  dst4
  * receives nwidth * nheight * 4 f32, bit for bit what ipk_gofloat_cfa_* -> ipk_demosaic_run write for such a frame (E = +0.0); the full-size 1- and
@@ -515,7 +531,8 @@ typedef struct {
                                       gofloat + demosaic pass (ipk_raw_scaled_demosaic_window / ipk_raster_scale_down_window) followed by the point-wise ops on
                                       that rectangle.  Same contract again.  The bit acts only together with bit 0: allow_fused = 8 still means "on" for every
                                       whole-frame route (any non-zero value does), but regions of previews are then cut from the whole result, as without the
-                                      bit.  Bit 2 does not window these frames, with or without bit 3.
+                                      bit.  Bit 2 does not window these frames, with or without bit 3.  Monochrome and three-sample raws have such a pass
+                                      under bit 7 only (below).
                                       Bit 4 (IPK_FUSED_PLAIN = 16), beside IPK_FUSED_ON as well: the frames whose OpDemosaic is a pass-through -- RGB8 / RGB16
                                       rasters with OpGoFloat crops, u16 monochrome and u16 three-sample raws -- run as the one launch ipk_plain_to_srgb where
                                       ipk_pipeline_fuses_plain says so, and regions of every frame on that launch (the uncropped rasters it always took
@@ -527,7 +544,12 @@ typedef struct {
                                       does: allow_fused = 32 is 0 to every route and report.
                                       Bit 6 (IPK_FUSED_SCALED_ROTATECROP = 64), beside IPK_FUSED_ON as well: an active OpRotateCrop behind an OpDemosaic that
                                       scales runs as TWO launches where ipk_pipeline_fuses_scaled_rotatecrop says so, whole frames and (windowed) regions.
-                                      Same contract: no hash, no result.  Like bit 5 it is nothing alone: allow_fused = 64 is 0 to every route and report. */
+                                      Same contract: no hash, no result.  Like bit 5 it is nothing alone: allow_fused = 64 is 0 to every route and report.
+                                      Monochrome and three-sample raws take this route under bit 7 only (below).
+                                      Bit 7 (IPK_FUSED_PLAIN_PREVIEWS = 128), beside IPK_FUSED_ON as well: a monochrome or three-sample raw (u16 or f32) whose
+                                      OpDemosaic scales runs OpGoFloat + OpDemosaic as the one launch ipk_plain_scale_down where ipk_pipeline_scales_plain says
+                                      so; bits 3 and 6 then take such frames as they take the other previews.  Same contract: no hash, no result.  Like bits 3
+                                      and 4, allow_fused = 128 alone still means "on" for every older route (any non-zero value does). */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -547,8 +569,9 @@ typedef enum {
   IPK_FUSED_ON = 1,                /* the one-launch routes where legal (any non-zero value means this) */
   IPK_FUSED_FOUR_COLOUR = 2,       /* bit 1: four-colour filters take the one-launch route too */
   IPK_FUSED_WINDOW_REGIONS = 4,    /* bit 2: regions of the fuse_rotatecrop / fuse_scaledown routes run as a window of their one launch */
-  IPK_FUSED_WINDOW_PREVIEWS = 8,   /* bit 3 (beside bit 0): regions of downscaled previews (OpDemosaic's scaled_demosaic branch, scale >= minscale, and rasters
-                                      under a size limit) run as a window of the scaling pass, where ipk_pipeline_windows_preview says so.
+  IPK_FUSED_WINDOW_PREVIEWS = 8,   /* bit 3 (beside bit 0): regions of downscaled previews (OpDemosaic's scaled_demosaic branch, scale >= minscale, rasters
+                                      under a size limit and, with bit 7 beside it, monochrome / three-sample raws under a size limit) run as a window of the
+                                      scaling pass, where ipk_pipeline_windows_preview says so.
                                       Measured (profiles/r13_preview_regions.txt; 50 MP X-Trans -> 2160x1440 | 24 MP RGGB -> 1500x1000, u8, without -> with
                                       the bit): device form, 1/16 of the area 0.096 -> 0.032 | 0.063 -> 0.029 ms, 1/4 0.095 -> 0.045 | 0.068 -> 0.034 ms, the
                                       whole area 0.098 -> 0.090 | 0.068 -> 0.059 ms (the copy is saved); host form, 1/16 1.86 -> 0.17 ms (99.5 -> 6.3 MB
@@ -570,9 +593,28 @@ typedef enum {
                                       of k_fused_resample's cached-buffer source mode over the rectangle instead of OpRotateCrop over the whole frame plus the
                                       gather launch.  The trade-off: while the bit is set that call never fills hash 2 (see ipk_pipeline_run_cached_region).
                                       Measurements: profiles/r16_cached_resample.txt */
-  IPK_FUSED_SCALED_ROTATECROP = 64 /* bit 6 (beside bit 0): a straightened or cropped frame whose OpDemosaic scales (with an angle the reverse size fold usually
+  IPK_FUSED_SCALED_ROTATECROP = 64,/* bit 6 (beside bit 0): a straightened or cropped frame whose OpDemosaic scales (with an angle the reverse size fold usually
                                       lands a pixel short, so this is the common straightened frame, and every straightened preview) runs as two launches
-                                      instead of the staged ops, where ipk_pipeline_fuses_scaled_rotatecrop says so; regions of such frames are windowed */
+                                      instead of the staged ops, where ipk_pipeline_fuses_scaled_rotatecrop says so; regions of such frames are windowed.
+                                      Monochrome and three-sample raws only together with bit 7 */
+  IPK_FUSED_PLAIN_PREVIEWS = 128   /* bit 7 (beside bit 0): downscaled previews of monochrome and three-sample raws (cpp == 1 without a filter, cpp == 3; u16
+                                      and f32) run OpGoFloat + OpDemosaic's scale_down_opbuf branch as ONE pass over the source (ipk_plain_scale_down: the
+                                      monochrome / three-sample modes of ipk_raw_scaled_demosaic's general kernel) where ipk_pipeline_scales_plain says so,
+                                      instead of a full-size 16-byte-per-pixel buffer and a tap-by-tap pass over it.  With bit 3 their regions are windowed,
+                                      with bit 6 their straightened previews run as two launches.
+                                      Measured (profiles/r18_plain_previews.txt; 6000x4000 noise, wall clock, medians, the parent build's run -> this route;
+                                      the parent's spread is 0.002 .. 0.015 ms throughout): under maxwidth 1500 to u8, whole frame | 1/16 | 1/4 of the area: mono
+                                      u16 0.546 -> 0.093 | 0.541 -> 0.039 | 0.544 -> 0.047 ms, mono f32 0.538 -> 0.094 | 0.533 -> 0.039 | 0.537 -> 0.048, cpp3
+                                      u16 0.551 -> 0.127 | 0.546 -> 0.042 | 0.550 -> 0.056, cpp3 f32 0.554 -> 0.147 | 0.551 -> 0.042 | 0.553 -> 0.057 (to f32
+                                      the same within 0.005 ms); under maxwidth 400 to u8 (skip 15: windows of 16 x 16 taps, one thread per output pixel) mono
+                                      u16 0.681 -> 0.115 | 0.675 -> 0.084 | 0.675 -> 0.086, mono f32 0.674 -> 0.123 | 0.670 -> 0.083 | 0.669 -> 0.091, cpp3 u16
+                                      0.690 -> 0.173 | 0.684 -> 0.103 | 0.684 -> 0.121, cpp3 f32 0.694 -> 0.271 | 0.687 -> 0.103 | 0.688 -> 0.145.  Straightened
+                                      (bits 6 and 7): mono u16 at rotation 0.02 under maxwidth 3000 to u8, whole frame 0.690 -> 0.264 ms.  No measured case was NOT
+                                      faster than the parent's run beyond its spread; none is excluded.  The cost to the carrier kernel's mosaic mode (one
+                                      launch-uniform branch outside the row loop): 6000x4000 RGGB u16 under maxwidth 400 (skip 15, k_raw_scaled_demosaic<uint16_t>),
+                                      parent 0.149 ms (spread 0.001) -> 0.148 ms.  Not measured: the host form of the regions, regions of the straightened
+                                      case, 100 MP frames, 16-bit outputs, photo-like data, and the 8-sample mosaic kernels (k_raw_scaled_demosaic_w8 / _w8m:
+                                      their code is untouched, their argument block grew by five words) */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -622,7 +664,8 @@ IPK_API int ipk_pipeline_fuses_four_colour(const ipk_pipeline_desc *d, int out_t
 /* Does a region of this descriptor (ipk_pipeline_region / _run_region / ipk_host_pipeline_run_region) run as a window of its scaling gofloat + demosaic
  * pass?  1 when d->allow_fused has IPK_FUSED_ON and IPK_FUSED_WINDOW_PREVIEWS set, OpRotateCrop is a no-op, and the staged drivers run OpGoFloat and
  * OpDemosaic as the one scaling pass: a one-sample-per-pixel CFA mosaic with a valid filter (three or four colours) at scale >= minscale
- * (src/ops/demosaic.rs:33-50), or an RGB8 / RGB16 raster at scale > 1 that does not take the fast path.  0 otherwise -- mono and three-sample raws, an
+ * (src/ops/demosaic.rs:33-50), an RGB8 / RGB16 raster at scale > 1 that does not take the fast path, or -- with IPK_FUSED_PLAIN_PREVIEWS set as well -- a
+ * monochrome or three-sample raw at scale > 1 (ipk_pipeline_scales_plain).  0 otherwise -- mono and three-sample raws without that bit, an
  * active rotatecrop behind a scaling demosaic, 1 < scale < minscale (IPK_FUSED_WINDOW_REGIONS' ground), full-size frames (windowed whatever the
  * bits); a negative error code for a descriptor ipk_pipeline_sizes refuses.  Whole-frame drivers do not depend on the bit.  No GPU needed. */
 IPK_API int ipk_pipeline_windows_preview(const ipk_pipeline_desc *d, int out_type);
@@ -633,14 +676,23 @@ IPK_API int ipk_pipeline_windows_preview(const ipk_pipeline_desc *d, int out_typ
  * -- uncropped rasters included: their one launch does not depend on the bit (only their regions do) --, f32 monochrome / three-sample raws
  * (staged: the launch has no f32 form), mosaics; a negative error code for a descriptor ipk_pipeline_sizes refuses.  No GPU needed. */
 IPK_API int ipk_pipeline_fuses_plain(const ipk_pipeline_desc *d, int out_type);
+/* Do ipk_pipeline_run and the cached, batch, host, multi-device and region drivers run this descriptor's OpGoFloat and its scaling OpDemosaic as the ONE
+ * launch ipk_plain_scale_down BECAUSE of IPK_FUSED_PLAIN_PREVIEWS?  1 when d->allow_fused has IPK_FUSED_ON and IPK_FUSED_PLAIN_PREVIEWS set, the frame
+ * does not take the fast path, the source is a raw that OpGoFloat does not treat as a mosaic -- cpp == 1 with is_cfa == 0, or cpp == 3; IPK_SRC_U16 or
+ * IPK_SRC_F32 -- and OpDemosaic scales (scale > 1).  0 otherwise: mosaics and rasters (their scaling passes do not depend on the bit), full-size frames
+ * (IPK_FUSED_PLAIN's ground), the bit without IPK_FUSED_ON.  The stage keeps its name, "gofloat+demosaic" ("region gofloat+demosaic" for a windowed
+ * region); the cached drivers store the buffer under the demosaic hash with the source's monochrome flag, and hash 0 is then never filled.  A negative
+ * error code for a descriptor ipk_pipeline_sizes refuses.  No GPU needed. */
+IPK_API int ipk_pipeline_scales_plain(const ipk_pipeline_desc *d, int out_type);
 /* Does ipk_pipeline_run (and the host, batch and multi-device drivers; the cached drivers are unchanged) run this descriptor's frame as TWO launches: the
  * scaling gofloat + demosaic pass into the negotiated demosaic-size RGBE buffer, then ONE resampling launch over that buffer (k_fused_resample's 4-channel
  * source mode: OpRotateCrop's transform_buffer, tolab..gamma and the quantiser), then OpTransform's permutation if there is one?  1 when d->allow_fused has
  * IPK_FUSED_ON and IPK_FUSED_SCALED_ROTATECROP set, the frame does not take the fast path, OpRotateCrop is active and accepts its crops on the
  * demosaic-size buffer, OpDemosaic scales (scale > 1), the resampling launch admits the transform (windows of at most 3x3), and pass 1 exists as one
  * launch: a one-sample-per-pixel mosaic with a valid three-colour filter at scale >= minscale (ipk_raw_scaled_demosaic) or at 1 < scale < minscale with
- * geometry ipk_raw_demosaic_scaled takes, or an RGB8 / RGB16 raster (ipk_raster_scale_down).  0 otherwise: filters with a fourth colour (E is not +0.0
- * there), monochrome and three-sample raws, scale <= 1 (fuse_rotatecrop's ground), a no-op rotatecrop, the bit without IPK_FUSED_ON.  Regions of such a
+ * geometry ipk_raw_demosaic_scaled takes, an RGB8 / RGB16 raster (ipk_raster_scale_down), or -- with IPK_FUSED_PLAIN_PREVIEWS set as well -- a monochrome
+ * or three-sample raw (ipk_plain_scale_down, E = +0.0).  0 otherwise: filters with a fourth colour (E is not +0.0
+ * there), monochrome and three-sample raws without that bit, scale <= 1 (fuse_rotatecrop's ground), a no-op rotatecrop, the bit without IPK_FUSED_ON.  Regions of such a
  * descriptor are windowed under the same bit: pass 1 runs over the footprint F of the region's rectangle in the demosaic-size buffer, pass 2 over the
  * rectangle, and ipk_pipeline_region reports what pass 1 reads for F plus the crop offset.  ipk_timing names the stages "gofloat+demosaic",
  * "rotatecrop+to_lab+basecurve+from_lab+gamma" and "transform".  A negative error code for a descriptor ipk_pipeline_sizes refuses.  No GPU needed.

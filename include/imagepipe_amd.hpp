@@ -304,6 +304,7 @@ class Pipeline {
   bool fuse_plain = false;                 // ipk_pipeline_desc.allow_fused bit 4 (IPK_FUSED_PLAIN): cropped RGB8 / RGB16 rasters and u16 monochrome / three-sample raws as one launch where fuses_plain() says so; regions of every frame on the raster launch windowed
   bool resample_cached = false;            // ipk_pipeline_desc.allow_fused bit 5 (IPK_FUSED_CACHED_RESAMPLE): run_region with a cache resamples the region from the cached demosaic buffer when the rotatecrop buffer is missing, where resamples_cached_region() says so; that call then never fills the rotatecrop hash
   bool fuse_scaled_rotatecrop = false;     // ipk_pipeline_desc.allow_fused bit 6 (IPK_FUSED_SCALED_ROTATECROP): an active OpRotateCrop behind a scaling OpDemosaic as two launches where fuses_scaled_rotatecrop() says so; regions of such frames windowed
+  bool scale_plain = false;                // ipk_pipeline_desc.allow_fused bit 7 (IPK_FUSED_PLAIN_PREVIEWS): downscaled previews of monochrome / three-sample raws (u16, f32) run gofloat + demosaic as the one launch ipk_plain_scale_down where scales_plain() says so; window_previews and fuse_scaled_rotatecrop then take them too
   bool window_previews = false;            // ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
   int last_ops_run = 0xFF;                 // bit i: op i executed in the last run (0 = served from the cache)
   uint64_t source_id = 0;                  // identifies the frame inside a shared PipelineCache (extension, see the C header)
@@ -400,6 +401,7 @@ class Pipeline {
     if (fuse_plain && d.allow_fused) d.allow_fused |= IPK_FUSED_PLAIN;
     if (resample_cached && d.allow_fused) d.allow_fused |= IPK_FUSED_CACHED_RESAMPLE;
     if (fuse_scaled_rotatecrop && d.allow_fused) d.allow_fused |= IPK_FUSED_SCALED_ROTATECROP;
+    if (scale_plain && d.allow_fused) d.allow_fused |= IPK_FUSED_PLAIN_PREVIEWS;
     return d;
   }
   // does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop; no GPU needed)?  out_type: IPK_OUT_*
@@ -414,6 +416,8 @@ class Pipeline {
   bool fuses_plain(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_fuses_plain(&d, out_type) == 1; }
   // does the run take the two-launch route through a scaling OpDemosaic and an active OpRotateCrop (ipk_pipeline_fuses_scaled_rotatecrop)?
   bool fuses_scaled_rotatecrop(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_fuses_scaled_rotatecrop(&d, out_type) == 1; }
+  // do OpGoFloat and the scaling OpDemosaic of this monochrome / three-sample raw run as the one launch ipk_plain_scale_down (ipk_pipeline_scales_plain)?
+  bool scales_plain(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_scales_plain(&d, out_type) == 1; }
   // would a region from the cache be resampled straight from the cached demosaic buffer (ipk_pipeline_resamples_cached_region)?
   bool resamples_cached_region(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_resamples_cached_region(&d, out_type) == 1; }
  private:
