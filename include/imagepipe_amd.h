@@ -804,7 +804,9 @@ IPK_API int ipk_cache_get(ipk_cache *cache, const uint8_t *key32, const float **
 /* Pipeline::run / output_8bit / output_16bit with Some(cache): resumes after the last op whose hash is in the
  * cache, stores every buffer it materialises under that op's hash, writes the final image to the DEVICE buffer
  * dst.  *ops_run (may be NULL) = bit i set when op i executed (0 = served from the cache).  With nothing
- * memoised and a fusable chain the whole run is one ipk_raw_to_srgb launch and only the final buffer is stored. */
+ * memoised and a fusable chain the whole run is one ipk_raw_to_srgb launch and only the final buffer is stored.
+ * The order of the cache traffic: one `get` per hash, 0 to 7 in that order, each hit refreshed as it is found (the last hit wins), then one `put` per
+ * executed op in op order; where gofloat + demosaic run as one pass, hash 0 is never stored. */
 IPK_API int ipk_pipeline_run_cached(const ipk_pipeline_desc *d, const void *src, uint64_t source_id, ipk_cache *cache,
                                     int out_type, void *dst, int *ops_run, int *used_fused, void *stream);
 
@@ -832,6 +834,9 @@ IPK_API int ipk_pipeline_region_gather(const ipk_pipeline_desc *d, int out_type,
  *     a no-op curve, linear gamma, a no-op transform).  Nothing computed on the rectangle enters the cache.
  * The whole-frame one-launch shortcut ipk_pipeline_run_cached takes with nothing memoised is NOT taken here: the point of this call is that the next edit
  * finds the RGBE buffer.  Hits at hashes 3..6 are not used either: entering at the RGBE buffer is one launch whatever lies behind it.
+ * The order of the cache traffic: a `get` of hash 7; on a miss, where the resampling route below is open, a `contains` of hash 2, which refreshes nothing,
+ * counts neither a hit nor a miss and chooses between that route and the gather above; then a `get` per hash 0..2 (0..1 on the resampling route) in that order and a `put`
+ * per executed whole-frame op in op order.
  * The borrowed buffer may be evicted once the call has returned; freeing it waits for the device, so the enqueued launch is safe.
  * ipk_timing_begin/end see "region to_lab+basecurve+from_lab+gamma+transform" (and "quantise" where it is separate; the two-launch form: "region
  * to_lab+basecurve+from_lab+gamma", then "transform").  No host-pointer or batch form.
