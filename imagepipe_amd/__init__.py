@@ -17,13 +17,14 @@ import torch
 from . import _lib
 from ._lib import (IpkError, FusedParams, PipelineDesc, OUT_F32, OUT_U8, OUT_U16, SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16,
                    OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN,
-                   ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO)
+                   ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO, FUSED_BATCH_PREVIEWS)
 
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
            "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "raw_to_srgb_resampled_window", "raw_to_srgb_scaled_window",
            "transform_window_footprint", "raw_scaled_demosaic_window", "raw_demosaic_scaled", "raster_scale_down_window", "scaled_window_footprint", "plain_scale_down",
-           "plain_scale_down_window", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FusedPlan", "IpkError"]
+           "plain_scale_down_window", "raw_scaled_demosaic_batch", "plain_scale_down_batch", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FUSED_BATCH_PREVIEWS",
+           "FusedPlan", "IpkError"]
 
 _initialized_device = None
 
@@ -609,6 +610,7 @@ class Pipeline:
         self.resample_cached = False          # ipk_pipeline_desc.allow_fused bit 5 (IPK_FUSED_CACHED_RESAMPLE): run_region with a cache resamples the region from the cached demosaic buffer when the rotatecrop buffer is missing, where resamples_cached_region() says so; that call then never fills the rotatecrop hash
         self.fuse_scaled_rotatecrop = False   # ipk_pipeline_desc.allow_fused bit 6 (IPK_FUSED_SCALED_ROTATECROP): an active OpRotateCrop behind a scaling OpDemosaic as two launches where fuses_scaled_rotatecrop() says so; regions of such frames windowed
         self.scale_plain = False              # ipk_pipeline_desc.allow_fused bit 7 (IPK_FUSED_PLAIN_PREVIEWS): downscaled previews of monochrome / three-sample raws (u16, f32) run gofloat + demosaic as the one launch ipk_plain_scale_down where scales_plain() says so; window_previews and fuse_scaled_rotatecrop then take them too
+        self.batch_previews = False           # ipk_pipeline_desc.allow_fused bit 8 (IPK_FUSED_BATCH_PREVIEWS): run_batch() runs downscaled previews as one scaling launch group and one point-wise pass per chunk of frames where batches_previews() says so
         self.window_previews = False          # ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
 
     @staticmethod
@@ -684,6 +686,8 @@ class Pipeline:
             d.allow_fused |= _lib.FUSED_SCALED_ROTATECROP
         if self.scale_plain and d.allow_fused:
             d.allow_fused |= _lib.FUSED_PLAIN_PREVIEWS
+        if self.batch_previews and d.allow_fused:
+            d.allow_fused |= _lib.FUSED_BATCH_PREVIEWS
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -724,6 +728,36 @@ class Pipeline:
         """Do OpGoFloat and the scaling OpDemosaic of this monochrome / three-sample raw run as the one launch ipk_plain_scale_down (ipk_pipeline_scales_plain, host-only)?"""
         d = self.desc()
         return bool(_lib.check(lib().ipk_pipeline_scales_plain(C.byref(d), out_type), "ipk_pipeline_scales_plain"))
+
+    def batches_previews(self, n, out_type=OUT_F32):
+        """Does run_batch() of n frames run them as batched previews (ipk_pipeline_batches_previews, host-only)?  (taken, chunk, pass1_batched): the
+        frames per chunk and whether a chunk's scaling pass is the general kernel's one batch launch (else a launch per frame); (False, 0, False)
+        when the batch is n single runs."""
+        d = self.desc()
+        chunk, p1 = C.c_size_t(0), C.c_int(0)
+        rc = _lib.check(lib().ipk_pipeline_batches_previews(C.byref(d), out_type, int(n), C.byref(chunk), C.byref(p1)), "ipk_pipeline_batches_previews")
+        return bool(rc), int(chunk.value), bool(p1.value)
+
+    def run_batch(self, srcs, out_type=OUT_F32, out: Optional[torch.Tensor] = None):
+        """A caller's loop of run() / output_8bit() / output_16bit() over the frames of a shoot (ipk_pipeline_run_batch): srcs are device tensors shaped
+        like this pipeline's own source, one result each.  Returns an (n, h, w, 3) device tensor of the output type (u16 bits in int16) -- `out` when
+        given, else ONE fresh allocation, so that the results follow each other in memory, which is what lets batches of previews
+        (batch_previews / batches_previews()) run their point-wise pass once per chunk.  Sets last_used_fused."""
+        d = self.desc()
+        _, (fw, fh) = self.sizes()
+        n = len(srcs)
+        dt = {OUT_F32: torch.float32, OUT_U8: torch.uint8, OUT_U16: torch.int16}[out_type]
+        if out is None:
+            out = torch.empty((n, fh, fw, 3), dtype=dt, device="cuda")
+        if out.dtype != dt or out.numel() != n * fh * fw * 3 or not out.is_contiguous():
+            raise ValueError("run_batch: out must be a contiguous %s tensor of %d x %d x %d x 3 elements" % (dt, n, fh, fw))
+        step = fh * fw * 3 * out.element_size()
+        sp = (C.c_void_p * max(n, 1))(*[_ptr(t).value for t in srcs])
+        dp = (C.c_void_p * max(n, 1))(*[out.data_ptr() + i * step for i in range(n)])
+        used = C.c_int(0)
+        _lib.check(lib().ipk_pipeline_run_batch(C.byref(d), sp, dp, n, out_type, C.byref(used), _stream()), "ipk_pipeline_run_batch")
+        self.last_used_fused = bool(used.value)
+        return out.view(n, fh, fw, 3)
 
     def resamples_cached_region(self, out_type=OUT_F32) -> bool:
         """Would run_region with a cache resample the region straight from the cached demosaic buffer (ipk_pipeline_resamples_cached_region, host-only)?"""
@@ -1051,6 +1085,40 @@ def plain_scale_down_window(src: torch.Tensor, kind, owidth, x, y, width, height
         out = torch.empty(wh * ww * 4, dtype=torch.float32, device="cuda")
     _lib.check(lib().ipk_plain_scale_down_window(src.data_ptr(), st, kind, owidth, x, y, width, height, b, w, nwidth, nheight, wx, wy, ww, wh,
                                                  out.data_ptr(), _stream()), "ipk_plain_scale_down_window")
+    return out
+
+
+def _frame_ptrs(srcs):
+    return (C.c_void_p * max(len(srcs), 1))(*[t.data_ptr() for t in srcs])
+
+
+def raw_scaled_demosaic_batch(srcs: Sequence[torch.Tensor], owidth, x, y, width, height, black0, white0, cfa, nwidth, nheight, *, is_float=None,
+                              out: Optional[torch.Tensor] = None):
+    """ipk_raw_scaled_demosaic_batch: gofloat + scaled_demosaic of the sensor window (x, y, width, height) of every frame of srcs -- owidth-pitched u16
+    (int16 / uint16 tensors) or f32 frames of one shape -- into len(srcs) packed nwidth x nheight results, one launch per 64 frames where the geometry
+    selects the general kernel, one per frame otherwise.  is_float: the sample type of an empty batch (else read from the frames).  Returns the
+    n*nheight*nwidth*4 f32 device tensor; slice i is what the single-frame call gives for srcs[i]."""
+    n = len(srcs)
+    st = SRC_F32 if (srcs[0].dtype == torch.float32 if n else bool(is_float)) else SRC_U16
+    if out is None:
+        out = torch.empty(n * nheight * nwidth * 4, dtype=torch.float32, device="cuda")
+    _lib.check(lib().ipk_raw_scaled_demosaic_batch(_frame_ptrs(srcs), n, st, owidth, x, y, width, height, black0, white0, cfa.encode(), nwidth, nheight,
+                                                   out.data_ptr(), _stream()), "ipk_raw_scaled_demosaic_batch")
+    return out
+
+
+def plain_scale_down_batch(srcs: Sequence[torch.Tensor], kind, owidth, x, y, width, height, black4, white4, nwidth, nheight, *,
+                           out: Optional[torch.Tensor] = None):
+    """ipk_plain_scale_down_batch: plain_scale_down of every frame of srcs (one shape, one kind, one set of levels) into len(srcs) packed results: one
+    launch per 64 frames for PLAIN_MONO / PLAIN_RGB, one per frame for PLAIN_RASTER.  Returns the n*nheight*nwidth*4 f32 device tensor."""
+    n = len(srcs)
+    dt = srcs[0].dtype if n else torch.int16
+    st = (SRC_RGB8 if dt == torch.uint8 else SRC_RGB16) if kind == PLAIN_RASTER else (SRC_F32 if dt == torch.float32 else SRC_U16)
+    b, w = _plain_levels(kind, black4, white4)
+    if out is None:
+        out = torch.empty(n * nheight * nwidth * 4, dtype=torch.float32, device="cuda")
+    _lib.check(lib().ipk_plain_scale_down_batch(_frame_ptrs(srcs), n, st, kind, owidth, x, y, width, height, b, w, nwidth, nheight, out.data_ptr(),
+                                                _stream()), "ipk_plain_scale_down_batch")
     return out
 
 

@@ -16,6 +16,7 @@ SCHED_AUTO, SCHED_SPLIT = 0, 1
 FUSED_ON, FUSED_FOUR_COLOUR, FUSED_WINDOW_REGIONS, FUSED_WINDOW_PREVIEWS, FUSED_PLAIN, FUSED_CACHED_RESAMPLE = 1, 2, 4, 8, 16, 32   # ipk_pipeline_desc.allow_fused
 FUSED_SCALED_ROTATECROP = 64
 FUSED_PLAIN_PREVIEWS = 128
+FUSED_BATCH_PREVIEWS = 256
 PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO = 0, 1, 2                                                          # ipk_plain_kind
 OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN = range(9)
 ROT_NORMAL, ROT_90, ROT_180, ROT_270 = range(4)
@@ -138,6 +139,8 @@ SIGNATURES = {
     "ipk_raster_scale_down_window": (C.c_int, [_vp, C.c_int, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp]),
     "ipk_plain_scale_down": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz, _sz, _sz, _fp, _fp, _sz, _sz, _vp, _vp]),
     "ipk_plain_scale_down_window": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz, _sz, _sz, _fp, _fp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "ipk_raw_scaled_demosaic_batch": (C.c_int, [C.POINTER(_vp), _sz, C.c_int, _sz, _sz, _sz, _sz, _sz, C.c_float, C.c_float, C.c_char_p, _sz, _sz, _vp, _vp]),
+    "ipk_plain_scale_down_batch": (C.c_int, [C.POINTER(_vp), _sz, C.c_int, C.c_int, _sz, _sz, _sz, _sz, _sz, _fp, _fp, _sz, _sz, _vp, _vp]),
     "ipk_scaled_window_footprint": (C.c_int, [_sz, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _szp]),
     "ipk_demosaic_run": (C.c_int, [_vp, _sz, _sz, _sz, C.c_char_p, _sz, _sz, _vp, _szp, _szp, _vp]),
     "ipk_rotatecrop": (C.c_int, [_vp, _sz, _sz, _sz, _fp, _vp, _szp, _szp, _vp]),
@@ -223,6 +226,7 @@ SIGNATURES = {
     "ipk_pipeline_fuses_plain": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
     "ipk_pipeline_fuses_scaled_rotatecrop": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
     "ipk_pipeline_scales_plain": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
+    "ipk_pipeline_batches_previews": (C.c_int, [C.POINTER(PipelineDesc), C.c_int, _sz, _szp, C.POINTER(C.c_int)]),
     "ipk_pipeline_resamples_cached_region": (C.c_int, [C.POINTER(PipelineDesc), C.c_int]),
     "ipk_pipeline_hashes": (C.c_int, [C.POINTER(PipelineDesc), C.c_int, C.c_uint64, C.c_char_p]),
     "ipk_cache_new": (C.c_int, [_sz, C.POINTER(C.c_void_p)]),

@@ -877,6 +877,68 @@ int ipk_raw_scaled_demosaic(const void *src, int src_type, size_t owidth, size_t
                             float black0, float white0, const char *cfa_pat, size_t nwidth, size_t nheight, float *dst4, void *stream) {
   return raw_scaled_demosaic_impl(src, src_type, owidth, x, y, width, height, black0, white0, cfa_pat, nwidth, nheight, nullptr, dst4, stream);
 }
+// n frames of one shape into n packed results: the general kernel's batch launch (one per 64 frames) where the whole-frame call would select that kernel,
+// else the whole-frame call's own launch per frame, into slice i (a slice is nwidth * nheight * 16 bytes, so every slice is aligned as dst4 is and the
+// selection is the same for all).  Nothing is enqueued unless every frame is admitted
+namespace {
+int raw_scaled_demosaic_batch_impl(const void *const *srcs, size_t n, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0,
+                                   float white0, const char *cfa_pat, size_t nwidth, size_t nheight, float *dst4, void *stream) {
+  REQUIRE_INIT();
+  if (n == 0) return IPK_OK;
+  if (!srcs || !dst4 || !cfa_pat || !dims_ok(width, height) || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32))
+    return fail(IPK_ERR_INVALID, "bad raw_scaled_demosaic_batch arguments");
+  for (size_t i = 0; i < n; ++i) if (!srcs[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
+  const size_t slice = nwidth * nheight * 4;
+  if (!ipk::raw_scaled_demosaic_general(width, height, nwidth, nheight, (reinterpret_cast<uintptr_t>(dst4) & 15) == 0, false)) {
+    for (size_t i = 0; i < n; ++i) {
+      const int rc = raw_scaled_demosaic_impl(srcs[i], src_type, owidth, x, y, width, height, black0, white0, cfa_pat, nwidth, nheight, nullptr, dst4 + i * slice, stream);
+      if (rc) return rc;
+    }
+    return IPK_OK;
+  }
+  ipk::Cfa cfa; DevCfa dev; int rc = get_cfa(cfa_pat, cfa, dev); if (rc) return rc;
+  const int norm_fast = validate_cdiv_for_range(black0, white0 - black0, src_type == IPK_SRC_U16) ? 1 : 0;
+  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(nullptr, owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0, nullptr, nullptr, srcs, n);
+  else ipk::launch_raw_scaled_demosaic<float>(nullptr, owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0, nullptr, nullptr, srcs, n);
+  HIPCHK(hipGetLastError());
+  return IPK_OK;
+}
+// the same for monochrome and three-sample raws, whose launches are always the general kernel's; IPK_PLAIN_RASTER forwards frame by frame
+int plain_scale_down_batch_impl(const void *const *srcs, size_t n, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                const float *black4, const float *white4, size_t nwidth, size_t nheight, float *dst4, void *stream) {
+  REQUIRE_INIT();
+  if (n == 0) return IPK_OK;
+  if (!srcs) return fail(IPK_ERR_INVALID, "bad plain_scale_down_batch arguments");
+  for (size_t i = 0; i < n; ++i) if (!srcs[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
+  const size_t slice = nwidth * nheight * 4;
+  if (kind == IPK_PLAIN_RASTER) {
+    for (size_t i = 0; i < n; ++i) {
+      const int rc = raster_scale_down_impl(srcs[i], src_type, owidth, x, y, width, height, nwidth, nheight, nullptr, dst4 ? dst4 + i * slice : nullptr, stream);
+      if (rc) return rc;
+    }
+    return IPK_OK;
+  }
+  if (kind != IPK_PLAIN_RGB && kind != IPK_PLAIN_MONO) return fail(IPK_ERR_INVALID, "bad plain kind");
+  if (!dst4 || !black4 || !white4 || !dims_ok(width, height) || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32))
+    return fail(IPK_ERR_INVALID, "bad plain_scale_down_batch arguments");
+  if (x + width > owidth) return fail(IPK_ERR_INVALID, "plain_scale_down_batch: window wider than the source pitch");
+  ipk::PlainLevels pl;
+  pl.layout = kind == IPK_PLAIN_MONO ? 1 : 3;
+  for (int c = 0; c < 3; ++c) { pl.black[c] = black4[c]; pl.white[c] = white4[c]; }
+  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(nullptr, owidth, x, y, width, height, 0.0f, 0.0f, 0, 0, nwidth, nheight, nullptr, 0, 0, dst4, S(stream), 0, 0, 0, nullptr, &pl, srcs, n);
+  else ipk::launch_raw_scaled_demosaic<float>(nullptr, owidth, x, y, width, height, 0.0f, 0.0f, 0, 0, nwidth, nheight, nullptr, 0, 0, dst4, S(stream), 0, 0, 0, nullptr, &pl, srcs, n);
+  HIPCHK(hipGetLastError());
+  return IPK_OK;
+}
+}  // namespace
+int ipk_raw_scaled_demosaic_batch(const void *const *srcs, size_t n, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                  float black0, float white0, const char *cfa_pat, size_t nwidth, size_t nheight, float *dst4, void *stream) {
+  return raw_scaled_demosaic_batch_impl(srcs, n, src_type, owidth, x, y, width, height, black0, white0, cfa_pat, nwidth, nheight, dst4, stream);
+}
+int ipk_plain_scale_down_batch(const void *const *srcs, size_t n, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                               const float *black4, const float *white4, size_t nwidth, size_t nheight, float *dst4, void *stream) {
+  return plain_scale_down_batch_impl(srcs, n, src_type, kind, owidth, x, y, width, height, black4, white4, nwidth, nheight, dst4, stream);
+}
 // the columns [wx, wx + ww) and rows [wy, wy + wh) of the same result: the same kernel, its grid laid over the window
 int ipk_raw_scaled_demosaic_window(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
                                    const char *cfa_pat, size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream) {
@@ -2949,6 +3011,75 @@ void HostLanes::release() {
 // ------------------------------------------------------------------------------------------
 // A caller looping Pipeline::run over the frames of a shoot (src/pipeline.rs:246-249: frames are independent), device pointers
 // ------------------------------------------------------------------------------------------
+namespace {
+// IPK_FUSED_BATCH_PREVIEWS: a batch of staged frames whose gofloat + demosaic is the one scaling pass (gofloat_demosaic_one_pass) and whose every later op
+// is point-wise (OpRotateCrop and OpTransform no-ops) runs chunk by chunk as one scaling launch group into one RGBE scratch, then the chain over the
+// previews lying one after another.  dw * dh >= 256 is the one-pass chain's own floor, kept per frame: the batch uses the kernels a single frame would.
+// chunk: frames per scratch (at most 64, at most 256 MiB of RGBE); pass1_batched: pass 1 is the general scaling kernel's batch launch (the scratch slices
+// are 16-byte aligned), else one launch per frame of the kernel the frame selects
+struct BatchPreviews { size_t chunk; bool pass1_batched; };
+bool batches_previews(const ipk_pipeline_desc *d, const Negotiated &n, const Route &rt, size_t frames, BatchPreviews &bp) {
+  bp.chunk = 0; bp.pass1_batched = false;
+  if (!opted(d, IPK_FUSED_BATCH_PREVIEWS) || frames <= 1 || rt.kind != kStaged || !gofloat_demosaic_one_pass(d, n) || !n.rc.noop() || !n.transform_noop ||
+      n.dw * n.dh < 256) return false;
+  bp.chunk = std::min<size_t>(64, std::max<size_t>(1, ((size_t)256 << 20) / (n.dw * n.dh * 16)));
+  bp.pass1_batched = n.raw && ipk::raw_scaled_demosaic_general(n.r.width, n.r.height, n.dw, n.dh, true, !n.cfa_branch);
+  return true;
+}
+int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, void *const *dsts, size_t n,
+                       int out_type, int *used_fused, void *stream) {
+  const size_t px = ng.dw * ng.dh, slice = px * 4, out_bytes = px * 3 * out_elem_size(out_type);
+  const bool f32_out = out_type == IPK_OUT_F32;
+  const int monochrome = one_pass_monochrome(d, ng);
+  for (size_t i0 = 0; i0 < n; i0 += bp.chunk) {
+    const size_t m = std::min(bp.chunk, n - i0);
+    if (m == 1) { const int rc = ipk_pipeline_run(d, srcs[i0], dsts[i0], out_type, used_fused, stream); if (rc < 0) return rc; continue; }
+    StageTimer tm(S(stream));
+    Scratch sc(S(stream));
+    void *buf = nullptr;
+    int rc = sc.get(m * slice * sizeof(float), &buf); if (rc) return rc;
+    float *rgbe = static_cast<float *>(buf);
+    // pass 1: the chunk's RGBE previews, one after another
+    if (bp.pass1_batched) {
+      rc = ng.cfa_branch ? raw_scaled_demosaic_batch_impl(srcs + i0, m, d->src_type, d->width, ng.r.x, ng.r.y, ng.r.width, ng.r.height, d->blacklevels[0],
+                                                          d->whitelevels[0], d->cfa, ng.dw, ng.dh, rgbe, stream)
+                         : plain_scale_down_batch_impl(srcs + i0, m, d->src_type, d->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO, d->width, ng.r.x, ng.r.y, ng.r.width,
+                                                       ng.r.height, d->blacklevels, d->whitelevels, ng.dw, ng.dh, rgbe, stream);
+      if (rc < 0) return rc;
+    } else {
+      for (size_t i = 0; i < m; ++i) { rc = launch_gofloat_demosaic(d, ng, srcs[i0 + i], nullptr, rgbe + i * slice, stream); if (rc < 0) return rc; }
+    }
+    tm.mark("batch gofloat+demosaic");
+    // pass 2: the chain once per maximal run of frames whose destinations follow each other in memory
+    for (size_t j = 0; j < m;) {
+      size_t k = j + 1;
+      while (k < m && dsts[i0 + k] == static_cast<char *>(dsts[i0 + k - 1]) + out_bytes) ++k;
+      rc = ipk_pointwise_chain_out(rgbe + j * slice, ng.dw, (k - j) * ng.dh, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
+                                   ng.linear, out_type, dsts[i0 + j], stream);
+      if (rc < 0) return rc;
+      tm.mark(f32_out ? "batch to_lab+basecurve+from_lab+gamma" : "batch to_lab+basecurve+from_lab+gamma+quantise");
+      j = k;
+    }
+  }
+  return IPK_OK;
+}
+}  // namespace
+
+// IPK_FUSED_BATCH_PREVIEWS: does a batch of n frames of this descriptor run as batched previews (1) or frame by frame (0)?  The driver's own test (no GPU)
+int ipk_pipeline_batches_previews(const ipk_pipeline_desc *d, int out_type, size_t n, size_t *chunk, int *pass1_batched) {
+  if (chunk) *chunk = 0;
+  if (pass1_batched) *pass1_batched = 0;
+  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  Negotiated ng; const int rc = negotiate(d, out_type, ng); if (rc) return rc;
+  Route rt; choose_route(d, ng, out_type, rt);
+  BatchPreviews bp;
+  if (!batches_previews(d, ng, rt, n, bp)) return 0;
+  if (chunk) *chunk = bp.chunk;
+  if (pass1_batched) *pass1_batched = bp.pass1_batched ? 1 : 0;
+  return 1;
+}
+
 int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *srcs, void *const *dsts, size_t n, int out_type, int *used_fused, void *stream) {
   REQUIRE_INIT();
   if (!d || (n && (!srcs || !dsts))) return fail(IPK_ERR_INVALID, "null argument");
@@ -2965,6 +3096,11 @@ int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *srcs, 
     if (rc == IPK_OK && used_fused) *used_fused = 1;
     return rc;
   }
+  // Or a batch of previews under IPK_FUSED_BATCH_PREVIEWS: a scaling launch group and the chain per chunk (run_batch_previews)
+  BatchPreviews bp;
+  if (n > 1 && (d->allow_fused & IPK_FUSED_BATCH_PREVIEWS) && negotiate(d, out_type, ng) == IPK_OK &&
+      (choose_route(d, ng, out_type, rt), batches_previews(d, ng, rt, n, bp)))
+    return run_batch_previews(d, ng, bp, srcs, dsts, n, out_type, used_fused, stream);
   for (size_t i = 0; i < n; ++i) { const int rc = ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); if (rc < 0) return rc; }
   return IPK_OK;
 }

@@ -670,15 +670,29 @@ void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, si
   else IPK_LAUNCH_TAG(t, k_raster_scale_down<uint8_t>, grid, dim3(128), 0, s, static_cast<const uint8_t *>(src), a, gr, reinterpret_cast<float4 *>(dst4));
 }
 
+// the frames of a batch launch: up to kBatchMax per launch, passed by value as a kernel argument (no host or device memory with a lifetime)
+constexpr int kBatchMax = 64;
+// k_raw_scaled_demosaic's batch mode (launch-uniform): on = 1, gridDim.z frames of one shape whose sources are src[0 .. gridDim.z); on = 0 (gridDim.z
+// == 1): the kernel's own src and dst arguments, src[] is not read
+struct ScaledBatch { const void *src[kBatchMax]; uint32_t on; };
+
 // OpGoFloat (CFA branch) + scaling::scaled_demosaic in one pass over the raw sensor frame: dst4 = scaled_demosaic(gofloat(src)).
 // T = uint16_t or float sensor samples; writes f32 RGBE.  (src/ops/gofloat.rs:122-130,158-166 + src/scaling.rs:132-145)
+// Batch mode (bp.on): blockIdx.z is the frame -- its source comes from bp, its result is the z-th out_rows x out_cols slice behind dst.  Nothing else a lane
+// computes depends on z: bounds, centres, weights, the CFA phase and the store's row and column are functions of the absolute row and column as ever
 template <typename T>
-__global__ void k_raw_scaled_demosaic(const T *__restrict__ src, TransformArgs a, const uint8_t *__restrict__ cfa48, float *__restrict__ dst) {
+__global__ void k_raw_scaled_demosaic(const T *__restrict__ src0, TransformArgs a, const uint8_t *__restrict__ cfa48, float *__restrict__ dst0, ScaledBatch bp) {
   __shared__ uint8_t s_cfa[48 * 48];
   const bool mosaic = a.layout == 0;                                        // launch-uniform: so is the barrier
   if (mosaic) {
     for (int i = threadIdx.x; i < 48 * 48; i += blockDim.x) s_cfa[i] = cfa48[i];
     __syncthreads();
+  }
+  const T *__restrict__ src = src0;
+  float *__restrict__ dst = dst0;
+  if (bp.on) {
+    src = static_cast<const T *>(bp.src[blockIdx.z]);
+    dst = dst0 + (size_t)blockIdx.z * (a.out_r1 - a.out_r0) * (a.out_c1 - a.out_c0) * 4;
   }
   const uint32_t col = a.out_c0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (col >= a.out_c1) return;
@@ -1142,7 +1156,8 @@ __global__ __launch_bounds__(256, C4 ? 6 : 7) void k_raw_scaled_demosaic_w8m(con
 template <typename T>
 void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
                                 int norm_fast, int has_fourth_colour, size_t nwidth, size_t nheight, const uint8_t *cfa48_dev, int pw, int ph, float *dst4, hipStream_t s,
-                                size_t band_src_row0, size_t band_out_row0, size_t band_out_rows, const ResampleWindow *win, const PlainLevels *plain) {
+                                size_t band_src_row0, size_t band_out_row0, size_t band_out_rows, const ResampleWindow *win, const PlainLevels *plain,
+                                const void *const *batch_srcs, size_t batch_n) {
   if (plain) { black0 = plain->black[0]; white0 = plain->white[0]; norm_fast = 0; has_fourth_colour = 1; }
   TransformArgs a{};
   a.width = (uint32_t)width; a.height = (uint32_t)height; a.nwidth = (uint32_t)nwidth; a.nheight = (uint32_t)nheight; a.components = 4;
@@ -1172,25 +1187,44 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
   a.xcd_gx = 0; a.xcd_gy = 0; a.xcd_group = 0;
   // launch-log tag: the host-known switches the kernels branch on, "norm_fast=.,norm_light=.,fast_x=.,fast_y=.,xcd=." (xcd: 0 plain grid, 1 XCD row
   // grouping with no leftover rows, 2 grouping with leftover rows); window launches, and only they, append ",win=1"; the monochrome / three-sample
-  // launches, and only they, append ",plain=1" / ",plain=3" behind that (table entries 96..191 / 192..287)
+  // launches, and only they, append ",plain=1" / ",plain=3" behind that (table entries 96..191 / 192..287); batch launches, and only they, append
+  // ",batch=1" behind all of it (entries 288..575)
   auto tag = [&](int xcd) -> const char * {
     if (!g_log_on.load(std::memory_order_relaxed)) return nullptr;         // the table is built, and read, only while the log is on
     static const std::vector<std::string> tags = [] {
       std::vector<std::string> t;
-      for (int i = 0; i < 288; ++i) {
-        const int j = i % 96;
-        char b[96]; snprintf(b, sizeof(b), "norm_fast=%d,norm_light=%d,fast_x=%d,fast_y=%d,xcd=%d%s%s", j & 1, (j >> 1) & 1, (j >> 2) & 1, (j >> 3) & 1, (j % 48) >> 4, j >= 48 ? ",win=1" : "",
-                             i >= 192 ? ",plain=3" : i >= 96 ? ",plain=1" : "");
+      for (int i = 0; i < 576; ++i) {
+        const int j = i % 96, k = i % 288;
+        char b[112]; snprintf(b, sizeof(b), "norm_fast=%d,norm_light=%d,fast_x=%d,fast_y=%d,xcd=%d%s%s%s", j & 1, (j >> 1) & 1, (j >> 2) & 1, (j >> 3) & 1, (j % 48) >> 4, j >= 48 ? ",win=1" : "",
+                              k >= 192 ? ",plain=3" : k >= 96 ? ",plain=1" : "", i >= 288 ? ",batch=1" : "");
         t.push_back(b);
       }
       return t;
     }();
-    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4)) + (win ? 48 : 0) + (a.layout == 3 ? 192 : a.layout == 1 ? 96 : 0)].c_str();
+    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4)) + (win ? 48 : 0) + (a.layout == 3 ? 192 : a.layout == 1 ? 96 : 0) +
+                (batch_n ? 288 : 0)].c_str();
   };
   a.components = has_fourth_colour ? 4 : 3;               // the w8 kernel skips the fourth bin for three-colour filters (it stays 0.0)
   // windows of at most 8 x 8 samples: floor(skip*(c+1)) - floor(skip*c) + 1 <= ceil(skip) + 1 (mosaics only: the 8-sample kernels have no plain mode)
-  if (!plain && a.skip_x_x >= 1.0f && a.skip_x_x <= 7.0f && a.skip_y_y >= 1.0f && a.skip_y_y <= 7.0f && width >= 8 &&
-      (reinterpret_cast<uintptr_t>(dst4) & 15) == 0) {
+  const bool general = raw_scaled_demosaic_general(width, height, nwidth, nheight, (reinterpret_cast<uintptr_t>(dst4) & 15) == 0, plain != nullptr);
+  if (batch_n) {
+    // Frames of one shape behind one launch per kBatchMax of them: the general kernel's batch mode.  The caller asked raw_scaled_demosaic_general first (the
+    // window-8 kernels have no such mode: nothing is launched for a geometry that selects them) and passes whole frames.  grid_rows_few's block budget is
+    // shared by the frames of a launch, one block row per frame at the least
+    if (!general || band_out_rows || win || !batch_srcs) return;
+    const size_t slice = out_rows * out_cols * 4;
+    for (size_t i0 = 0; i0 < batch_n; i0 += (size_t)kBatchMax) {
+      const size_t nb = std::min<size_t>((size_t)kBatchMax, batch_n - i0);
+      ScaledBatch bp;
+      for (size_t i = 0; i < (size_t)kBatchMax; ++i) bp.src[i] = i < nb ? batch_srcs[i0 + i] : nullptr;
+      bp.on = 1;
+      dim3 grid = grid_rows_few(out_cols, out_rows, 128, (unsigned)(8192 / nb));
+      grid.z = (unsigned)nb;
+      IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid, dim3(128), 0, s, static_cast<const T *>(nullptr), a, cfa48_dev, dst4 + i0 * slice, bp);
+    }
+    return;
+  }
+  if (!general) {
     const unsigned gx = (unsigned)((out_cols + 255) / 256);
     // 21 blocks per CU = 3 full rounds of the 7 resident ones.  Round 4 sweep (50 MP X-Trans -> 2160x1440, one box, ms): 1620 / 1792 / 2688 / 3584 / 5376 /
     // 7168 blocks 0.064 / 0.059 / 0.058 / 0.0565 / 0.0563 / 0.0565 with the plain grid, 0.064 / 0.061 / 0.060 / 0.057 / 0.059 / 0.058 with runs of two
@@ -1227,10 +1261,13 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
     IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic_w8<T>, grid, dim3(256), 0, s, src, a, cfa48_dev, dst4);
     return;
   }
-  IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(out_cols, out_rows, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst4);
+  ScaledBatch one;                                                           // batch mode off: the table is not read
+  for (int i = 0; i < kBatchMax; ++i) one.src[i] = nullptr;
+  one.on = 0;
+  IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(out_cols, out_rows, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst4, one);
 }
-template void launch_raw_scaled_demosaic<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *, const PlainLevels *);
-template void launch_raw_scaled_demosaic<float>(const float *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *, const PlainLevels *);
+template void launch_raw_scaled_demosaic<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *, const PlainLevels *, const void *const *, size_t);
+template void launch_raw_scaled_demosaic<float>(const float *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *, const PlainLevels *, const void *const *, size_t);
 template void launch_transform_buffer<float>(const float *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, float *, hipStream_t);
 template void launch_transform_buffer<uint8_t>(const uint8_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint8_t *, hipStream_t);
 template void launch_transform_buffer<uint16_t>(const uint16_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint16_t *, hipStream_t);
@@ -2340,7 +2377,6 @@ struct RgbeStage {
 // branches in the row loop; with them folded away the f32 kernel is 4 % faster.  Anything else runs the CMN = false variant.
 // ROT = the launch works in rotated space (see OriFlips): any of the seven non-Normal orientations, wave-uniform dispatch on a.ori.
 // the frames of a batch launch: up to kBatchMax per launch, passed by value as the second kernel argument (1 KB of kernarg)
-constexpr int kBatchMax = 64;
 struct BatchPtrs { const void *src[kBatchMax]; void *dst[kBatchMax]; };
 // WIN variants (k_fused_bayer_window, ipk_pipeline_run_region): the launch computes the cropped frame's columns [x0, x1) -- the region's columns rounded
 // out to whole 4-pixel lane groups and clipped to the frame -- and stores only the region's columns [c0, c1), packed at `pitch` pixels per output row.

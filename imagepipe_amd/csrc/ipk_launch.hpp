@@ -44,7 +44,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // sample; wrap: the grid cap holds), k_gofloat_cfa_v4 [rowwrap=] (more rows than grid rows), the ipk_raw_scaled_demosaic kernels
 // [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows; their window launches,
 // ipk_raw_scaled_demosaic_window, append win=1: [norm_fast=,...,xcd=,win=1]; the monochrome / three-sample launches of k_raw_scaled_demosaic by
-// ipk_plain_scale_down append plain=1 / plain=3 behind that), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
+// ipk_plain_scale_down append plain=1 / plain=3 behind that; its batch launches -- ipk_raw_scaled_demosaic_batch / ipk_plain_scale_down_batch -- append
+// batch=1 behind all of it: [...,xcd=0,batch=1] / [...,xcd=0,plain=1,batch=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form); the gather
 // launches of k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2> (a GatherSource: ipk_pipeline_run_cached_region) append
 // gather=1: [fast_ok=,gather=1] -- flat launches never carry the key;
@@ -83,7 +84,20 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
                                 size_t nwidth, size_t nheight, const uint8_t *cfa48_dev, int pattern_width, int pattern_height, float *dst4, hipStream_t s,
                                 size_t band_src_row0 = 0, size_t band_out_row0 = 0, size_t band_out_rows = 0,    // band_out_rows == 0: the whole frame
                                 const ResampleWindow *win = nullptr,                                             // not together with a band
-                                const PlainLevels *plain = nullptr);
+                                const PlainLevels *plain = nullptr,
+                                const void *const *batch_srcs = nullptr, size_t batch_n = 0);                    // batch mode, below (src is not read)
+// Which kernel a whole-frame, band or window launch of launch_raw_scaled_demosaic takes: true = the general kernel k_raw_scaled_demosaic<T> (a skip above
+// 7 or below 1, a frame under 8 samples wide, a destination off a 16-byte boundary, every plain layout), false = a window-8 kernel.  The launcher's own
+// test, with its f32 skips
+inline bool raw_scaled_demosaic_general(size_t width, size_t height, size_t nwidth, size_t nheight, bool dst_aligned16, bool plain) {
+  const float skip_x = ((float)((int64_t)width - 1) - 0.0f) / ((float)(nwidth - 1));
+  const float skip_y = ((float)((int64_t)height - 1) - 0.0f) / ((float)(nheight - 1));
+  return !(!plain && skip_x >= 1.0f && skip_x <= 7.0f && skip_y >= 1.0f && skip_y <= 7.0f && width >= 8 && dst_aligned16);
+}
+// Batch mode (batch_n > 0; whole frames only, and only where raw_scaled_demosaic_general holds -- nothing is launched otherwise): batch_srcs[0 .. batch_n)
+// are the frames of one shape (a host array, read before the call returns: the pointers travel by value in the kernel's arguments), dst4 holds batch_n
+// packed nwidth x nheight results one after another, slice i bit-identical to the single-frame launch of batch_srcs[i].  One launch per 64 frames,
+// blockIdx.z the frame; the launches append batch=1 to the tag: [norm_fast=,...,xcd=0,batch=1] / [...,xcd=0,plain=1,batch=1]
 
 void launch_tolab(const float *src4, size_t npix, const float *mul4, const float *cm12, const void *lab_pairs, float *dst3,
                   int num_cus, hipStream_t s);

@@ -266,6 +266,18 @@ IPK_API int ipk_plain_scale_down(const void *src, int src_type, int kind, size_t
 IPK_API int ipk_plain_scale_down_window(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height,
                                         const float *black4, const float *white4, size_t nwidth, size_t nheight,
                                         size_t wx, size_t wy, size_t ww, size_t wh, float *dst4, void *stream);
+/* The batch forms of ipk_raw_scaled_demosaic and ipk_plain_scale_down: n sensor frames of one shape and one set of parameters, srcs[i] frame i's first
+ * sample (a host array of device pointers, read before the call returns).  dst4 receives n * nwidth * nheight * 4 packed f32, slice i bit-identical to
+ * the whole-frame call on srcs[i], and nothing else is written.  Where the whole-frame call would select the general kernel (one thread per output
+ * pixel: a skip above 7 or below 1, a frame under 8 samples wide, dst4 off a 16-byte boundary; every IPK_PLAIN_RGB / IPK_PLAIN_MONO launch) the frames
+ * run as ONE launch per 64 of them, a frame per grid plane -- a thumbnail alone leaves most of the chip idle and a pixel's window cannot be split;
+ * otherwise (the window-8 kernels; IPK_PLAIN_RASTER) as one launch per frame of the kernel the whole-frame call selects, into slice i: slices are
+ * 16-byte aligned whenever dst4 is, so the selection is the same for every frame.  Admission and errors are those of the whole-frame forms; n = 0 is
+ * IPK_OK with nothing enqueued, a null srcs[i] IPK_ERR_INVALID with nothing enqueued. */
+IPK_API int ipk_raw_scaled_demosaic_batch(const void *const *srcs, size_t n, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                          float black0, float white0, const char *cfa, size_t nwidth, size_t nheight, float *dst4, void *stream);
+IPK_API int ipk_plain_scale_down_batch(const void *const *srcs, size_t n, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width,
+                                       size_t height, const float *black4, const float *white4, size_t nwidth, size_t nheight, float *dst4, void *stream);
 /* OpGoFloat::run_raw (CFA branch) followed by OpDemosaic::run's LAST branch -- demosaic::full, then scale_down_opbuf to nwidth x nheight
  * (src/ops/demosaic.rs:51-59: 1 < scale < minscale) -- in one launch over the raw sensor frame: ipk_raw_scaled_demosaic's sibling below minscale.  dst4
  * receives nwidth * nheight * 4 f32, bit for bit what ipk_gofloat_cfa_* -> ipk_demosaic_run write for such a frame (E = +0.0); the full-size 1- and
@@ -549,7 +561,11 @@ typedef struct {
                                       Bit 7 (IPK_FUSED_PLAIN_PREVIEWS = 128), beside IPK_FUSED_ON as well: a monochrome or three-sample raw (u16 or f32) whose
                                       OpDemosaic scales runs OpGoFloat + OpDemosaic as the one launch ipk_plain_scale_down where ipk_pipeline_scales_plain says
                                       so; bits 3 and 6 then take such frames as they take the other previews.  Same contract: no hash, no result.  Like bits 3
-                                      and 4, allow_fused = 128 alone still means "on" for every older route (any non-zero value does). */
+                                      and 4, allow_fused = 128 alone still means "on" for every older route (any non-zero value does).
+                                      Bit 8 (IPK_FUSED_BATCH_PREVIEWS = 256), beside IPK_FUSED_ON as well, concerns ipk_pipeline_run_batch (and the drivers that
+                                      go through it) alone: a batch of downscaled previews runs as one scaling launch group and one point-wise pass per chunk
+                                      of frames where ipk_pipeline_batches_previews says so.  Same contract: no hash, no result, no other driver or report
+                                      depends on it.  Like bits 3, 4 and 7, allow_fused = 256 alone still means "on" for every older route. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -597,7 +613,7 @@ typedef enum {
                                       lands a pixel short, so this is the common straightened frame, and every straightened preview) runs as two launches
                                       instead of the staged ops, where ipk_pipeline_fuses_scaled_rotatecrop says so; regions of such frames are windowed.
                                       Monochrome and three-sample raws only together with bit 7 */
-  IPK_FUSED_PLAIN_PREVIEWS = 128   /* bit 7 (beside bit 0): downscaled previews of monochrome and three-sample raws (cpp == 1 without a filter, cpp == 3; u16
+  IPK_FUSED_PLAIN_PREVIEWS = 128,  /* bit 7 (beside bit 0): downscaled previews of monochrome and three-sample raws (cpp == 1 without a filter, cpp == 3; u16
                                       and f32) run OpGoFloat + OpDemosaic's scale_down_opbuf branch as ONE pass over the source (ipk_plain_scale_down: the
                                       monochrome / three-sample modes of ipk_raw_scaled_demosaic's general kernel) where ipk_pipeline_scales_plain says so,
                                       instead of a full-size 16-byte-per-pixel buffer and a tap-by-tap pass over it.  With bit 3 their regions are windowed,
@@ -615,6 +631,17 @@ typedef enum {
                                       parent 0.149 ms (spread 0.001) -> 0.148 ms.  Not measured: the host form of the regions, regions of the straightened
                                       case, 100 MP frames, 16-bit outputs, photo-like data, and the 8-sample mosaic kernels (k_raw_scaled_demosaic_w8 / _w8m:
                                       their code is untouched, their argument block grew by five words) */
+  IPK_FUSED_BATCH_PREVIEWS = 256   /* bit 8 (beside bit 0): ipk_pipeline_run_batch runs a batch of downscaled previews -- staged frames whose OpGoFloat +
+                                      OpDemosaic is the one scaling pass (mosaics at scale >= minscale, rasters under a size limit, monochrome / three-sample
+                                      raws under bit 7), OpRotateCrop and OpTransform no-ops, at least 256 pixels per preview -- chunk by chunk: the scaling
+                                      pass of a chunk as ONE launch per 64 frames where the frames select the general kernel (ipk_raw_scaled_demosaic_batch /
+                                      ipk_plain_scale_down_batch; else a launch per frame), then the point-wise chain ONCE over the previews lying one after
+                                      another, where ipk_pipeline_batches_previews says so.  A thumbnail's scaling launch is far too small to fill the chip
+                                      and its windows cannot be split across lanes (one accumulator, y outer, x inner): frames are the parallelism left.
+                                      Out of scope, falling to the per-frame loop: non-Normal orientations and active rotatecrops in a batch; batch forms of
+                                      the window-8 kernels and the raster scaler (a launch per frame inside the route); the host-buffer batch
+                                      (ipk_host_pipeline_run_batch is unchanged); band (multi-GPU single-frame) forms; the bit as a default.
+                                      Measurements: profiles/r19_batch_previews.txt */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -757,6 +784,20 @@ IPK_API int ipk_host_pipeline_run_batch(const ipk_pipeline_desc *d, const void *
  * n calls of ipk_pipeline_run.  Results are what n calls of ipk_pipeline_run give. */
 IPK_API int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *srcs, void *const *dsts, size_t n, int out_type,
                                    int *used_fused, void *stream);
+/* Does ipk_pipeline_run_batch (and ipk_pipeline_run_batch_multi, member by member) run n frames of this descriptor as batched previews BECAUSE of
+ * IPK_FUSED_BATCH_PREVIEWS?  1 when d->allow_fused has IPK_FUSED_ON and IPK_FUSED_BATCH_PREVIEWS set, n > 1, the frame is staged and its OpGoFloat +
+ * OpDemosaic is the one scaling pass (a one-sample-per-pixel mosaic at scale >= minscale, an RGB8 / RGB16 raster at scale > 1 off the fast path, or --
+ * with IPK_FUSED_PLAIN_PREVIEWS -- a monochrome or three-sample raw at scale > 1), OpRotateCrop is a no-op, the orientation is Normal, and the preview
+ * has at least 256 pixels (the one-pass chain's floor, kept per frame).  0 otherwise, and the batch is n calls of ipk_pipeline_run as before; a negative
+ * error code for a descriptor ipk_pipeline_sizes refuses.  *chunk (may be NULL; 0 when the answer is not 1) receives the frames per chunk,
+ * min(64, max(1, 256 MiB / (demosaic_w * demosaic_h * 16))); *pass1_batched (may be NULL) 1 when a chunk's scaling pass is the general kernel's batch
+ * launch (ipk_raw_scaled_demosaic_batch's rule on the 16-byte aligned scratch; every monochrome / three-sample raw), 0 when it is a launch per frame
+ * (skips from 1 to 7 on a mosaic at least 8 samples wide; rasters).  Per chunk: pass 1 writes the chunk's RGBE previews into one scratch buffer, pass 2
+ * runs ipk_pointwise_chain_out once per maximal run of frames whose destinations follow each other in memory (dsts[i + 1] == dsts[i] + demosaic_w *
+ * demosaic_h * 3 samples) -- scattered destinations cost one chain launch per frame and nothing else; a chunk of one frame is ipk_pipeline_run.  Results
+ * and *used_fused are what n calls of ipk_pipeline_run give.  ipk_timing names the stages "batch gofloat+demosaic" and
+ * "batch to_lab+basecurve+from_lab+gamma+quantise" (without "+quantise" for f32).  No GPU needed. */
+IPK_API int ipk_pipeline_batches_previews(const ipk_pipeline_desc *d, int out_type, size_t n, size_t *chunk, int *pass1_batched);
 /* The same over the DEVICE SET (ipk_init_devices) from one host thread: frame i runs on set member i mod N, so srcs[i] / dsts[i] must live on
  * that member's device.  Nothing is exchanged between devices and every result stays where it was computed (frames are independent pipelines,
  * src/pipeline.rs:246-249).  Enqueues on one internal stream per member and returns; ipk_devices_sync waits for all of them.  Without a device

@@ -305,6 +305,7 @@ class Pipeline {
   bool resample_cached = false;            // ipk_pipeline_desc.allow_fused bit 5 (IPK_FUSED_CACHED_RESAMPLE): run_region with a cache resamples the region from the cached demosaic buffer when the rotatecrop buffer is missing, where resamples_cached_region() says so; that call then never fills the rotatecrop hash
   bool fuse_scaled_rotatecrop = false;     // ipk_pipeline_desc.allow_fused bit 6 (IPK_FUSED_SCALED_ROTATECROP): an active OpRotateCrop behind a scaling OpDemosaic as two launches where fuses_scaled_rotatecrop() says so; regions of such frames windowed
   bool scale_plain = false;                // ipk_pipeline_desc.allow_fused bit 7 (IPK_FUSED_PLAIN_PREVIEWS): downscaled previews of monochrome / three-sample raws (u16, f32) run gofloat + demosaic as the one launch ipk_plain_scale_down where scales_plain() says so; window_previews and fuse_scaled_rotatecrop then take them too
+  bool batch_previews = false;             // ipk_pipeline_desc.allow_fused bit 8 (IPK_FUSED_BATCH_PREVIEWS): run_batch() runs downscaled previews as one scaling launch group and one point-wise pass per chunk of frames where batches_previews() says so
   bool window_previews = false;            // ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
   int last_ops_run = 0xFF;                 // bit i: op i executed in the last run (0 = served from the cache)
   uint64_t source_id = 0;                  // identifies the frame inside a shared PipelineCache (extension, see the C header)
@@ -356,6 +357,20 @@ class Pipeline {
     last_region_windowed = win != 0;
     return o;
   }
+  // A caller's loop of run() / output_8bit / output_16bit over the frames of a shoot (ipk_pipeline_run_batch): raws are device pointers to frames shaped
+  // like this pipeline's own source.  ONE device allocation of raws.size() results of out_type, one after another -- which is what lets batches of
+  // previews (batch_previews / batches_previews()) run their point-wise pass once per chunk
+  DeviceArray run_batch(const std::vector<const void *> &raws, int out_type = IPK_OUT_F32) {
+    ipk_pipeline_desc d = desc();
+    size_t fw, fh; std::tie(fw, fh) = final_size();
+    const size_t step = fw * fh * 3 * (out_type == IPK_OUT_F32 ? 4 : out_type == IPK_OUT_U8 ? 1 : 2);
+    DeviceArray o(std::max<size_t>(raws.size() * step, 1));
+    std::vector<void *> outs(raws.size());
+    for (size_t i = 0; i < raws.size(); ++i) outs[i] = static_cast<char *>(o.get()) + i * step;
+    check(ipk_pipeline_run_batch(&d, raws.data(), outs.data(), raws.size(), out_type, nullptr, nullptr), "pipeline_run_batch");
+    check(ipk_stream_sync(nullptr), "sync");
+    return o;
+  }
   bool last_region_windowed = false;
   // ophashes of pipeline.rs:342-361
   std::vector<std::array<uint8_t, 32>> hashes(int out_type = IPK_OUT_F32) const {
@@ -402,6 +417,7 @@ class Pipeline {
     if (resample_cached && d.allow_fused) d.allow_fused |= IPK_FUSED_CACHED_RESAMPLE;
     if (fuse_scaled_rotatecrop && d.allow_fused) d.allow_fused |= IPK_FUSED_SCALED_ROTATECROP;
     if (scale_plain && d.allow_fused) d.allow_fused |= IPK_FUSED_PLAIN_PREVIEWS;
+    if (batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_PREVIEWS;
     return d;
   }
   // does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop; no GPU needed)?  out_type: IPK_OUT_*
@@ -418,6 +434,15 @@ class Pipeline {
   bool fuses_scaled_rotatecrop(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_fuses_scaled_rotatecrop(&d, out_type) == 1; }
   // do OpGoFloat and the scaling OpDemosaic of this monochrome / three-sample raw run as the one launch ipk_plain_scale_down (ipk_pipeline_scales_plain)?
   bool scales_plain(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_scales_plain(&d, out_type) == 1; }
+  // does run_batch() of n frames run them as batched previews (ipk_pipeline_batches_previews)?  chunk / pass1_batched (optional): the frames per chunk, and
+  // whether a chunk's scaling pass is the general kernel's one batch launch
+  bool batches_previews(size_t n, int out_type = IPK_OUT_F32, size_t *chunk = nullptr, bool *pass1_batched = nullptr) const {
+    const ipk_pipeline_desc d = desc(); size_t c = 0; int p1 = 0;
+    const bool taken = ipk_pipeline_batches_previews(&d, out_type, n, &c, &p1) == 1;
+    if (chunk) *chunk = c;
+    if (pass1_batched) *pass1_batched = p1 != 0;
+    return taken;
+  }
   // would a region from the cache be resampled straight from the cached demosaic buffer (ipk_pipeline_resamples_cached_region)?
   bool resamples_cached_region(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_resamples_cached_region(&d, out_type) == 1; }
  private:
