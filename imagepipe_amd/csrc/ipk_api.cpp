@@ -815,6 +815,35 @@ namespace {
 bool window_ok(size_t nwidth, size_t nheight, size_t wx, size_t wy, size_t ww, size_t wh) {
   return ww != 0 && wh != 0 && wx <= nwidth && ww <= nwidth - wx && wy <= nheight && wh <= nheight - wy;
 }
+// One launch of the scaling kernels (ipk_launch.hpp, ScaledDemosaicLaunch).  scaled_geometry states what every form shares -- the sensor window, the result's size,
+// the destination -- and the caller adds its band, window or batch; launch_scaled adds what the source is: a mosaic (cfa_pat: its device tables, black[0] /
+// white[0] as its levels and whether their division has the fast form) or, cfa_pat == null, a monochrome / three-sample raw of plain_kind with its level pairs
+ipk::ScaledDemosaicLaunch scaled_geometry(const void *src, size_t owidth, size_t x, size_t y, size_t width, size_t height, size_t nwidth, size_t nheight, float *dst4) {
+  ipk::ScaledDemosaicLaunch l{};
+  l.src = src; l.owidth = owidth;
+  l.x = x; l.y = y; l.width = width; l.height = height;
+  l.nwidth = nwidth; l.nheight = nheight;
+  l.dst4 = dst4;
+  return l;
+}
+int launch_scaled(ipk::ScaledDemosaicLaunch l, int src_type, const char *cfa_pat, int plain_kind, const float *black, const float *white, void *stream) {
+  ipk::PlainLevels pl;
+  l.src_is_u16 = src_type == IPK_SRC_U16;
+  if (cfa_pat) {
+    ipk::Cfa cfa; DevCfa dev; int rc = get_cfa(cfa_pat, cfa, dev); if (rc) return rc;
+    l.black0 = black[0]; l.white0 = white[0];
+    l.norm_fast = validate_cdiv_for_range(l.black0, l.white0 - l.black0, l.src_is_u16) ? 1 : 0;
+    l.has_fourth_colour = cfa.three_colour() ? 0 : 1;
+    l.cfa48_dev = dev.cfa48; l.pattern_width = (int)cfa.width; l.pattern_height = (int)cfa.height;
+  } else {
+    pl.layout = plain_kind == IPK_PLAIN_MONO ? 1 : 3;
+    for (int c = 0; c < 3; ++c) { pl.black[c] = black[c]; pl.white[c] = white[c]; }
+    l.plain = &pl;
+  }
+  ipk::launch_raw_scaled_demosaic(l, S(stream));
+  HIPCHK(hipGetLastError());
+  return IPK_OK;
+}
 // the whole-frame form (win == null) and the window form: one admission, one launcher
 int raw_scaled_demosaic_impl(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
                              const char *cfa_pat, size_t nwidth, size_t nheight, const ipk::ResampleWindow *win, float *dst4, void *stream) {
@@ -823,12 +852,9 @@ int raw_scaled_demosaic_impl(const void *src, int src_type, size_t owidth, size_
     return fail(IPK_ERR_INVALID, "bad raw_scaled_demosaic arguments");
   if (win && !window_ok(nwidth, nheight, win->col0, win->row0, win->cols, win->rows))
     return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", win->col0, win->row0, win->cols, win->rows, nwidth, nheight);
-  ipk::Cfa cfa; DevCfa dev; int rc = get_cfa(cfa_pat, cfa, dev); if (rc) return rc;
-  const int norm_fast = validate_cdiv_for_range(black0, white0 - black0, src_type == IPK_SRC_U16) ? 1 : 0;
-  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(static_cast<const uint16_t *>(src), owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0, win);
-  else ipk::launch_raw_scaled_demosaic<float>(static_cast<const float *>(src), owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0, win);
-  HIPCHK(hipGetLastError());
-  return IPK_OK;
+  ipk::ScaledDemosaicLaunch l = scaled_geometry(src, owidth, x, y, width, height, nwidth, nheight, dst4);
+  l.win = win;
+  return launch_scaled(l, src_type, cfa_pat, 0, &black0, &white0, stream);
 }
 int raster_scale_down_impl(const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height, size_t nwidth, size_t nheight,
                            const ipk::ResampleWindow *win, float *dst4, void *stream) {
@@ -855,13 +881,9 @@ int plain_scale_down_impl(const void *src, int src_type, int kind, size_t owidth
   if (x + width > owidth) return fail(IPK_ERR_INVALID, "plain_scale_down: window wider than the source pitch");
   if (win && !window_ok(nwidth, nheight, win->col0, win->row0, win->cols, win->rows))
     return fail(IPK_ERR_INVALID, "window (%zu, %zu) %zux%zu is empty or outside the %zux%zu result", win->col0, win->row0, win->cols, win->rows, nwidth, nheight);
-  ipk::PlainLevels pl;
-  pl.layout = kind == IPK_PLAIN_MONO ? 1 : 3;
-  for (int c = 0; c < 3; ++c) { pl.black[c] = black4[c]; pl.white[c] = white4[c]; }
-  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(static_cast<const uint16_t *>(src), owidth, x, y, width, height, 0.0f, 0.0f, 0, 0, nwidth, nheight, nullptr, 0, 0, dst4, S(stream), 0, 0, 0, win, &pl);
-  else ipk::launch_raw_scaled_demosaic<float>(static_cast<const float *>(src), owidth, x, y, width, height, 0.0f, 0.0f, 0, 0, nwidth, nheight, nullptr, 0, 0, dst4, S(stream), 0, 0, 0, win, &pl);
-  HIPCHK(hipGetLastError());
-  return IPK_OK;
+  ipk::ScaledDemosaicLaunch l = scaled_geometry(src, owidth, x, y, width, height, nwidth, nheight, dst4);
+  l.win = win;
+  return launch_scaled(l, src_type, nullptr, kind, black4, white4, stream);
 }
 }  // namespace
 int ipk_plain_scale_down(const void *src, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height, const float *black4,
@@ -896,12 +918,9 @@ int raw_scaled_demosaic_batch_impl(const void *const *srcs, size_t n, int src_ty
     }
     return IPK_OK;
   }
-  ipk::Cfa cfa; DevCfa dev; int rc = get_cfa(cfa_pat, cfa, dev); if (rc) return rc;
-  const int norm_fast = validate_cdiv_for_range(black0, white0 - black0, src_type == IPK_SRC_U16) ? 1 : 0;
-  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(nullptr, owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0, nullptr, nullptr, srcs, n);
-  else ipk::launch_raw_scaled_demosaic<float>(nullptr, owidth, x, y, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), 0, 0, 0, nullptr, nullptr, srcs, n);
-  HIPCHK(hipGetLastError());
-  return IPK_OK;
+  ipk::ScaledDemosaicLaunch l = scaled_geometry(nullptr, owidth, x, y, width, height, nwidth, nheight, dst4);
+  l.batch_srcs = srcs; l.batch_n = n;
+  return launch_scaled(l, src_type, cfa_pat, 0, &black0, &white0, stream);
 }
 // the same for monochrome and three-sample raws, whose launches are always the general kernel's; IPK_PLAIN_RASTER forwards frame by frame
 int plain_scale_down_batch_impl(const void *const *srcs, size_t n, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width, size_t height,
@@ -922,13 +941,9 @@ int plain_scale_down_batch_impl(const void *const *srcs, size_t n, int src_type,
   if (!dst4 || !black4 || !white4 || !dims_ok(width, height) || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32))
     return fail(IPK_ERR_INVALID, "bad plain_scale_down_batch arguments");
   if (x + width > owidth) return fail(IPK_ERR_INVALID, "plain_scale_down_batch: window wider than the source pitch");
-  ipk::PlainLevels pl;
-  pl.layout = kind == IPK_PLAIN_MONO ? 1 : 3;
-  for (int c = 0; c < 3; ++c) { pl.black[c] = black4[c]; pl.white[c] = white4[c]; }
-  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(nullptr, owidth, x, y, width, height, 0.0f, 0.0f, 0, 0, nwidth, nheight, nullptr, 0, 0, dst4, S(stream), 0, 0, 0, nullptr, &pl, srcs, n);
-  else ipk::launch_raw_scaled_demosaic<float>(nullptr, owidth, x, y, width, height, 0.0f, 0.0f, 0, 0, nwidth, nheight, nullptr, 0, 0, dst4, S(stream), 0, 0, 0, nullptr, &pl, srcs, n);
-  HIPCHK(hipGetLastError());
-  return IPK_OK;
+  ipk::ScaledDemosaicLaunch l = scaled_geometry(nullptr, owidth, x, y, width, height, nwidth, nheight, dst4);
+  l.batch_srcs = srcs; l.batch_n = n;
+  return launch_scaled(l, src_type, nullptr, kind, black4, white4, stream);
 }
 }  // namespace
 int ipk_raw_scaled_demosaic_batch(const void *const *srcs, size_t n, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
@@ -963,12 +978,9 @@ int ipk_raw_scaled_demosaic_band(const void *src, int src_type, size_t owidth, s
     if (band->src_row0 > from || band->src_row0 + band->src_rows <= to)
       return fail(IPK_ERR_INVALID, "band slab rows [%zu,%zu) do not cover the window rows [%zu,%zu]", band->src_row0, band->src_row0 + band->src_rows, from, to);
   }
-  ipk::Cfa cfa; DevCfa dev; int rc = get_cfa(cfa_pat, cfa, dev); if (rc) return rc;
-  const int norm_fast = validate_cdiv_for_range(black0, white0 - black0, src_type == IPK_SRC_U16) ? 1 : 0;
-  if (src_type == IPK_SRC_U16) ipk::launch_raw_scaled_demosaic<uint16_t>(static_cast<const uint16_t *>(src), owidth, x, 0, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), band->src_row0, band->out_row0, band->out_rows);
-  else ipk::launch_raw_scaled_demosaic<float>(static_cast<const float *>(src), owidth, x, 0, width, height, black0, white0, norm_fast, cfa.three_colour() ? 0 : 1, nwidth, nheight, dev.cfa48, (int)cfa.width, (int)cfa.height, dst4, S(stream), band->src_row0, band->out_row0, band->out_rows);
-  HIPCHK(hipGetLastError());
-  return IPK_OK;
+  ipk::ScaledDemosaicLaunch l = scaled_geometry(src, owidth, x, 0, width, height, nwidth, nheight, dst4);
+  l.band_src_row0 = band->src_row0; l.band_out_row0 = band->out_row0; l.band_out_rows = band->out_rows;
+  return launch_scaled(l, src_type, cfa_pat, 0, &black0, &white0, stream);
 }
 
 // OpGoFloat::run_other + scale_down_opbuf in one pass over a raster (used by the pipeline drivers when OpDemosaic::run would take its
@@ -993,32 +1005,45 @@ int ipk_scaled_window_footprint(size_t width, size_t height, size_t nwidth, size
   return IPK_OK;
 }
 
-int ipk_demosaic_run(const float *src, size_t width, size_t height, size_t colors, const char *cfa_pat,
-                     size_t demosaic_width, size_t demosaic_height, float *dst4, size_t *out_width, size_t *out_height, void *stream) {
-  REQUIRE_INIT();
+// OpDemosaic::run's dispatch (demosaic.rs:41-59) on the input's shape and the negotiated size: the branch and the output's size, or an error.  No GPU
+enum DemosaicBranch { kDemosaicNoop, kDemosaicScaleOpbuf, kDemosaicScaled, kDemosaicFullScaled, kDemosaicFull };
+static int demosaic_plan(size_t width, size_t height, size_t colors, const char *cfa_pat, size_t demosaic_width, size_t demosaic_height,
+                         size_t *out_width, size_t *out_height) {
   if (colors != 1 && colors != 4) return fail(IPK_ERR_INVALID, "demosaic expects 1 or 4 colours");
   const float scale = ipk::calculate_scaling_total(width, height, demosaic_width, demosaic_height).scale;
   ipk::Cfa cfa;
   if (!ipk::Cfa::parse(cfa_pat ? cfa_pat : "", cfa)) return cfa_fail(cfa_pat);
   const float minscale = ipk::demosaic_minscale(cfa.width);
-  if (scale <= 1.0f && colors == 4) { *out_width = width; *out_height = height; return IPK_NOOP; }        // demosaic.rs:41-43
-  if (colors == 4) {                                                                                       // :44-46
-    *out_width = demosaic_width; *out_height = demosaic_height;
-    return ipk_scale_down_opbuf(src, width, height, demosaic_width, demosaic_height, dst4, stream);
-  }
-  if (scale >= minscale) {                                                                                 // :47-50
-    *out_width = demosaic_width; *out_height = demosaic_height;
-    return ipk_scaled_demosaic(src, width, height, cfa_pat, demosaic_width, demosaic_height, dst4, stream);
-  }
-  if (scale > 1.0f) {                                                                                      // :54-56
-    Scratch sc(S(stream)); void *full = nullptr;
-    int rc = sc.get(width * height * 4 * sizeof(float), &full); if (rc) return rc;
-    rc = ipk_demosaic_full(src, width, height, cfa_pat, static_cast<float *>(full), stream); if (rc) return rc;
-    *out_width = demosaic_width; *out_height = demosaic_height;
-    return ipk_scale_down_opbuf(static_cast<float *>(full), width, height, demosaic_width, demosaic_height, dst4, stream);
-  }
+  *out_width = demosaic_width; *out_height = demosaic_height;
+  if (scale <= 1.0f && colors == 4) { *out_width = width; *out_height = height; return kDemosaicNoop; }   // demosaic.rs:41-43
+  if (colors == 4) return kDemosaicScaleOpbuf;                                                             // :44-46
+  if (scale >= minscale) return kDemosaicScaled;                                                           // :47-50
+  if (scale > 1.0f) return kDemosaicFullScaled;                                                            // :54-56
   *out_width = width; *out_height = height;                                                                // :57-59
-  return ipk_demosaic_full(src, width, height, cfa_pat, dst4, stream);
+  return kDemosaicFull;
+}
+// the launches of a branch demosaic_plan chose (a negative `branch`, its error, is handed back)
+static int demosaic_launch(int branch, const float *src, size_t width, size_t height, const char *cfa_pat, size_t demosaic_width, size_t demosaic_height,
+                           float *dst4, void *stream) {
+  switch (branch) {
+    case kDemosaicNoop: return IPK_NOOP;
+    case kDemosaicScaleOpbuf: return ipk_scale_down_opbuf(src, width, height, demosaic_width, demosaic_height, dst4, stream);
+    case kDemosaicScaled: return ipk_scaled_demosaic(src, width, height, cfa_pat, demosaic_width, demosaic_height, dst4, stream);
+    case kDemosaicFullScaled: {
+      Scratch sc(S(stream)); void *full = nullptr;
+      int rc = sc.get(width * height * 4 * sizeof(float), &full); if (rc) return rc;
+      rc = ipk_demosaic_full(src, width, height, cfa_pat, static_cast<float *>(full), stream); if (rc) return rc;
+      return ipk_scale_down_opbuf(static_cast<float *>(full), width, height, demosaic_width, demosaic_height, dst4, stream);
+    }
+    case kDemosaicFull: return ipk_demosaic_full(src, width, height, cfa_pat, dst4, stream);
+  }
+  return branch;
+}
+int ipk_demosaic_run(const float *src, size_t width, size_t height, size_t colors, const char *cfa_pat,
+                     size_t demosaic_width, size_t demosaic_height, float *dst4, size_t *out_width, size_t *out_height, void *stream) {
+  REQUIRE_INIT();
+  const int branch = demosaic_plan(width, height, colors, cfa_pat, demosaic_width, demosaic_height, out_width, out_height);
+  return demosaic_launch(branch, src, width, height, cfa_pat, demosaic_width, demosaic_height, dst4, stream);
 }
 
 int ipk_rotatecrop(const float *src, size_t width, size_t height, size_t colors, const float *p, float *dst,
@@ -1431,6 +1456,16 @@ int ipk_plain_to_srgb(const void *src, int src_type, int kind, size_t owidth, si
   return IPK_OK;
 }
 
+// The sensor-source half of a k_fused_resample set-up: the cropped frame's first sample and geometry, the levels, and whether gofloat's division must be a
+// true one
+static void fused_sensor_source(ipk::FusedLaunch &f, const void *src, int src_type, size_t owidth, size_t x, size_t y, size_t width, size_t height,
+                                float black0, float white0) {
+  f.src_is_u16 = src_type == IPK_SRC_U16;
+  f.src = static_cast<const char *>(src) + (y * owidth + x) * (f.src_is_u16 ? 2 : 4);
+  f.width = width; f.height = height; f.owidth = owidth;
+  f.black0 = black0; f.white0 = white0;
+  f.exact_norm = validate_cdiv_for_range(black0, white0 - black0, f.src_is_u16) ? 0 : 1;
+}
 // The launch behind ipk_raw_to_srgb_resampled (corners: its six corner coordinates) and ipk_raw_to_srgb_scaled (corners == NULL: scale_down_opbuf's
 // transform), k_fused_resample: the checks both share, then the plan from the cropped frame's sides, or the refusal (nothing is enqueued then)
 // win (the window forms): the rectangle of the nwidth x nheight result the launch is laid over; dst then holds exactly its pixels
@@ -1455,13 +1490,8 @@ static int resampled_launch(const ipk_fused_params *p, const void *src, const in
   if (!admitted) return fail(IPK_ERR_UNSUPPORTED, "%s", refusal);
   PointwisePrep pp;
   { int rc = pp.prepare(0, p->wb_coeffs, p->cam_to_xyz_normalized, p->exposure, p->points, p->npoints, p->linear); if (rc) return rc; }
-  const size_t esz = p->src_type == IPK_SRC_U16 ? 2 : 4;
-  pp.f.src = static_cast<const char *>(src) + (p->y * p->owidth + p->x) * esz;      // the cropped frame's first sample
+  fused_sensor_source(pp.f, src, p->src_type, p->owidth, p->x, p->y, p->width, p->height, p->black0, p->white0);
   pp.f.dst = dst;
-  pp.f.src_is_u16 = p->src_type == IPK_SRC_U16;
-  pp.f.width = p->width; pp.f.height = p->height; pp.f.owidth = p->owidth;
-  pp.f.black0 = p->black0; pp.f.white0 = p->white0;
-  pp.f.exact_norm = validate_cdiv_for_range(p->black0, p->white0 - p->black0, pp.f.src_is_u16) ? 0 : 1;
   pp.f.out_type = p->out_type;
   if (ipk::launch_fused_resample(pp.f, plan, nwidth, nheight, dev.lookups, S(stream), win) != 0)
     return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
@@ -1514,13 +1544,8 @@ static int raw_demosaic_scaled_impl(const void *src, int src_type, size_t owidth
   if (!ipk::scaledown_plan(width, height, nwidth, nheight, plan)) return fail(IPK_ERR_UNSUPPORTED, "%s", kScaledRefusal);
   PointwisePrep pp;                                                          // the mode reads none of the point-wise parameters: any ordinary set
   { int rc = pp.prepare(1, nullptr, nullptr, 0.0f, nullptr, 0, 1); if (rc) return rc; }
-  const size_t esz = src_type == IPK_SRC_U16 ? 2 : 4;
-  pp.f.src = static_cast<const char *>(src) + (y * owidth + x) * esz;        // the cropped frame's first sample
+  fused_sensor_source(pp.f, src, src_type, owidth, x, y, width, height, black0, white0);
   pp.f.dst = dst4;
-  pp.f.src_is_u16 = src_type == IPK_SRC_U16;
-  pp.f.width = width; pp.f.height = height; pp.f.owidth = owidth;
-  pp.f.black0 = black0; pp.f.white0 = white0;
-  pp.f.exact_norm = validate_cdiv_for_range(black0, white0 - black0, pp.f.src_is_u16) ? 0 : 1;
   pp.f.out_type = IPK_OUT_F32;
   if (ipk::launch_fused_resample(pp.f, plan, nwidth, nheight, dev.lookups, S(stream), win, 0, 1) != 0)
     return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
@@ -2131,8 +2156,70 @@ int launch_gofloat_demosaic(const ipk_pipeline_desc *d, const Negotiated &n, con
   return raw_scaled_demosaic_impl(src, d->src_type, d->width, n.r.x, n.r.y, n.r.width, n.r.height, d->blacklevels[0], d->whitelevels[0], d->cfa,
                                   n.dw, n.dh, win, dst, stream);
 }
-int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scratch &sc, void *buf, size_t w, size_t h, size_t colors, int monochrome,
-             size_t want_w, size_t want_h, void *dst, StageTimer &tm, void *stream);
+// ---- The eight ops of Pipeline::run (pipeline.rs:155-164), each stated once: what it makes of its input's shape (plan_op: no GPU, nothing allocated) and
+// the launch that writes it (launch_op).  The scratch driver (run_staged / run_tail) and the cache driver (run_cached_ops) are loops over the two ----
+struct OpShape { size_t w, h, colors; int mono; int branch = 0; };         // branch: of op 1's output, the DemosaicBranch that writes it
+const char *const kOpLabels[8] = {"gofloat", "demosaic", "rotatecrop", "to_lab", "basecurve", "from_lab", "gamma", "transform"};
+// IPK_NOOP: the op hands its input on (out = in); IPK_OK: `out` is the shape of the buffer it writes.  Op 0 has no input: `in` is not read
+int plan_op(int op, const ipk_pipeline_desc *d, const Negotiated &n, const OpShape &in, OpShape &out) {
+  out = in;
+  switch (op) {
+    case 0: out.w = n.r.width; out.h = n.r.height; return gofloat_shape(d, n, out.colors, out.mono);
+    case 1: {
+      const int branch = demosaic_plan(in.w, in.h, in.colors, d->cfa, n.dw, n.dh, &out.w, &out.h);
+      out.colors = 4; out.branch = branch;
+      return branch < 0 ? branch : branch == kDemosaicNoop ? IPK_NOOP : IPK_OK;
+    }
+    case 2: return ipk_rotatecrop(nullptr, in.w, in.h, in.colors, d->rotatecrop, nullptr, &out.w, &out.h, nullptr);
+    case 3: out.colors = 3; return IPK_OK;
+    case 4: return curve_is_noop(d->exposure, d->npoints) ? IPK_NOOP : IPK_OK;
+    case 5: return IPK_OK;
+    case 6: return n.linear ? IPK_NOOP : IPK_OK;                            // gamma.rs:17-18
+    default: {
+      if (n.transform_noop) return IPK_NOOP;                               // transform.rs:68-69
+      bool t, fx, fy; ipk::orientation_to_flips(n.orientation, t, fx, fy);
+      if (t) std::swap(out.w, out.h);
+      return IPK_OK;
+    }
+  }
+}
+// op `op` from the buffer `in` of shape `s` (op 0: from the source) into `out`, which holds `to`, the shape plan_op gave
+int launch_op(int op, const ipk_pipeline_desc *d, const Negotiated &n, const void *src, const float *in, const OpShape &s, float *out, const OpShape &to,
+              void *stream) {
+  size_t ow, oh;
+  switch (op) {
+    case 0: return launch_gofloat(d, n, src, out, stream);
+    case 1: return demosaic_launch(to.branch, in, s.w, s.h, d->cfa, n.dw, n.dh, out, stream);
+    case 2: return ipk_rotatecrop(in, s.w, s.h, s.colors, d->rotatecrop, out, &ow, &oh, stream);
+    case 3: return ipk_tolab(in, s.w, s.h, s.mono, d->wb_coeffs, d->cam_to_xyz_normalized, out, stream);
+    case 4: return ipk_basecurve(in, s.w, s.h, d->exposure, d->points, d->npoints, out, stream);
+    case 5: return ipk_fromlab(in, s.w, s.h, out, stream);
+    case 6: return ipk_gamma(in, s.w, s.h, 3, 0, out, stream);
+    default: return ipk_rotate_buffer(in, s.w, s.h, n.orientation, out, &ow, &oh, stream);
+  }
+}
+
+// Window `win` of OpRotateCrop's nw x nh result, resampled from the dense RGBE f32 buffer in front of the op with the chain and the quantiser behind it,
+// then OpTransform: k_fused_resample's cached-buffer source mode inside launch_then_orient.  b: the buffer -- w x h pixels, `pitch` pixels from row to
+// row, E = +0.0 everywhere -- and its monochrome flag; label: the launch's stage
+struct RgbeBuffer { const void *p; size_t pitch, w, h; int mono; };
+int resample_rgbe_window(const ipk_pipeline_desc *d, const Negotiated &n, const RgbeBuffer &b, const ipk::ResamplePlan &plan, size_t nw, size_t nh,
+                         const ipk::ResampleWindow &win, const char *label, StageTimer &tm, size_t want_w, size_t want_h, void *dst, int out_type, void *stream) {
+  PointwisePrep pp;
+  int rc = pp.prepare(b.mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
+  pp.f.src = b.p; pp.f.src_is_u16 = false; pp.f.out_type = out_type;
+  pp.f.width = b.w; pp.f.height = b.h; pp.f.owidth = b.pitch;
+  pp.f.black0 = 0.0f; pp.f.white0 = 1.0f;                                  // not read in this mode
+  return launch_then_orient(win.cols, win.rows, out_type, !n.transform_noop, n.orientation, want_w, want_h, dst, stream, [&](void *out) -> int {
+    pp.f.dst = out;
+    if (ipk::launch_fused_resample(pp.f, plan, nw, nh, nullptr, S(stream), &win, 1) != 0)
+      return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
+    HIPCHK(hipGetLastError());
+    tm.mark(label);
+    if (!n.transform_noop) tm.rest = "transform";
+    return IPK_OK;
+  });
+}
 
 // ---- kScaledRotateCrop: the scaling pass into the n.dw x n.dh RGBE buffer, then the resampling launch over it (choose_route / scaled_rotatecrop) ----
 // Every tile box of the resampling launch over window w2 -- the kernel's rs_box: the extremes of the windows at the tile's four corner pixels -- lies
@@ -2184,156 +2271,80 @@ int run_scaled_rotatecrop(const ipk_pipeline_desc *d, const Negotiated &n, const
   tm.mark(win ? "region gofloat+demosaic" : "gofloat+demosaic");
   // pass 2 addresses its source in the buffer's own coordinates: the pointer is moved back by F's origin and the pitch is F's width, so pixel (x, y) of
   // the buffer is pixel (x - F.x, y - F.y) of the scratch; the kernel reads tile boxes only, all inside F (above)
-  PointwisePrep pp;
-  rc = pp.prepare(one_pass_monochrome(d, n), d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
-  pp.f.src = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(buf) - (uintptr_t)(F.y * F.w + F.x) * 4 * sizeof(float));
-  pp.f.src_is_u16 = false; pp.f.out_type = rt.fp.out_type;
-  pp.f.width = n.dw; pp.f.height = n.dh; pp.f.owidth = F.w;
-  pp.f.black0 = 0.0f; pp.f.white0 = 1.0f;                                  // not read in this mode
-  return launch_then_orient(w2.cols, w2.rows, rt.fp.out_type, !n.transform_noop, n.orientation, want_w, want_h, dst, stream, [&](void *out) -> int {
-    pp.f.dst = out;
-    if (ipk::launch_fused_resample(pp.f, rt.plan2, rt.rcp.nw, rt.rcp.nh, nullptr, S(stream), &w2, 1) != 0)
-      return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
-    HIPCHK(hipGetLastError());
-    tm.mark(win ? rt.region_label : rt.label);
-    if (!n.transform_noop) tm.rest = "transform";
-    return IPK_OK;
-  });
+  const RgbeBuffer b = {reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(buf) - (uintptr_t)(F.y * F.w + F.x) * 4 * sizeof(float)), F.w, n.dw, n.dh,
+                        one_pass_monochrome(d, n)};
+  return resample_rgbe_window(d, n, b, rt.plan2, rt.rcp.nw, rt.rcp.nh, w2, win ? rt.region_label : rt.label, tm, want_w, want_h, dst, rt.fp.out_type, stream);
 }
 
 // ---- staged path: the eight ops in the reference's order (pipeline.rs:155-164) ----
-int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, const void *src, void *dst, StageTimer &tm, void *stream) {
-  Scratch sc(S(stream));
-  size_t w = n.r.width, h = n.r.height, colors;
-  int monochrome, rc;
-  void *buf = nullptr;
-  // gofloat (+ demosaic when OpDemosaic::run would scale: one pass over the source)
-  const bool demosaic_done = gofloat_demosaic_one_pass(d, n);
-  if (demosaic_done) {
-    colors = 4; monochrome = one_pass_monochrome(d, n);
-    rc = sc.get(n.dw * n.dh * 4 * sizeof(float), &buf); if (rc) return rc;
-    rc = launch_gofloat_demosaic(d, n, src, nullptr, static_cast<float *>(buf), stream);
-    w = n.dw; h = n.dh;
-  } else {
-    rc = gofloat_shape(d, n, colors, monochrome); if (rc) return rc;
-    rc = sc.get(w * h * colors * sizeof(float), &buf); if (rc) return rc;
-    rc = launch_gofloat(d, n, src, static_cast<float *>(buf), stream);
-  }
-  if (rc < 0) return rc;
-  tm.mark(demosaic_done ? "gofloat+demosaic" : "gofloat");
-  // demosaic
-  if (!demosaic_done) {
-    void *o = nullptr; size_t ow, oh;
-    rc = sc.get(std::max(w * h, n.dw * n.dh) * 4 * sizeof(float), &o); if (rc) return rc;
-    rc = ipk_demosaic_run(static_cast<const float *>(buf), w, h, colors, d->cfa, n.dw, n.dh, static_cast<float *>(o), &ow, &oh, stream);
-    if (rc < 0) return rc;
-    if (rc == IPK_NOOP) sc.release(o); else { sc.release(buf); buf = o; w = ow; h = oh; colors = 4; }
-    tm.mark("demosaic");
-  }
-  // rotatecrop
-  {
-    size_t ow, oh;
-    rc = ipk_rotatecrop(static_cast<const float *>(buf), w, h, colors, d->rotatecrop, nullptr, &ow, &oh, stream);
-    if (rc < 0) return rc;
-    if (rc != IPK_NOOP) {
-      void *o = nullptr;
-      rc = sc.get(ow * oh * colors * sizeof(float), &o); if (rc) return rc;
-      rc = ipk_rotatecrop(static_cast<const float *>(buf), w, h, colors, d->rotatecrop, static_cast<float *>(o), &ow, &oh, stream);
-      if (rc < 0) return rc;
-      sc.release(buf); buf = o; w = ow; h = oh;
-    }
-    tm.mark("rotatecrop");
-  }
-  return run_tail(d, n, out_type, sc, buf, w, h, colors, monochrome, n.fw, n.fh, dst, tm, stream);
-}
-// What follows OpRotateCrop: tolab..gamma, OpTransform and the quantisation of the w x h buffer `buf` (colors samples per pixel, owned by sc), into dst,
-// which holds want_w x want_h pixels of out_type -- the negotiated result behind run_staged, the region behind a window launch (ipk_pipeline_run_region
-// under IPK_FUSED_WINDOW_PREVIEWS).  Every op here is point-wise or a permutation, so a rectangle of the buffer gives that rectangle of the result
-int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scratch &sc, void *buf, size_t w, size_t h, size_t colors, int monochrome,
+// The scratch driver: ops [from, 8) and the quantisation, from the buffer `buf` of shape `shape` (op from - 1's, owned by sc; from == 0: none), into dst, which
+// holds want_w x want_h pixels of out_type -- the negotiated result behind run_staged, the region behind a window launch (ipk_pipeline_run_region under
+// IPK_FUSED_WINDOW_PREVIEWS: from = 3, where every op is point-wise or a permutation, so a rectangle of the buffer gives that rectangle of the result).
+// A scratch buffer per executed op, its input released behind it; the shapes are planned before anything is enqueued, so the last executed op writes
+// straight into dst when the caller wants f32
+int run_tail(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, Scratch &sc, const void *src, int from, void *buf, const OpShape &shape,
              size_t want_w, size_t want_h, void *dst, StageTimer &tm, void *stream) {
-  int rc;
+  int rc, last = -1;
   auto produced = [&](size_t pw, size_t ph) {
     return pw == want_w && ph == want_h ? IPK_OK : fail(IPK_ERR_INVALID, "internal: produced %zux%zu, negotiated %zux%zu", pw, ph, want_w, want_h);
   };
-  const size_t n3 = w * h * 3 * sizeof(float);
+  OpShape shp[9]; bool runs[8];
+  shp[from] = shape;
+  for (int i = from; i < 8; ++i) {
+    rc = plan_op(i, d, n, shp[i], shp[i + 1]); if (rc < 0) return rc;
+    runs[i] = rc != IPK_NOOP;
+    if (runs[i]) last = i;
+  }
   const bool f32_out = out_type == IPK_OUT_F32;
-  bool chained = false;
-  if (fused_on(d) && colors == 4 && !f32_out && n.transform_noop && w * h >= 256) {
-    // ... and with output8bit / output16bit in the same pass when the caller wants 8 or 16 bits and nothing follows: the f32 image never exists
-    rc = produced(w, h); if (rc) return rc;
-    rc = ipk_pointwise_chain_out(static_cast<const float *>(buf), w, h, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
-                                 n.linear, out_type, dst, stream);
-    if (rc < 0) return rc;
-    tm.rest = nullptr;
-    tm.mark("to_lab+basecurve+from_lab+gamma+quantise");
-    return IPK_OK;
+  for (int i = from; i < 8; ++i) {
+    const size_t w = shp[i].w, h = shp[i].h;
+    if (i == 3 && fused_on(d) && shp[3].colors == 4) {
+      // tolab + basecurve + fromlab + gamma in one pass (no cache wants the three intermediates) ...
+      const float *in = static_cast<const float *>(buf);
+      if (!f32_out && n.transform_noop && w * h >= 256) {
+        // ... and with output8bit / output16bit in the same pass when the caller wants 8 or 16 bits and nothing follows: the f32 image never exists
+        rc = produced(w, h); if (rc) return rc;
+        rc = ipk_pointwise_chain_out(in, w, h, shp[3].mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear, out_type, dst, stream);
+        if (rc < 0) return rc;
+        tm.rest = nullptr;
+        tm.mark("to_lab+basecurve+from_lab+gamma+quantise");
+        return IPK_OK;
+      }
+      void *o = dst;
+      if (!(f32_out && n.transform_noop)) { rc = sc.get(w * h * 3 * sizeof(float), &o); if (rc) return rc; }
+      rc = ipk_pointwise_chain(in, w, h, shp[3].mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear, static_cast<float *>(o), stream);
+      if (rc < 0) return rc;
+      sc.release(buf); buf = o;
+      tm.mark("to_lab+basecurve+from_lab+gamma");
+      i = 6;                                                               // on to OpTransform
+      continue;
+    }
+    if (i == 7 && runs[7] && !f32_out) {
+      // transform -- for the 8- and 16-bit outputs after the quantise loop instead of before it (orient)
+      tm.rest = "quantise+transform";
+      return launch_then_orient(w, h, out_type, true, n.orientation, want_w, want_h, dst, stream, [&](void *q) { return quantise(buf, w * h * 3, out_type, q, stream); });
+    }
+    if (runs[i]) {
+      void *o = dst;
+      if (!(f32_out && i == last)) { rc = sc.get(shp[i + 1].w * shp[i + 1].h * shp[i + 1].colors * sizeof(float), &o); if (rc) return rc; }
+      rc = launch_op(i, d, n, src, static_cast<const float *>(buf), shp[i], static_cast<float *>(o), shp[i + 1], stream); if (rc < 0) return rc;
+      sc.release(buf); buf = o;
+    }
+    if (runs[i] || i < 6) tm.mark(kOpLabels[i]);                           // (gamma and transform show as stages only where they run)
   }
-  if (fused_on(d) && colors == 4) {
-    // tolab + basecurve + fromlab + gamma in one pass (no cache wants the three intermediates)
-    void *o = nullptr;
-    if (f32_out && n.transform_noop) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
-    rc = ipk_pointwise_chain(static_cast<const float *>(buf), w, h, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
-                             n.linear, static_cast<float *>(o), stream);
-    if (rc < 0) return rc;
-    sc.release(buf); buf = o; colors = 3; chained = true;
-    tm.mark("to_lab+basecurve+from_lab+gamma");
-  }
-  // tolab
-  if (!chained) {
-    void *o = nullptr;
-    rc = sc.get(w * h * 3 * sizeof(float), &o); if (rc) return rc;
-    rc = ipk_tolab(static_cast<const float *>(buf), w, h, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, static_cast<float *>(o), stream);
-    if (rc < 0) return rc;
-    sc.release(buf); buf = o; colors = 3;
-    tm.mark("to_lab");
-  }
-  // basecurve
-  if (!chained) {
-    void *o = nullptr;
-    rc = sc.get(n3, &o); if (rc) return rc;
-    rc = ipk_basecurve(static_cast<const float *>(buf), w, h, d->exposure, d->points, d->npoints, static_cast<float *>(o), stream);
-    if (rc < 0) return rc;
-    if (rc == IPK_NOOP) sc.release(o); else { sc.release(buf); buf = o; }
-    tm.mark("basecurve");
-  }
-  // the last f32 stage writes straight into dst when the caller wants f32
-  const bool gamma_runs = !n.linear;
-  // fromlab
-  if (!chained) {
-    void *o = nullptr;
-    const bool last = f32_out && !gamma_runs && n.transform_noop;
-    if (last) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
-    rc = ipk_fromlab(static_cast<const float *>(buf), w, h, static_cast<float *>(o), stream);
-    if (rc < 0) return rc;
-    sc.release(buf); buf = o;
-    tm.mark("from_lab");
-  }
-  // gamma
-  if (gamma_runs && !chained) {
-    void *o = nullptr;
-    const bool last = f32_out && n.transform_noop;
-    if (last) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
-    rc = ipk_gamma(static_cast<const float *>(buf), w, h, 3, 0, static_cast<float *>(o), stream);
-    if (rc < 0) return rc;
-    sc.release(buf); buf = o;
-    tm.mark("gamma");
-  }
-  // transform -- for the 8- and 16-bit outputs after the quantise loop instead of before it (orient)
-  if (!n.transform_noop && !f32_out) {
-    tm.rest = "quantise+transform";
-    return launch_then_orient(w, h, out_type, true, n.orientation, want_w, want_h, dst, stream, [&](void *q) { return quantise(buf, w * h * 3, out_type, q, stream); });
-  }
-  if (!n.transform_noop) {
-    void *o = nullptr; size_t ow, oh;
-    if (f32_out) o = dst; else { rc = sc.get(n3, &o); if (rc) return rc; }
-    rc = ipk_rotate_buffer(static_cast<const float *>(buf), w, h, n.orientation, static_cast<float *>(o), &ow, &oh, stream);
-    if (rc < 0) return rc;
-    sc.release(buf); buf = o; w = ow; h = oh;
-    tm.mark("transform");
-  }
-  rc = produced(w, h); if (rc) return rc;
-  if (out_type != IPK_OUT_F32) { tm.rest = "quantise"; rc = quantise(buf, w * h * 3, out_type, dst, stream); }
+  rc = produced(shp[8].w, shp[8].h); if (rc) return rc;
+  if (!f32_out) { tm.rest = "quantise"; rc = quantise(buf, shp[8].w * shp[8].h * 3, out_type, dst, stream); }
   return rc < 0 ? rc : IPK_OK;
+}
+int run_staged(const ipk_pipeline_desc *d, const Negotiated &n, int out_type, const void *src, void *dst, StageTimer &tm, void *stream) {
+  Scratch sc(S(stream));
+  void *buf = nullptr;
+  if (!gofloat_demosaic_one_pass(d, n)) return run_tail(d, n, out_type, sc, src, 0, nullptr, OpShape{}, n.fw, n.fh, dst, tm, stream);
+  // gofloat + demosaic as one pass over the source where OpDemosaic::run would scale: op 0's buffer never exists
+  int rc = sc.get(n.dw * n.dh * 4 * sizeof(float), &buf); if (rc) return rc;
+  rc = launch_gofloat_demosaic(d, n, src, nullptr, static_cast<float *>(buf), stream); if (rc < 0) return rc;
+  tm.mark("gofloat+demosaic");
+  return run_tail(d, n, out_type, sc, src, 2, buf, OpShape{n.dw, n.dh, 4, one_pass_monochrome(d, n)}, n.fw, n.fh, dst, tm, stream);
 }
 }  // namespace
 
@@ -2359,44 +2370,45 @@ int ipk_pipeline_run(const ipk_pipeline_desc *d, const void *src, void *dst, int
   return rc;
 }
 // Which route a descriptor takes, for callers and CPU tests: the drivers' own choose_route on the drivers' own negotiation (no GPU)
-static int report_route(const ipk_pipeline_desc *d, int out_type, Route &rt) {
+// r.d: the descriptor as the drivers read it (taken and folded), for the reports that go on to ask a driver's own test with r.n and r.rt
+namespace { struct RouteReport { ipk_pipeline_desc d; Negotiated n; Route rt; }; }
+static int report_route(const ipk_pipeline_desc *d, int out_type, RouteReport &r) {
   if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; const int rc = negotiate(d, out_type, n); if (rc) return rc;
-  choose_route(d, n, out_type, rt);
+  const int rc = negotiate(d, out_type, r.n); if (rc) return rc;
+  choose_route(d, r.n, out_type, r.rt);
+  r.d = *d;
   return IPK_OK;
 }
 // does an active rotatecrop run inside the one launch (fuse_rotatecrop)?
 int ipk_pipeline_fuses_rotatecrop(const ipk_pipeline_desc *d, int out_type) {
-  Route rt; const int rc = report_route(d, out_type, rt);
-  return rc ? rc : rt.kind == kFusedResample;
+  RouteReport r; const int rc = report_route(d, out_type, r);
+  return rc ? rc : r.rt.kind == kFusedResample;
 }
 // allow_fused's IPK_FUSED_FOUR_COLOUR bit: does a frame whose filter has a fourth colour run as the one raw->sRGB launch?
 int ipk_pipeline_fuses_four_colour(const ipk_pipeline_desc *d, int out_type) {
-  Route rt; const int rc = report_route(d, out_type, rt);
-  return rc ? rc : rt.kind == kFusedRaw && rt.four;
+  RouteReport r; const int rc = report_route(d, out_type, r);
+  return rc ? rc : r.rt.kind == kFusedRaw && r.rt.four;
 }
 // fuse_scaledown: does OpDemosaic's full + scale_down_opbuf branch run inside the one launch?
 int ipk_pipeline_fuses_scaledown(const ipk_pipeline_desc *d, int out_type) {
-  Route rt; const int rc = report_route(d, out_type, rt);
-  return rc ? rc : rt.kind == kFusedScaledown;
+  RouteReport r; const int rc = report_route(d, out_type, r);
+  return rc ? rc : r.rt.kind == kFusedScaledown;
 }
 // IPK_FUSED_SCALED_ROTATECROP: does an active OpRotateCrop behind a scaling OpDemosaic run as the two launches of scaled_rotatecrop()?
 int ipk_pipeline_fuses_scaled_rotatecrop(const ipk_pipeline_desc *d, int out_type) {
-  Route rt; const int rc = report_route(d, out_type, rt);
-  return rc ? rc : rt.kind == kScaledRotateCrop;
+  RouteReport r; const int rc = report_route(d, out_type, r);
+  return rc ? rc : r.rt.kind == kScaledRotateCrop;
 }
 // IPK_FUSED_PLAIN_PREVIEWS: do OpGoFloat and a scaling OpDemosaic of a monochrome / three-sample raw run as the one launch ipk_plain_scale_down?
 int ipk_pipeline_scales_plain(const ipk_pipeline_desc *d, int out_type) {
-  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; const int rc = negotiate(d, out_type, n); if (rc) return rc;
-  return (ipk_pipeline_takes_fastpath(d, out_type) != 1 && scales_plain(d, n)) ? 1 : 0;
+  RouteReport r; const int rc = report_route(d, out_type, r);
+  return rc ? rc : (r.rt.kind != kFastPath && scales_plain(&r.d, r.n)) ? 1 : 0;
 }
 // IPK_FUSED_PLAIN: does a cropped raster / a u16 three-sample or monochrome raw run as the one launch ipk_plain_to_srgb (the whole-frame half of the bit)?
 int ipk_pipeline_fuses_plain(const ipk_pipeline_desc *d, int out_type) {
-  Route rt; const int rc = report_route(d, out_type, rt);
-  return rc ? rc : rt.kind == kFusedRaster && rt.plain;
+  RouteReport r; const int rc = report_route(d, out_type, r);
+  return rc ? rc : r.rt.kind == kFusedRaster && r.rt.plain;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2474,12 +2486,8 @@ int region_gather(const Negotiated &n, size_t x, size_t y, size_t w, size_t h, R
 
 // IPK_FUSED_WINDOW_PREVIEWS: does a region of this descriptor run as a window of its scaling gofloat + demosaic pass?
 int ipk_pipeline_windows_preview(const ipk_pipeline_desc *d, int out_type) {
-  Route rt;
-  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; const int rc = negotiate(d, out_type, n); if (rc) return rc;
-  choose_route(d, n, out_type, rt);
-  return windows_preview(d, n, rt) ? 1 : 0;
+  RouteReport r; const int rc = report_route(d, out_type, r);
+  return rc ? rc : windows_preview(&r.d, r.n, r.rt) ? 1 : 0;
 }
 
 int ipk_pipeline_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, size_t *src_x, size_t *src_y, size_t *src_w,
@@ -2555,7 +2563,7 @@ int ipk_pipeline_run_region(const ipk_pipeline_desc *d, const void *src, size_t 
     rc = sc.get(pl.win.cols * pl.win.rows * 4 * sizeof(float), &buf); if (rc) return rc;
     rc = launch_gofloat_demosaic(d, n, src, &pl.win, static_cast<float *>(buf), stream); if (rc < 0) return rc;
     tm.mark("region gofloat+demosaic");
-    return run_tail(d, n, out_type, sc, buf, pl.win.cols, pl.win.rows, 4, one_pass_monochrome(d, n), w, h, dst, tm, stream);
+    return run_tail(d, n, out_type, sc, src, 3, buf, OpShape{pl.win.cols, pl.win.rows, 4, one_pass_monochrome(d, n)}, w, h, dst, tm, stream);
   }
   // the one-launch routes: the window launch writes the rectangle into dst, or into scratch for OpTransform's permutation
   if (rt.kind == kScaledRotateCrop) return run_scaled_rotatecrop(d, n, rt, src, &pl.win, w, h, dst, stream);
@@ -2676,67 +2684,22 @@ int pointwise_ops_mask(bool has_curve, const Negotiated &n) { return 0x28 | (has
 // ipk_pipeline_run_cached (to = 8) and ipk_pipeline_run_cached_region (to = 3: the RGBE buffer its gather launch reads)
 int run_cached_ops(const ipk_pipeline_desc *d, const Negotiated &n, const ipk::BufHash hs[8], const void *src, ipk_cache *cache, int from, int to,
                    CBufP &buf, int &mask, void *stream) {
-  int rc = IPK_OK;
   for (int i = from; i < to; ++i) {
     CBufP o;
-    switch (i) {
-      case 0: {                                                          // gofloat
-        if (gofloat_demosaic_one_pass(d, n) && !cache->lru.contains(hs[1])) {   // + demosaic in the same pass when it would scale
-          rc = cbuf_new(n.dw, n.dh, 4, one_pass_monochrome(d, n), o); if (rc) return rc;
-          rc = launch_gofloat_demosaic(d, n, src, nullptr, static_cast<float *>(o->p), stream); if (rc < 0) return rc;
-          mask |= 3; buf = o; cache->lru.put(hs[1], o, o->bytes()); i = 1;   // op 1's output; op 0's is never materialised
-          continue;
-        }
-        size_t colors; int mono;
-        rc = gofloat_shape(d, n, colors, mono); if (rc) return rc;
-        rc = cbuf_new(n.r.width, n.r.height, colors, mono, o); if (rc) return rc;
-        rc = launch_gofloat(d, n, src, static_cast<float *>(o->p), stream);
-        break;
-      }
-      case 1: {                                                          // demosaic
-        size_t ow, oh;
-        rc = cbuf_new(std::max(buf->w, n.dw), std::max(buf->h, n.dh), 4, buf->mono, o); if (rc) return rc;
-        rc = ipk_demosaic_run(static_cast<const float *>(buf->p), buf->w, buf->h, buf->colors, d->cfa, n.dw, n.dh, static_cast<float *>(o->p), &ow, &oh, stream);
-        if (rc >= 0 && rc != IPK_NOOP) { o->w = ow; o->h = oh; }
-        break;
-      }
-      case 2: {                                                          // rotatecrop
-        size_t ow, oh;
-        rc = ipk_rotatecrop(static_cast<const float *>(buf->p), buf->w, buf->h, buf->colors, d->rotatecrop, nullptr, &ow, &oh, stream);
-        if (rc < 0 || rc == IPK_NOOP) break;
-        rc = cbuf_new(ow, oh, buf->colors, buf->mono, o); if (rc) return rc;
-        rc = ipk_rotatecrop(static_cast<const float *>(buf->p), buf->w, buf->h, buf->colors, d->rotatecrop, static_cast<float *>(o->p), &ow, &oh, stream);
-        break;
-      }
-      case 3:                                                            // to_lab
-        rc = cbuf_new(buf->w, buf->h, 3, buf->mono, o); if (rc) return rc;
-        rc = ipk_tolab(static_cast<const float *>(buf->p), buf->w, buf->h, buf->mono, d->wb_coeffs, d->cam_to_xyz_normalized, static_cast<float *>(o->p), stream);
-        break;
-      case 4:                                                            // basecurve
-        if (curve_is_noop(d->exposure, d->npoints)) { rc = IPK_NOOP; break; }
-        rc = cbuf_new(buf->w, buf->h, 3, buf->mono, o); if (rc) return rc;
-        rc = ipk_basecurve(static_cast<const float *>(buf->p), buf->w, buf->h, d->exposure, d->points, d->npoints, static_cast<float *>(o->p), stream);
-        break;
-      case 5:                                                            // from_lab
-        rc = cbuf_new(buf->w, buf->h, 3, buf->mono, o); if (rc) return rc;
-        rc = ipk_fromlab(static_cast<const float *>(buf->p), buf->w, buf->h, static_cast<float *>(o->p), stream);
-        break;
-      case 6:                                                            // gamma
-        if (n.linear) { rc = IPK_NOOP; break; }
-        rc = cbuf_new(buf->w, buf->h, 3, buf->mono, o); if (rc) return rc;
-        rc = ipk_gamma(static_cast<const float *>(buf->p), buf->w, buf->h, 3, 0, static_cast<float *>(o->p), stream);
-        break;
-      case 7: {                                                          // transform
-        if (n.transform_noop) { rc = IPK_NOOP; break; }
-        size_t ow, oh;
-        rc = cbuf_new(buf->w, buf->h, 3, buf->mono, o); if (rc) return rc;
-        rc = ipk_rotate_buffer(static_cast<const float *>(buf->p), buf->w, buf->h, n.orientation, static_cast<float *>(o->p), &ow, &oh, stream);
-        if (rc >= 0) { o->w = ow; o->h = oh; }
-        break;
-      }
+    if (i == 0 && gofloat_demosaic_one_pass(d, n) && !cache->lru.contains(hs[1])) {   // gofloat + demosaic in the same pass when it would scale
+      int rc = cbuf_new(n.dw, n.dh, 4, one_pass_monochrome(d, n), o); if (rc) return rc;
+      rc = launch_gofloat_demosaic(d, n, src, nullptr, static_cast<float *>(o->p), stream); if (rc < 0) return rc;
+      mask |= 3; buf = o; cache->lru.put(hs[1], o, o->bytes()); i = 1;     // op 1's output; op 0's is never materialised
+      continue;
     }
-    if (rc < 0) return rc;
-    if (rc != IPK_NOOP) buf = o;                                         // a no-op hands its input on (the same Arc under a second key)
+    const OpShape in = buf ? OpShape{buf->w, buf->h, buf->colors, buf->mono} : OpShape{};
+    OpShape out;
+    int rc = plan_op(i, d, n, in, out); if (rc < 0) return rc;
+    if (rc != IPK_NOOP) {                                                  // a no-op hands its input on (the same Arc under a second key)
+      rc = cbuf_new(out.w, out.h, out.colors, out.mono, o); if (rc) return rc;
+      rc = launch_op(i, d, n, src, static_cast<const float *>(buf ? buf->p : nullptr), in, static_cast<float *>(o->p), out, stream); if (rc < 0) return rc;
+      buf = o;
+    }
     mask |= 1 << i;
     cache->lru.put(hs[i], buf, buf->bytes());
   }
@@ -2806,11 +2769,9 @@ bool cached_resample(const ipk_pipeline_desc *d, const Negotiated &n, int out_ty
 }
 }  // namespace
 int ipk_pipeline_resamples_cached_region(const ipk_pipeline_desc *d, int out_type) {
-  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated n; const int rc = negotiate(d, out_type, n); if (rc) return rc;
+  RouteReport r; const int rc = report_route(d, out_type, r);
   CachedResample c;
-  return cached_resample(d, n, out_type, c) ? 1 : 0;
+  return rc ? rc : cached_resample(&r.d, r.n, out_type, c) ? 1 : 0;
 }
 
 int ipk_pipeline_region_gather(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, size_t w, size_t h, size_t *buf_w, size_t *buf_h,
@@ -2865,21 +2826,10 @@ struct CachedRegion {
       return fail(IPK_ERR_INVALID, "internal: produced %zux%zux%zu in front of rotatecrop (negotiated %zux%zu), rotatecrop to %zux%zu (negotiated %zux%zu)",
                   buf->w, buf->h, buf->colors, cr.sw, cr.sh, cr.r.nw, cr.r.nh, rg.bw, rg.bh);
     if (mask) tm.mark("gofloat..demosaic");
-    PointwisePrep pp;
-    rc = pp.prepare(buf->mono, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints, n.linear); if (rc) return rc;
-    pp.f.src = buf->p; pp.f.src_is_u16 = false; pp.f.out_type = out_type;
-    pp.f.width = buf->w; pp.f.height = buf->h; pp.f.owidth = buf->w;
-    pp.f.black0 = 0.0f; pp.f.white0 = 1.0f;                                // not read in this mode
-    rc = launch_then_orient(rg.win.cols, rg.win.rows, out_type, !n.transform_noop, n.orientation, w, h, dst, stream, [&](void *out) -> int {
-      pp.f.dst = out;
-      if (ipk::launch_fused_resample(pp.f, cr.plan, rg.bw, rg.bh, nullptr, S(stream), &rg.win, 1) != 0)
-        return fail(IPK_ERR_HIP, "kernel launch failed (nothing was enqueued)");
-      HIPCHK(hipGetLastError());
-      tm.mark("region rotatecrop+to_lab+basecurve+from_lab+gamma");
-      if (!n.transform_noop) tm.rest = "transform";
-      return IPK_OK;
-    });
-    mask |= (1 << 2) | pointwise_ops_mask(pp.f.has_curve, n);
+    const RgbeBuffer b = {buf->p, buf->w, buf->w, buf->h, buf->mono};
+    rc = resample_rgbe_window(d, n, b, cr.plan, rg.bw, rg.bh, rg.win, "region rotatecrop+to_lab+basecurve+from_lab+gamma", tm, w, h, dst, out_type, stream);
+    if (rc < 0) return rc;
+    mask |= (1 << 2) | pointwise_ops_mask(!curve_is_noop(d->exposure, d->npoints), n);
     // `buf` may be evicted (and its memory freed) as soon as we return; hipFree waits for the device, so the launch above is safe
     return rc;
   }
@@ -3069,12 +3019,9 @@ int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const B
 int ipk_pipeline_batches_previews(const ipk_pipeline_desc *d, int out_type, size_t n, size_t *chunk, int *pass1_batched) {
   if (chunk) *chunk = 0;
   if (pass1_batched) *pass1_batched = 0;
-  if (!d) return fail(IPK_ERR_INVALID, "null descriptor");
-  IPK_FOLD_CFA(ipk_pipeline_desc, d)
-  Negotiated ng; const int rc = negotiate(d, out_type, ng); if (rc) return rc;
-  Route rt; choose_route(d, ng, out_type, rt);
+  RouteReport r; const int rc = report_route(d, out_type, r); if (rc) return rc;
   BatchPreviews bp;
-  if (!batches_previews(d, ng, rt, n, bp)) return 0;
+  if (!batches_previews(&r.d, r.n, r.rt, n, bp)) return 0;
   if (chunk) *chunk = bp.chunk;
   if (pass1_batched) *pass1_batched = bp.pass1_batched ? 1 : 0;
   return 1;

@@ -1154,35 +1154,34 @@ __global__ __launch_bounds__(256, C4 ? 6 : 7) void k_raw_scaled_demosaic_w8m(con
   }
 }
 template <typename T>
-void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0,
-                                int norm_fast, int has_fourth_colour, size_t nwidth, size_t nheight, const uint8_t *cfa48_dev, int pw, int ph, float *dst4, hipStream_t s,
-                                size_t band_src_row0, size_t band_out_row0, size_t band_out_rows, const ResampleWindow *win, const PlainLevels *plain,
-                                const void *const *batch_srcs, size_t batch_n) {
-  if (plain) { black0 = plain->black[0]; white0 = plain->white[0]; norm_fast = 0; has_fourth_colour = 1; }
+static void launch_raw_scaled_demosaic_typed(const ScaledDemosaicLaunch &l, hipStream_t s) {
+  const T *const src = static_cast<const T *>(l.src);
+  float black0 = l.black0, white0 = l.white0; int norm_fast = l.norm_fast, has_fourth_colour = l.has_fourth_colour;
+  if (l.plain) { black0 = l.plain->black[0]; white0 = l.plain->white[0]; norm_fast = 0; has_fourth_colour = 1; }
   TransformArgs a{};
-  a.width = (uint32_t)width; a.height = (uint32_t)height; a.nwidth = (uint32_t)nwidth; a.nheight = (uint32_t)nheight; a.components = 4;
+  a.width = (uint32_t)l.width; a.height = (uint32_t)l.height; a.nwidth = (uint32_t)l.nwidth; a.nheight = (uint32_t)l.nheight; a.components = 4;
   a.tlx = 0.0f; a.tly = 0.0f;                                               // scale_down_buffer's corners (scaling.rs:35-48)
-  a.skip_x_x = ((float)((int64_t)width - 1) - 0.0f) / ((float)(nwidth - 1));
-  a.skip_x_y = (0.0f - 0.0f) / ((float)(nwidth - 1));
-  a.skip_y_x = (0.0f - 0.0f) / ((float)(nheight - 1));
-  a.skip_y_y = ((float)((int64_t)height - 1) - 0.0f) / ((float)(nheight - 1));
+  a.skip_x_x = ((float)((int64_t)l.width - 1) - 0.0f) / ((float)(l.nwidth - 1));
+  a.skip_x_y = (0.0f - 0.0f) / ((float)(l.nwidth - 1));
+  a.skip_y_x = (0.0f - 0.0f) / ((float)(l.nheight - 1));
+  a.skip_y_y = ((float)((int64_t)l.height - 1) - 0.0f) / ((float)(l.nheight - 1));
   a.inv_skip_x_x = 1.0f / a.skip_x_x; a.inv_skip_y_y = 1.0f / a.skip_y_y;
   a.fast_x = cdiv_host_ok(a.skip_x_x); a.fast_y = cdiv_host_ok(a.skip_y_y);
-  a.has_cfa = 1; a.norm = 1; a.min0 = black0; a.range0 = white0 - black0; a.src_pitch = owidth; a.src_x = x; a.src_y = y;
+  a.has_cfa = 1; a.norm = 1; a.min0 = black0; a.range0 = white0 - black0; a.src_pitch = l.owidth; a.src_x = l.x; a.src_y = l.y;
   a.norm_fast = norm_fast; a.inv_range0 = 1.0f / a.range0;
   a.norm_light = (std::fabs(black0) >= 0x1p-70f && std::fabs(black0) <= 0x1p70f) ? 1 : 0;
-  if (plain) {                                                              // true divisions only: neither shortcut of the mosaic kernels applies
-    a.layout = plain->layout; a.has_cfa = 0; a.norm_light = 0;
-    a.min1 = plain->black[1]; a.range1 = plain->white[1] - plain->black[1]; a.min2 = plain->black[2]; a.range2 = plain->white[2] - plain->black[2];
+  if (l.plain) {                                                            // true divisions only: neither shortcut of the mosaic kernels applies
+    a.layout = l.plain->layout; a.has_cfa = 0; a.norm_light = 0;
+    a.min1 = l.plain->black[1]; a.range1 = l.plain->white[1] - l.plain->black[1]; a.min2 = l.plain->black[2]; a.range2 = l.plain->white[2] - l.plain->black[2];
   }
   // whole frame, or the output-row band [band_out_row0, +band_out_rows) of a frame sharded across GPUs: `src` then points at sensor
   // row y + band_src_row0 (the slab's first row), which is folded into src_y; window bounds still clamp against the full height
-  a.out_r0 = 0; a.out_r1 = (uint32_t)nheight;
-  if (band_out_rows) { a.out_r0 = (uint32_t)band_out_row0; a.out_r1 = (uint32_t)(band_out_row0 + band_out_rows); a.src_y = (uint64_t)0 - (uint64_t)band_src_row0; }
+  a.out_r0 = 0; a.out_r1 = (uint32_t)l.nheight;
+  if (l.band_out_rows) { a.out_r0 = (uint32_t)l.band_out_row0; a.out_r1 = (uint32_t)(l.band_out_row0 + l.band_out_rows); a.src_y = (uint64_t)0 - (uint64_t)l.band_src_row0; }
   // or the window `win` of the result: rows as a band whose source is the whole frame (src_y stays), columns through out_c0 / out_c1; the grid below
   // is laid over out_rows x out_cols, the kernel is chosen as for the whole frame
-  a.out_c0 = 0; a.out_c1 = (uint32_t)nwidth;
-  if (win) { a.out_r0 = (uint32_t)win->row0; a.out_r1 = (uint32_t)(win->row0 + win->rows); a.out_c0 = (uint32_t)win->col0; a.out_c1 = (uint32_t)(win->col0 + win->cols); }
+  a.out_c0 = 0; a.out_c1 = (uint32_t)l.nwidth;
+  if (l.win) { a.out_r0 = (uint32_t)l.win->row0; a.out_r1 = (uint32_t)(l.win->row0 + l.win->rows); a.out_c0 = (uint32_t)l.win->col0; a.out_c1 = (uint32_t)(l.win->col0 + l.win->cols); }
   const size_t out_rows = a.out_r1 - a.out_r0, out_cols = a.out_c1 - a.out_c0;
   a.xcd_gx = 0; a.xcd_gy = 0; a.xcd_group = 0;
   // launch-log tag: the host-known switches the kernels branch on, "norm_fast=.,norm_light=.,fast_x=.,fast_y=.,xcd=." (xcd: 0 plain grid, 1 XCD row
@@ -1201,26 +1200,26 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
       }
       return t;
     }();
-    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4)) + (win ? 48 : 0) + (a.layout == 3 ? 192 : a.layout == 1 ? 96 : 0) +
-                (batch_n ? 288 : 0)].c_str();
+    return tags[(size_t)((a.norm_fast ? 1 : 0) | (a.norm_light ? 2 : 0) | (a.fast_x ? 4 : 0) | (a.fast_y ? 8 : 0) | (xcd << 4)) + (l.win ? 48 : 0) + (a.layout == 3 ? 192 : a.layout == 1 ? 96 : 0) +
+                (l.batch_n ? 288 : 0)].c_str();
   };
   a.components = has_fourth_colour ? 4 : 3;               // the w8 kernel skips the fourth bin for three-colour filters (it stays 0.0)
   // windows of at most 8 x 8 samples: floor(skip*(c+1)) - floor(skip*c) + 1 <= ceil(skip) + 1 (mosaics only: the 8-sample kernels have no plain mode)
-  const bool general = raw_scaled_demosaic_general(width, height, nwidth, nheight, (reinterpret_cast<uintptr_t>(dst4) & 15) == 0, plain != nullptr);
-  if (batch_n) {
+  const bool general = raw_scaled_demosaic_general(l.width, l.height, l.nwidth, l.nheight, (reinterpret_cast<uintptr_t>(l.dst4) & 15) == 0, l.plain != nullptr);
+  if (l.batch_n) {
     // Frames of one shape behind one launch per kBatchMax of them: the general kernel's batch mode.  The caller asked raw_scaled_demosaic_general first (the
     // window-8 kernels have no such mode: nothing is launched for a geometry that selects them) and passes whole frames.  grid_rows_few's block budget is
     // shared by the frames of a launch, one block row per frame at the least
-    if (!general || band_out_rows || win || !batch_srcs) return;
+    if (!general || l.band_out_rows || l.win || !l.batch_srcs) return;
     const size_t slice = out_rows * out_cols * 4;
-    for (size_t i0 = 0; i0 < batch_n; i0 += (size_t)kBatchMax) {
-      const size_t nb = std::min<size_t>((size_t)kBatchMax, batch_n - i0);
+    for (size_t i0 = 0; i0 < l.batch_n; i0 += (size_t)kBatchMax) {
+      const size_t nb = std::min<size_t>((size_t)kBatchMax, l.batch_n - i0);
       ScaledBatch bp;
-      for (size_t i = 0; i < (size_t)kBatchMax; ++i) bp.src[i] = i < nb ? batch_srcs[i0 + i] : nullptr;
+      for (size_t i = 0; i < (size_t)kBatchMax; ++i) bp.src[i] = i < nb ? l.batch_srcs[i0 + i] : nullptr;
       bp.on = 1;
       dim3 grid = grid_rows_few(out_cols, out_rows, 128, (unsigned)(8192 / nb));
       grid.z = (unsigned)nb;
-      IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid, dim3(128), 0, s, static_cast<const T *>(nullptr), a, cfa48_dev, dst4 + i0 * slice, bp);
+      IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid, dim3(128), 0, s, static_cast<const T *>(nullptr), a, l.cfa48_dev, l.dst4 + i0 * slice, bp);
     }
     return;
   }
@@ -1235,8 +1234,8 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
     const unsigned want = std::max(1u, total_blocks / gx);
     const dim3 grid2(gx, (unsigned)std::min<size_t>(out_rows, want), 1);
     const dim3 grid = grid2;
-    if (pw > 0 && ph > 0 && (uint32_t)(pw * ph) <= kW8MaxCells && 48 % pw == 0 && 48 % ph == 0) {
-      const size_t lds = (size_t)pw * ph * kW8CellF4 * 4 * sizeof(float);
+    if (l.pattern_width > 0 && l.pattern_height > 0 && (uint32_t)(l.pattern_width * l.pattern_height) <= kW8MaxCells && 48 % l.pattern_width == 0 && 48 % l.pattern_height == 0) {
+      const size_t lds = (size_t)l.pattern_width * l.pattern_height * kW8CellF4 * 4 * sizeof(float);
       dim3 grid = grid2;
       a.xcd_gx = 0; a.xcd_gy = 0;
       {
@@ -1248,26 +1247,28 @@ void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y,
       }
       const char *t = tag(a.xcd_group == 0 ? 0 : (out_rows > a.xcd_gy ? 2 : 1));
       if (has_fourth_colour) {
-        if (a.skip_x_x >= 4.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 5, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
-        else if (a.skip_x_x >= 2.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 3, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
-        else IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 2, true>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
+        if (a.skip_x_x >= 4.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 5, true>), grid, dim3(256), lds, s, src, a, l.cfa48_dev, (uint32_t)l.pattern_width, (uint32_t)l.pattern_height, l.dst4);
+        else if (a.skip_x_x >= 2.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 3, true>), grid, dim3(256), lds, s, src, a, l.cfa48_dev, (uint32_t)l.pattern_width, (uint32_t)l.pattern_height, l.dst4);
+        else IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 2, true>), grid, dim3(256), lds, s, src, a, l.cfa48_dev, (uint32_t)l.pattern_width, (uint32_t)l.pattern_height, l.dst4);
       } else {
-        if (a.skip_x_x >= 4.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 5, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
-        else if (a.skip_x_x >= 2.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 3, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
-        else IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 2, false>), grid, dim3(256), lds, s, src, a, cfa48_dev, (uint32_t)pw, (uint32_t)ph, dst4);
+        if (a.skip_x_x >= 4.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 5, false>), grid, dim3(256), lds, s, src, a, l.cfa48_dev, (uint32_t)l.pattern_width, (uint32_t)l.pattern_height, l.dst4);
+        else if (a.skip_x_x >= 2.0f) IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 3, false>), grid, dim3(256), lds, s, src, a, l.cfa48_dev, (uint32_t)l.pattern_width, (uint32_t)l.pattern_height, l.dst4);
+        else IPK_LAUNCH_TAG(t, (k_raw_scaled_demosaic_w8m<T, 2, false>), grid, dim3(256), lds, s, src, a, l.cfa48_dev, (uint32_t)l.pattern_width, (uint32_t)l.pattern_height, l.dst4);
       }
       return;
     }
-    IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic_w8<T>, grid, dim3(256), 0, s, src, a, cfa48_dev, dst4);
+    IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic_w8<T>, grid, dim3(256), 0, s, src, a, l.cfa48_dev, l.dst4);
     return;
   }
   ScaledBatch one;                                                           // batch mode off: the table is not read
   for (int i = 0; i < kBatchMax; ++i) one.src[i] = nullptr;
   one.on = 0;
-  IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(out_cols, out_rows, 128, 8192), dim3(128), 0, s, src, a, cfa48_dev, dst4, one);
+  IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(out_cols, out_rows, 128, 8192), dim3(128), 0, s, src, a, l.cfa48_dev, l.dst4, one);
 }
-template void launch_raw_scaled_demosaic<uint16_t>(const uint16_t *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *, const PlainLevels *, const void *const *, size_t);
-template void launch_raw_scaled_demosaic<float>(const float *, size_t, size_t, size_t, size_t, size_t, float, float, int, int, size_t, size_t, const uint8_t *, int, int, float *, hipStream_t, size_t, size_t, size_t, const ResampleWindow *, const PlainLevels *, const void *const *, size_t);
+void launch_raw_scaled_demosaic(const ScaledDemosaicLaunch &l, hipStream_t s) {
+  if (l.src_is_u16) launch_raw_scaled_demosaic_typed<uint16_t>(l, s);
+  else launch_raw_scaled_demosaic_typed<float>(l, s);
+}
 template void launch_transform_buffer<float>(const float *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, float *, hipStream_t);
 template void launch_transform_buffer<uint8_t>(const uint8_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint8_t *, hipStream_t);
 template void launch_transform_buffer<uint16_t>(const uint16_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint16_t *, hipStream_t);

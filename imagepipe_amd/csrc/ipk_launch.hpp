@@ -79,13 +79,20 @@ void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, si
 // k_raw_scaled_demosaic<T>, whatever the skips and dst4's alignment, read no filter (cfa48_dev may be null; black0 / white0, norm_fast and the pattern
 // size are ignored), and append plain=1 / plain=3 to the tag: [norm_fast=0,...,xcd=0,plain=1] / [...,xcd=0,win=1,plain=3]
 struct PlainLevels { int layout; float black[3], white[3]; };
-template <typename T>
-void launch_raw_scaled_demosaic(const T *src, size_t owidth, size_t x, size_t y, size_t width, size_t height, float black0, float white0, int norm_fast, int has_fourth_colour,
-                                size_t nwidth, size_t nheight, const uint8_t *cfa48_dev, int pattern_width, int pattern_height, float *dst4, hipStream_t s,
-                                size_t band_src_row0 = 0, size_t band_out_row0 = 0, size_t band_out_rows = 0,    // band_out_rows == 0: the whole frame
-                                const ResampleWindow *win = nullptr,                                             // not together with a band
-                                const PlainLevels *plain = nullptr,
-                                const void *const *batch_srcs = nullptr, size_t batch_n = 0);                    // batch mode, below (src is not read)
+struct ScaledDemosaicLaunch {
+  const void *src; bool src_is_u16;
+  size_t owidth, x, y, width, height;
+  float black0, white0;
+  int norm_fast, has_fourth_colour;
+  size_t nwidth, nheight;
+  const uint8_t *cfa48_dev; int pattern_width, pattern_height;
+  float *dst4;
+  size_t band_src_row0, band_out_row0, band_out_rows;      // band_out_rows == 0: the whole frame
+  const ResampleWindow *win;                               // not together with a band
+  const PlainLevels *plain;
+  const void *const *batch_srcs; size_t batch_n;           // batch mode, below (src is not read)
+};
+void launch_raw_scaled_demosaic(const ScaledDemosaicLaunch &l, hipStream_t s);
 // Which kernel a whole-frame, band or window launch of launch_raw_scaled_demosaic takes: true = the general kernel k_raw_scaled_demosaic<T> (a skip above
 // 7 or below 1, a frame under 8 samples wide, a destination off a 16-byte boundary, every plain layout), false = a window-8 kernel.  The launcher's own
 // test, with its f32 skips
