@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (IpkError, FusedParams, PipelineDesc, OUT_F32, OUT_U8, OUT_U16, SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16,
+from ._lib import (IpkError, FusedParams, PipelineDesc, ChainParams, OUT_F32, OUT_U8, OUT_U16, SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16,
                    OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN,
                    ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO, FUSED_BATCH_PREVIEWS)
 
@@ -23,7 +23,8 @@ __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", 
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
            "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "raw_to_srgb_resampled_window", "raw_to_srgb_scaled_window",
            "transform_window_footprint", "raw_scaled_demosaic_window", "raw_demosaic_scaled", "raster_scale_down_window", "scaled_window_footprint", "plain_scale_down",
-           "plain_scale_down_window", "raw_scaled_demosaic_batch", "plain_scale_down_batch", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FUSED_BATCH_PREVIEWS",
+           "plain_scale_down_window", "raw_scaled_demosaic_batch", "plain_scale_down_batch", "chain_params", "pointwise_chain_out_batch",
+           "batch_each_plan", "run_batch_each", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FUSED_BATCH_PREVIEWS",
            "FusedPlan", "IpkError"]
 
 _initialized_device = None
@@ -1120,6 +1121,79 @@ def plain_scale_down_batch(srcs: Sequence[torch.Tensor], kind, owidth, x, y, wid
     _lib.check(lib().ipk_plain_scale_down_batch(_frame_ptrs(srcs), n, st, kind, owidth, x, y, width, height, b, w, nwidth, nheight, out.data_ptr(),
                                                 _stream()), "ipk_plain_scale_down_batch")
     return out
+
+
+def chain_params(wb_coeffs=(1.0, 1.0, 1.0, 0.0), cam_to_xyz_normalized=None, exposure=0.0, points=()):
+    """ipk_chain_params: the descriptor fields OpToLab and OpBaseCurve read, for one frame of pointwise_chain_out_batch.  points: (x, y) pairs"""
+    p = ChainParams()
+    p.wb_coeffs = _farr(wb_coeffs, 4)
+    p.cam_to_xyz_normalized = _farr(np.zeros(12, np.float32) if cam_to_xyz_normalized is None else cam_to_xyz_normalized, 12)
+    p.exposure = float(exposure)
+    pts, npts = _points(points)
+    p.npoints = npts
+    for i in range(2 * npts):
+        p.points[i] = pts[i]
+    return p
+
+
+def pointwise_chain_out_batch(srcs4: Sequence[torch.Tensor], width, height, params, *, monochrome=False, linear=False, out_type=OUT_F32,
+                              outs: Optional[Sequence[torch.Tensor]] = None):
+    """ipk_pointwise_chain_out_batch: tolab..gamma (+ quantisation) over len(srcs4) 4-channel f32 device buffers of width x height pixels, frame i with
+    params[i] (chain_params()) into outs[i] -- given, or views of ONE fresh allocation.  One launch per 64 frames; frame i is bit-identical to the
+    single-frame call.  Returns the list of output tensors (u16 bits in int16)."""
+    n = len(srcs4)
+    if len(params) != n:
+        raise ValueError("pointwise_chain_out_batch: as many parameter sets as frames")
+    dt = {OUT_F32: torch.float32, OUT_U8: torch.uint8, OUT_U16: torch.int16}[out_type]
+    if outs is None:
+        whole = torch.empty((max(n, 1), height, width, 3), dtype=dt, device="cuda")
+        outs = [whole[i] for i in range(n)]
+    if len(outs) != n or any(o.dtype != dt or o.numel() != height * width * 3 or not o.is_contiguous() for o in outs):
+        raise ValueError("pointwise_chain_out_batch: outs must be %d contiguous %s tensors of %d x %d x 3 elements" % (n, dt, height, width))
+    arr = (ChainParams * max(n, 1))(*params)
+    _lib.check(lib().ipk_pointwise_chain_out_batch(_frame_ptrs(srcs4), width, height, int(bool(monochrome)), arr, n, int(bool(linear)), out_type,
+                                                   _frame_ptrs(outs), _stream()), "ipk_pointwise_chain_out_batch")
+    return list(outs)
+
+
+def _desc_ptrs(pipes):
+    ds = [p.desc() for p in pipes]
+    return ds, (C.POINTER(PipelineDesc) * max(len(ds), 1))(*[C.pointer(d) for d in ds])
+
+
+def batch_each_plan(pipes, out_type=OUT_F32):
+    """The plan run_batch_each follows (ipk_pipeline_batch_each_plan, host-only): per frame (route, run_first) -- route 0 a single run, 1 the uniform
+    batch, 2 varied previews (one scaling launch group and ONE point-wise launch per chunk, per-frame parameters from a device table); run_first the
+    first frame of the frame's run of same-shaped descriptors."""
+    n = len(pipes)
+    _ds, dp = _desc_ptrs(pipes)
+    route, first = (C.c_int * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    _lib.check(lib().ipk_pipeline_batch_each_plan(dp, n, out_type, route, first), "ipk_pipeline_batch_each_plan")
+    return [(int(route[i]), int(first[i])) for i in range(n)]
+
+
+def run_batch_each(pipes, srcs: Sequence[torch.Tensor], out_type=OUT_F32, outs: Optional[Sequence[torch.Tensor]] = None):
+    """A shoot whose files carry their own colour settings (ipk_pipeline_run_batch_each): one Pipeline per frame -- each with its own white balance,
+    matrix, exposure and curve -- and srcs[i] shaped like pipes[i]'s own source.  Results are what pipes[i].run() / output_8bit() / output_16bit() give
+    frame by frame; frames that differ only in those point-wise settings run as batched previews where batch_each_plan() says 2 (batch_previews set on
+    every member).  Returns the list of (h, w, 3) device tensors of the output type (u16 bits in int16) -- `outs` when given, else fresh ones -- and sets
+    every member's last_used_fused to what the last frame's run leaves."""
+    n = len(pipes)
+    if len(srcs) != n:
+        raise ValueError("run_batch_each: as many frames as pipelines")
+    dt = {OUT_F32: torch.float32, OUT_U8: torch.uint8, OUT_U16: torch.int16}[out_type]
+    sizes = [p.sizes()[1] for p in pipes]
+    if outs is None:
+        outs = [torch.empty((fh, fw, 3), dtype=dt, device="cuda") for fw, fh in sizes]
+    if len(outs) != n or any(o.dtype != dt or o.numel() != fw * fh * 3 or not o.is_contiguous() for o, (fw, fh) in zip(outs, sizes)):
+        raise ValueError("run_batch_each: outs must be contiguous %s tensors of each frame's final size" % dt)
+    _ds, dp = _desc_ptrs(pipes)
+    sp = (C.c_void_p * max(n, 1))(*[_ptr(t).value for t in srcs])
+    used = C.c_int(0)
+    _lib.check(lib().ipk_pipeline_run_batch_each(dp, sp, _frame_ptrs(outs), n, out_type, C.byref(used), _stream()), "ipk_pipeline_run_batch_each")
+    for p in pipes:
+        p.last_used_fused = bool(used.value)
+    return [o.view(fh, fw, 3) for o, (fw, fh) in zip(outs, sizes)]
 
 
 def scaled_window_footprint(width, height, nwidth, nheight, window):

@@ -70,6 +70,14 @@ class PipelineDesc(_SizedDesc):
     ]
 
 
+class ChainParams(_SizedDesc):
+    """ipk_chain_params: the descriptor fields OpToLab and OpBaseCurve read"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("wb_coeffs", C.c_float * 4), ("cam_to_xyz_normalized", C.c_float * 12),
+        ("exposure", C.c_float), ("npoints", C.c_int), ("points", C.c_float * 128),
+    ]
+
+
 class StageTime(C.Structure):
     """ipk_stage_time"""
     _fields_ = [("name", C.c_char * 88), ("ms", C.c_float)]
@@ -170,6 +178,9 @@ SIGNATURES = {
     "ipk_host_pipeline_run_region": (C.c_int, [C.POINTER(PipelineDesc), _vp, _sz, _sz, _sz, _sz, _vp, C.c_int, C.POINTER(C.c_int)]),
     "ipk_host_pipeline_run_batch": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int)]),
     "ipk_pipeline_run_batch": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int), _vp]),
+    "ipk_pipeline_run_batch_each": (C.c_int, [C.POINTER(C.POINTER(PipelineDesc)), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int), _vp]),
+    "ipk_pipeline_batch_each_plan": (C.c_int, [C.POINTER(C.POINTER(PipelineDesc)), _sz, C.c_int, C.POINTER(C.c_int), _szp]),
+    "ipk_pointwise_chain_out_batch": (C.c_int, [C.POINTER(_vp), _sz, _sz, C.c_int, C.POINTER(ChainParams), _sz, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
     "ipk_pipeline_run_batch_multi": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int)]),
     "ipk_host_pipeline_run_batch_multi": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int)]),
     "ipk_devices_sync": (C.c_int, []),

@@ -2976,20 +2976,21 @@ bool batches_previews(const ipk_pipeline_desc *d, const Negotiated &n, const Rou
   bp.pass1_batched = n.raw && ipk::raw_scaled_demosaic_general(n.r.width, n.r.height, n.dw, n.dh, true, !n.cfa_branch);
   return true;
 }
-int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, void *const *dsts, size_t n,
-                       int out_type, int *used_fused, void *stream) {
-  const size_t px = ng.dw * ng.dh, slice = px * 4, out_bytes = px * 3 * out_elem_size(out_type);
-  const bool f32_out = out_type == IPK_OUT_F32;
-  const int monochrome = one_pass_monochrome(d, ng);
+// The chunk walk both preview batches share (run_batch_previews, run_batch_each's varied runs): d states the levels, crops, filter and size limit of every
+// frame.  A chunk of one frame is single(i); a longer one gets its scratch, pass 1 -- the chunk's RGBE previews one after another, slice floats apart --
+// and then pass2(i0, m, rgbe, slice, tm), which enqueues the point-wise work of frames i0 .. i0 + m and marks its stages
+extern "C++" template <typename Single, typename Pass2>
+int run_preview_chunks(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, size_t n, void *stream, Single single,
+                       Pass2 pass2) {
+  const size_t slice = ng.dw * ng.dh * 4;
   for (size_t i0 = 0; i0 < n; i0 += bp.chunk) {
     const size_t m = std::min(bp.chunk, n - i0);
-    if (m == 1) { const int rc = ipk_pipeline_run(d, srcs[i0], dsts[i0], out_type, used_fused, stream); if (rc < 0) return rc; continue; }
+    if (m == 1) { const int rc = single(i0); if (rc < 0) return rc; continue; }
     StageTimer tm(S(stream));
     Scratch sc(S(stream));
     void *buf = nullptr;
     int rc = sc.get(m * slice * sizeof(float), &buf); if (rc) return rc;
     float *rgbe = static_cast<float *>(buf);
-    // pass 1: the chunk's RGBE previews, one after another
     if (bp.pass1_batched) {
       rc = ng.cfa_branch ? raw_scaled_demosaic_batch_impl(srcs + i0, m, d->src_type, d->width, ng.r.x, ng.r.y, ng.r.width, ng.r.height, d->blacklevels[0],
                                                           d->whitelevels[0], d->cfa, ng.dw, ng.dh, rgbe, stream)
@@ -3000,18 +3001,170 @@ int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const B
       for (size_t i = 0; i < m; ++i) { rc = launch_gofloat_demosaic(d, ng, srcs[i0 + i], nullptr, rgbe + i * slice, stream); if (rc < 0) return rc; }
     }
     tm.mark("batch gofloat+demosaic");
-    // pass 2: the chain once per maximal run of frames whose destinations follow each other in memory
-    for (size_t j = 0; j < m;) {
-      size_t k = j + 1;
-      while (k < m && dsts[i0 + k] == static_cast<char *>(dsts[i0 + k - 1]) + out_bytes) ++k;
-      rc = ipk_pointwise_chain_out(rgbe + j * slice, ng.dw, (k - j) * ng.dh, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points, d->npoints,
-                                   ng.linear, out_type, dsts[i0 + j], stream);
-      if (rc < 0) return rc;
-      tm.mark(f32_out ? "batch to_lab+basecurve+from_lab+gamma" : "batch to_lab+basecurve+from_lab+gamma+quantise");
-      j = k;
-    }
+    rc = pass2(i0, m, rgbe, slice, tm); if (rc < 0) return rc;
   }
   return IPK_OK;
+}
+int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, void *const *dsts, size_t n,
+                       int out_type, int *used_fused, void *stream) {
+  const size_t out_bytes = ng.dw * ng.dh * 3 * out_elem_size(out_type);
+  const bool f32_out = out_type == IPK_OUT_F32;
+  const int monochrome = one_pass_monochrome(d, ng);
+  return run_preview_chunks(d, ng, bp, srcs, n, stream,
+    [&](size_t i) { return ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); },
+    // pass 2: the chain once per maximal run of frames whose destinations follow each other in memory
+    [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
+      for (size_t j = 0; j < m;) {
+        size_t k = j + 1;
+        while (k < m && dsts[i0 + k] == static_cast<char *>(dsts[i0 + k - 1]) + out_bytes) ++k;
+        const int rc = ipk_pointwise_chain_out(rgbe + j * slice, ng.dw, (k - j) * ng.dh, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points,
+                                               d->npoints, ng.linear, out_type, dsts[i0 + j], stream);
+        if (rc < 0) return rc;
+        tm.mark(f32_out ? "batch to_lab+basecurve+from_lab+gamma" : "batch to_lab+basecurve+from_lab+gamma+quantise");
+        j = k;
+      }
+      return (int)IPK_OK;
+    });
+}
+
+// ipk_pointwise_chain_out_batch: every frame's parameters through PointwisePrep::prepare (so normalize_wbs, the spline, has_curve and fast_ok are the single
+// form's, per frame) before anything is enqueued, then one frame-table launch per 64 frames (launch_chain_batch), its table in the scratch pool.  stage: the
+// name marked behind every launch
+int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height, int monochrome, const ipk_chain_params *params, size_t n, int linear, int out_type,
+                         void *const *dsts, void *stream, StageTimer &tm, const char *stage) {
+  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
+  if (!dims_ok(width, height)) return fail(IPK_ERR_INVALID, "bad pointwise_chain_out_batch arguments");
+  if (n == 0) return IPK_OK;
+  if (!srcs4 || !dsts || !params) return fail(IPK_ERR_INVALID, "null argument");
+  if (n > (size_t)1 << 20) return fail(IPK_ERR_INVALID, "batch too large");
+  const size_t npix = width * height, dalign = out_elem_size(out_type);
+  if (out_type != IPK_OUT_F32 && npix < 256)
+    return fail(IPK_ERR_UNSUPPORTED, "pointwise_chain_out_batch needs at least 256 pixels per frame for 8- and 16-bit outputs");
+  std::vector<PointwisePrep> pps(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (!srcs4[i] || !dsts[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
+    if (reinterpret_cast<uintptr_t>(srcs4[i]) % 16 != 0 || reinterpret_cast<uintptr_t>(dsts[i]) % dalign != 0)
+      return fail(IPK_ERR_INVALID, "frame %zu: the source needs 16-byte alignment, the destination its element's", i);
+    if (params[i].struct_size != sizeof(ipk_chain_params))
+      return fail(IPK_ERR_INVALID, "params[%zu].struct_size is %u, not sizeof(ipk_chain_params) = %zu", i, params[i].struct_size, sizeof(ipk_chain_params));
+    const ipk_chain_params &p = params[i];
+    const int rc = pps[i].prepare(monochrome, p.wb_coeffs, p.cam_to_xyz_normalized, p.exposure, p.points, p.npoints, linear);
+    if (rc) { const std::string why = g_err; return fail(rc, "params[%zu]: %s", i, why.c_str()); }
+    pps[i].f.src = srcs4[i]; pps[i].f.dst = dsts[i]; pps[i].f.out_type = out_type;
+  }
+  std::vector<ipk::FusedLaunch> fl;
+  for (size_t i0 = 0; i0 < n; i0 += ipk::kChainBatchMax) {
+    const size_t m = std::min(ipk::kChainBatchMax, n - i0);
+    fl.clear();
+    for (size_t i = 0; i < m; ++i) fl.push_back(pps[i0 + i].f);
+    Scratch sc(S(stream));
+    void *table = nullptr;
+    { const int rc = sc.get(ipk::chain_batch_table_bytes(m), &table); if (rc) return rc; }
+    const int lrc = ipk::launch_chain_batch(fl.data(), m, npix, out_type, table, S(stream));
+    if (lrc == -4) return fail(IPK_ERR_HIP, "pointwise_chain_out_batch: the table upload or the launch could not be enqueued");
+    if (lrc != 0) return fail(IPK_ERR_UNSUPPORTED, "pointwise_chain_out_batch: frame too small");
+    tm.mark(stage);
+  }
+  return IPK_OK;
+}
+
+// ---- n frames, n descriptors (ipk_pipeline_run_batch_each): the plan ----
+// Same-shaped: every field equal but the five OpToLab and OpBaseCurve read.  a and b are taken and folded (so cfa compares as the drivers read it and
+// padding never enters); sa / sb are the struct_size values the callers wrote.  Floats compare by their bits
+bool same_bits(const float *a, const float *b, size_t n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
+bool same_shape(const ipk_pipeline_desc &a, uint32_t sa, const ipk_pipeline_desc &b, uint32_t sb) {
+  return sa == sb && a.src_type == b.src_type && a.width == b.width && a.height == b.height && a.cpp == b.cpp && a.is_cfa == b.is_cfa &&
+         std::strcmp(a.cfa, b.cfa) == 0 && a.crop_top == b.crop_top && a.crop_right == b.crop_right && a.crop_bottom == b.crop_bottom &&
+         a.crop_left == b.crop_left && same_bits(a.blacklevels, b.blacklevels, 4) && same_bits(a.whitelevels, b.whitelevels, 4) &&
+         same_bits(a.rotatecrop, b.rotatecrop, 5) && a.rotation == b.rotation && a.fliph == b.fliph && a.flipv == b.flipv && a.maxwidth == b.maxwidth &&
+         a.maxheight == b.maxheight && a.linear == b.linear && a.allow_fused == b.allow_fused && a.use_fastpath == b.use_fastpath &&
+         a.cfa_width == b.cfa_width && a.cfa_height == b.cfa_height && a.schedule == b.schedule && a.fuse_rotatecrop == b.fuse_rotatecrop &&
+         a.reserved1 == b.reserved1 && a.fuse_scaledown == b.fuse_scaledown;
+}
+bool same_pointwise(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) {
+  return same_bits(a.wb_coeffs, b.wb_coeffs, 4) && same_bits(a.cam_to_xyz_normalized, b.cam_to_xyz_normalized, 12) && same_bits(&a.exposure, &b.exposure, 1) &&
+         a.npoints == b.npoints && same_bits(a.points, b.points, 128);
+}
+int take_folded(const ipk_pipeline_desc *d, ipk_pipeline_desc &out) {
+  IPK_FOLD_CFA(ipk_pipeline_desc, d)
+  out = *d;
+  return IPK_OK;
+}
+enum { kEachSingle = 0, kEachUniform = 1, kEachVaried = 2 };
+struct EachPlan {
+  std::vector<ipk_pipeline_desc> d;                  // taken and folded
+  std::vector<int> route; std::vector<size_t> run_first;
+  struct Varied { Negotiated ng; BatchPreviews bp; };
+  std::map<size_t, Varied> varied;                   // by the run's first frame
+};
+// validates every descriptor as ipk_pipeline_run does (and the curve's point count, as the batch driver does), then cuts the runs
+int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, EachPlan &p) {
+  if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
+  if (n && !descs) return fail(IPK_ERR_INVALID, "null argument");
+  if (n > (size_t)1 << 20) return fail(IPK_ERR_INVALID, "batch too large");
+  p.d.resize(n); p.route.assign(n, kEachSingle); p.run_first.assign(n, 0);
+  std::vector<uint32_t> sizes(n);
+  // the raster fast path is decided by the five point-wise fields themselves (default_ops_other): a frame that takes it shares no run with one that
+  // does not, so every frame of a run is on the route ipk_pipeline_run would choose for it
+  std::vector<char> fast(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    if (!descs[i]) return fail(IPK_ERR_INVALID, "null descriptor at index %zu", i);
+    sizes[i] = descs[i]->struct_size;
+    int rc = take_folded(descs[i], p.d[i]);
+    if (!rc) rc = validate_desc(&p.d[i], out_type, kCheckFuse | kCheckCurve);
+    if (!rc) {
+      fast[i] = ipk_pipeline_takes_fastpath(&p.d[i], out_type) == 1;
+      if (fast[i]) { if (p.d[i].width < 1 || p.d[i].height < 1) rc = fail(IPK_ERR_INVALID, "empty source"); }
+      else { Negotiated ng; rc = negotiate(&p.d[i], out_type, ng); }
+    }
+    if (rc) { const std::string why = g_err; return fail(rc, "descriptor %zu: %s", i, why.c_str()); }
+  }
+  for (size_t a = 0; a < n;) {
+    size_t b = a + 1;
+    while (b < n && fast[a] == fast[b] && same_shape(p.d[a], sizes[a], p.d[b], sizes[b])) ++b;
+    for (size_t i = a; i < b; ++i) p.run_first[i] = a;
+    const size_t m = b - a;
+    bool all_equal = true;
+    for (size_t i = a + 1; i < b; ++i) all_equal = all_equal && same_pointwise(p.d[a], p.d[i]);
+    EachPlan::Varied v; Route rt;
+    if (m > 1 && !all_equal && !fast[a] && opted(&p.d[a], IPK_FUSED_BATCH_PREVIEWS) &&
+        negotiate(&p.d[a], out_type, v.ng) == IPK_OK && (choose_route(&p.d[a], v.ng, out_type, rt), batches_previews(&p.d[a], v.ng, rt, m, v.bp))) {
+      for (size_t i = a; i < b; ++i) p.route[i] = kEachVaried;
+      p.varied[a] = v;
+    } else {
+      for (size_t j = a; j < b;) {                   // maximal sub-runs of equal descriptors: the uniform batch, which keeps its own routes
+        size_t k = j + 1;
+        while (k < b && same_pointwise(p.d[j], p.d[k])) ++k;
+        if (k - j > 1) for (size_t i = j; i < k; ++i) p.route[i] = kEachUniform;
+        j = k;
+      }
+    }
+    a = b;
+  }
+  return IPK_OK;
+}
+void chain_params_of(const ipk_pipeline_desc &d, ipk_chain_params &c) {
+  c.struct_size = (uint32_t)sizeof(c);
+  std::memcpy(c.wb_coeffs, d.wb_coeffs, sizeof(c.wb_coeffs));
+  std::memcpy(c.cam_to_xyz_normalized, d.cam_to_xyz_normalized, sizeof(c.cam_to_xyz_normalized));
+  c.exposure = d.exposure; c.npoints = d.npoints; std::memcpy(c.points, d.points, sizeof(c.points));
+}
+// a varied run: the chunks and pass 1 of run_batch_previews on the run's first descriptor, then ONE frame-table launch per chunk, frame i's record from
+// descriptor i and its destination dsts[i] wherever it lies
+int run_batch_each_varied(const ipk_pipeline_desc *ds, const EachPlan::Varied &v, const void *const *srcs, void *const *dsts, size_t n, int out_type,
+                          int *used_fused, void *stream) {
+  const int monochrome = one_pass_monochrome(ds, v.ng);
+  const char *stage = out_type == IPK_OUT_F32 ? "batch-each to_lab+basecurve+from_lab+gamma" : "batch-each to_lab+basecurve+from_lab+gamma+quantise";
+  std::vector<ipk_chain_params> cp;
+  std::vector<const float *> s4;
+  return run_preview_chunks(ds, v.ng, v.bp, srcs, n, stream,
+    [&](size_t i) { return ipk_pipeline_run(ds + i, srcs[i], dsts[i], out_type, used_fused, stream); },
+    [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
+      cp.resize(m); s4.resize(m);
+      for (size_t i = 0; i < m; ++i) { chain_params_of(ds[i0 + i], cp[i]); s4[i] = rgbe + i * slice; }
+      if (used_fused) *used_fused = 0;
+      return chain_out_batch_impl(s4.data(), v.ng.dw, v.ng.dh, monochrome, cp.data(), m, v.ng.linear, out_type, dsts + i0, stream, tm, stage);
+    });
 }
 }  // namespace
 
@@ -3049,6 +3202,53 @@ int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *srcs, 
       (choose_route(d, ng, out_type, rt), batches_previews(d, ng, rt, n, bp)))
     return run_batch_previews(d, ng, bp, srcs, dsts, n, out_type, used_fused, stream);
   for (size_t i = 0; i < n; ++i) { const int rc = ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); if (rc < 0) return rc; }
+  return IPK_OK;
+}
+
+// ipk_pointwise_chain_out for n same-sized buffers, each with its own parameters and destination: one frame-table launch per 64 frames
+int ipk_pointwise_chain_out_batch(const float *const *srcs4, size_t width, size_t height, int monochrome, const void *params, size_t n, int linear,
+                                  int out_type, void *const *dsts, void *stream) {
+  REQUIRE_INIT();
+  StageTimer tm(S(stream));
+  return chain_out_batch_impl(srcs4, width, height, monochrome, static_cast<const ipk_chain_params *>(params), n, linear, out_type, dsts, stream, tm,
+                              "pointwise_chain_out_batch");
+}
+// The plan of ipk_pipeline_run_batch_each, for callers and CPU tests (no GPU)
+int ipk_pipeline_batch_each_plan(const ipk_pipeline_desc *const *descs, size_t n, int out_type, int *route, size_t *run_first) {
+  EachPlan p;
+  { const int rc = plan_each(descs, n, out_type, p); if (rc) return rc; }
+  for (size_t i = 0; i < n; ++i) { if (route) route[i] = p.route[i]; if (run_first) run_first[i] = p.run_first[i]; }
+  return IPK_OK;
+}
+// n frames, n descriptors: the plan's runs in order -- a varied run as one scaling launch group and one frame-table launch per chunk, runs of equal
+// descriptors through ipk_pipeline_run_batch, every other frame through ipk_pipeline_run
+int ipk_pipeline_run_batch_each(const ipk_pipeline_desc *const *descs, const void *const *srcs, void *const *dsts, size_t n, int out_type, int *used_fused,
+                                void *stream) {
+  REQUIRE_INIT();
+  if (n && (!descs || !srcs || !dsts)) return fail(IPK_ERR_INVALID, "null argument");
+  EachPlan p;
+  { const int rc = plan_each(descs, n, out_type, p); if (rc) return rc; }
+  for (size_t i = 0; i < n; ++i) {
+    if (!srcs[i] || !dsts[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
+    // a curve the launches would refuse, before anything is enqueued (every route but the fast path builds it)
+    const ipk_pipeline_desc &d = p.d[i];
+    if (!curve_is_noop(d.exposure, d.npoints) && ipk_pipeline_takes_fastpath(&d, out_type) != 1) {
+      ipk::Spline sp;
+      const int rc = build_curve(d.exposure, d.points, d.npoints, sp);
+      if (rc) { const std::string why = g_err; return fail(rc, "descriptor %zu: %s", i, why.c_str()); }
+    }
+  }
+  if (used_fused) *used_fused = 0;
+  for (size_t a = 0; a < n;) {
+    size_t b = a + 1;
+    while (b < n && p.route[b] == p.route[a] && p.run_first[b] == p.run_first[a] && (p.route[a] != kEachUniform || same_pointwise(p.d[a], p.d[b]))) ++b;
+    int rc;
+    if (p.route[a] == kEachVaried) rc = run_batch_each_varied(&p.d[a], p.varied.at(a), srcs + a, dsts + a, b - a, out_type, used_fused, stream);
+    else if (p.route[a] == kEachUniform) rc = ipk_pipeline_run_batch(&p.d[a], srcs + a, dsts + a, b - a, out_type, used_fused, stream);
+    else { b = a + 1; rc = ipk_pipeline_run(&p.d[a], srcs[a], dsts[a], out_type, used_fused, stream); }
+    if (rc < 0) return rc;
+    a = b;
+  }
   return IPK_OK;
 }
 

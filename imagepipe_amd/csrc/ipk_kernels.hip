@@ -3426,7 +3426,15 @@ __device__ __forceinline__ void pointwise_chain_body(const FusedArgs &a, uint64_
 }
 template <bool TOLAB_ONLY>
 __global__ __launch_bounds__(1024) void k_pointwise_chain(FusedArgs a, uint64_t npix) { pointwise_chain_body<TOLAB_ONLY>(a, npix); }
-__global__ __launch_bounds__(1024) void k_pointwise_chain_small(FusedArgs a, uint64_t npix) { pointwise_chain_body<false, 1>(a, npix); }
+// Frame-table mode (frames != null; launch_chain_batch): the grid's y plane is the frame, and the block takes EVERY argument from frames[blockIdx.y] -- a whole
+// FusedArgs per frame in device memory, filled by the host as chain_args fills the kernel's own: source, destination, multipliers, matrix, curve, has_curve,
+// fast_ok (linear, rgbm and the tables are the same in every record).  The index is block-uniform and the table is read-only for the launch, so the record is
+// read with the uniform loads the kernel arguments are read with; the block fills s_par / s_knots / s_grid from it and walks its own frame's npix pixels, so
+// the clamped tail is the frame's.  The mode is chosen here, once per block: a launch without a table runs the body on its arguments as it always did.
+__global__ __launch_bounds__(1024) void k_pointwise_chain_small(FusedArgs a, uint64_t npix, const FusedArgs *__restrict__ frames) {
+  if (IPK_RARE(frames != nullptr)) pointwise_chain_body<false, 1>(frames[blockIdx.y], npix);
+  else pointwise_chain_body<false, 1>(a, npix);
+}
 // OpToLab alone: two resident blocks per CU (eight waves per SIMD) are the point of its two-pixel form, so the register budget is stated (64)
 template <>
 __global__ __launch_bounds__(1024, 8) void k_pointwise_chain<true>(FusedArgs a, uint64_t npix) { pointwise_chain_body<true>(a, npix); }
@@ -3463,7 +3471,7 @@ int launch_pointwise_chain(const FusedLaunch &f, size_t npix, hipStream_t s, con
   const unsigned cus = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   if (npix < (size_t)cus * 16u * 256u * 6u) {                              // fewer than six long chunks per wave (6.3 MP on 256 CUs): the two-pixel form
     const size_t chunks = (npix + 127) / 128;
-    IPK_LAUNCH_TAG(chain_tag(a), k_pointwise_chain_small, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(cus, (chunks + 15) / 16))), dim3(1024), 0, s, a, (uint64_t)npix);
+    IPK_LAUNCH_TAG(chain_tag(a), k_pointwise_chain_small, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(cus, (chunks + 15) / 16))), dim3(1024), 0, s, a, (uint64_t)npix, (const FusedArgs *)nullptr);
     return 0;
   }
   const size_t chunks = (npix + 255) / 256;
@@ -3556,8 +3564,9 @@ __device__ __forceinline__ void plain_load4(const FusedArgs &a, const SrcT *__re
   }
 }
 template <typename SrcT, int OUT>
-__global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npix, const LutPair *__restrict__ gamma_reverse) {
-  constexpr bool RGBE = std::is_same<SrcT, Rgbe32>::value;
+__global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npix, const LutPair *__restrict__ gamma_reverse, const FusedArgs *__restrict__ frames) {
+  static_assert(!std::is_same<SrcT, Rgbe32>::value, "the Rgbe32 instantiations are the specialisations below");
+  (void)frames;                                                        // the frame-table mode of the Rgbe32 specialisations: null here, never read
   constexpr bool Q8 = OUT == 1;                                         // OpGamma + output8bit as one step lookup (ipk_device.hpp Q8Entry)
   __shared__ __attribute__((aligned(16))) LabTab s_lab[kLutPairs + 4];
   __shared__ __attribute__((aligned(16))) typename std::conditional<Q8, Q8Entry, typename std::conditional<OUT == 0, float, GamTab>::type>::type s_gam[kLutPairs + 4];
@@ -3583,19 +3592,10 @@ __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npi
   const uint64_t nchunks = (npix + 255) / 256;
   uint32_t *stg = s_stage + (threadIdx.x >> 6) * STG;
   const SrcT *src = reinterpret_cast<const SrcT *>(a.src);
-  const bool plain = !RGBE && (a.plain_rect | a.plain_levels) != 0;   // ipk_plain_to_srgb's modes: off on every launch of ipk_raster_to_srgb / ipk_pointwise_chain_out
+  const bool plain = (a.plain_rect | a.plain_levels) != 0;             // ipk_plain_to_srgb's modes: off on every launch of ipk_raster_to_srgb
   for (uint64_t chunk = wave; chunk < nchunks; chunk += nwaves) {
     const uint64_t base = min(chunk * 256, npix - 256);                // the last chunk ends at the last pixel
     float4 px[4];
-    if constexpr (RGBE) {
-      if (IPK_RARE(a.gather != 0)) {                                   // wave-uniform, host-set: a region from the cache (the 8- and 16-bit outputs)
-        gather_load4(a, base + 4u * lane, px);
-      } else {
-        const float *p4 = reinterpret_cast<const float *>(a.src) + (base + 4u * lane) * 4;
-        #pragma unroll
-        for (int j = 0; j < 4; ++j) px[j] = ld_stream4(p4 + 4 * j);
-      }
-    } else
     if (IPK_RARE(plain)) {                                             // rectangle and / or raw levels (wave-uniform): the lane's four pixels one by one
       plain_load4(a, src, s_expand, base + 4u * lane, px);
     } else
@@ -3616,12 +3616,6 @@ __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npi
     }
     PixOut o[4];
     bool bad = a.fast_ok == 0;
-    if (RGBE) {                                                        // the fast form drops the E term: legal while the fourth channel is +0.0 (pointwise_chain_body)
-      uint32_t wbits = 0u;
-      #pragma unroll
-      for (int j = 0; j < 4; ++j) wbits |= __float_as_uint(px[j].w);
-      bad |= wbits != 0u;
-    }
     if (a.fast_ok) bad |= pointwise4_fast<true>(a, s_par, s_lab, s_gam, s_knots, px, o, a.has_curve != 0, a.linear != 0, 0, nullptr, s_grid);
     if (__builtin_amdgcn_ballot_w64(bad) != 0) {
       #pragma unroll
@@ -3636,6 +3630,69 @@ __global__ __launch_bounds__(1024) void k_raster_chain(FusedArgs a, uint64_t npi
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
 }
+// The Rgbe32 instantiations (OUT 1 | 2; ipk_pointwise_chain_out): the same walk over 16-byte pixels, stated on its own because it runs on either of two
+// argument blocks -- the kernel's, or, in the frame-table mode (frames != null; k_pointwise_chain_small has the account), frames[blockIdx.y], where "the
+// last chunk ends at the last pixel" is said of that frame's npix.  The mode is chosen once per block, in the specialisations below
+template <int OUT>
+__device__ __forceinline__ void rgbe_chain_body(const FusedArgs &a, uint64_t npix) {
+  constexpr bool Q8 = OUT == 1;
+  __shared__ __attribute__((aligned(16))) LabTab s_lab[kLutPairs + 4];
+  __shared__ __attribute__((aligned(16))) typename std::conditional<Q8, Q8Entry, GamTab>::type s_gam[kLutPairs + 4];
+  __shared__ __attribute__((aligned(16))) float s_knots[kKnotFloats];
+  __shared__ float s_par[32];
+  constexpr int STG = OUT == 1 ? 192 : 384;
+  __shared__ __attribute__((aligned(16))) uint32_t s_stage[16 * STG];
+  stage_table_direct(s_lab, a.lab_table, a.lab_pairs);
+  if constexpr (Q8) stage_q8_direct(s_gam, a.gam_q8); else stage_table_direct(s_gam, a.gam_table, a.gam_pairs);
+  if (threadIdx.x < 4) s_par[threadIdx.x] = a.tolab.mul[threadIdx.x];
+  else if (threadIdx.x < 16) s_par[threadIdx.x] = a.tolab.cm[threadIdx.x - 4];
+  else if (threadIdx.x < 25) s_par[threadIdx.x] = a.rgbm.m[threadIdx.x - 16];
+  if (threadIdx.x < kSplineMaxKnots) fill_knots(s_knots, a.spline, (int)threadIdx.x);
+  __shared__ __attribute__((aligned(16))) float s_grid[kGridFloats];
+  if (a.spline.grid_ok) fill_grid(s_grid, a.spline, (int)threadIdx.x);
+  sync_after_lds_direct();
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const uint64_t nchunks = (npix + 255) / 256;
+  uint32_t *stg = s_stage + (threadIdx.x >> 6) * STG;
+  for (uint64_t chunk = wave; chunk < nchunks; chunk += nwaves) {
+    const uint64_t base = min(chunk * 256, npix - 256);                // the last chunk ends at the last pixel
+    float4 px[4];
+    if (IPK_RARE(a.gather != 0)) {                                     // wave-uniform, host-set: a region from the cache (the 8- and 16-bit outputs)
+      gather_load4(a, base + 4u * lane, px);
+    } else {
+      const float *p4 = reinterpret_cast<const float *>(a.src) + (base + 4u * lane) * 4;
+      #pragma unroll
+      for (int j = 0; j < 4; ++j) px[j] = ld_stream4(p4 + 4 * j);
+    }
+    PixOut o[4];
+    uint32_t wbits = 0u;                                               // the fast form drops the E term: legal while the fourth channel is +0.0 (pointwise_chain_body)
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) wbits |= __float_as_uint(px[j].w);
+    bool bad = a.fast_ok == 0 || wbits != 0u;
+    if (a.fast_ok) bad |= pointwise4_fast<true>(a, s_par, s_lab, s_gam, s_knots, px, o, a.has_curve != 0, a.linear != 0, 0, nullptr, s_grid);
+    if (__builtin_amdgcn_ballot_w64(bad) != 0) {
+      #pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const PixOut e = pointwise_exact(a, s_lab, s_gam, s_knots, px[j]);
+        if (bad) o[j] = e;
+      }
+    }
+    if constexpr (Q8) OutStage<1>::stage_bits(stg, lane, o); else OutStage<OUT>::stage(stg, lane, o);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    OutStage<OUT>::flush(stg, lane, a.dst, (size_t)base);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+template <>
+__global__ __launch_bounds__(1024) void k_raster_chain<Rgbe32, 1>(FusedArgs a, uint64_t npix, const LutPair *__restrict__, const FusedArgs *__restrict__ frames) {
+  if (IPK_RARE(frames != nullptr)) rgbe_chain_body<1>(frames[blockIdx.y], npix); else rgbe_chain_body<1>(a, npix);
+}
+template <>
+__global__ __launch_bounds__(1024) void k_raster_chain<Rgbe32, 2>(FusedArgs a, uint64_t npix, const LutPair *__restrict__, const FusedArgs *__restrict__ frames) {
+  if (IPK_RARE(frames != nullptr)) rgbe_chain_body<2>(frames[blockIdx.y], npix); else rgbe_chain_body<2>(a, npix);
+}
 // the log tag of a k_raster_chain<uint8_t | uint16_t> launch: fast_ok alone, as ever, on launches that use neither mode (the log keeps the pointer: literals only)
 static const char *raster_tag(const FusedArgs &a) {
   static const char *const tags[2][2][3] = {
@@ -3647,9 +3704,9 @@ template <typename SrcT>
 static void launch_raster_t(const FusedArgs &a, size_t npix, int out_type, const void *gamma_reverse, unsigned blocks, hipStream_t s) {
   const LutPair *gr = reinterpret_cast<const LutPair *>(gamma_reverse);
   const char *tag = raster_tag(a);
-  if (out_type == 0) IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 0>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
-  else if (out_type == 1) IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
-  else IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr);
+  if (out_type == 0) IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 0>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr, (const FusedArgs *)nullptr);
+  else if (out_type == 1) IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr, (const FusedArgs *)nullptr);
+  else IPK_LAUNCH_TAG(tag, (k_raster_chain<SrcT, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, gr, (const FusedArgs *)nullptr);
 }
 // OpToLab..OpGamma + output8bit / output16bit over a 4-channel f32 OpBuffer in one pass (f.out_type 1 or 2; npix >= 256)
 int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s, const GatherSource *gather) {
@@ -3660,9 +3717,31 @@ int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s, con
   const size_t chunks = (npix + 255) / 256;
   const unsigned cap = (unsigned)(f.num_cus > 0 ? f.num_cus : 256);
   const unsigned blocks = std::max(1u, (unsigned)std::min<size_t>(cap, (chunks + 15) / 16));
-  if (f.out_type == 1) IPK_LAUNCH_TAG(chain_tag(a), (k_raster_chain<Rgbe32, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
-  else IPK_LAUNCH_TAG(chain_tag(a), (k_raster_chain<Rgbe32, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr);
+  if (f.out_type == 1) IPK_LAUNCH_TAG(chain_tag(a), (k_raster_chain<Rgbe32, 1>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr, (const FusedArgs *)nullptr);
+  else IPK_LAUNCH_TAG(chain_tag(a), (k_raster_chain<Rgbe32, 2>), dim3(blocks), dim3(1024), 0, s, a, (uint64_t)npix, (const LutPair *)nullptr, (const FusedArgs *)nullptr);
   return 0;
+}
+// The frame-table launch of the chain (ipk_launch.hpp): frames[i]'s arguments as chain_args makes them for a single launch, uploaded stream-ordered into
+// table_dev, then ONE launch with a grid plane per frame
+size_t chain_batch_table_bytes(size_t n) { return n * sizeof(FusedArgs); }
+int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s) {
+  if (n == 0 || n > kChainBatchMax || npix == 0 || out_type < 0 || out_type > 2 || (out_type != 0 && npix < 256) || !table_dev) return -1;
+  std::vector<FusedArgs> table(n);
+  bool fast_all = true;
+  for (size_t i = 0; i < n; ++i) {
+    table[i] = chain_args(frames[i]);
+    table[i].gam_q8 = reinterpret_cast<const Q8Entry *>(frames[i].gam_q8);
+    fast_all = fast_all && frames[i].fast_ok;
+  }
+  if (hipMemcpyAsync(table_dev, table.data(), n * sizeof(FusedArgs), hipMemcpyHostToDevice, s) != hipSuccess) return -4;   // (pageable: consumed before it returns)
+  const unsigned cus = (unsigned)(frames[0].num_cus > 0 ? frames[0].num_cus : 256);
+  const dim3 grid(chain_batch_blocks(npix, out_type, n, cus), (unsigned)n);
+  const char *tag = fast_all ? "fast_ok=1,batch=1" : "fast_ok=0,batch=1";
+  const FusedArgs *dev = static_cast<const FusedArgs *>(table_dev);
+  if (out_type == 0) IPK_LAUNCH_TAG(tag, k_pointwise_chain_small, grid, dim3(1024), 0, s, table[0], (uint64_t)npix, dev);
+  else if (out_type == 1) IPK_LAUNCH_TAG(tag, (k_raster_chain<Rgbe32, 1>), grid, dim3(1024), 0, s, table[0], (uint64_t)npix, (const LutPair *)nullptr, dev);
+  else IPK_LAUNCH_TAG(tag, (k_raster_chain<Rgbe32, 2>), grid, dim3(1024), 0, s, table[0], (uint64_t)npix, (const LutPair *)nullptr, dev);
+  return launch_status();
 }
 int launch_raster_chain(const FusedLaunch &f, size_t npix, int src_is_u16, const void *gamma_reverse_pairs, hipStream_t s, const PlainSource *plain) {
   if (npix < 256) return -1;

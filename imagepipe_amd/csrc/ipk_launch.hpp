@@ -2,6 +2,7 @@
 // Plain C++ declarations so the C-ABI layer (ipk_api.cpp) never sees device code.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include "ipk_host.hpp"
@@ -48,7 +49,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // batch=1 behind all of it: [...,xcd=0,batch=1] / [...,xcd=0,plain=1,batch=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form); the gather
 // launches of k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2> (a GatherSource: ipk_pipeline_run_cached_region) append
-// gather=1: [fast_ok=,gather=1] -- flat launches never carry the key;
+// gather=1: [fast_ok=,gather=1] -- flat launches never carry the key; the frame-table launches of k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2>
+// (launch_chain_batch: ipk_pointwise_chain_out_batch) carry [fast_ok=,batch=1], fast_ok the AND over the launch's frames;
 // k_raster_chain's launches by ipk_plain_to_srgb append rect=1 in rectangle mode (a rectangle narrower than the source's pitch) and levels=1 / levels=2
 // in the three-sample / monochrome raw sample modes, in that order: [fast_ok=,rect=1], [fast_ok=,levels=2], [fast_ok=,rect=1,levels=1] -- launches
 // that use neither mode (ipk_raster_to_srgb, ipk_pointwise_chain_out, a full-width raster rectangle) carry [fast_ok=] and nothing else;
@@ -187,6 +189,23 @@ int launch_pointwise_chain(const FusedLaunch &f, size_t npix, hipStream_t s, con
 int launch_tolab_fast(const FusedLaunch &f, size_t npix, hipStream_t s);   // OpToLab alone on the chain's fast form
 // OpToLab..OpGamma + output8bit / output16bit in one pass over a 4-channel f32 buffer (f.out_type 1 / 2, f.gam_q8 set; npix >= 256): -1 otherwise
 int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s, const GatherSource *gather = nullptr);
+// The frame-table mode of the same launches (k_pointwise_chain_small for out_type 0 whatever the frame size, k_raster_chain<Rgbe32, 1 | 2> for 1 / 2):
+// n <= kChainBatchMax buffers of npix pixels each, frame i with the src, dst, multipliers, matrix, curve, has_curve and fast_ok of frames[i] (a host array,
+// read before the call returns; linear, rgbm9 and the tables must be the same in all of them).  The launcher writes one argument record per frame into
+// table_dev -- chain_batch_table_bytes(n) bytes of device memory the caller keeps alive until the launch has run (the context's scratch pool) -- with a
+// stream-ordered copy in front of the launch; the grid's y plane is the frame and chain_batch_blocks(...) blocks walk each frame, which reads its record
+// instead of the kernel's arguments and is otherwise the single launch of that frame: bit-identical, the tail handling on the frame's own npix.  The log
+// tags such launches [fast_ok=,batch=1]: fast_ok=1 when every frame's record allows the fast form, 0 when at least one frame takes the literal form
+// throughout.  out_type 1 / 2 need npix >= 256.  -1 (nothing enqueued) outside these bounds, -4 when the copy or the launch could not be enqueued
+constexpr size_t kChainBatchMax = 64;
+size_t chain_batch_table_bytes(size_t n);
+// blocks per frame: what a single launch of the frame gets (sixteen wave-chunks of 128 / 256 pixels per block), capped so that the launch's n planes
+// together come to about one block per CU
+inline unsigned chain_batch_blocks(size_t npix, int out_type, size_t n, unsigned cus) {
+  const size_t chunks = out_type == 0 ? (npix + 127) / 128 : (npix + 255) / 256;
+  return (unsigned)std::max<size_t>(1, std::min<size_t>((chunks + 15) / 16, (cus + n - 1) / n));
+}
+int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s);
 // run_other + OpToLab..OpGamma + quantisation in one pass over an RGB8 / RGB16 raster (npix >= 256; f.out_type selects the output)
 // plain (optional; ipk_plain_to_srgb): the launch covers a width-pixel-wide rectangle of npix pixels whose first sample is f.src, inside an image whose rows
 // are owidth pixels apart, and f.dst holds its npix * 3 packed samples.  levels: 0 the raster's samples; 1 a three-sample u16 raw, each channel

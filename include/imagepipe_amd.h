@@ -479,6 +479,27 @@ IPK_API int ipk_pointwise_chain(const float *src4, size_t width, size_t height, 
 IPK_API int ipk_pointwise_chain_out(const float *src4, size_t width, size_t height, int monochrome, const float *wb_coeffs,
                                     const float *cam_to_xyz_normalized, float exposure, const float *points, int npoints, int linear,
                                     int out_type, void *dst, void *stream);
+/* the fields of a descriptor OpToLab and OpBaseCurve read (src/ops/colorspaces.rs:89-112, src/ops/curves.rs:33-49): what may differ between the frames of
+ * one launch.  struct_size = sizeof(ipk_chain_params) (any other value is IPK_ERR_INVALID) */
+typedef struct { uint32_t struct_size; float wb_coeffs[4]; float cam_to_xyz_normalized[12];
+                 float exposure; int npoints; float points[128]; } ipk_chain_params;
+/* ipk_pointwise_chain_out for n same-sized 4-channel buffers, each with its own parameters and its own destination: frame i is bit-identical to
+ * ipk_pointwise_chain_out(srcs4[i], width, height, monochrome, params[i]..., linear, out_type, dsts[i], stream), and nothing else is written.  One launch
+ * per 64 frames (the call loops for larger n): a launch-uniform mode of the single form's kernels -- k_pointwise_chain_small for IPK_OUT_F32 at every frame
+ * size (frames are the parallelism), k_raster_chain<Rgbe32, 1 | 2> for IPK_OUT_U8 / IPK_OUT_U16 -- in which a grid plane is a frame and the block reads
+ * its frame's source, destination, multipliers, matrix, curve, has_curve and fast_ok from a table in device memory instead of from the kernel's
+ * arguments; linear and the lookup tables stay launch-wide, the tail handling is each frame's own.  Every params[i] goes through the single form's host
+ * preparation (normalize_wbs, the spline, has_curve, fast_ok: all per frame) BEFORE anything is enqueued: an invalid or degenerate curve, a null
+ * srcs4[i] / dsts[i] or a misaligned pointer fails the whole call with IPK_ERR_INVALID, names the index in ipk_last_error and writes nothing.
+ * IPK_OUT_U8 / IPK_OUT_U16 need at least 256 pixels PER FRAME (IPK_ERR_UNSUPPORTED below that, like the single form); IPK_OUT_F32 takes any size >= 1.
+ * srcs4[i] needs 16-byte alignment, dsts[i] only its element's.  n = 0 is IPK_OK.  The host arrays are read before the call returns.  The table lives in
+ * the context's scratch pool and is uploaded with a stream-ordered copy from pageable host memory in front of each launch: the host may wait there for
+ * the stream's earlier work, and the call cannot be captured into a graph.  monochrome = 1: params' wb_coeffs and matrix are not read, as in the single
+ * form.  ipk_timing names each launch "pointwise_chain_out_batch".  params points to n ipk_chain_params; it is declared const void * because the type
+ * table the generated Rust binding is checked against (tests/test_rust_binding.py) is closed: the C++ mirror takes the typed pointer. */
+IPK_API int ipk_pointwise_chain_out_batch(const float *const *srcs4, size_t width, size_t height, int monochrome,
+                                          const void *params /* n ipk_chain_params */, size_t n, int linear,
+                                          int out_type, void *const *dsts, void *stream);
 /* The raster-source counterpart of ipk_raw_to_srgb: OpGoFloat::run_other (src/ops/gofloat.rs:171-201; RGB8 through
  * expand_srgb_gamma(input8bit(v)), RGB16 through input16bit(v)) + OpToLab + OpBaseCurve + OpFromLab + OpGamma (+ output8bit /
  * output16bit, src/pipeline.rs:408-414,455-461) in one pass from the width*height*3 source samples to width*height*3 outputs of
@@ -805,6 +826,53 @@ IPK_API int ipk_pipeline_batches_previews(const ipk_pipeline_desc *d, int out_ty
 IPK_API int ipk_pipeline_run_batch_multi(const ipk_pipeline_desc *d, const void *const *srcs, void *const *dsts, size_t n, int out_type,
                                          int *used_fused);
 IPK_API int ipk_devices_sync(void);
+/* n DEVICE frames, n descriptors: a shoot whose files carry their own colour settings (Pipeline::new_from_file per file, each Pipeline with its own ops,
+ * src/pipeline.rs:246-284).  The results are bit for bit what ipk_pipeline_run(descs[i], srcs[i], dsts[i], ...) gives, called for i = 0 .. n - 1 in that
+ * order on `stream`, and *used_fused (may be NULL) holds what the last frame's run leaves.  Every descriptor is validated as ipk_pipeline_run validates it
+ * (and its curve is built) BEFORE anything is enqueued: an invalid descriptor or a null srcs[i] / dsts[i] fails with IPK_ERR_INVALID, names the index in
+ * ipk_last_error and writes nothing.  n = 0 is IPK_OK.  The host arrays are read before the call returns.
+ * The plan, which ipk_pipeline_batch_each_plan reports without a GPU (route[i], run_first[i]; either may be NULL): two descriptors are SAME-SHAPED when
+ * every field is equal except wb_coeffs, cam_to_xyz_normalized, exposure, npoints and points -- field by field, cfa as a string after the drivers' usual
+ * folding, floats by their bits, padding not at all; struct_size, allow_fused, linear, schedule and the fuse flags count as shape.  One thing the five
+ * fields themselves decide counts as shape too: ipk_pipeline_takes_fastpath (the raster fast path is taken for the DEFAULT ops only), so a raster with
+ * default ops and an edited one are never same-shaped under IPK_OUT_U8 / IPK_OUT_U16, and every frame of a run is on the route ipk_pipeline_run would
+ * choose for it.  The frames are cut, in order, into maximal runs of consecutive same-shaped descriptors; run_first[i] is the first frame of frame
+ * i's run.  For a run of m frames:
+ *   route 2, varied previews: m > 1, ipk_pipeline_batches_previews(descs[run_first], out_type, m, ...) answers 1 (so allow_fused needs IPK_FUSED_ON |
+ *     IPK_FUSED_BATCH_PREVIEWS: no new bit) and the descriptors are not all equal in the five fields.  Chunks follow that report's chunk; pass 1 is the
+ *     uniform route's pass 1 -- one set of levels, crops and filter per chunk -- and pass 2 is ONE ipk_pointwise_chain_out_batch launch per chunk: source i
+ *     the scratch's slice i, parameters descriptor i's, destination dsts[i] wherever it lies (scattered destinations cost nothing here).  A final chunk
+ *     of one frame is ipk_pipeline_run.  ipk_timing names the stages "batch gofloat+demosaic" and "batch-each to_lab+basecurve+from_lab+gamma+quantise"
+ *     (without "+quantise" for f32);
+ *   route 1, uniform: otherwise, inside the run, maximal sub-runs of two or more consecutive descriptors that are equal in the five fields as well go
+ *     to ipk_pipeline_run_batch -- a run on the varied route's ground whose five fields happen to be all equal included -- which keeps the persistent
+ *     full-size launch and the uniform preview batch for callers who happen to have them;
+ *   route 0, single: every other frame, through ipk_pipeline_run.
+ * Out of scope: per-frame settings inside the persistent full-size launch ipk_raw_to_srgb_batch (one parameter set; full-size frames with varied
+ * settings are route 0 each); per-frame levels, crops or filters inside one scaling launch (they cut the run); non-Normal orientations and active
+ * rotatecrops inside a varied run (ipk_pipeline_batches_previews answers 0: frame by frame, or route 1 where identical); the host-buffer batch drivers;
+ * the multi-device driver (it may follow by calling this one member by member); band forms; the bit as a default; graph capture (the table upload of
+ * ipk_pointwise_chain_out_batch is a copy from pageable host memory).
+ * Measured (profiles/r20_batch_each.txt; device-resident noise frames to u8, every frame with its own wb_coeffs and exposure, wall clock, medians, ms per
+ * frame; the parent build's only offer -- a loop of ipk_pipeline_run, two launches per frame -- -> this call with the bit set | this build's uniform
+ * ipk_pipeline_run_batch on one descriptor; the parent's spread is 0.0003 .. 0.0034 ms throughout): 24 MP RGGB u16 -> 256 wide, n = 2 / 8 / 16 / 64:
+ * 0.212 -> 0.116 | 0.114, 0.220 -> 0.055 | 0.053, 0.219 -> 0.066 | 0.064, 0.218 -> 0.053 | 0.052; -> 400 wide: 0.124 -> 0.085 | 0.083, 0.124 -> 0.065 |
+ * 0.063, 0.123 -> 0.060 | 0.058, 0.122 -> 0.056 | 0.055; 50 MP X-Trans u16 -> 270 wide: 0.378 -> 0.227 | 0.225, 0.391 -> 0.174 | 0.172, 0.390 -> 0.155 |
+ * 0.153, 0.389 -> 0.144 | 0.144; 24 MP mono u16 -> 256 wide: 0.143 -> 0.080 | 0.078, 0.154 -> 0.050 | 0.049, 0.153 -> 0.062 | 0.061, 0.153 -> 0.052 |
+ * 0.051.  No measured case at n >= 8 was slower than the parent's loop; none is excluded.  The distance to the uniform batch (the table upload and the
+ * per-frame staging) is +0.001 .. +0.003 ms per frame at n <= 16 and within 0.0005 ms at n = 64.  With the bit clear the call is the parent's loop plus
+ * the plan, and that shows: up to 0.0018 ms per frame above the parent's loop (0.1248 against 0.1230 at n = 16, 400 wide), OUTSIDE the parent's spread in
+ * several readings (400 wide: +0.0017 at n = 8 against a spread of 0.0012, +0.0018 at n = 16 against 0.0008, +0.0015 at n = 64 against 0.0003; 256
+ * wide: +0.0015 at n = 16 against 0.0006, +0.0012 at n = 64 against 0.0005; mono: +0.0007 at n = 64 against 0.0003).  A caller without the bit loses that much against its own loop.  The carriers' launches outside the mode stayed inside the
+ * parent's spread: ipk_pointwise_chain_out at 2160x1440 to f32 0.0400 -> 0.0398 ms, to u8 0.0397 -> 0.0389; at 6000x4000 to f32 0.2013 -> 0.1970, to u8
+ * 0.1777 -> 0.1807 (spread 0.0041); the cached-region gather launch over 1/16 of a 24 MP frame to u8 0.0447 -> 0.0446.  Not measured: f32 sources, f32
+ * and 16-bit outputs, scattered destinations, per-frame matrices and curves, batches above 64 frames, rasters and the window-8 geometries, mixed
+ * batches, photo-like data. */
+IPK_API int ipk_pipeline_run_batch_each(const ipk_pipeline_desc *const *descs, const void *const *srcs, void *const *dsts,
+                                        size_t n, int out_type, int *used_fused, void *stream);
+/* host-only, no GPU: the plan the call above follows.  IPK_ERR_INVALID for a null or invalid descriptor (the index is named in ipk_last_error) */
+IPK_API int ipk_pipeline_batch_each_plan(const ipk_pipeline_desc *const *descs, size_t n, int out_type,
+                                         int *route /* n */, size_t *run_first /* n */);
 /* HOST frames in, HOST results out, over the device set: the drop-in for a caller looping Pipeline::run / output_8bit over a shoot on a
  * multi-GPU node.  One host thread per member runs ipk_host_pipeline_run_batch on the frames dealt to it (frame i -> member i mod N), so all
  * GPUs upload, compute and download concurrently; the caller's Vecs are the "gather".  Synchronous at return; results are what n calls of

@@ -445,6 +445,42 @@ class Pipeline {
   }
   // would a region from the cache be resampled straight from the cached demosaic buffer (ipk_pipeline_resamples_cached_region)?
   bool resamples_cached_region(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_resamples_cached_region(&d, out_type) == 1; }
+  // A shoot whose files carry their own colour settings: one Pipeline per frame, raws[i] shaped like pipes[i]'s own source (ipk_pipeline_run_batch_each).
+  // ONE device allocation, the results of out_type one after another in frame order; offsets (optional) receives each result's byte offset.  Frames that
+  // differ only in white balance, matrix, exposure and curve run as batched previews where batch_each_plan() says 2 (batch_previews on every member)
+  static DeviceArray run_batch_each(const std::vector<const Pipeline *> &pipes, const std::vector<const void *> &raws, int out_type = IPK_OUT_F32,
+                                    std::vector<size_t> *offsets = nullptr) {
+    if (pipes.size() != raws.size()) throw Error("run_batch_each: as many pipelines as frames");
+    std::vector<ipk_pipeline_desc> ds(pipes.size());
+    std::vector<const ipk_pipeline_desc *> dp(pipes.size());
+    std::vector<size_t> off(pipes.size());
+    const size_t esz = out_type == IPK_OUT_F32 ? 4 : out_type == IPK_OUT_U8 ? 1 : 2;
+    size_t total = 0;
+    for (size_t i = 0; i < pipes.size(); ++i) {
+      ds[i] = pipes[i]->desc(); dp[i] = &ds[i];
+      size_t fw, fh; std::tie(fw, fh) = pipes[i]->final_size();
+      off[i] = total; total += (fw * fh * 3 * esz + 15) / 16 * 16;
+    }
+    DeviceArray o(std::max<size_t>(total, 1));
+    std::vector<void *> outs(pipes.size());
+    for (size_t i = 0; i < pipes.size(); ++i) outs[i] = static_cast<char *>(o.get()) + off[i];
+    check(ipk_pipeline_run_batch_each(dp.data(), raws.data(), outs.data(), pipes.size(), out_type, nullptr, nullptr), "pipeline_run_batch_each");
+    check(ipk_stream_sync(nullptr), "sync");
+    if (offsets) *offsets = off;
+    return o;
+  }
+  // the plan run_batch_each follows (ipk_pipeline_batch_each_plan; no GPU needed): per frame (route, first frame of its run); route 0 single, 1 uniform, 2 varied
+  static std::vector<std::pair<int, size_t>> batch_each_plan(const std::vector<const Pipeline *> &pipes, int out_type = IPK_OUT_F32) {
+    std::vector<ipk_pipeline_desc> ds(pipes.size());
+    std::vector<const ipk_pipeline_desc *> dp(pipes.size());
+    for (size_t i = 0; i < pipes.size(); ++i) { ds[i] = pipes[i]->desc(); dp[i] = &ds[i]; }
+    std::vector<int> route(pipes.size()); std::vector<size_t> first(pipes.size());
+    check(ipk_pipeline_batch_each_plan(dp.data(), pipes.size(), out_type, route.data(), first.data()), "pipeline_batch_each_plan");
+    std::vector<std::pair<int, size_t>> plan(pipes.size());
+    for (size_t i = 0; i < pipes.size(); ++i) plan[i] = {route[i], first[i]};
+    return plan;
+  }
+
  private:
   explicit Pipeline(ImageSource img) : globals{std::move(img), PipelineSettings()}, ops(globals.image) {}
   std::pair<size_t, size_t> final_size() const {
@@ -457,6 +493,17 @@ class Pipeline {
     last_used_fused = fused != 0;
   }
 };
+
+// ipk_pointwise_chain_out_batch on the typed parameter array: tolab..gamma (+ quantisation) over srcs4.size() same-sized 4-channel device buffers, frame i
+// with params[i] into dsts[i]; one launch per 64 frames
+inline ipk_chain_params chain_params() { ipk_chain_params p{}; p.struct_size = (uint32_t)sizeof(p); return p; }
+inline void pointwise_chain_out_batch(const std::vector<const float *> &srcs4, size_t width, size_t height, bool monochrome,
+                                      const std::vector<ipk_chain_params> &params, bool linear, int out_type, const std::vector<void *> &dsts, void *stream = nullptr) {
+  if (params.size() != srcs4.size() || dsts.size() != srcs4.size()) throw Error("pointwise_chain_out_batch: as many parameter sets and destinations as frames");
+  const ipk_chain_params *p = params.data();
+  check(ipk_pointwise_chain_out_batch(srcs4.data(), width, height, monochrome ? 1 : 0, p, srcs4.size(), linear ? 1 : 0, out_type, dsts.data(), stream),
+        "pointwise_chain_out_batch");
+}
 
 // ---- several devices from ONE process (imagepipe_amd.h, "Several devices from ONE process") --------------------------------------------------
 // The reference is one process whose callers loop Pipeline::run over the frames of a shoot (src/lib.rs:21-26, src/pipeline.rs:246-249).
