@@ -17,14 +17,14 @@ import torch
 from . import _lib
 from ._lib import (IpkError, FusedParams, PipelineDesc, ChainParams, OUT_F32, OUT_U8, OUT_U16, SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16,
                    OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN,
-                   ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO, FUSED_BATCH_PREVIEWS)
+                   ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO, FUSED_BATCH_PREVIEWS, FUSED_BATCH_ORIENTED)
 
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
            "OpTransform", "raw_to_srgb", "raw_to_srgb_resampled", "raw_to_srgb_scaled", "raw_to_srgb_resampled_window", "raw_to_srgb_scaled_window",
            "transform_window_footprint", "raw_scaled_demosaic_window", "raw_demosaic_scaled", "raster_scale_down_window", "scaled_window_footprint", "plain_scale_down",
            "plain_scale_down_window", "raw_scaled_demosaic_batch", "plain_scale_down_batch", "chain_params", "pointwise_chain_out_batch",
-           "batch_each_plan", "run_batch_each", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FUSED_BATCH_PREVIEWS",
+           "batch_each_plan", "run_batch_each", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FUSED_BATCH_PREVIEWS", "FUSED_BATCH_ORIENTED",
            "FusedPlan", "IpkError"]
 
 _initialized_device = None
@@ -612,6 +612,7 @@ class Pipeline:
         self.fuse_scaled_rotatecrop = False   # ipk_pipeline_desc.allow_fused bit 6 (IPK_FUSED_SCALED_ROTATECROP): an active OpRotateCrop behind a scaling OpDemosaic as two launches where fuses_scaled_rotatecrop() says so; regions of such frames windowed
         self.scale_plain = False              # ipk_pipeline_desc.allow_fused bit 7 (IPK_FUSED_PLAIN_PREVIEWS): downscaled previews of monochrome / three-sample raws (u16, f32) run gofloat + demosaic as the one launch ipk_plain_scale_down where scales_plain() says so; window_previews and fuse_scaled_rotatecrop then take them too
         self.batch_previews = False           # ipk_pipeline_desc.allow_fused bit 8 (IPK_FUSED_BATCH_PREVIEWS): run_batch() runs downscaled previews as one scaling launch group and one point-wise pass per chunk of frames where batches_previews() says so
+        self.batch_oriented = False           # ipk_pipeline_desc.allow_fused bit 9 (IPK_FUSED_BATCH_ORIENTED), set only together with batch_previews: batched previews take frames of any orientation (OpTransform folded into the point-wise pass), and run_batch_each lets rotation / fliph / flipv differ inside a run
         self.window_previews = False          # ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
 
     @staticmethod
@@ -689,6 +690,8 @@ class Pipeline:
             d.allow_fused |= _lib.FUSED_PLAIN_PREVIEWS
         if self.batch_previews and d.allow_fused:
             d.allow_fused |= _lib.FUSED_BATCH_PREVIEWS
+            if self.batch_oriented:
+                d.allow_fused |= _lib.FUSED_BATCH_ORIENTED
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -1137,20 +1140,29 @@ def chain_params(wb_coeffs=(1.0, 1.0, 1.0, 0.0), cam_to_xyz_normalized=None, exp
 
 
 def pointwise_chain_out_batch(srcs4: Sequence[torch.Tensor], width, height, params, *, monochrome=False, linear=False, out_type=OUT_F32,
-                              outs: Optional[Sequence[torch.Tensor]] = None):
+                              outs: Optional[Sequence[torch.Tensor]] = None, orientations: Optional[Sequence[int]] = None):
     """ipk_pointwise_chain_out_batch: tolab..gamma (+ quantisation) over len(srcs4) 4-channel f32 device buffers of width x height pixels, frame i with
     params[i] (chain_params()) into outs[i] -- given, or views of ONE fresh allocation.  One launch per 64 frames; frame i is bit-identical to the
-    single-frame call.  Returns the list of output tensors (u16 bits in int16)."""
+    single-frame call.  orientations (optional, one ipk_orientation value per frame): ipk_pointwise_chain_out_batch_oriented -- frame i leaves as
+    OpTransform's image under orientations[i], the permutation folded into the launch's loads; fresh outputs are then (width, height, 3) for the four
+    transposing orientations.  Returns the list of output tensors (u16 bits in int16)."""
     n = len(srcs4)
-    if len(params) != n:
-        raise ValueError("pointwise_chain_out_batch: as many parameter sets as frames")
+    if len(params) != n or (orientations is not None and len(orientations) != n):
+        raise ValueError("pointwise_chain_out_batch: as many parameter sets (and orientations) as frames")
     dt = {OUT_F32: torch.float32, OUT_U8: torch.uint8, OUT_U16: torch.int16}[out_type]
     if outs is None:
         whole = torch.empty((max(n, 1), height, width, 3), dtype=dt, device="cuda")
         outs = [whole[i] for i in range(n)]
+        if orientations is not None:
+            outs = [o.view(width, height, 3) if 4 <= int(r) <= 7 else o for o, r in zip(outs, orientations)]
     if len(outs) != n or any(o.dtype != dt or o.numel() != height * width * 3 or not o.is_contiguous() for o in outs):
         raise ValueError("pointwise_chain_out_batch: outs must be %d contiguous %s tensors of %d x %d x 3 elements" % (n, dt, height, width))
     arr = (ChainParams * max(n, 1))(*params)
+    if orientations is not None:
+        ori = (C.c_int * max(n, 1))(*[int(r) for r in orientations])
+        _lib.check(lib().ipk_pointwise_chain_out_batch_oriented(_frame_ptrs(srcs4), width, height, int(bool(monochrome)), arr, ori, n, int(bool(linear)),
+                                                                out_type, _frame_ptrs(outs), _stream()), "ipk_pointwise_chain_out_batch_oriented")
+        return list(outs)
     _lib.check(lib().ipk_pointwise_chain_out_batch(_frame_ptrs(srcs4), width, height, int(bool(monochrome)), arr, n, int(bool(linear)), out_type,
                                                    _frame_ptrs(outs), _stream()), "ipk_pointwise_chain_out_batch")
     return list(outs)
@@ -1175,8 +1187,8 @@ def batch_each_plan(pipes, out_type=OUT_F32):
 def run_batch_each(pipes, srcs: Sequence[torch.Tensor], out_type=OUT_F32, outs: Optional[Sequence[torch.Tensor]] = None):
     """A shoot whose files carry their own colour settings (ipk_pipeline_run_batch_each): one Pipeline per frame -- each with its own white balance,
     matrix, exposure and curve -- and srcs[i] shaped like pipes[i]'s own source.  Results are what pipes[i].run() / output_8bit() / output_16bit() give
-    frame by frame; frames that differ only in those point-wise settings run as batched previews where batch_each_plan() says 2 (batch_previews set on
-    every member).  Returns the list of (h, w, 3) device tensors of the output type (u16 bits in int16) -- `outs` when given, else fresh ones -- and sets
+    frame by frame; frames that differ only in those point-wise settings -- and, with batch_oriented set on every member as well, in rotation, fliph
+    and flipv -- run as batched previews where batch_each_plan() says 2 (batch_previews set on every member).  Returns the list of (h, w, 3) device tensors of the output type (u16 bits in int16) -- `outs` when given, else fresh ones -- and sets
     every member's last_used_fused to what the last frame's run leaves."""
     n = len(pipes)
     if len(srcs) != n:

@@ -17,6 +17,7 @@ FUSED_ON, FUSED_FOUR_COLOUR, FUSED_WINDOW_REGIONS, FUSED_WINDOW_PREVIEWS, FUSED_
 FUSED_SCALED_ROTATECROP = 64
 FUSED_PLAIN_PREVIEWS = 128
 FUSED_BATCH_PREVIEWS = 256
+FUSED_BATCH_ORIENTED = 512
 PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO = 0, 1, 2                                                          # ipk_plain_kind
 OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN = range(9)
 ROT_NORMAL, ROT_90, ROT_180, ROT_270 = range(4)
@@ -181,6 +182,8 @@ SIGNATURES = {
     "ipk_pipeline_run_batch_each": (C.c_int, [C.POINTER(C.POINTER(PipelineDesc)), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int), _vp]),
     "ipk_pipeline_batch_each_plan": (C.c_int, [C.POINTER(C.POINTER(PipelineDesc)), _sz, C.c_int, C.POINTER(C.c_int), _szp]),
     "ipk_pointwise_chain_out_batch": (C.c_int, [C.POINTER(_vp), _sz, _sz, C.c_int, C.POINTER(ChainParams), _sz, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
+    "ipk_pointwise_chain_out_batch_oriented": (C.c_int, [C.POINTER(_vp), _sz, _sz, C.c_int, C.POINTER(ChainParams), C.POINTER(C.c_int), _sz, C.c_int, C.c_int,
+                                                         C.POINTER(_vp), _vp]),
     "ipk_pipeline_run_batch_multi": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int)]),
     "ipk_host_pipeline_run_batch_multi": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int)]),
     "ipk_devices_sync": (C.c_int, []),

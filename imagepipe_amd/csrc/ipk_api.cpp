@@ -2464,6 +2464,23 @@ int plan_region(const ipk_pipeline_desc *d, int out_type, size_t x, size_t y, si
 // ops produce is held against n.fw x n.fh), not the forward fold's
 // win: the unrotated rectangle of the buffer the region comes from; transposed: the orientation swaps rows and columns (g.x_step is then +-bw)
 struct RegionGather { size_t bw, bh; ipk::GatherSource g; ipk::ResampleWindow win; bool transposed; };
+// the walk itself: the w-wide region behind rectangle win of a buffer bw pixels wide, under the flips of the orientation.  The region's pixel (0, 0) is
+// the window's corner the flips name; a step along u moves one column, along v one row of the buffer
+ipk::GatherSource gather_walk(size_t bw, const ipk::ResampleWindow &win, bool t, bool fx, bool fy, size_t w) {
+  const int64_t W = (int64_t)bw, du = fx ? -1 : 1, dv = fy ? -W : W;
+  const int64_t col = (int64_t)(fx ? win.col0 + win.cols - 1 : win.col0), row = (int64_t)(fy ? win.row0 + win.rows - 1 : win.row0);
+  ipk::GatherSource g;
+  g.base = row * W + col;
+  g.x_step = t ? dv : du; g.y_step = t ? du : dv;
+  g.width = w;
+  return g;
+}
+// the whole-frame case: a bw x bh buffer read as its orientation's image (bh wide where the orientation transposes), every index inside the buffer
+ipk::GatherSource frame_gather(size_t bw, size_t bh, int orientation) {
+  bool t, fx, fy; ipk::orientation_to_flips(orientation, t, fx, fy);
+  ipk::ResampleWindow win; win.row0 = 0; win.col0 = 0; win.rows = bh; win.cols = bw;
+  return gather_walk(bw, win, t, fx, fy, t ? bh : bw);
+}
 int region_gather(const Negotiated &n, size_t x, size_t y, size_t w, size_t h, RegionGather &rg) {
   bool t = false, fx = false, fy = false;
   if (!n.transform_noop) ipk::orientation_to_flips(n.orientation, t, fx, fy);
@@ -2471,12 +2488,8 @@ int region_gather(const Negotiated &n, size_t x, size_t y, size_t w, size_t h, R
   ipk::ResampleWindow &win = rg.win;
   const int rc = region_window(n, rg.bw, rg.bh, x, y, w, h, win, t, fx, fy); if (rc) return rc;
   rg.transposed = t;
-  // the region's pixel (0, 0) is the window's corner the flips name; a step along u moves one column, along v one row of the buffer
-  const int64_t W = (int64_t)rg.bw, du = fx ? -1 : 1, dv = fy ? -W : W;
-  const int64_t col = (int64_t)(fx ? win.col0 + win.cols - 1 : win.col0), row = (int64_t)(fy ? win.row0 + win.rows - 1 : win.row0);
-  rg.g.base = row * W + col;
-  rg.g.x_step = t ? dv : du; rg.g.y_step = t ? du : dv;
-  rg.g.width = w;
+  rg.g = gather_walk(rg.bw, win, t, fx, fy, w);
+  const int64_t W = (int64_t)rg.bw;
   const int64_t far = rg.g.base + (int64_t)(w - 1) * rg.g.x_step + (int64_t)(h - 1) * rg.g.y_step, cnt = W * (int64_t)rg.bh;
   const int64_t cx1 = rg.g.base + (int64_t)(w - 1) * rg.g.x_step, cy1 = rg.g.base + (int64_t)(h - 1) * rg.g.y_step;
   for (int64_t c : {rg.g.base, far, cx1, cy1}) if (c < 0 || c >= cnt) return fail(IPK_ERR_INVALID, "internal: the region's gather leaves the %zux%zu buffer", rg.bw, rg.bh);
@@ -2963,15 +2976,19 @@ void HostLanes::release() {
 // ------------------------------------------------------------------------------------------
 namespace {
 // IPK_FUSED_BATCH_PREVIEWS: a batch of staged frames whose gofloat + demosaic is the one scaling pass (gofloat_demosaic_one_pass) and whose every later op
-// is point-wise (OpRotateCrop and OpTransform no-ops) runs chunk by chunk as one scaling launch group into one RGBE scratch, then the chain over the
+// is point-wise (OpRotateCrop a no-op; OpTransform too, or a permutation under IPK_FUSED_BATCH_ORIENTED) runs chunk by chunk as one scaling launch group into one RGBE scratch, then the chain over the
 // previews lying one after another.  dw * dh >= 256 is the one-pass chain's own floor, kept per frame: the batch uses the kernels a single frame would.
 // chunk: frames per scratch (at most 64, at most 256 MiB of RGBE); pass1_batched: pass 1 is the general scaling kernel's batch launch (the scratch slices
 // are 16-byte aligned), else one launch per frame of the kernel the frame selects
 struct BatchPreviews { size_t chunk; bool pass1_batched; };
 bool batches_previews(const ipk_pipeline_desc *d, const Negotiated &n, const Route &rt, size_t frames, BatchPreviews &bp) {
   bp.chunk = 0; bp.pass1_batched = false;
-  if (!opted(d, IPK_FUSED_BATCH_PREVIEWS) || frames <= 1 || rt.kind != kStaged || !gofloat_demosaic_one_pass(d, n) || !n.rc.noop() || !n.transform_noop ||
-      n.dw * n.dh < 256) return false;
+  if (!opted(d, IPK_FUSED_BATCH_PREVIEWS) || frames <= 1 || rt.kind != kStaged || !gofloat_demosaic_one_pass(d, n) || !n.rc.noop() || n.dw * n.dh < 256) return false;
+  if (!n.transform_noop) {
+    // IPK_FUSED_BATCH_ORIENTED: OpTransform rides in pass 2's loads (chain_out_batch_impl), where its image of the preview is the negotiated result
+    bool t, fx, fy; ipk::orientation_to_flips(n.orientation, t, fx, fy);
+    if (!opted(d, IPK_FUSED_BATCH_ORIENTED) || (t ? n.dh : n.dw) != n.fw || (t ? n.dw : n.dh) != n.fh) return false;
+  }
   bp.chunk = std::min<size_t>(64, std::max<size_t>(1, ((size_t)256 << 20) / (n.dw * n.dh * 16)));
   bp.pass1_batched = n.raw && ipk::raw_scaled_demosaic_general(n.r.width, n.r.height, n.dw, n.dh, true, !n.cfa_branch);
   return true;
@@ -3005,11 +3022,34 @@ int run_preview_chunks(const ipk_pipeline_desc *d, const Negotiated &ng, const B
   }
   return IPK_OK;
 }
+int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height, int monochrome, const ipk_chain_params *params, const int *orientations, size_t n,
+                         int linear, int out_type, void *const *dsts, void *stream, StageTimer &tm, const char *stage, const char *stage_oriented = nullptr);
+void chain_params_of(const ipk_pipeline_desc &d, ipk_chain_params &c) {
+  c.struct_size = (uint32_t)sizeof(c);
+  std::memcpy(c.wb_coeffs, d.wb_coeffs, sizeof(c.wb_coeffs));
+  std::memcpy(c.cam_to_xyz_normalized, d.cam_to_xyz_normalized, sizeof(c.cam_to_xyz_normalized));
+  c.exposure = d.exposure; c.npoints = d.npoints; std::memcpy(c.points, d.points, sizeof(c.points));
+}
 int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, void *const *dsts, size_t n,
                        int out_type, int *used_fused, void *stream) {
   const size_t out_bytes = ng.dw * ng.dh * 3 * out_elem_size(out_type);
   const bool f32_out = out_type == IPK_OUT_F32;
   const int monochrome = one_pass_monochrome(d, ng);
+  if (!ng.transform_noop) {
+    // IPK_FUSED_BATCH_ORIENTED: pass 2 is one frame-table launch per chunk, every record with the descriptor's orientation (a destination is not a
+    // slice of one flat image here, so frames following each other in memory gain nothing)
+    ipk_chain_params one; chain_params_of(*d, one);
+    std::vector<ipk_chain_params> cp; std::vector<const float *> s4; std::vector<int> ori;
+    return run_preview_chunks(d, ng, bp, srcs, n, stream,
+      [&](size_t i) { return ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); },
+      [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
+        cp.assign(m, one); ori.assign(m, ng.orientation); s4.resize(m);
+        for (size_t i = 0; i < m; ++i) s4[i] = rgbe + i * slice;
+        if (used_fused) *used_fused = 0;
+        const char *stage = f32_out ? "batch to_lab+basecurve+from_lab+gamma+transform" : "batch to_lab+basecurve+from_lab+gamma+transform+quantise";
+        return chain_out_batch_impl(s4.data(), ng.dw, ng.dh, monochrome, cp.data(), ori.data(), m, ng.linear, out_type, dsts + i0, stream, tm, stage);
+      });
+  }
   return run_preview_chunks(d, ng, bp, srcs, n, stream,
     [&](size_t i) { return ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); },
     // pass 2: the chain once per maximal run of frames whose destinations follow each other in memory
@@ -3030,8 +3070,11 @@ int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const B
 // ipk_pointwise_chain_out_batch: every frame's parameters through PointwisePrep::prepare (so normalize_wbs, the spline, has_curve and fast_ok are the single
 // form's, per frame) before anything is enqueued, then one frame-table launch per 64 frames (launch_chain_batch), its table in the scratch pool.  stage: the
 // name marked behind every launch
-int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height, int monochrome, const ipk_chain_params *params, size_t n, int linear, int out_type,
-                         void *const *dsts, void *stream, StageTimer &tm, const char *stage) {
+// orientations (optional, n ipk_orientation values): frame i leaves as OpTransform's image of its result -- its record gathers through frame_gather, the
+// permutation folded into the loads -- height wide where the orientation transposes.  Null, or Normal / Unknown throughout: the launches of old.
+// stage_oriented (optional): the name behind a launch with at least one oriented frame, where it differs
+int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height, int monochrome, const ipk_chain_params *params, const int *orientations, size_t n,
+                         int linear, int out_type, void *const *dsts, void *stream, StageTimer &tm, const char *stage, const char *stage_oriented) {
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   if (!dims_ok(width, height)) return fail(IPK_ERR_INVALID, "bad pointwise_chain_out_batch arguments");
   if (n == 0) return IPK_OK;
@@ -3047,36 +3090,47 @@ int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height,
       return fail(IPK_ERR_INVALID, "frame %zu: the source needs 16-byte alignment, the destination its element's", i);
     if (params[i].struct_size != sizeof(ipk_chain_params))
       return fail(IPK_ERR_INVALID, "params[%zu].struct_size is %u, not sizeof(ipk_chain_params) = %zu", i, params[i].struct_size, sizeof(ipk_chain_params));
+    if (orientations && (orientations[i] < 0 || orientations[i] > 8)) return fail(IPK_ERR_INVALID, "orientations[%zu] is %d, not an ipk_orientation", i, orientations[i]);
     const ipk_chain_params &p = params[i];
     const int rc = pps[i].prepare(monochrome, p.wb_coeffs, p.cam_to_xyz_normalized, p.exposure, p.points, p.npoints, linear);
     if (rc) { const std::string why = g_err; return fail(rc, "params[%zu]: %s", i, why.c_str()); }
     pps[i].f.src = srcs4[i]; pps[i].f.dst = dsts[i]; pps[i].f.out_type = out_type;
   }
   std::vector<ipk::FusedLaunch> fl;
+  std::vector<ipk::GatherSource> gs;
   for (size_t i0 = 0; i0 < n; i0 += ipk::kChainBatchMax) {
     const size_t m = std::min(ipk::kChainBatchMax, n - i0);
-    fl.clear();
-    for (size_t i = 0; i < m; ++i) fl.push_back(pps[i0 + i].f);
+    fl.clear(); gs.clear();
+    bool oriented = false;
+    for (size_t i = 0; i < m; ++i) {
+      fl.push_back(pps[i0 + i].f);
+      const int o = orientations ? orientations[i0 + i] : IPK_OR_NORMAL;
+      ipk::GatherSource g = {0, 0, 0, 0};                                  // width 0: the flat walk
+      if (o != IPK_OR_NORMAL && o != IPK_OR_UNKNOWN) { g = frame_gather(width, height, o); oriented = true; }
+      gs.push_back(g);
+    }
     Scratch sc(S(stream));
     void *table = nullptr;
     { const int rc = sc.get(ipk::chain_batch_table_bytes(m), &table); if (rc) return rc; }
-    const int lrc = ipk::launch_chain_batch(fl.data(), m, npix, out_type, table, S(stream));
+    const int lrc = ipk::launch_chain_batch(fl.data(), m, npix, out_type, table, S(stream), oriented ? gs.data() : nullptr);
     if (lrc == -4) return fail(IPK_ERR_HIP, "pointwise_chain_out_batch: the table upload or the launch could not be enqueued");
     if (lrc != 0) return fail(IPK_ERR_UNSUPPORTED, "pointwise_chain_out_batch: frame too small");
-    tm.mark(stage);
+    tm.mark(oriented && stage_oriented ? stage_oriented : stage);
   }
   return IPK_OK;
 }
 
 // ---- n frames, n descriptors (ipk_pipeline_run_batch_each): the plan ----
-// Same-shaped: every field equal but the five OpToLab and OpBaseCurve read.  a and b are taken and folded (so cfa compares as the drivers read it and
+// Same-shaped: every field equal but the five OpToLab and OpBaseCurve read -- and, where both descriptors carry IPK_FUSED_BATCH_ORIENTED beside the two bits
+// it acts with, the three OpTransform reads (plan_each then holds the negotiated demosaic sizes against each other).  a and b are taken and folded (so cfa compares as the drivers read it and
 // padding never enters); sa / sb are the struct_size values the callers wrote.  Floats compare by their bits
 bool same_bits(const float *a, const float *b, size_t n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
-bool same_shape(const ipk_pipeline_desc &a, uint32_t sa, const ipk_pipeline_desc &b, uint32_t sb) {
+bool same_orientation(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) { return a.rotation == b.rotation && a.fliph == b.fliph && a.flipv == b.flipv; }
+bool same_shape(const ipk_pipeline_desc &a, uint32_t sa, const ipk_pipeline_desc &b, uint32_t sb, bool oriented_ok = false) {
   return sa == sb && a.src_type == b.src_type && a.width == b.width && a.height == b.height && a.cpp == b.cpp && a.is_cfa == b.is_cfa &&
          std::strcmp(a.cfa, b.cfa) == 0 && a.crop_top == b.crop_top && a.crop_right == b.crop_right && a.crop_bottom == b.crop_bottom &&
          a.crop_left == b.crop_left && same_bits(a.blacklevels, b.blacklevels, 4) && same_bits(a.whitelevels, b.whitelevels, 4) &&
-         same_bits(a.rotatecrop, b.rotatecrop, 5) && a.rotation == b.rotation && a.fliph == b.fliph && a.flipv == b.flipv && a.maxwidth == b.maxwidth &&
+         same_bits(a.rotatecrop, b.rotatecrop, 5) && (oriented_ok || same_orientation(a, b)) && a.maxwidth == b.maxwidth &&
          a.maxheight == b.maxheight && a.linear == b.linear && a.allow_fused == b.allow_fused && a.use_fastpath == b.use_fastpath &&
          a.cfa_width == b.cfa_width && a.cfa_height == b.cfa_height && a.schedule == b.schedule && a.fuse_rotatecrop == b.fuse_rotatecrop &&
          a.reserved1 == b.reserved1 && a.fuse_scaledown == b.fuse_scaledown;
@@ -3107,6 +3161,10 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
   // the raster fast path is decided by the five point-wise fields themselves (default_ops_other): a frame that takes it shares no run with one that
   // does not, so every frame of a run is on the route ipk_pipeline_run would choose for it
   std::vector<char> fast(n, 0);
+  // IPK_FUSED_BATCH_ORIENTED: a frame whose own batch of previews would fold OpTransform into pass 2 may differ from its neighbour in rotation, fliph and
+  // flipv too, while both negotiate the same demosaic size (the scaling pass's filter): ori[i] = the frame qualifies, dwh[i] = that size
+  std::vector<char> ori(n, 0);
+  std::vector<std::pair<size_t, size_t>> dwh(n);
   for (size_t i = 0; i < n; ++i) {
     if (!descs[i]) return fail(IPK_ERR_INVALID, "null descriptor at index %zu", i);
     sizes[i] = descs[i]->struct_size;
@@ -3115,17 +3173,25 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
     if (!rc) {
       fast[i] = ipk_pipeline_takes_fastpath(&p.d[i], out_type) == 1;
       if (fast[i]) { if (p.d[i].width < 1 || p.d[i].height < 1) rc = fail(IPK_ERR_INVALID, "empty source"); }
-      else { Negotiated ng; rc = negotiate(&p.d[i], out_type, ng); }
+      else {
+        Negotiated ng; rc = negotiate(&p.d[i], out_type, ng);
+        if (!rc && opted(&p.d[i], IPK_FUSED_BATCH_PREVIEWS) && opted(&p.d[i], IPK_FUSED_BATCH_ORIENTED)) {
+          Route rt; BatchPreviews bp;
+          choose_route(&p.d[i], ng, out_type, rt);
+          ori[i] = batches_previews(&p.d[i], ng, rt, 2, bp);
+          dwh[i] = {ng.dw, ng.dh};
+        }
+      }
     }
     if (rc) { const std::string why = g_err; return fail(rc, "descriptor %zu: %s", i, why.c_str()); }
   }
   for (size_t a = 0; a < n;) {
     size_t b = a + 1;
-    while (b < n && fast[a] == fast[b] && same_shape(p.d[a], sizes[a], p.d[b], sizes[b])) ++b;
+    while (b < n && fast[a] == fast[b] && same_shape(p.d[a], sizes[a], p.d[b], sizes[b], ori[a] && ori[b] && dwh[a] == dwh[b])) ++b;
     for (size_t i = a; i < b; ++i) p.run_first[i] = a;
     const size_t m = b - a;
     bool all_equal = true;
-    for (size_t i = a + 1; i < b; ++i) all_equal = all_equal && same_pointwise(p.d[a], p.d[i]);
+    for (size_t i = a + 1; i < b; ++i) all_equal = all_equal && same_pointwise(p.d[a], p.d[i]) && same_orientation(p.d[a], p.d[i]);
     EachPlan::Varied v; Route rt;
     if (m > 1 && !all_equal && !fast[a] && opted(&p.d[a], IPK_FUSED_BATCH_PREVIEWS) &&
         negotiate(&p.d[a], out_type, v.ng) == IPK_OK && (choose_route(&p.d[a], v.ng, out_type, rt), batches_previews(&p.d[a], v.ng, rt, m, v.bp))) {
@@ -3134,7 +3200,7 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
     } else {
       for (size_t j = a; j < b;) {                   // maximal sub-runs of equal descriptors: the uniform batch, which keeps its own routes
         size_t k = j + 1;
-        while (k < b && same_pointwise(p.d[j], p.d[k])) ++k;
+        while (k < b && same_pointwise(p.d[j], p.d[k]) && same_orientation(p.d[j], p.d[k])) ++k;
         if (k - j > 1) for (size_t i = j; i < k; ++i) p.route[i] = kEachUniform;
         j = k;
       }
@@ -3143,27 +3209,28 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
   }
   return IPK_OK;
 }
-void chain_params_of(const ipk_pipeline_desc &d, ipk_chain_params &c) {
-  c.struct_size = (uint32_t)sizeof(c);
-  std::memcpy(c.wb_coeffs, d.wb_coeffs, sizeof(c.wb_coeffs));
-  std::memcpy(c.cam_to_xyz_normalized, d.cam_to_xyz_normalized, sizeof(c.cam_to_xyz_normalized));
-  c.exposure = d.exposure; c.npoints = d.npoints; std::memcpy(c.points, d.points, sizeof(c.points));
-}
 // a varied run: the chunks and pass 1 of run_batch_previews on the run's first descriptor, then ONE frame-table launch per chunk, frame i's record from
-// descriptor i and its destination dsts[i] wherever it lies
+// descriptor i -- its composed orientation included, where the run's frames carry their own -- and its destination dsts[i] wherever it lies
 int run_batch_each_varied(const ipk_pipeline_desc *ds, const EachPlan::Varied &v, const void *const *srcs, void *const *dsts, size_t n, int out_type,
                           int *used_fused, void *stream) {
   const int monochrome = one_pass_monochrome(ds, v.ng);
   const char *stage = out_type == IPK_OUT_F32 ? "batch-each to_lab+basecurve+from_lab+gamma" : "batch-each to_lab+basecurve+from_lab+gamma+quantise";
+  const char *stage_oriented = out_type == IPK_OUT_F32 ? "batch-each to_lab+basecurve+from_lab+gamma+transform"
+                                                       : "batch-each to_lab+basecurve+from_lab+gamma+transform+quantise";
   std::vector<ipk_chain_params> cp;
   std::vector<const float *> s4;
+  std::vector<int> ori;
   return run_preview_chunks(ds, v.ng, v.bp, srcs, n, stream,
     [&](size_t i) { return ipk_pipeline_run(ds + i, srcs[i], dsts[i], out_type, used_fused, stream); },
     [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
-      cp.resize(m); s4.resize(m);
-      for (size_t i = 0; i < m; ++i) { chain_params_of(ds[i0 + i], cp[i]); s4[i] = rgbe + i * slice; }
+      cp.resize(m); s4.resize(m); ori.resize(m);
+      for (size_t i = 0; i < m; ++i) {
+        chain_params_of(ds[i0 + i], cp[i]); s4[i] = rgbe + i * slice;
+        ori[i] = ipk::transform_orientation(ds[i0 + i].rotation, ds[i0 + i].fliph != 0, ds[i0 + i].flipv != 0);   // Negotiated::orientation of frame i
+      }
       if (used_fused) *used_fused = 0;
-      return chain_out_batch_impl(s4.data(), v.ng.dw, v.ng.dh, monochrome, cp.data(), m, v.ng.linear, out_type, dsts + i0, stream, tm, stage);
+      return chain_out_batch_impl(s4.data(), v.ng.dw, v.ng.dh, monochrome, cp.data(), ori.data(), m, v.ng.linear, out_type, dsts + i0, stream, tm, stage,
+                                  stage_oriented);
     });
 }
 }  // namespace
@@ -3210,8 +3277,16 @@ int ipk_pointwise_chain_out_batch(const float *const *srcs4, size_t width, size_
                                   int out_type, void *const *dsts, void *stream) {
   REQUIRE_INIT();
   StageTimer tm(S(stream));
-  return chain_out_batch_impl(srcs4, width, height, monochrome, static_cast<const ipk_chain_params *>(params), n, linear, out_type, dsts, stream, tm,
+  return chain_out_batch_impl(srcs4, width, height, monochrome, static_cast<const ipk_chain_params *>(params), nullptr, n, linear, out_type, dsts, stream, tm,
                               "pointwise_chain_out_batch");
+}
+// the same with an orientation per frame: OpTransform's permutation folded into each frame's loads
+int ipk_pointwise_chain_out_batch_oriented(const float *const *srcs4, size_t width, size_t height, int monochrome, const void *params, const int *orientations,
+                                           size_t n, int linear, int out_type, void *const *dsts, void *stream) {
+  REQUIRE_INIT();
+  StageTimer tm(S(stream));
+  return chain_out_batch_impl(srcs4, width, height, monochrome, static_cast<const ipk_chain_params *>(params), orientations, n, linear, out_type, dsts, stream,
+                              tm, "pointwise_chain_out_batch_oriented");
 }
 // The plan of ipk_pipeline_run_batch_each, for callers and CPU tests (no GPU)
 int ipk_pipeline_batch_each_plan(const ipk_pipeline_desc *const *descs, size_t n, int out_type, int *route, size_t *run_first) {
@@ -3241,7 +3316,7 @@ int ipk_pipeline_run_batch_each(const ipk_pipeline_desc *const *descs, const voi
   if (used_fused) *used_fused = 0;
   for (size_t a = 0; a < n;) {
     size_t b = a + 1;
-    while (b < n && p.route[b] == p.route[a] && p.run_first[b] == p.run_first[a] && (p.route[a] != kEachUniform || same_pointwise(p.d[a], p.d[b]))) ++b;
+    while (b < n && p.route[b] == p.route[a] && p.run_first[b] == p.run_first[a] && (p.route[a] != kEachUniform || (same_pointwise(p.d[a], p.d[b]) && same_orientation(p.d[a], p.d[b])))) ++b;
     int rc;
     if (p.route[a] == kEachVaried) rc = run_batch_each_varied(&p.d[a], p.varied.at(a), srcs + a, dsts + a, b - a, out_type, used_fused, stream);
     else if (p.route[a] == kEachUniform) rc = ipk_pipeline_run_batch(&p.d[a], srcs + a, dsts + a, b - a, out_type, used_fused, stream);

@@ -2721,6 +2721,9 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
 
     const bool store_aligned = (OUTS == 0 || OUTS == 3) ? true : ((OUTS == 1) ? ((a.W & 3u) == 0) : ((a.W & 1u) == 0));
     const uint32_t Hm1 = a.H - 1, Wm1 = a.W - 1;
+    // the last row the source holds: the frame's, or -- a band's slab ends with its lower halo row -- row out_r1.  The rows loaded ahead stop there: the
+    // loads of rows r + 2 and r + 3 were clamped to the FRAME and read up to two rows past a slab's end (values never used; a fault where the slab ends a mapping)
+    const uint32_t Lm1 = min(Hm1, a.out_r1);
     const bool col_edge = lane_on && (col0 == 0 || col0 + 3 >= Wm1);
 
     RowWin P = {0, 0, 0, 0, 0, 0}, C, N = {0, 0, 0, 0, 0, 0};
@@ -2731,7 +2734,7 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
     RawRowT raw_next;
     {
       const RawRowT rp = issue_row(r0 > 0 ? r0 - 1 : 0u), rc = issue_row(r0), rn = issue_row(min(r0 + 1, Hm1));
-      raw_next = issue_row(min(r0 + 2, Hm1));
+      raw_next = issue_row(min(r0 + 2, Lm1));
       P = finish_row(rp, fP); C = finish_row(rc, fC); N = finish_row(rn, fN);
     }
     arrive();
@@ -2870,7 +2873,7 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
           RgbeStage::store_direct(frame_dst, (size_t)(r - a.out_r0) * a.W + col0, nvalid, px);
         }
         __builtin_amdgcn_sched_barrier(0);
-        raw_next = issue_row(min(r + 3, Hm1));
+        raw_next = issue_row(min(r + 3, Lm1));
         P = NN; fP = fNN;
         if (GEN) ry = (ry + 1 == a.gen_ph) ? 0u : ry + 1;
         return;
@@ -2915,7 +2918,7 @@ __device__ __forceinline__ void fused_bayer_body(const FusedArgs &a, const Batch
         if (lane_on) OutStore<OUTS>::store(frame_dst, (size_t)(r - a.out_r0) * a.W + col0, nvalid, o, store_aligned);
       }
       __builtin_amdgcn_sched_barrier(0);
-      raw_next = issue_row(min(r + 3, Hm1));
+      raw_next = issue_row(min(r + 3, Lm1));
       P = NN; fP = fNN;
       if (GEN) ry = (ry + 1 == a.gen_ph) ? 0u : ry + 1;
     };
@@ -3428,7 +3431,8 @@ template <bool TOLAB_ONLY>
 __global__ __launch_bounds__(1024) void k_pointwise_chain(FusedArgs a, uint64_t npix) { pointwise_chain_body<TOLAB_ONLY>(a, npix); }
 // Frame-table mode (frames != null; launch_chain_batch): the grid's y plane is the frame, and the block takes EVERY argument from frames[blockIdx.y] -- a whole
 // FusedArgs per frame in device memory, filled by the host as chain_args fills the kernel's own: source, destination, multipliers, matrix, curve, has_curve,
-// fast_ok (linear, rgbm and the tables are the same in every record).  The index is block-uniform and the table is read-only for the launch, so the record is
+// fast_ok (linear, rgbm and the tables are the same in every record), and, where the frame carries an orientation, gather with its own W and steps: the
+// body reads the mode from the record it runs on, so one launch mixes flat and gathering frames (npix is the launch's: an orientation keeps the count).  The index is block-uniform and the table is read-only for the launch, so the record is
 // read with the uniform loads the kernel arguments are read with; the block fills s_par / s_knots / s_grid from it and walks its own frame's npix pixels, so
 // the clamped tail is the frame's.  The mode is chosen here, once per block: a launch without a table runs the body on its arguments as it always did.
 __global__ __launch_bounds__(1024) void k_pointwise_chain_small(FusedArgs a, uint64_t npix, const FusedArgs *__restrict__ frames) {
@@ -3724,19 +3728,23 @@ int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s, con
 // The frame-table launch of the chain (ipk_launch.hpp): frames[i]'s arguments as chain_args makes them for a single launch, uploaded stream-ordered into
 // table_dev, then ONE launch with a grid plane per frame
 size_t chain_batch_table_bytes(size_t n) { return n * sizeof(FusedArgs); }
-int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s) {
+int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s, const GatherSource *gathers) {
   if (n == 0 || n > kChainBatchMax || npix == 0 || out_type < 0 || out_type > 2 || (out_type != 0 && npix < 256) || !table_dev) return -1;
   std::vector<FusedArgs> table(n);
-  bool fast_all = true;
+  bool fast_all = true, oriented = false;
   for (size_t i = 0; i < n; ++i) {
     table[i] = chain_args(frames[i]);
     table[i].gam_q8 = reinterpret_cast<const Q8Entry *>(frames[i].gam_q8);
     fast_all = fast_all && frames[i].fast_ok;
+    if (gathers && gathers[i].width != 0) {                                // this frame's record gathers: its own W and steps, the launch's npix
+      if (!set_gather(table[i], &gathers[i], npix)) return -1;
+      oriented = true;
+    }
   }
   if (hipMemcpyAsync(table_dev, table.data(), n * sizeof(FusedArgs), hipMemcpyHostToDevice, s) != hipSuccess) return -4;   // (pageable: consumed before it returns)
   const unsigned cus = (unsigned)(frames[0].num_cus > 0 ? frames[0].num_cus : 256);
   const dim3 grid(chain_batch_blocks(npix, out_type, n, cus), (unsigned)n);
-  const char *tag = fast_all ? "fast_ok=1,batch=1" : "fast_ok=0,batch=1";
+  const char *tag = oriented ? (fast_all ? "fast_ok=1,batch=1,orient=1" : "fast_ok=0,batch=1,orient=1") : (fast_all ? "fast_ok=1,batch=1" : "fast_ok=0,batch=1");
   const FusedArgs *dev = static_cast<const FusedArgs *>(table_dev);
   if (out_type == 0) IPK_LAUNCH_TAG(tag, k_pointwise_chain_small, grid, dim3(1024), 0, s, table[0], (uint64_t)npix, dev);
   else if (out_type == 1) IPK_LAUNCH_TAG(tag, (k_raster_chain<Rgbe32, 1>), grid, dim3(1024), 0, s, table[0], (uint64_t)npix, (const LutPair *)nullptr, dev);

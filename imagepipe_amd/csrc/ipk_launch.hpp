@@ -50,7 +50,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form); the gather
 // launches of k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2> (a GatherSource: ipk_pipeline_run_cached_region) append
 // gather=1: [fast_ok=,gather=1] -- flat launches never carry the key; the frame-table launches of k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2>
-// (launch_chain_batch: ipk_pointwise_chain_out_batch) carry [fast_ok=,batch=1], fast_ok the AND over the launch's frames;
+// (launch_chain_batch: ipk_pointwise_chain_out_batch) carry [fast_ok=,batch=1], fast_ok the AND over the launch's frames, and [fast_ok=,batch=1,orient=1]
+// when at least one frame's record gathers (ipk_pointwise_chain_out_batch_oriented);
 // k_raster_chain's launches by ipk_plain_to_srgb append rect=1 in rectangle mode (a rectangle narrower than the source's pitch) and levels=1 / levels=2
 // in the three-sample / monochrome raw sample modes, in that order: [fast_ok=,rect=1], [fast_ok=,levels=2], [fast_ok=,rect=1,levels=1] -- launches
 // that use neither mode (ipk_raster_to_srgb, ipk_pointwise_chain_out, a full-width raster rectangle) carry [fast_ok=] and nothing else;
@@ -197,6 +198,9 @@ int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s, con
 // instead of the kernel's arguments and is otherwise the single launch of that frame: bit-identical, the tail handling on the frame's own npix.  The log
 // tags such launches [fast_ok=,batch=1]: fast_ok=1 when every frame's record allows the fast form, 0 when at least one frame takes the literal form
 // throughout.  out_type 1 / 2 need npix >= 256.  -1 (nothing enqueued) outside these bounds, -4 when the copy or the launch could not be enqueued
+// gathers (optional, n entries): frame i with gathers[i].width != 0 runs in gather mode on its own record -- its npix pixels are a gathers[i].width-wide
+// rectangle read through gathers[i]'s base and steps (an orientation folded into the loads: npix % width == 0, else -1) -- and a launch with at least one
+// such frame is tagged [fast_ok=,batch=1,orient=1].  Null, or every width 0: the launch and the tag above
 constexpr size_t kChainBatchMax = 64;
 size_t chain_batch_table_bytes(size_t n);
 // blocks per frame: what a single launch of the frame gets (sixteen wave-chunks of 128 / 256 pixels per block), capped so that the launch's n planes
@@ -205,7 +209,7 @@ inline unsigned chain_batch_blocks(size_t npix, int out_type, size_t n, unsigned
   const size_t chunks = out_type == 0 ? (npix + 127) / 128 : (npix + 255) / 256;
   return (unsigned)std::max<size_t>(1, std::min<size_t>((chunks + 15) / 16, (cus + n - 1) / n));
 }
-int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s);
+int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s, const GatherSource *gathers = nullptr);
 // run_other + OpToLab..OpGamma + quantisation in one pass over an RGB8 / RGB16 raster (npix >= 256; f.out_type selects the output)
 // plain (optional; ipk_plain_to_srgb): the launch covers a width-pixel-wide rectangle of npix pixels whose first sample is f.src, inside an image whose rows
 // are owidth pixels apart, and f.dst holds its npix * 3 packed samples.  levels: 0 the raster's samples; 1 a three-sample u16 raw, each channel

@@ -500,6 +500,22 @@ typedef struct { uint32_t struct_size; float wb_coeffs[4]; float cam_to_xyz_norm
 IPK_API int ipk_pointwise_chain_out_batch(const float *const *srcs4, size_t width, size_t height, int monochrome,
                                           const void *params /* n ipk_chain_params */, size_t n, int linear,
                                           int out_type, void *const *dsts, void *stream);
+/* The same with an orientation per frame: frame i is bit-identical to ipk_pointwise_chain_out (for IPK_OUT_F32, ipk_pointwise_chain) of srcs4[i] with
+ * params[i], followed by ipk_rotate_image_u8 / _u16 / ipk_rotate_buffer with orientations[i].  dsts[i] receives width*height*3 samples -- a height-wide
+ * image for the four transposing orientations (Transpose, Rotate90, Transverse, Rotate270) -- and nothing else is written.  IPK_OR_UNKNOWN is Normal.
+ * orientations == NULL, or every entry Normal or Unknown, is exactly ipk_pointwise_chain_out_batch: the same launches with the same [fast_ok=,batch=1]
+ * tags.  Otherwise the record of an oriented frame carries the gather mode of the chain kernels (the whole-frame case of the mapping
+ * ipk_pipeline_region_gather reports: the output's width, and base, x_step, y_step into the source), so OpTransform's permutation is folded into the
+ * frame's loads; a launch with at least one such record is tagged [fast_ok=,batch=1,orient=1].  All eight orientations and all three outputs take that
+ * mode: a flip keeps a lane's pixels consecutive in memory, forwards or backwards, and a transposing orientation reads one source pixel per lane a source
+ * row apart.  There is no tiled walk for the transposing orientations, so the host predicate "tile or gather" is constantly gather: a transposed tile walk
+ * through the wave's stage buffer (32 x 8 output pixels per wave, loaded along source rows, tag orient=2) was built for k_raster_chain<Rgbe32, 1 | 2>,
+ * bit-exact at 128 / 126 VGPRs without scratch, measured against this form and deleted (IPK_FUSED_BATCH_ORIENTED has the figures).  Validation is that of
+ * ipk_pointwise_chain_out_batch, before anything is enqueued; an orientation outside 0..8 is IPK_ERR_INVALID with the index in ipk_last_error.  The floor
+ * of 256 pixels per frame for 8 and 16 bits and the 64 frames per launch stay.  ipk_timing names each launch "pointwise_chain_out_batch_oriented". */
+IPK_API int ipk_pointwise_chain_out_batch_oriented(const float *const *srcs4, size_t width, size_t height, int monochrome,
+                                                   const void *params /* n ipk_chain_params */, const int *orientations /* n ipk_orientation, or NULL */,
+                                                   size_t n, int linear, int out_type, void *const *dsts, void *stream);
 /* The raster-source counterpart of ipk_raw_to_srgb: OpGoFloat::run_other (src/ops/gofloat.rs:171-201; RGB8 through
  * expand_srgb_gamma(input8bit(v)), RGB16 through input16bit(v)) + OpToLab + OpBaseCurve + OpFromLab + OpGamma (+ output8bit /
  * output16bit, src/pipeline.rs:408-414,455-461) in one pass from the width*height*3 source samples to width*height*3 outputs of
@@ -586,7 +602,11 @@ typedef struct {
                                       Bit 8 (IPK_FUSED_BATCH_PREVIEWS = 256), beside IPK_FUSED_ON as well, concerns ipk_pipeline_run_batch (and the drivers that
                                       go through it) alone: a batch of downscaled previews runs as one scaling launch group and one point-wise pass per chunk
                                       of frames where ipk_pipeline_batches_previews says so.  Same contract: no hash, no result, no other driver or report
-                                      depends on it.  Like bits 3, 4 and 7, allow_fused = 256 alone still means "on" for every older route. */
+                                      depends on it.  Like bits 3, 4 and 7, allow_fused = 256 alone still means "on" for every older route.
+                                      Bit 9 (IPK_FUSED_BATCH_ORIENTED = 512) acts beside bits 0 and 8 only: the batched previews take frames of any
+                                      orientation, OpTransform folded into the point-wise pass, and ipk_pipeline_run_batch_each lets rotation, fliph and flipv
+                                      differ inside a run.  Same contract: no hash, no result, no other driver or report depends on it; allow_fused = 512
+                                      alone still means "on" for every older route. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -652,17 +672,53 @@ typedef enum {
                                       parent 0.149 ms (spread 0.001) -> 0.148 ms.  Not measured: the host form of the regions, regions of the straightened
                                       case, 100 MP frames, 16-bit outputs, photo-like data, and the 8-sample mosaic kernels (k_raw_scaled_demosaic_w8 / _w8m:
                                       their code is untouched, their argument block grew by five words) */
-  IPK_FUSED_BATCH_PREVIEWS = 256   /* bit 8 (beside bit 0): ipk_pipeline_run_batch runs a batch of downscaled previews -- staged frames whose OpGoFloat +
+  IPK_FUSED_BATCH_PREVIEWS = 256,  /* bit 8 (beside bit 0): ipk_pipeline_run_batch runs a batch of downscaled previews -- staged frames whose OpGoFloat +
                                       OpDemosaic is the one scaling pass (mosaics at scale >= minscale, rasters under a size limit, monochrome / three-sample
                                       raws under bit 7), OpRotateCrop and OpTransform no-ops, at least 256 pixels per preview -- chunk by chunk: the scaling
                                       pass of a chunk as ONE launch per 64 frames where the frames select the general kernel (ipk_raw_scaled_demosaic_batch /
                                       ipk_plain_scale_down_batch; else a launch per frame), then the point-wise chain ONCE over the previews lying one after
                                       another, where ipk_pipeline_batches_previews says so.  A thumbnail's scaling launch is far too small to fill the chip
                                       and its windows cannot be split across lanes (one accumulator, y outer, x inner): frames are the parallelism left.
-                                      Out of scope, falling to the per-frame loop: non-Normal orientations and active rotatecrops in a batch; batch forms of
+                                      Out of scope, falling to the per-frame loop: non-Normal orientations without bit 9 and active rotatecrops in a batch; batch forms of
                                       the window-8 kernels and the raster scaler (a launch per frame inside the route); the host-buffer batch
                                       (ipk_host_pipeline_run_batch is unchanged); band (multi-GPU single-frame) forms; the bit as a default.
                                       Measurements: profiles/r19_batch_previews.txt */
+  IPK_FUSED_BATCH_ORIENTED = 512   /* bit 9 (beside bits 0 and 8; nothing without either): a batch of previews may carry orientations.  OpTransform
+                                      behind a no-op OpRotateCrop is a dihedral permutation of the preview, and pass 2 of the batch folds it into its
+                                      loads: ONE frame-table launch per chunk (ipk_pointwise_chain_out_batch_oriented), each frame's record with the gather
+                                      walk of its own orientation, instead of the scaling pass, the chain, the quantise and the transform per frame.
+                                      ipk_pipeline_batches_previews then answers 1 for the seven other orientations too, ipk_pipeline_run_batch runs an
+                                      oriented descriptor that way, and ipk_pipeline_run_batch_each keeps landscape and portrait frames of one shoot in one
+                                      run where they negotiate the same demosaic size (see there).  Without the bit every plan, launch, tag and stage
+                                      name is what it was.  Every orientation walks the gather mode the chain kernels already have
+                                      (ipk_pipeline_run_cached_region's): a flip keeps a lane's pixels consecutive in memory, forwards or backwards; a
+                                      transposing orientation reads one source pixel per lane a source row apart.
+                                      Out of scope: active rotatecrops in a batch; per-frame levels, crops or size limits inside one scaling launch;
+                                      the host-buffer batch drivers; band forms; the bit as a default; graph capture.
+                                      Measured (profiles/r21_batch_oriented.txt; device-resident noise frames under a square box, every frame with its
+                                      own wb_coeffs and exposure, wall clock, medians, ms per frame; the parent build's only offer -- a loop of
+                                      ipk_pipeline_run -- -> ipk_pipeline_run_batch_each with the bit; the parent's spread is 0.0003 .. 0.0045 ms), every
+                                      frame Rotate90 to u8, n = 2 / 8 / 16 / 64: 24 MP RGGB u16 -> 256x170: 0.217 -> 0.123, 0.224 -> 0.060, 0.223 -> 0.072,
+                                      0.222 -> 0.060; -> 400x266: 0.128 -> 0.092, 0.129 -> 0.071, 0.128 -> 0.067, 0.127 -> 0.063; 50 MP X-Trans u16 ->
+                                      270x180: 0.381 -> 0.233, 0.394 -> 0.179, 0.394 -> 0.162, 0.392 -> 0.151; 24 MP mono u16 -> 256x170: 0.147 -> 0.081,
+                                      0.157 -> 0.051, 0.157 -> 0.064, 0.156 -> 0.052: x1.4 .. x1.8 at n = 2, x1.8 .. x3.7 at n >= 8.  Normal and Rotate90
+                                      alternating, and Rotate90 to u16, are within 0.002 ms of those figures.  The price of orientation, against this
+                                      build's all-Normal batch on the same frames: +0.002 .. +0.004 ms per frame at n = 2, -0.0005 .. +0.002 at n >= 8.
+                                      No measured case was slower than the parent's loop; none is excluded.  The carriers' launches outside the mode
+                                      stayed inside the parent's spread (their device code is the parent's): ipk_pointwise_chain_out at 2160x1440 to f32
+                                      0.0397 -> 0.0398 ms, to u8 0.0397 -> 0.0395; at 6000x4000 to f32 0.1962 -> 0.1981 (spread 0.0107), to u8 0.1794 ->
+                                      0.1756 (0.0084); the cached-region gather launch over 1/16 of a 24 MP frame to u8 0.0449 -> 0.0451.
+                                      The transposed tile walk (see ipk_pointwise_chain_out_batch_oriented) against this gather (the file's second
+                                      part), Rotate90 batches, gather minus tile walk in ms per frame: -> 400x266 to u8 +0.0003 / +0.0001 / +0.0010 / +0.0009 at n = 2 / 8 / 16 / 64
+                                      (beyond the two builds' spreads at n = 16 and 64 only, by 1.5 %), X-Trans -> 270x180 to u8 -0.0017 / +0.0003 /
+                                      -0.0020 / +0.0006 and to u16 -0.0004 / -0.0003 / -0.0014 / -0.0010, all inside spreads of 0.003 .. 0.007: at
+                                      most 0.001 ms of frames that take 0.06 .. 0.15 (presumably because a 0.7 MB preview's transposing reads are
+                                      served from the caches; not profiled).  It had to be faster beyond the spreads in both rows to stay, and no
+                                      X-Trans reading was, so it was deleted.
+                                      Not measured: f32 outputs, f32 sources, the other six orientations, scattered destinations, per-frame matrices
+                                      and curves, batches above 64 frames, rasters and the window-8 geometries, previews larger than 400 wide (where
+                                      the transposing gather's cost must grow towards the 3.3x of ipk_pipeline_run_cached_region's 24 MP region),
+                                      the uniform route (ipk_pipeline_run_batch on one oriented descriptor), photo-like data */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -808,7 +864,8 @@ IPK_API int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const
 /* Does ipk_pipeline_run_batch (and ipk_pipeline_run_batch_multi, member by member) run n frames of this descriptor as batched previews BECAUSE of
  * IPK_FUSED_BATCH_PREVIEWS?  1 when d->allow_fused has IPK_FUSED_ON and IPK_FUSED_BATCH_PREVIEWS set, n > 1, the frame is staged and its OpGoFloat +
  * OpDemosaic is the one scaling pass (a one-sample-per-pixel mosaic at scale >= minscale, an RGB8 / RGB16 raster at scale > 1 off the fast path, or --
- * with IPK_FUSED_PLAIN_PREVIEWS -- a monochrome or three-sample raw at scale > 1), OpRotateCrop is a no-op, the orientation is Normal, and the preview
+ * with IPK_FUSED_PLAIN_PREVIEWS -- a monochrome or three-sample raw at scale > 1), OpRotateCrop is a no-op, the orientation is Normal (or Unknown) --
+ * or d->allow_fused has IPK_FUSED_BATCH_ORIENTED as well and OpTransform's image of the demosaic size is the negotiated result -- and the preview
  * has at least 256 pixels (the one-pass chain's floor, kept per frame).  0 otherwise, and the batch is n calls of ipk_pipeline_run as before; a negative
  * error code for a descriptor ipk_pipeline_sizes refuses.  *chunk (may be NULL; 0 when the answer is not 1) receives the frames per chunk,
  * min(64, max(1, 256 MiB / (demosaic_w * demosaic_h * 16))); *pass1_batched (may be NULL) 1 when a chunk's scaling pass is the general kernel's batch
@@ -817,7 +874,9 @@ IPK_API int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const
  * runs ipk_pointwise_chain_out once per maximal run of frames whose destinations follow each other in memory (dsts[i + 1] == dsts[i] + demosaic_w *
  * demosaic_h * 3 samples) -- scattered destinations cost one chain launch per frame and nothing else; a chunk of one frame is ipk_pipeline_run.  Results
  * and *used_fused are what n calls of ipk_pipeline_run give.  ipk_timing names the stages "batch gofloat+demosaic" and
- * "batch to_lab+basecurve+from_lab+gamma+quantise" (without "+quantise" for f32).  No GPU needed. */
+ * "batch to_lab+basecurve+from_lab+gamma+quantise" (without "+quantise" for f32).  An oriented descriptor (IPK_FUSED_BATCH_ORIENTED) has another
+ * pass 2: ONE ipk_pointwise_chain_out_batch_oriented launch per chunk, every record with the descriptor's orientation, wherever the destinations lie,
+ * named "batch to_lab+basecurve+from_lab+gamma+transform+quantise" (without "+quantise" for f32).  No GPU needed. */
 IPK_API int ipk_pipeline_batches_previews(const ipk_pipeline_desc *d, int out_type, size_t n, size_t *chunk, int *pass1_batched);
 /* The same over the DEVICE SET (ipk_init_devices) from one host thread: frame i runs on set member i mod N, so srcs[i] / dsts[i] must live on
  * that member's device.  Nothing is exchanged between devices and every result stays where it was computed (frames are independent pipelines,
@@ -833,23 +892,29 @@ IPK_API int ipk_devices_sync(void);
  * ipk_last_error and writes nothing.  n = 0 is IPK_OK.  The host arrays are read before the call returns.
  * The plan, which ipk_pipeline_batch_each_plan reports without a GPU (route[i], run_first[i]; either may be NULL): two descriptors are SAME-SHAPED when
  * every field is equal except wb_coeffs, cam_to_xyz_normalized, exposure, npoints and points -- field by field, cfa as a string after the drivers' usual
- * folding, floats by their bits, padding not at all; struct_size, allow_fused, linear, schedule and the fuse flags count as shape.  One thing the five
+ * folding, floats by their bits, padding not at all; struct_size, allow_fused, linear, schedule and the fuse flags count as shape.  Where BOTH
+ * descriptors carry IPK_FUSED_BATCH_ORIENTED beside IPK_FUSED_ON | IPK_FUSED_BATCH_PREVIEWS, each would batch its own previews
+ * (ipk_pipeline_batches_previews answers 1 for it) and both negotiate the same demosaic size (ipk_pipeline_sizes), rotation, fliph and flipv may
+ * differ as well: eight fields instead of five.  The demosaic size decides the scaling pass's filter; under one maxwidth alone a Rotate90 / Rotate270
+ * frame negotiates another one than a Normal frame (transform_forward swaps the sides before the clamp) and still cuts the run, under a square box
+ * (maxwidth == maxheight) frames of equal source size agree, and fliph / flipv never enter the fold.  One thing the five
  * fields themselves decide counts as shape too: ipk_pipeline_takes_fastpath (the raster fast path is taken for the DEFAULT ops only), so a raster with
  * default ops and an edited one are never same-shaped under IPK_OUT_U8 / IPK_OUT_U16, and every frame of a run is on the route ipk_pipeline_run would
  * choose for it.  The frames are cut, in order, into maximal runs of consecutive same-shaped descriptors; run_first[i] is the first frame of frame
  * i's run.  For a run of m frames:
  *   route 2, varied previews: m > 1, ipk_pipeline_batches_previews(descs[run_first], out_type, m, ...) answers 1 (so allow_fused needs IPK_FUSED_ON |
- *     IPK_FUSED_BATCH_PREVIEWS: no new bit) and the descriptors are not all equal in the five fields.  Chunks follow that report's chunk; pass 1 is the
+ *     IPK_FUSED_BATCH_PREVIEWS: no new bit) and the descriptors are not all equal in the five (eight) fields.  Chunks follow that report's chunk; pass 1 is the
  *     uniform route's pass 1 -- one set of levels, crops and filter per chunk -- and pass 2 is ONE ipk_pointwise_chain_out_batch launch per chunk: source i
  *     the scratch's slice i, parameters descriptor i's, destination dsts[i] wherever it lies (scattered destinations cost nothing here).  A final chunk
  *     of one frame is ipk_pipeline_run.  ipk_timing names the stages "batch gofloat+demosaic" and "batch-each to_lab+basecurve+from_lab+gamma+quantise"
- *     (without "+quantise" for f32);
- *   route 1, uniform: otherwise, inside the run, maximal sub-runs of two or more consecutive descriptors that are equal in the five fields as well go
+ *     (without "+quantise" for f32); a chunk with at least one oriented frame is ONE ipk_pointwise_chain_out_batch_oriented launch, frame i with its
+ *     descriptor's composed orientation and dsts[i] of its own final size, named "batch-each to_lab+basecurve+from_lab+gamma+transform+quantise";
+ *   route 1, uniform: otherwise, inside the run, maximal sub-runs of two or more consecutive descriptors that are equal in the five (eight) fields as well go
  *     to ipk_pipeline_run_batch -- a run on the varied route's ground whose five fields happen to be all equal included -- which keeps the persistent
  *     full-size launch and the uniform preview batch for callers who happen to have them;
  *   route 0, single: every other frame, through ipk_pipeline_run.
  * Out of scope: per-frame settings inside the persistent full-size launch ipk_raw_to_srgb_batch (one parameter set; full-size frames with varied
- * settings are route 0 each); per-frame levels, crops or filters inside one scaling launch (they cut the run); non-Normal orientations and active
+ * settings are route 0 each); per-frame levels, crops or filters inside one scaling launch (they cut the run); non-Normal orientations without IPK_FUSED_BATCH_ORIENTED and active
  * rotatecrops inside a varied run (ipk_pipeline_batches_previews answers 0: frame by frame, or route 1 where identical); the host-buffer batch drivers;
  * the multi-device driver (it may follow by calling this one member by member); band forms; the bit as a default; graph capture (the table upload of
  * ipk_pointwise_chain_out_batch is a copy from pageable host memory).

@@ -306,6 +306,7 @@ class Pipeline {
   bool fuse_scaled_rotatecrop = false;     // ipk_pipeline_desc.allow_fused bit 6 (IPK_FUSED_SCALED_ROTATECROP): an active OpRotateCrop behind a scaling OpDemosaic as two launches where fuses_scaled_rotatecrop() says so; regions of such frames windowed
   bool scale_plain = false;                // ipk_pipeline_desc.allow_fused bit 7 (IPK_FUSED_PLAIN_PREVIEWS): downscaled previews of monochrome / three-sample raws (u16, f32) run gofloat + demosaic as the one launch ipk_plain_scale_down where scales_plain() says so; window_previews and fuse_scaled_rotatecrop then take them too
   bool batch_previews = false;             // ipk_pipeline_desc.allow_fused bit 8 (IPK_FUSED_BATCH_PREVIEWS): run_batch() runs downscaled previews as one scaling launch group and one point-wise pass per chunk of frames where batches_previews() says so
+  bool batch_oriented = false;             // ipk_pipeline_desc.allow_fused bit 9 (IPK_FUSED_BATCH_ORIENTED), set only together with batch_previews: batched previews take frames of any orientation (OpTransform folded into the point-wise pass), and run_batch_each lets rotation / fliph / flipv differ inside a run
   bool window_previews = false;            // ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
   int last_ops_run = 0xFF;                 // bit i: op i executed in the last run (0 = served from the cache)
   uint64_t source_id = 0;                  // identifies the frame inside a shared PipelineCache (extension, see the C header)
@@ -418,6 +419,7 @@ class Pipeline {
     if (fuse_scaled_rotatecrop && d.allow_fused) d.allow_fused |= IPK_FUSED_SCALED_ROTATECROP;
     if (scale_plain && d.allow_fused) d.allow_fused |= IPK_FUSED_PLAIN_PREVIEWS;
     if (batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_PREVIEWS;
+    if (batch_oriented && batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_ORIENTED;
     return d;
   }
   // does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop; no GPU needed)?  out_type: IPK_OUT_*
@@ -447,7 +449,8 @@ class Pipeline {
   bool resamples_cached_region(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_resamples_cached_region(&d, out_type) == 1; }
   // A shoot whose files carry their own colour settings: one Pipeline per frame, raws[i] shaped like pipes[i]'s own source (ipk_pipeline_run_batch_each).
   // ONE device allocation, the results of out_type one after another in frame order; offsets (optional) receives each result's byte offset.  Frames that
-  // differ only in white balance, matrix, exposure and curve run as batched previews where batch_each_plan() says 2 (batch_previews on every member)
+  // differ only in white balance, matrix, exposure and curve -- and, with batch_oriented on every member, in rotation, fliph and flipv -- run as batched
+  // previews where batch_each_plan() says 2 (batch_previews on every member)
   static DeviceArray run_batch_each(const std::vector<const Pipeline *> &pipes, const std::vector<const void *> &raws, int out_type = IPK_OUT_F32,
                                     std::vector<size_t> *offsets = nullptr) {
     if (pipes.size() != raws.size()) throw Error("run_batch_each: as many pipelines as frames");
@@ -503,6 +506,17 @@ inline void pointwise_chain_out_batch(const std::vector<const float *> &srcs4, s
   const ipk_chain_params *p = params.data();
   check(ipk_pointwise_chain_out_batch(srcs4.data(), width, height, monochrome ? 1 : 0, p, srcs4.size(), linear ? 1 : 0, out_type, dsts.data(), stream),
         "pointwise_chain_out_batch");
+}
+// the same with an orientation per frame (ipk_pointwise_chain_out_batch_oriented): dsts[i] receives frame i as OpTransform's image under orientations[i]
+// (ipk_orientation values; an empty vector: every frame Normal), height wide where the orientation transposes
+inline void pointwise_chain_out_batch_oriented(const std::vector<const float *> &srcs4, size_t width, size_t height, bool monochrome,
+                                               const std::vector<ipk_chain_params> &params, const std::vector<int> &orientations, bool linear, int out_type,
+                                               const std::vector<void *> &dsts, void *stream = nullptr) {
+  if (params.size() != srcs4.size() || dsts.size() != srcs4.size() || (!orientations.empty() && orientations.size() != srcs4.size()))
+    throw Error("pointwise_chain_out_batch_oriented: as many parameter sets, orientations and destinations as frames");
+  const ipk_chain_params *p = params.data();
+  check(ipk_pointwise_chain_out_batch_oriented(srcs4.data(), width, height, monochrome ? 1 : 0, p, orientations.empty() ? nullptr : orientations.data(),
+                                               srcs4.size(), linear ? 1 : 0, out_type, dsts.data(), stream), "pointwise_chain_out_batch_oriented");
 }
 
 // ---- several devices from ONE process (imagepipe_amd.h, "Several devices from ONE process") --------------------------------------------------
