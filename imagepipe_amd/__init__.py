@@ -15,9 +15,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (IpkError, FusedParams, PipelineDesc, ChainParams, OUT_F32, OUT_U8, OUT_U16, SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16,
+from ._lib import (IpkError, FusedParams, PipelineDesc, ChainParams, ScaledFrame, OUT_F32, OUT_U8, OUT_U16, SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16,
                    OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN,
-                   ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO, FUSED_BATCH_PREVIEWS, FUSED_BATCH_ORIENTED)
+                   ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO, FUSED_BATCH_PREVIEWS, FUSED_BATCH_ORIENTED,
+                   FUSED_BATCH_SENSOR)
 
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
@@ -25,6 +26,7 @@ __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", 
            "transform_window_footprint", "raw_scaled_demosaic_window", "raw_demosaic_scaled", "raster_scale_down_window", "scaled_window_footprint", "plain_scale_down",
            "plain_scale_down_window", "raw_scaled_demosaic_batch", "plain_scale_down_batch", "chain_params", "pointwise_chain_out_batch",
            "batch_each_plan", "run_batch_each", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FUSED_BATCH_PREVIEWS", "FUSED_BATCH_ORIENTED",
+           "FUSED_BATCH_SENSOR", "scaled_frame", "scaled_demosaic_batch_each",
            "FusedPlan", "IpkError"]
 
 _initialized_device = None
@@ -613,6 +615,7 @@ class Pipeline:
         self.scale_plain = False              # ipk_pipeline_desc.allow_fused bit 7 (IPK_FUSED_PLAIN_PREVIEWS): downscaled previews of monochrome / three-sample raws (u16, f32) run gofloat + demosaic as the one launch ipk_plain_scale_down where scales_plain() says so; window_previews and fuse_scaled_rotatecrop then take them too
         self.batch_previews = False           # ipk_pipeline_desc.allow_fused bit 8 (IPK_FUSED_BATCH_PREVIEWS): run_batch() runs downscaled previews as one scaling launch group and one point-wise pass per chunk of frames where batches_previews() says so
         self.batch_oriented = False           # ipk_pipeline_desc.allow_fused bit 9 (IPK_FUSED_BATCH_ORIENTED), set only together with batch_previews: batched previews take frames of any orientation (OpTransform folded into the point-wise pass), and run_batch_each lets rotation / fliph / flipv differ inside a run
+        self.batch_sensor = False             # ipk_pipeline_desc.allow_fused bit 10 (IPK_FUSED_BATCH_SENSOR), set only together with batch_previews: run_batch_each lets width, height, cfa, the crops and the levels differ inside a run whose frames negotiate one demosaic size (one frame-table scaling launch per chunk)
         self.window_previews = False          # ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
 
     @staticmethod
@@ -692,6 +695,8 @@ class Pipeline:
             d.allow_fused |= _lib.FUSED_BATCH_PREVIEWS
             if self.batch_oriented:
                 d.allow_fused |= _lib.FUSED_BATCH_ORIENTED
+            if self.batch_sensor:
+                d.allow_fused |= _lib.FUSED_BATCH_SENSOR
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -1126,6 +1131,33 @@ def plain_scale_down_batch(srcs: Sequence[torch.Tensor], kind, owidth, x, y, wid
     return out
 
 
+def scaled_frame(owidth, x, y, width, height, black4, white4, cfa=""):
+    """ipk_scaled_frame: one frame of scaled_demosaic_batch_each -- its pitch in pixels, sensor window, levels (a number, or up to four) and filter"""
+    f = ScaledFrame()
+    f.owidth, f.x, f.y, f.width, f.height = owidth, x, y, width, height
+    lv = lambda v: _farr((list(np.atleast_1d(np.asarray(v, np.float32))) + [0.0] * 4)[:4], 4)
+    f.black4, f.white4 = lv(black4), lv(white4)
+    f.cfa = cfa.encode() if isinstance(cfa, str) else bytes(cfa)
+    return f
+
+
+def scaled_demosaic_batch_each(srcs: Sequence[torch.Tensor], frames, nwidth, nheight, *, kind=-1, is_float=None, out: Optional[torch.Tensor] = None):
+    """ipk_scaled_demosaic_batch_each: gofloat + scaled_demosaic (kind -1, mosaics) or plain_scale_down (PLAIN_RGB / PLAIN_MONO) of len(srcs) sensor frames
+    of one sample type, frame i with the pitch, window, levels and filter of frames[i] (scaled_frame()), into len(srcs) packed nwidth x nheight results:
+    one frame-table launch of the general scaling kernel per 64 frames.  Every frame must select that kernel (a skip above 7 or below 1, or under 8
+    samples wide; every plain frame).  Returns the n*nheight*nwidth*4 f32 device tensor; slice i is what the single-frame call gives for frame i."""
+    n = len(srcs)
+    if len(frames) != n:
+        raise ValueError("scaled_demosaic_batch_each: as many frame records as frames")
+    st = SRC_F32 if (srcs[0].dtype == torch.float32 if n else bool(is_float)) else SRC_U16
+    if out is None:
+        out = torch.empty(n * nheight * nwidth * 4, dtype=torch.float32, device="cuda")
+    arr = (ScaledFrame * max(n, 1))(*frames)
+    _lib.check(lib().ipk_scaled_demosaic_batch_each(_frame_ptrs(srcs), arr, n, st, kind, nwidth, nheight, out.data_ptr(), _stream()),
+               "ipk_scaled_demosaic_batch_each")
+    return out
+
+
 def chain_params(wb_coeffs=(1.0, 1.0, 1.0, 0.0), cam_to_xyz_normalized=None, exposure=0.0, points=()):
     """ipk_chain_params: the descriptor fields OpToLab and OpBaseCurve read, for one frame of pointwise_chain_out_batch.  points: (x, y) pairs"""
     p = ChainParams()
@@ -1176,7 +1208,8 @@ def _desc_ptrs(pipes):
 def batch_each_plan(pipes, out_type=OUT_F32):
     """The plan run_batch_each follows (ipk_pipeline_batch_each_plan, host-only): per frame (route, run_first) -- route 0 a single run, 1 the uniform
     batch, 2 varied previews (one scaling launch group and ONE point-wise launch per chunk, per-frame parameters from a device table); run_first the
-    first frame of the frame's run of same-shaped descriptors."""
+    first frame of the frame's run of same-shaped descriptors.  With batch_sensor set on the members as well, frames that differ in sensor size, crops,
+    filter or levels share a run where each selects the general scaling kernel and all negotiate one demosaic size."""
     n = len(pipes)
     _ds, dp = _desc_ptrs(pipes)
     route, first = (C.c_int * max(n, 1))(), (C.c_size_t * max(n, 1))()
@@ -1188,7 +1221,8 @@ def run_batch_each(pipes, srcs: Sequence[torch.Tensor], out_type=OUT_F32, outs: 
     """A shoot whose files carry their own colour settings (ipk_pipeline_run_batch_each): one Pipeline per frame -- each with its own white balance,
     matrix, exposure and curve -- and srcs[i] shaped like pipes[i]'s own source.  Results are what pipes[i].run() / output_8bit() / output_16bit() give
     frame by frame; frames that differ only in those point-wise settings -- and, with batch_oriented set on every member as well, in rotation, fliph
-    and flipv -- run as batched previews where batch_each_plan() says 2 (batch_previews set on every member).  Returns the list of (h, w, 3) device tensors of the output type (u16 bits in int16) -- `outs` when given, else fresh ones -- and sets
+    and flipv, and with batch_sensor in width, height, cfa, the crops and the levels (one frame-table scaling launch per chunk) -- run as batched
+    previews where batch_each_plan() says 2 (batch_previews set on every member).  Returns the list of (h, w, 3) device tensors of the output type (u16 bits in int16) -- `outs` when given, else fresh ones -- and sets
     every member's last_used_fused to what the last frame's run leaves."""
     n = len(pipes)
     if len(srcs) != n:

@@ -18,6 +18,7 @@ FUSED_SCALED_ROTATECROP = 64
 FUSED_PLAIN_PREVIEWS = 128
 FUSED_BATCH_PREVIEWS = 256
 FUSED_BATCH_ORIENTED = 512
+FUSED_BATCH_SENSOR = 1024
 PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO = 0, 1, 2                                                          # ipk_plain_kind
 OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN = range(9)
 ROT_NORMAL, ROT_90, ROT_180, ROT_270 = range(4)
@@ -76,6 +77,14 @@ class ChainParams(_SizedDesc):
     _fields_ = [
         ("struct_size", C.c_uint32), ("wb_coeffs", C.c_float * 4), ("cam_to_xyz_normalized", C.c_float * 12),
         ("exposure", C.c_float), ("npoints", C.c_int), ("points", C.c_float * 128),
+    ]
+
+
+class ScaledFrame(_SizedDesc):
+    """ipk_scaled_frame: the sensor window, levels and filter of one frame of ipk_scaled_demosaic_batch_each"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("owidth", _sz), ("x", _sz), ("y", _sz), ("width", _sz), ("height", _sz),
+        ("black4", C.c_float * 4), ("white4", C.c_float * 4), ("cfa", C.c_char * 160),
     ]
 
 
@@ -150,6 +159,7 @@ SIGNATURES = {
     "ipk_plain_scale_down_window": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz, _sz, _sz, _fp, _fp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _vp]),
     "ipk_raw_scaled_demosaic_batch": (C.c_int, [C.POINTER(_vp), _sz, C.c_int, _sz, _sz, _sz, _sz, _sz, C.c_float, C.c_float, C.c_char_p, _sz, _sz, _vp, _vp]),
     "ipk_plain_scale_down_batch": (C.c_int, [C.POINTER(_vp), _sz, C.c_int, C.c_int, _sz, _sz, _sz, _sz, _sz, _fp, _fp, _sz, _sz, _vp, _vp]),
+    "ipk_scaled_demosaic_batch_each": (C.c_int, [C.POINTER(_vp), C.POINTER(ScaledFrame), _sz, C.c_int, C.c_int, _sz, _sz, _vp, _vp]),
     "ipk_scaled_window_footprint": (C.c_int, [_sz, _sz, _sz, _sz, _sz, _sz, _sz, _sz, _szp]),
     "ipk_demosaic_run": (C.c_int, [_vp, _sz, _sz, _sz, C.c_char_p, _sz, _sz, _vp, _szp, _szp, _vp]),
     "ipk_rotatecrop": (C.c_int, [_vp, _sz, _sz, _sz, _fp, _vp, _szp, _szp, _vp]),

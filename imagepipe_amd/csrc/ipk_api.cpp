@@ -2989,17 +2989,76 @@ bool batches_previews(const ipk_pipeline_desc *d, const Negotiated &n, const Rou
     bool t, fx, fy; ipk::orientation_to_flips(n.orientation, t, fx, fy);
     if (!opted(d, IPK_FUSED_BATCH_ORIENTED) || (t ? n.dh : n.dw) != n.fw || (t ? n.dw : n.dh) != n.fh) return false;
   }
-  bp.chunk = std::min<size_t>(64, std::max<size_t>(1, ((size_t)256 << 20) / (n.dw * n.dh * 16)));
-  bp.pass1_batched = n.raw && ipk::raw_scaled_demosaic_general(n.r.width, n.r.height, n.dw, n.dh, true, !n.cfa_branch);
+  // (a descriptor no launch would take -- a preview of 2^24 pixels and more, whose byte count may wrap to 0, or a sensor side of 2^31 and more, which the
+  // kernel selection cannot convert -- still gets an answer here: a frame per chunk, no batch launch)
+  const size_t cap_px = (size_t)1 << 24;                                    // 256 MiB of RGBE
+  bp.chunk = n.dw > cap_px / n.dh ? 1 : std::min<size_t>(64, std::max<size_t>(1, ((size_t)256 << 20) / (n.dw * n.dh * 16)));
+  bp.pass1_batched = n.raw && dims_ok(n.r.width, n.r.height) && ipk::raw_scaled_demosaic_general(n.r.width, n.r.height, n.dw, n.dh, true, !n.cfa_branch);
   return true;
+}
+// ipk_scaled_demosaic_batch_each: every frame validated and admitted (its filter's device table fetched) before anything is enqueued, then one frame-table
+// launch per 64 frames (launch_raw_scaled_demosaic_each), its table in the scratch pool.  stage: the name marked behind every launch
+int scaled_batch_each_impl(const void *const *srcs, const ipk_scaled_frame *frames, size_t n, int src_type, int kind, size_t nwidth, size_t nheight, float *dst4,
+                           void *stream, StageTimer &tm, const char *stage) {
+  if (n == 0) return IPK_OK;
+  if (kind == IPK_PLAIN_RASTER) return fail(IPK_ERR_UNSUPPORTED, "scaled_demosaic_batch_each: the raster scaler has no frame-table mode");
+  if (kind != -1 && kind != IPK_PLAIN_RGB && kind != IPK_PLAIN_MONO) return fail(IPK_ERR_INVALID, "bad kind");
+  if (!srcs || !frames || !dst4 || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32) || n > (size_t)1 << 20)
+    return fail(IPK_ERR_INVALID, "bad scaled_demosaic_batch_each arguments");
+  const bool plain = kind != -1;
+  std::vector<ipk::ScaledFrameLaunch> fl(n);
+  for (size_t i = 0; i < n; ++i) {
+    const ipk_scaled_frame &f = frames[i];
+    if (!srcs[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
+    if (f.struct_size != sizeof(ipk_scaled_frame))
+      return fail(IPK_ERR_INVALID, "frames[%zu].struct_size is %u, not sizeof(ipk_scaled_frame) = %zu", i, f.struct_size, sizeof(ipk_scaled_frame));
+    if (!dims_ok(f.width, f.height)) return fail(IPK_ERR_INVALID, "frames[%zu]: bad dimensions", i);
+    if (f.x > f.owidth || f.width > f.owidth - f.x) return fail(IPK_ERR_INVALID, "frames[%zu]: window wider than the source pitch", i);
+    ipk::ScaledFrameLaunch &l = fl[i];
+    l.src = srcs[i]; l.owidth = f.owidth; l.x = f.x; l.y = f.y; l.width = f.width; l.height = f.height; l.cfa48_dev = nullptr;
+    for (int c = 0; c < 3; ++c) { l.black[c] = f.black4[plain ? c : 0]; l.white[c] = f.white4[plain ? c : 0]; }
+    if (!plain) {
+      char pat[sizeof(f.cfa)]; std::memcpy(pat, f.cfa, sizeof(pat)); pat[sizeof(pat) - 1] = 0;
+      ipk::Cfa cfa; DevCfa dev;
+      const int rc = get_cfa(pat, cfa, dev);
+      if (rc) { const std::string why = g_err; return fail(rc, "frames[%zu]: %s", i, why.c_str()); }
+      l.cfa48_dev = dev.cfa48;
+    }
+    if (!ipk::raw_scaled_demosaic_general(f.width, f.height, nwidth, nheight, true, plain))
+      return fail(IPK_ERR_UNSUPPORTED, "frames[%zu]: %zux%zu -> %zux%zu selects a window-8 kernel, which has no frame-table mode", i, f.width, f.height, nwidth, nheight);
+  }
+  const size_t slice = nwidth * nheight * 4;
+  for (size_t i0 = 0; i0 < n; i0 += ipk::kScaledEachMax) {
+    const size_t m = std::min(ipk::kScaledEachMax, n - i0);
+    Scratch sc(S(stream));
+    void *table = nullptr;
+    { const int rc = sc.get(ipk::scaled_each_table_bytes(m), &table); if (rc) return rc; }
+    const int lrc = ipk::launch_raw_scaled_demosaic_each(fl.data() + i0, m, src_type == IPK_SRC_U16, plain ? (kind == IPK_PLAIN_MONO ? 1 : 3) : 0, nwidth, nheight,
+                                                         dst4 + i0 * slice, table, S(stream));
+    if (lrc == -4) return fail(IPK_ERR_HIP, "scaled_demosaic_batch_each: the table upload or the launch could not be enqueued");
+    if (lrc != 0) return fail(IPK_ERR_INVALID, "scaled_demosaic_batch_each: the launcher refused the frames");
+    tm.mark(stage);
+  }
+  return IPK_OK;
+}
+// the sensor fields of a descriptor: what IPK_FUSED_BATCH_SENSOR lets differ inside a run (cfa_width / cfa_height are folded into cfa)
+bool same_bits(const float *a, const float *b, size_t n);
+bool same_sensor(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) {
+  return a.width == b.width && a.height == b.height && std::strcmp(a.cfa, b.cfa) == 0 && a.cfa_width == b.cfa_width && a.cfa_height == b.cfa_height &&
+         a.crop_top == b.crop_top && a.crop_right == b.crop_right && a.crop_bottom == b.crop_bottom && a.crop_left == b.crop_left &&
+         same_bits(a.blacklevels, b.blacklevels, 4) && same_bits(a.whitelevels, b.whitelevels, 4);
 }
 // The chunk walk both preview batches share (run_batch_previews, run_batch_each's varied runs): d states the levels, crops, filter and size limit of every
 // frame.  A chunk of one frame is single(i); a longer one gets its scratch, pass 1 -- the chunk's RGBE previews one after another, slice floats apart --
-// and then pass2(i0, m, rgbe, slice, tm), which enqueues the point-wise work of frames i0 .. i0 + m and marks its stages
+// and then pass2(i0, m, rgbe, slice, tm), which enqueues the point-wise work of frames i0 .. i0 + m and marks its stages.
+// each / ngs (optional, n entries: a varied run under IPK_FUSED_BATCH_SENSOR whose frames differ in their sensor fields; bp.pass1_batched holds for every one
+// of them): frame i's levels, crops and filter are each[i]'s, its window ngs[i]'s.  A chunk whose frames agree in them is the uniform launch on the chunk's
+// first descriptor, another is ONE frame-table launch (scaled_batch_each_impl), marked "batch-each gofloat+demosaic"
 extern "C++" template <typename Single, typename Pass2>
 int run_preview_chunks(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, size_t n, void *stream, Single single,
-                       Pass2 pass2) {
+                       Pass2 pass2, const ipk_pipeline_desc *each = nullptr, const Negotiated *ngs = nullptr) {
   const size_t slice = ng.dw * ng.dh * 4;
+  std::vector<ipk_scaled_frame> sf;
   for (size_t i0 = 0; i0 < n; i0 += bp.chunk) {
     const size_t m = std::min(bp.chunk, n - i0);
     if (m == 1) { const int rc = single(i0); if (rc < 0) return rc; continue; }
@@ -3008,16 +3067,33 @@ int run_preview_chunks(const ipk_pipeline_desc *d, const Negotiated &ng, const B
     void *buf = nullptr;
     int rc = sc.get(m * slice * sizeof(float), &buf); if (rc) return rc;
     float *rgbe = static_cast<float *>(buf);
-    if (bp.pass1_batched) {
-      rc = ng.cfa_branch ? raw_scaled_demosaic_batch_impl(srcs + i0, m, d->src_type, d->width, ng.r.x, ng.r.y, ng.r.width, ng.r.height, d->blacklevels[0],
-                                                          d->whitelevels[0], d->cfa, ng.dw, ng.dh, rgbe, stream)
-                         : plain_scale_down_batch_impl(srcs + i0, m, d->src_type, d->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO, d->width, ng.r.x, ng.r.y, ng.r.width,
-                                                       ng.r.height, d->blacklevels, d->whitelevels, ng.dw, ng.dh, rgbe, stream);
+    const ipk_pipeline_desc *const dc = each ? &each[i0] : d;              // the chunk's first descriptor states a uniform launch's sensor settings
+    const Negotiated &nc = each ? ngs[i0] : ng;
+    bool table = false;
+    if (each) for (size_t i = 1; i < m; ++i) table = table || !same_sensor(each[i0], each[i0 + i]);
+    if (table) {
+      sf.assign(m, ipk_scaled_frame{});
+      for (size_t i = 0; i < m; ++i) {
+        const ipk_pipeline_desc &di = each[i0 + i]; const Negotiated &ni = ngs[i0 + i];
+        ipk_scaled_frame &f = sf[i];
+        f.struct_size = (uint32_t)sizeof(f);
+        f.owidth = di.width; f.x = ni.r.x; f.y = ni.r.y; f.width = ni.r.width; f.height = ni.r.height;
+        std::memcpy(f.black4, di.blacklevels, sizeof(f.black4)); std::memcpy(f.white4, di.whitelevels, sizeof(f.white4));
+        std::memcpy(f.cfa, di.cfa, sizeof(f.cfa));
+      }
+      rc = scaled_batch_each_impl(srcs + i0, sf.data(), m, d->src_type, ng.cfa_branch ? -1 : (d->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO), ng.dw, ng.dh, rgbe, stream,
+                                  tm, "batch-each gofloat+demosaic");
+      if (rc < 0) return rc;
+    } else if (bp.pass1_batched) {
+      rc = nc.cfa_branch ? raw_scaled_demosaic_batch_impl(srcs + i0, m, dc->src_type, dc->width, nc.r.x, nc.r.y, nc.r.width, nc.r.height, dc->blacklevels[0],
+                                                          dc->whitelevels[0], dc->cfa, nc.dw, nc.dh, rgbe, stream)
+                         : plain_scale_down_batch_impl(srcs + i0, m, dc->src_type, dc->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO, dc->width, nc.r.x, nc.r.y, nc.r.width,
+                                                       nc.r.height, dc->blacklevels, dc->whitelevels, nc.dw, nc.dh, rgbe, stream);
       if (rc < 0) return rc;
     } else {
-      for (size_t i = 0; i < m; ++i) { rc = launch_gofloat_demosaic(d, ng, srcs[i0 + i], nullptr, rgbe + i * slice, stream); if (rc < 0) return rc; }
+      for (size_t i = 0; i < m; ++i) { rc = launch_gofloat_demosaic(dc, nc, srcs[i0 + i], nullptr, rgbe + i * slice, stream); if (rc < 0) return rc; }
     }
-    tm.mark("batch gofloat+demosaic");
+    if (!table) tm.mark("batch gofloat+demosaic");
     rc = pass2(i0, m, rgbe, slice, tm); if (rc < 0) return rc;
   }
   return IPK_OK;
@@ -3124,15 +3200,14 @@ int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height,
 // Same-shaped: every field equal but the five OpToLab and OpBaseCurve read -- and, where both descriptors carry IPK_FUSED_BATCH_ORIENTED beside the two bits
 // it acts with, the three OpTransform reads (plan_each then holds the negotiated demosaic sizes against each other).  a and b are taken and folded (so cfa compares as the drivers read it and
 // padding never enters); sa / sb are the struct_size values the callers wrote.  Floats compare by their bits
+// sensor_ok (IPK_FUSED_BATCH_SENSOR; plan_each holds the rest of its rule): the eleven sensor fields -- same_sensor's -- are not compared either
 bool same_bits(const float *a, const float *b, size_t n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
 bool same_orientation(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) { return a.rotation == b.rotation && a.fliph == b.fliph && a.flipv == b.flipv; }
-bool same_shape(const ipk_pipeline_desc &a, uint32_t sa, const ipk_pipeline_desc &b, uint32_t sb, bool oriented_ok = false) {
-  return sa == sb && a.src_type == b.src_type && a.width == b.width && a.height == b.height && a.cpp == b.cpp && a.is_cfa == b.is_cfa &&
-         std::strcmp(a.cfa, b.cfa) == 0 && a.crop_top == b.crop_top && a.crop_right == b.crop_right && a.crop_bottom == b.crop_bottom &&
-         a.crop_left == b.crop_left && same_bits(a.blacklevels, b.blacklevels, 4) && same_bits(a.whitelevels, b.whitelevels, 4) &&
+bool same_shape(const ipk_pipeline_desc &a, uint32_t sa, const ipk_pipeline_desc &b, uint32_t sb, bool oriented_ok = false, bool sensor_ok = false) {
+  return sa == sb && a.src_type == b.src_type && a.cpp == b.cpp && a.is_cfa == b.is_cfa && (sensor_ok || same_sensor(a, b)) &&
          same_bits(a.rotatecrop, b.rotatecrop, 5) && (oriented_ok || same_orientation(a, b)) && a.maxwidth == b.maxwidth &&
          a.maxheight == b.maxheight && a.linear == b.linear && a.allow_fused == b.allow_fused && a.use_fastpath == b.use_fastpath &&
-         a.cfa_width == b.cfa_width && a.cfa_height == b.cfa_height && a.schedule == b.schedule && a.fuse_rotatecrop == b.fuse_rotatecrop &&
+         a.schedule == b.schedule && a.fuse_rotatecrop == b.fuse_rotatecrop &&
          a.reserved1 == b.reserved1 && a.fuse_scaledown == b.fuse_scaledown;
 }
 bool same_pointwise(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) {
@@ -3148,7 +3223,8 @@ enum { kEachSingle = 0, kEachUniform = 1, kEachVaried = 2 };
 struct EachPlan {
   std::vector<ipk_pipeline_desc> d;                  // taken and folded
   std::vector<int> route; std::vector<size_t> run_first;
-  struct Varied { Negotiated ng; BatchPreviews bp; };
+  struct Varied { Negotiated ng; BatchPreviews bp; bool sensor = false; };   // sensor: the run's frames differ in their sensor fields (IPK_FUSED_BATCH_SENSOR)
+  std::vector<Negotiated> ng;                        // of the frames that qualify for IPK_FUSED_BATCH_SENSOR (others: not read)
   std::map<size_t, Varied> varied;                   // by the run's first frame
 };
 // validates every descriptor as ipk_pipeline_run does (and the curve's point count, as the batch driver does), then cuts the runs
@@ -3165,6 +3241,11 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
   // flipv too, while both negotiate the same demosaic size (the scaling pass's filter): ori[i] = the frame qualifies, dwh[i] = that size
   std::vector<char> ori(n, 0);
   std::vector<std::pair<size_t, size_t>> dwh(n);
+  // IPK_FUSED_BATCH_SENSOR: a frame whose own batch of previews runs pass 1 as the general kernel's batch launch may differ from its neighbour in the sensor
+  // fields (same_sensor) too, while both negotiate the same demosaic size and agree in whether the filter has a fourth colour (src_type, cpp and is_cfa,
+  // hence the kernel's layout and the chain's monochrome flag, count as shape anyway): sen[i] = the frame qualifies, four[i] = its filter has one
+  std::vector<char> sen(n, 0), four(n, 0);
+  p.ng.resize(n);
   for (size_t i = 0; i < n; ++i) {
     if (!descs[i]) return fail(IPK_ERR_INVALID, "null descriptor at index %zu", i);
     sizes[i] = descs[i]->struct_size;
@@ -3181,18 +3262,29 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
           ori[i] = batches_previews(&p.d[i], ng, rt, 2, bp);
           dwh[i] = {ng.dw, ng.dh};
         }
+        if (!rc && opted(&p.d[i], IPK_FUSED_BATCH_PREVIEWS) && opted(&p.d[i], IPK_FUSED_BATCH_SENSOR)) {
+          Route rt; BatchPreviews bp;
+          choose_route(&p.d[i], ng, out_type, rt);
+          sen[i] = batches_previews(&p.d[i], ng, rt, 2, bp) && bp.pass1_batched;
+          dwh[i] = {ng.dw, ng.dh};
+          if (sen[i] && ng.cfa_branch) { ipk::Cfa cfa; four[i] = ipk::Cfa::parse(p.d[i].cfa, cfa) && cfa.valid() && !cfa.three_colour(); }
+          p.ng[i] = ng;
+        }
       }
     }
     if (rc) { const std::string why = g_err; return fail(rc, "descriptor %zu: %s", i, why.c_str()); }
   }
   for (size_t a = 0; a < n;) {
     size_t b = a + 1;
-    while (b < n && fast[a] == fast[b] && same_shape(p.d[a], sizes[a], p.d[b], sizes[b], ori[a] && ori[b] && dwh[a] == dwh[b])) ++b;
+    while (b < n && fast[a] == fast[b] && same_shape(p.d[a], sizes[a], p.d[b], sizes[b], ori[a] && ori[b] && dwh[a] == dwh[b],
+                                                     sen[a] && sen[b] && dwh[a] == dwh[b] && four[a] == four[b])) ++b;
     for (size_t i = a; i < b; ++i) p.run_first[i] = a;
     const size_t m = b - a;
     bool all_equal = true;
-    for (size_t i = a + 1; i < b; ++i) all_equal = all_equal && same_pointwise(p.d[a], p.d[i]) && same_orientation(p.d[a], p.d[i]);
     EachPlan::Varied v; Route rt;
+    for (size_t i = a + 1; i < b; ++i) v.sensor = v.sensor || !same_sensor(p.d[a], p.d[i]);
+    for (size_t i = a + 1; i < b; ++i) all_equal = all_equal && same_pointwise(p.d[a], p.d[i]) && same_orientation(p.d[a], p.d[i]);
+    all_equal = all_equal && !v.sensor;
     if (m > 1 && !all_equal && !fast[a] && opted(&p.d[a], IPK_FUSED_BATCH_PREVIEWS) &&
         negotiate(&p.d[a], out_type, v.ng) == IPK_OK && (choose_route(&p.d[a], v.ng, out_type, rt), batches_previews(&p.d[a], v.ng, rt, m, v.bp))) {
       for (size_t i = a; i < b; ++i) p.route[i] = kEachVaried;
@@ -3200,7 +3292,7 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
     } else {
       for (size_t j = a; j < b;) {                   // maximal sub-runs of equal descriptors: the uniform batch, which keeps its own routes
         size_t k = j + 1;
-        while (k < b && same_pointwise(p.d[j], p.d[k]) && same_orientation(p.d[j], p.d[k])) ++k;
+        while (k < b && same_pointwise(p.d[j], p.d[k]) && same_orientation(p.d[j], p.d[k]) && same_sensor(p.d[j], p.d[k])) ++k;
         if (k - j > 1) for (size_t i = j; i < k; ++i) p.route[i] = kEachUniform;
         j = k;
       }
@@ -3211,8 +3303,8 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
 }
 // a varied run: the chunks and pass 1 of run_batch_previews on the run's first descriptor, then ONE frame-table launch per chunk, frame i's record from
 // descriptor i -- its composed orientation included, where the run's frames carry their own -- and its destination dsts[i] wherever it lies
-int run_batch_each_varied(const ipk_pipeline_desc *ds, const EachPlan::Varied &v, const void *const *srcs, void *const *dsts, size_t n, int out_type,
-                          int *used_fused, void *stream) {
+int run_batch_each_varied(const ipk_pipeline_desc *ds, const EachPlan::Varied &v, const Negotiated *ngs, const void *const *srcs, void *const *dsts, size_t n,
+                          int out_type, int *used_fused, void *stream) {
   const int monochrome = one_pass_monochrome(ds, v.ng);
   const char *stage = out_type == IPK_OUT_F32 ? "batch-each to_lab+basecurve+from_lab+gamma" : "batch-each to_lab+basecurve+from_lab+gamma+quantise";
   const char *stage_oriented = out_type == IPK_OUT_F32 ? "batch-each to_lab+basecurve+from_lab+gamma+transform"
@@ -3231,7 +3323,7 @@ int run_batch_each_varied(const ipk_pipeline_desc *ds, const EachPlan::Varied &v
       if (used_fused) *used_fused = 0;
       return chain_out_batch_impl(s4.data(), v.ng.dw, v.ng.dh, monochrome, cp.data(), ori.data(), m, v.ng.linear, out_type, dsts + i0, stream, tm, stage,
                                   stage_oriented);
-    });
+    }, v.sensor ? ds : nullptr, v.sensor ? ngs : nullptr);
 }
 }  // namespace
 
@@ -3288,6 +3380,14 @@ int ipk_pointwise_chain_out_batch_oriented(const float *const *srcs4, size_t wid
   return chain_out_batch_impl(srcs4, width, height, monochrome, static_cast<const ipk_chain_params *>(params), orientations, n, linear, out_type, dsts, stream,
                               tm, "pointwise_chain_out_batch_oriented");
 }
+// ipk_raw_scaled_demosaic / ipk_plain_scale_down for n frames with their own windows, levels and filters into one result size: one frame-table launch per 64
+int ipk_scaled_demosaic_batch_each(const void *const *srcs, const void *frames, size_t n, int src_type, int kind, size_t nwidth, size_t nheight, float *dst4,
+                                   void *stream) {
+  REQUIRE_INIT();
+  StageTimer tm(S(stream));
+  return scaled_batch_each_impl(srcs, static_cast<const ipk_scaled_frame *>(frames), n, src_type, kind, nwidth, nheight, dst4, stream, tm,
+                                "scaled_demosaic_batch_each");
+}
 // The plan of ipk_pipeline_run_batch_each, for callers and CPU tests (no GPU)
 int ipk_pipeline_batch_each_plan(const ipk_pipeline_desc *const *descs, size_t n, int out_type, int *route, size_t *run_first) {
   EachPlan p;
@@ -3316,9 +3416,10 @@ int ipk_pipeline_run_batch_each(const ipk_pipeline_desc *const *descs, const voi
   if (used_fused) *used_fused = 0;
   for (size_t a = 0; a < n;) {
     size_t b = a + 1;
-    while (b < n && p.route[b] == p.route[a] && p.run_first[b] == p.run_first[a] && (p.route[a] != kEachUniform || (same_pointwise(p.d[a], p.d[b]) && same_orientation(p.d[a], p.d[b])))) ++b;
+    while (b < n && p.route[b] == p.route[a] && p.run_first[b] == p.run_first[a] &&
+           (p.route[a] != kEachUniform || (same_pointwise(p.d[a], p.d[b]) && same_orientation(p.d[a], p.d[b]) && same_sensor(p.d[a], p.d[b])))) ++b;
     int rc;
-    if (p.route[a] == kEachVaried) rc = run_batch_each_varied(&p.d[a], p.varied.at(a), srcs + a, dsts + a, b - a, out_type, used_fused, stream);
+    if (p.route[a] == kEachVaried) rc = run_batch_each_varied(&p.d[a], p.varied.at(a), &p.ng[a], srcs + a, dsts + a, b - a, out_type, used_fused, stream);
     else if (p.route[a] == kEachUniform) rc = ipk_pipeline_run_batch(&p.d[a], srcs + a, dsts + a, b - a, out_type, used_fused, stream);
     else { b = a + 1; rc = ipk_pipeline_run(&p.d[a], srcs[a], dsts[a], out_type, used_fused, stream); }
     if (rc < 0) return rc;

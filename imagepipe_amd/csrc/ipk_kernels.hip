@@ -674,25 +674,46 @@ void launch_raster_scale_down(const void *src, int src_is_u16, size_t owidth, si
 constexpr int kBatchMax = 64;
 // k_raw_scaled_demosaic's batch mode (launch-uniform): on = 1, gridDim.z frames of one shape whose sources are src[0 .. gridDim.z); on = 0 (gridDim.z
 // == 1): the kernel's own src and dst arguments, src[] is not read
-struct ScaledBatch { const void *src[kBatchMax]; uint32_t on; };
+// on = 2 (frame-table mode, launch_raw_scaled_demosaic_each): gridDim.z frames of one result size and layout, frame z described by frames[z]; src[] is not read
+struct ScaledBatch { const void *src[kBatchMax]; uint32_t on; const struct ScaledFrame *frames; };
+// One frame of a frame-table launch: everything of TransformArgs that follows from a frame's own sensor window and levels, with its source and (mosaics) its
+// filter's 48 x 48 device table.  nwidth, nheight, layout and the output window stay the launch's
+struct ScaledFrame {
+  const void *src; const uint8_t *cfa48;
+  uint64_t src_pitch, src_x, src_y;
+  uint32_t width, height;
+  float skip_x_x, skip_y_y, inv_skip_x_x, inv_skip_y_y;
+  int fast_x, fast_y;
+  float min0, range0, min1, range1, min2, range2;
+};
 
 // OpGoFloat (CFA branch) + scaling::scaled_demosaic in one pass over the raw sensor frame: dst4 = scaled_demosaic(gofloat(src)).
 // T = uint16_t or float sensor samples; writes f32 RGBE.  (src/ops/gofloat.rs:122-130,158-166 + src/scaling.rs:132-145)
 // Batch mode (bp.on): blockIdx.z is the frame -- its source comes from bp, its result is the z-th out_rows x out_cols slice behind dst.  Nothing else a lane
-// computes depends on z: bounds, centres, weights, the CFA phase and the store's row and column are functions of the absolute row and column as ever
+// computes depends on z: bounds, centres, weights, the CFA phase and the store's row and column are functions of the absolute row and column as ever.
+// Frame-table mode (bp.on == 2): the frame's sensor window, skips, levels and filter come from its ScaledFrame record as well; block-uniform as before
 template <typename T>
-__global__ void k_raw_scaled_demosaic(const T *__restrict__ src0, TransformArgs a, const uint8_t *__restrict__ cfa48, float *__restrict__ dst0, ScaledBatch bp) {
+__global__ void k_raw_scaled_demosaic(const T *__restrict__ src0, TransformArgs a, const uint8_t *__restrict__ cfa480, float *__restrict__ dst0, ScaledBatch bp) {
   __shared__ uint8_t s_cfa[48 * 48];
   const bool mosaic = a.layout == 0;                                        // launch-uniform: so is the barrier
+  const T *__restrict__ src = src0;
+  const uint8_t *__restrict__ cfa48 = cfa480;
+  float *__restrict__ dst = dst0;
+  if (bp.on == 2) {
+    // Frame-table mode: the block's frame brings its own window, skips, levels and filter.  One record, read through an address that depends on blockIdx.z
+    // alone (scalar loads), replaces the launch's values; the walk below is the same code on them
+    const ScaledFrame &f = bp.frames[blockIdx.z];
+    src = static_cast<const T *>(f.src); cfa48 = f.cfa48;
+    a.src_pitch = f.src_pitch; a.src_x = f.src_x; a.src_y = f.src_y; a.width = f.width; a.height = f.height;
+    a.skip_x_x = f.skip_x_x; a.skip_y_y = f.skip_y_y; a.inv_skip_x_x = f.inv_skip_x_x; a.inv_skip_y_y = f.inv_skip_y_y; a.fast_x = f.fast_x; a.fast_y = f.fast_y;
+    a.min0 = f.min0; a.range0 = f.range0; a.min1 = f.min1; a.range1 = f.range1; a.min2 = f.min2; a.range2 = f.range2;
+  } else if (bp.on) {
+    src = static_cast<const T *>(bp.src[blockIdx.z]);
+  }
+  if (bp.on) dst = dst0 + (size_t)blockIdx.z * (a.out_r1 - a.out_r0) * (a.out_c1 - a.out_c0) * 4;
   if (mosaic) {
     for (int i = threadIdx.x; i < 48 * 48; i += blockDim.x) s_cfa[i] = cfa48[i];
     __syncthreads();
-  }
-  const T *__restrict__ src = src0;
-  float *__restrict__ dst = dst0;
-  if (bp.on) {
-    src = static_cast<const T *>(bp.src[blockIdx.z]);
-    dst = dst0 + (size_t)blockIdx.z * (a.out_r1 - a.out_r0) * (a.out_c1 - a.out_c0) * 4;
   }
   const uint32_t col = a.out_c0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (col >= a.out_c1) return;
@@ -1216,7 +1237,7 @@ static void launch_raw_scaled_demosaic_typed(const ScaledDemosaicLaunch &l, hipS
       const size_t nb = std::min<size_t>((size_t)kBatchMax, l.batch_n - i0);
       ScaledBatch bp;
       for (size_t i = 0; i < (size_t)kBatchMax; ++i) bp.src[i] = i < nb ? l.batch_srcs[i0 + i] : nullptr;
-      bp.on = 1;
+      bp.on = 1; bp.frames = nullptr;
       dim3 grid = grid_rows_few(out_cols, out_rows, 128, (unsigned)(8192 / nb));
       grid.z = (unsigned)nb;
       IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid, dim3(128), 0, s, static_cast<const T *>(nullptr), a, l.cfa48_dev, l.dst4 + i0 * slice, bp);
@@ -1262,12 +1283,56 @@ static void launch_raw_scaled_demosaic_typed(const ScaledDemosaicLaunch &l, hipS
   }
   ScaledBatch one;                                                           // batch mode off: the table is not read
   for (int i = 0; i < kBatchMax; ++i) one.src[i] = nullptr;
-  one.on = 0;
+  one.on = 0; one.frames = nullptr;
   IPK_LAUNCH_TAG(tag(0), k_raw_scaled_demosaic<T>, grid_rows_few(out_cols, out_rows, 128, 8192), dim3(128), 0, s, src, a, l.cfa48_dev, l.dst4, one);
 }
 void launch_raw_scaled_demosaic(const ScaledDemosaicLaunch &l, hipStream_t s) {
   if (l.src_is_u16) launch_raw_scaled_demosaic_typed<uint16_t>(l, s);
   else launch_raw_scaled_demosaic_typed<float>(l, s);
+}
+// The frame-table launch of the general scaling kernel (ipk_launch.hpp): frame i's record as launch_raw_scaled_demosaic_typed states the same values for a
+// single launch of that frame -- the same f32 expressions for the skips, their reciprocals and the fast-division flags -- uploaded stream-ordered into
+// table_dev, then ONE launch with a grid plane per frame over the batch launch's grid
+static int launch_status();
+size_t scaled_each_table_bytes(size_t n) { return n * sizeof(ScaledFrame); }
+int launch_raw_scaled_demosaic_each(const ScaledFrameLaunch *frames, size_t n, bool src_is_u16, int layout, size_t nwidth, size_t nheight, float *dst4, void *table_dev,
+                                    hipStream_t s) {
+  if (n == 0 || n > kScaledEachMax || !frames || !dst4 || !table_dev || (layout != 0 && layout != 1 && layout != 3) || nwidth < 1 || nheight < 1 ||
+      nwidth > 0xFFFFFFFFull || nheight > 0xFFFFFFFFull) return -1;
+  std::vector<ScaledFrame> table(n);
+  for (size_t i = 0; i < n; ++i) {
+    const ScaledFrameLaunch &l = frames[i];
+    if (!l.src || (layout == 0 && !l.cfa48_dev) || l.width == 0 || l.height == 0 || l.width > 0xFFFFFFFFull || l.height > 0xFFFFFFFFull || l.x > l.owidth || l.width > l.owidth - l.x ||
+        !raw_scaled_demosaic_general(l.width, l.height, nwidth, nheight, true, layout != 0)) return -1;
+    ScaledFrame &f = table[i];
+    f.src = l.src; f.cfa48 = l.cfa48_dev;
+    f.src_pitch = l.owidth; f.src_x = l.x; f.src_y = l.y; f.width = (uint32_t)l.width; f.height = (uint32_t)l.height;
+    f.skip_x_x = ((float)((int64_t)l.width - 1) - 0.0f) / ((float)(nwidth - 1));
+    f.skip_y_y = ((float)((int64_t)l.height - 1) - 0.0f) / ((float)(nheight - 1));
+    f.inv_skip_x_x = 1.0f / f.skip_x_x; f.inv_skip_y_y = 1.0f / f.skip_y_y;
+    f.fast_x = cdiv_host_ok(f.skip_x_x); f.fast_y = cdiv_host_ok(f.skip_y_y);
+    f.min0 = l.black[0]; f.range0 = l.white[0] - l.black[0];
+    f.min1 = l.black[1]; f.range1 = l.white[1] - l.black[1]; f.min2 = l.black[2]; f.range2 = l.white[2] - l.black[2];
+  }
+  if (hipMemcpyAsync(table_dev, table.data(), n * sizeof(ScaledFrame), hipMemcpyHostToDevice, s) != hipSuccess) return -4;   // (pageable: consumed before it returns)
+  // what the kernel takes from the launch: the result's size, the layout and the whole-frame output window (and transform_buffer's zero corner and cross
+  // terms); every per-frame field stays zero -- a block never reads it
+  TransformArgs a{};
+  a.nwidth = (uint32_t)nwidth; a.nheight = (uint32_t)nheight; a.components = 4;
+  a.has_cfa = layout == 0 ? 1 : 0; a.norm = 1; a.layout = layout;
+  a.out_r0 = 0; a.out_r1 = (uint32_t)nheight; a.out_c0 = 0; a.out_c1 = (uint32_t)nwidth;
+  ScaledBatch bp;
+  for (int i = 0; i < kBatchMax; ++i) bp.src[i] = nullptr;
+  bp.on = 2; bp.frames = static_cast<const ScaledFrame *>(table_dev);
+  dim3 grid = grid_rows_few(nwidth, nheight, 128, (unsigned)(8192 / n));
+  grid.z = (unsigned)n;
+  // the digits describe no single frame: 0 throughout
+  const char *tag = layout == 3 ? "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,plain=3,batch=1,frames=1"
+                  : layout == 1 ? "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,plain=1,batch=1,frames=1"
+                                : "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,batch=1,frames=1";
+  if (src_is_u16) IPK_LAUNCH_TAG(tag, k_raw_scaled_demosaic<uint16_t>, grid, dim3(128), 0, s, static_cast<const uint16_t *>(nullptr), a, static_cast<const uint8_t *>(nullptr), dst4, bp);
+  else IPK_LAUNCH_TAG(tag, k_raw_scaled_demosaic<float>, grid, dim3(128), 0, s, static_cast<const float *>(nullptr), a, static_cast<const uint8_t *>(nullptr), dst4, bp);
+  return launch_status();
 }
 template void launch_transform_buffer<float>(const float *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, float *, hipStream_t);
 template void launch_transform_buffer<uint8_t>(const uint8_t *, size_t, size_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, size_t, size_t, size_t, const uint8_t *, uint8_t *, hipStream_t);

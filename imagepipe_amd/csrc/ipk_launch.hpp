@@ -46,7 +46,8 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // [norm_fast=,norm_light=,fast_x=,fast_y=,xcd=] (xcd: 0 plain grid, 1 XCD row grouping, 2 grouping with leftover rows; their window launches,
 // ipk_raw_scaled_demosaic_window, append win=1: [norm_fast=,...,xcd=,win=1]; the monochrome / three-sample launches of k_raw_scaled_demosaic by
 // ipk_plain_scale_down append plain=1 / plain=3 behind that; its batch launches -- ipk_raw_scaled_demosaic_batch / ipk_plain_scale_down_batch -- append
-// batch=1 behind all of it: [...,xcd=0,batch=1] / [...,xcd=0,plain=1,batch=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
+// batch=1 behind all of it: [...,xcd=0,batch=1] / [...,xcd=0,plain=1,batch=1]; the frame-table launches -- ipk_scaled_demosaic_batch_each -- append frames=1
+// behind batch=1 and print the four digits in front as 0: [norm_fast=0,...,xcd=0,batch=1,frames=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form); the gather
 // launches of k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2> (a GatherSource: ipk_pipeline_run_cached_region) append
 // gather=1: [fast_ok=,gather=1] -- flat launches never carry the key; the frame-table launches of k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2>
@@ -108,6 +109,20 @@ inline bool raw_scaled_demosaic_general(size_t width, size_t height, size_t nwid
 // are the frames of one shape (a host array, read before the call returns: the pointers travel by value in the kernel's arguments), dst4 holds batch_n
 // packed nwidth x nheight results one after another, slice i bit-identical to the single-frame launch of batch_srcs[i].  One launch per 64 frames,
 // blockIdx.z the frame; the launches append batch=1 to the tag: [norm_fast=,...,xcd=0,batch=1] / [...,xcd=0,plain=1,batch=1]
+// Frame-table mode (launch_raw_scaled_demosaic_each): n <= kScaledEachMax whole frames of one source type, layout (0 mosaic, 1 monochrome, 3 three-sample) and
+// result size, frame i with the source, pitch, sensor window, levels (layout 0 and 1 read pair 0 alone) and -- layout 0 -- 48 x 48 device filter table of
+// frames[i] (a host array, read before the call returns).  Every frame must select the general kernel for a 16-byte aligned destination
+// (raw_scaled_demosaic_general; dst4 itself needs element alignment only).  The launcher writes one record per frame into table_dev --
+// scaled_each_table_bytes(n) bytes of device memory the caller keeps alive until the launch has run (the context's scratch pool) -- with a stream-ordered
+// copy in front of the ONE launch; blockIdx.z is the frame over the batch launch's grid, a block reads its frame's record where the other modes read the
+// kernel's arguments and is otherwise the single launch of that frame: slice i of dst4 is bit-identical to it.  The tag appends frames=1 behind batch=1
+// and prints the four digits in front, which describe no single frame, as 0: [norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,batch=1,frames=1] /
+// [...,xcd=0,plain=1,batch=1,frames=1].  -1 (nothing enqueued) outside these bounds, -4 when the copy or the launch could not be enqueued
+struct ScaledFrameLaunch { const void *src; size_t owidth, x, y, width, height; float black[3], white[3]; const uint8_t *cfa48_dev; };
+constexpr size_t kScaledEachMax = 64;
+size_t scaled_each_table_bytes(size_t n);
+int launch_raw_scaled_demosaic_each(const ScaledFrameLaunch *frames, size_t n, bool src_is_u16, int layout, size_t nwidth, size_t nheight, float *dst4, void *table_dev,
+                                    hipStream_t s);
 
 void launch_tolab(const float *src4, size_t npix, const float *mul4, const float *cm12, const void *lab_pairs, float *dst3,
                   int num_cus, hipStream_t s);

@@ -278,6 +278,32 @@ IPK_API int ipk_raw_scaled_demosaic_batch(const void *const *srcs, size_t n, int
                                           float black0, float white0, const char *cfa, size_t nwidth, size_t nheight, float *dst4, void *stream);
 IPK_API int ipk_plain_scale_down_batch(const void *const *srcs, size_t n, int src_type, int kind, size_t owidth, size_t x, size_t y, size_t width,
                                        size_t height, const float *black4, const float *white4, size_t nwidth, size_t nheight, float *dst4, void *stream);
+/* one frame of ipk_scaled_demosaic_batch_each: the arguments of the whole-frame calls that may differ between the frames of one launch.
+ * struct_size = sizeof(ipk_scaled_frame) (any other value is IPK_ERR_INVALID, as for ipk_chain_params) */
+typedef struct { uint32_t struct_size;
+                 size_t owidth, x, y, width, height;   /* pitch in pixels, window origin, window size */
+                 float black4[4], white4[4];           /* mosaic: [0] only; IPK_PLAIN_RGB: [0..2]; IPK_PLAIN_MONO: [0] */
+                 char cfa[160];                        /* mosaic: letters or "WxH:letters"; plain kinds: ignored */
+               } ipk_scaled_frame;
+/* ipk_raw_scaled_demosaic_batch / ipk_plain_scale_down_batch for frames that carry their own sensor settings: n sensor frames of one source type and one
+ * kind (-1: mosaics, IPK_PLAIN_RGB, IPK_PLAIN_MONO) scaled to ONE nwidth x nheight, frame i with the pitch, window, levels and -- mosaics -- filter of
+ * frames[i] (n ipk_scaled_frame; declared const void * for the reason given at ipk_pointwise_chain_out_batch).  dst4 receives n * nwidth * nheight * 4
+ * packed f32, slice i bit-identical to ipk_raw_scaled_demosaic (mosaics) / ipk_plain_scale_down (the plain kinds) called with frame i's own arguments, and
+ * nothing else is written; dst4 needs element alignment only.  One launch per 64 frames: the frame-table mode of the general kernel
+ * k_raw_scaled_demosaic<T> -- a grid plane is a frame over the batch form's grid, and the block reads its frame's source, pitch, window, skips, levels and
+ * filter table from a record in device memory where the other modes read the kernel's arguments; the result's size, the layout and T stay launch-wide.
+ * Every tap, weight, order of accumulation and division is the single launch's.  The log tags such launches [norm_fast=0,norm_light=0,fast_x=0,fast_y=0,
+ * xcd=0,batch=1,frames=1] (plain=1 / plain=3 in front of batch=1 for the plain kinds); the four digits describe no single frame and are printed as 0.
+ * Admission: every frame must be one the general kernel takes for an aligned destination -- a skip (width - 1) / (nwidth - 1) or (height - 1) /
+ * (nheight - 1) (in f32) above 7 or below 1, or a frame under 8 samples wide; every frame of the plain kinds -- because the window-8 kernels have no such
+ * mode: another frame is IPK_ERR_UNSUPPORTED with its index in ipk_last_error, as is IPK_PLAIN_RASTER.  IPK_ERR_INVALID, the index named: a null srcs[i], a
+ * wrong struct_size, a filter that does not parse, x + width > owidth, empty or oversized dimensions.  Everything is validated before anything is enqueued;
+ * n = 0 is IPK_OK.  The host arrays are read before the call returns.  The table lives in the context's scratch pool and is uploaded with a stream-ordered
+ * copy from pageable host memory in front of each launch: the call cannot be captured into a graph.  ipk_timing names each launch
+ * "scaled_demosaic_batch_each". */
+IPK_API int ipk_scaled_demosaic_batch_each(const void *const *srcs, const void *frames /* n ipk_scaled_frame */, size_t n, int src_type,
+                                           int kind /* -1 mosaic, IPK_PLAIN_RGB, IPK_PLAIN_MONO */, size_t nwidth, size_t nheight, float *dst4,
+                                           void *stream);
 /* OpGoFloat::run_raw (CFA branch) followed by OpDemosaic::run's LAST branch -- demosaic::full, then scale_down_opbuf to nwidth x nheight
  * (src/ops/demosaic.rs:51-59: 1 < scale < minscale) -- in one launch over the raw sensor frame: ipk_raw_scaled_demosaic's sibling below minscale.  dst4
  * receives nwidth * nheight * 4 f32, bit for bit what ipk_gofloat_cfa_* -> ipk_demosaic_run write for such a frame (E = +0.0); the full-size 1- and
@@ -606,7 +632,12 @@ typedef struct {
                                       Bit 9 (IPK_FUSED_BATCH_ORIENTED = 512) acts beside bits 0 and 8 only: the batched previews take frames of any
                                       orientation, OpTransform folded into the point-wise pass, and ipk_pipeline_run_batch_each lets rotation, fliph and flipv
                                       differ inside a run.  Same contract: no hash, no result, no other driver or report depends on it; allow_fused = 512
-                                      alone still means "on" for every older route. */
+                                      alone still means "on" for every older route.
+                                      Bit 10 (IPK_FUSED_BATCH_SENSOR = 1024) acts beside bits 0 and 8 only: ipk_pipeline_run_batch_each lets the sensor
+                                      fields -- width, height, cfa, cfa_width, cfa_height, the four crops, blacklevels, whitelevels -- differ inside a run
+                                      whose frames negotiate one demosaic size, the scaling pass of such a chunk as one frame-table launch.  Same
+                                      contract: no hash, no result, no other driver or report depends on it; allow_fused = 1024 alone still means "on"
+                                      for every older route. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -683,7 +714,7 @@ typedef enum {
                                       the window-8 kernels and the raster scaler (a launch per frame inside the route); the host-buffer batch
                                       (ipk_host_pipeline_run_batch is unchanged); band (multi-GPU single-frame) forms; the bit as a default.
                                       Measurements: profiles/r19_batch_previews.txt */
-  IPK_FUSED_BATCH_ORIENTED = 512   /* bit 9 (beside bits 0 and 8; nothing without either): a batch of previews may carry orientations.  OpTransform
+  IPK_FUSED_BATCH_ORIENTED = 512,  /* bit 9 (beside bits 0 and 8; nothing without either): a batch of previews may carry orientations.  OpTransform
                                       behind a no-op OpRotateCrop is a dihedral permutation of the preview, and pass 2 of the batch folds it into its
                                       loads: ONE frame-table launch per chunk (ipk_pointwise_chain_out_batch_oriented), each frame's record with the gather
                                       walk of its own orientation, instead of the scaling pass, the chain, the quantise and the transform per frame.
@@ -693,8 +724,8 @@ typedef enum {
                                       name is what it was.  Every orientation walks the gather mode the chain kernels already have
                                       (ipk_pipeline_run_cached_region's): a flip keeps a lane's pixels consecutive in memory, forwards or backwards; a
                                       transposing orientation reads one source pixel per lane a source row apart.
-                                      Out of scope: active rotatecrops in a batch; per-frame levels, crops or size limits inside one scaling launch;
-                                      the host-buffer batch drivers; band forms; the bit as a default; graph capture.
+                                      Out of scope: active rotatecrops in a batch; per-frame size limits inside one scaling launch (levels, crops
+                                      and filters: bit 10); the host-buffer batch drivers; band forms; the bit as a default; graph capture.
                                       Measured (profiles/r21_batch_oriented.txt; device-resident noise frames under a square box, every frame with its
                                       own wb_coeffs and exposure, wall clock, medians, ms per frame; the parent build's only offer -- a loop of
                                       ipk_pipeline_run -- -> ipk_pipeline_run_batch_each with the bit; the parent's spread is 0.0003 .. 0.0045 ms), every
@@ -719,6 +750,37 @@ typedef enum {
                                       and curves, batches above 64 frames, rasters and the window-8 geometries, previews larger than 400 wide (where
                                       the transposing gather's cost must grow towards the 3.3x of ipk_pipeline_run_cached_region's 24 MP region),
                                       the uniform route (ipk_pipeline_run_batch on one oriented descriptor), photo-like data */
+  IPK_FUSED_BATCH_SENSOR = 1024    /* bit 10 (beside bits 0 and 8; nothing without either; combines with bit 9): the frames of a batch of previews may
+                                      carry their own sensor settings.  One camera's levels change with ISO and a folder holds more than one body, so
+                                      ipk_pipeline_run_batch_each keeps frames in one run that differ in width, height, cfa, cfa_width, cfa_height, the
+                                      crops, blacklevels or whitelevels, where each would batch its own previews through the general scaling kernel
+                                      (ipk_pipeline_batches_previews answers 1 with pass1_batched = 1) and all negotiate one demosaic size (see there).
+                                      Pass 1 of a chunk whose frames differ in these fields is ONE ipk_scaled_demosaic_batch_each launch -- the
+                                      frame-table mode of k_raw_scaled_demosaic<T>, frame i's record from descriptor i's own negotiation -- instead of a
+                                      loop of ipk_pipeline_run; a chunk whose frames agree in them is the uniform launch as before.  Without the bit
+                                      every plan, launch, tag and stage name is what it was.  The carrier kernel: 49 VGPRs, no scratch, in both
+                                      instantiations, before and after.
+                                      Out of scope: per-frame preview sizes (different demosaic sizes in one launch); batch forms of the window-8 kernels
+                                      and the raster scaler; active rotatecrops in a batch; the host-buffer batch drivers and the multi-device driver;
+                                      band forms; the bit as a default; graph capture.
+                                      Measured (profiles/r22_batch_sensor.txt; device-resident noise frames to u8, every frame with its own black and
+                                      white level and its own wb_coeffs, wall clock, medians, ms per frame; the parent build's only offer -- its
+                                      ipk_pipeline_run_batch_each, which cuts such a run into a loop of ipk_pipeline_run -- -> this call with the bit |
+                                      this build's route 2 on the same frames with EQUAL sensor fields; the parent's spread is 0.0008 .. 0.0201 ms, once 0.092),
+                                      n = 2 / 8 / 16 / 64: 24 MP RGGB u16 -> 256 wide: 0.299 -> 0.134 | 0.131, 0.247 -> 0.072 | 0.067, 0.236 -> 0.082 |
+                                      0.079, 0.227 -> 0.072 | 0.069; -> 400 wide: 0.236 -> 0.105 | 0.099, 0.196 -> 0.082 | 0.079, 0.187 -> 0.078 | 0.075,
+                                      0.181 -> 0.075 | 0.072; 50 MP X-Trans u16 -> 270 wide: 0.468 -> 0.247 | 0.244, 0.419 -> 0.192 | 0.189, 0.407 ->
+                                      0.174 | 0.171, 0.398 -> 0.166 | 0.161; 24 MP mono u16 -> 256 wide: 0.143 -> 0.081 | 0.079, 0.154 -> 0.050 | 0.048,
+                                      0.154 -> 0.063 | 0.063, 0.153 -> 0.052 | 0.052; 24 MP and 24.4 MP RGGB bodies alternating -> 256 wide: 0.298 ->
+                                      0.134, 0.246 -> 0.072, 0.234 -> 0.083, 0.226 -> 0.073: x1.8 .. x2.3 at n = 2, x2.2 .. x3.5 at n >= 8.  The price
+                                      of the table (sensor minus equal): +0.0001 .. +0.0064 ms per frame.  No measured case at n >= 8 was slower than
+                                      the parent's loop; none is excluded.  The kernel's untouched modes against the parent build:
+                                      ipk_raw_scaled_demosaic_batch 6000x4000 -> 256x170 at n = 8 0.412 -> 0.415 ms and at n = 64 3.329 -> 3.326 ms,
+                                      inside its spread; KNOWN LOSS: the single launch ipk_raw_scaled_demosaic 6000x4000 -> 400x266 0.1181 -> 0.1203 ms,
+                                      outside the parent's spread of 0.0017, and 0.1175 -> 0.1194 (spread 0.0034) in a second session with ten times the
+                                      samples: +0.002 ms (1.6 .. 1.9 %) both times; its disassembly holds the parent's vector loads one for one, the cause was not found.
+                                      Not measured: f32 sources, f32 and 16-bit outputs, per-frame crops and filters inside one series, three-sample
+                                      raws, batches above 64 frames, orientations beside sensor settings, mixed batches, photo-like data */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -898,13 +960,21 @@ IPK_API int ipk_devices_sync(void);
  * differ as well: eight fields instead of five.  The demosaic size decides the scaling pass's filter; under one maxwidth alone a Rotate90 / Rotate270
  * frame negotiates another one than a Normal frame (transform_forward swaps the sides before the clamp) and still cuts the run, under a square box
  * (maxwidth == maxheight) frames of equal source size agree, and fliph / flipv never enter the fold.  One thing the five
+ * Where BOTH descriptors carry IPK_FUSED_BATCH_SENSOR beside IPK_FUSED_ON | IPK_FUSED_BATCH_PREVIEWS, each would batch its own previews with the general
+ * scaling kernel's batch launch (ipk_pipeline_batches_previews answers 1 with pass1_batched = 1), both negotiate the same demosaic size and both agree in
+ * whether the filter has a fourth colour, the SENSOR fields may differ too: width, height, cfa (cfa_width, cfa_height), crop_top / right / bottom / left,
+ * blacklevels and whitelevels.  src_type, cpp and is_cfa still count as shape (they decide the kernel's instantiation, its layout and the chain's monochrome
+ * flag), as do maxwidth and maxheight; the orientation rule above combines with this one unchanged.  A run whose frames differ in a sensor field is
+ * route 2: pass 1 of a chunk whose frames differ in them is ONE ipk_scaled_demosaic_batch_each launch, frame i's window, levels and filter from descriptor
+ * i's own negotiation, named "batch-each gofloat+demosaic"; a chunk whose frames agree in them is the uniform launch on the chunk's first descriptor under
+ * the old name; pass 2 is what it is below.  One thing the five
  * fields themselves decide counts as shape too: ipk_pipeline_takes_fastpath (the raster fast path is taken for the DEFAULT ops only), so a raster with
  * default ops and an edited one are never same-shaped under IPK_OUT_U8 / IPK_OUT_U16, and every frame of a run is on the route ipk_pipeline_run would
  * choose for it.  The frames are cut, in order, into maximal runs of consecutive same-shaped descriptors; run_first[i] is the first frame of frame
  * i's run.  For a run of m frames:
  *   route 2, varied previews: m > 1, ipk_pipeline_batches_previews(descs[run_first], out_type, m, ...) answers 1 (so allow_fused needs IPK_FUSED_ON |
  *     IPK_FUSED_BATCH_PREVIEWS: no new bit) and the descriptors are not all equal in the five (eight) fields.  Chunks follow that report's chunk; pass 1 is the
- *     uniform route's pass 1 -- one set of levels, crops and filter per chunk -- and pass 2 is ONE ipk_pointwise_chain_out_batch launch per chunk: source i
+ *     uniform route's pass 1 -- one set of levels, crops and filter per chunk, or under IPK_FUSED_BATCH_SENSOR the frame-table launch above -- and pass 2 is ONE ipk_pointwise_chain_out_batch launch per chunk: source i
  *     the scratch's slice i, parameters descriptor i's, destination dsts[i] wherever it lies (scattered destinations cost nothing here).  A final chunk
  *     of one frame is ipk_pipeline_run.  ipk_timing names the stages "batch gofloat+demosaic" and "batch-each to_lab+basecurve+from_lab+gamma+quantise"
  *     (without "+quantise" for f32); a chunk with at least one oriented frame is ONE ipk_pointwise_chain_out_batch_oriented launch, frame i with its
@@ -914,7 +984,7 @@ IPK_API int ipk_devices_sync(void);
  *     full-size launch and the uniform preview batch for callers who happen to have them;
  *   route 0, single: every other frame, through ipk_pipeline_run.
  * Out of scope: per-frame settings inside the persistent full-size launch ipk_raw_to_srgb_batch (one parameter set; full-size frames with varied
- * settings are route 0 each); per-frame levels, crops or filters inside one scaling launch (they cut the run); non-Normal orientations without IPK_FUSED_BATCH_ORIENTED and active
+ * settings are route 0 each); per-frame preview sizes inside one scaling launch (they cut the run); non-Normal orientations without IPK_FUSED_BATCH_ORIENTED and active
  * rotatecrops inside a varied run (ipk_pipeline_batches_previews answers 0: frame by frame, or route 1 where identical); the host-buffer batch drivers;
  * the multi-device driver (it may follow by calling this one member by member); band forms; the bit as a default; graph capture (the table upload of
  * ipk_pointwise_chain_out_batch is a copy from pageable host memory).

@@ -307,6 +307,7 @@ class Pipeline {
   bool scale_plain = false;                // ipk_pipeline_desc.allow_fused bit 7 (IPK_FUSED_PLAIN_PREVIEWS): downscaled previews of monochrome / three-sample raws (u16, f32) run gofloat + demosaic as the one launch ipk_plain_scale_down where scales_plain() says so; window_previews and fuse_scaled_rotatecrop then take them too
   bool batch_previews = false;             // ipk_pipeline_desc.allow_fused bit 8 (IPK_FUSED_BATCH_PREVIEWS): run_batch() runs downscaled previews as one scaling launch group and one point-wise pass per chunk of frames where batches_previews() says so
   bool batch_oriented = false;             // ipk_pipeline_desc.allow_fused bit 9 (IPK_FUSED_BATCH_ORIENTED), set only together with batch_previews: batched previews take frames of any orientation (OpTransform folded into the point-wise pass), and run_batch_each lets rotation / fliph / flipv differ inside a run
+  bool batch_sensor = false;               // ipk_pipeline_desc.allow_fused bit 10 (IPK_FUSED_BATCH_SENSOR), set only together with batch_previews: run_batch_each lets width, height, cfa, the crops and the levels differ inside a run whose frames negotiate one demosaic size
   bool window_previews = false;            // ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
   int last_ops_run = 0xFF;                 // bit i: op i executed in the last run (0 = served from the cache)
   uint64_t source_id = 0;                  // identifies the frame inside a shared PipelineCache (extension, see the C header)
@@ -420,6 +421,7 @@ class Pipeline {
     if (scale_plain && d.allow_fused) d.allow_fused |= IPK_FUSED_PLAIN_PREVIEWS;
     if (batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_PREVIEWS;
     if (batch_oriented && batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_ORIENTED;
+    if (batch_sensor && batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_SENSOR;
     return d;
   }
   // does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop; no GPU needed)?  out_type: IPK_OUT_*
@@ -449,7 +451,7 @@ class Pipeline {
   bool resamples_cached_region(int out_type = IPK_OUT_F32) const { const ipk_pipeline_desc d = desc(); return ipk_pipeline_resamples_cached_region(&d, out_type) == 1; }
   // A shoot whose files carry their own colour settings: one Pipeline per frame, raws[i] shaped like pipes[i]'s own source (ipk_pipeline_run_batch_each).
   // ONE device allocation, the results of out_type one after another in frame order; offsets (optional) receives each result's byte offset.  Frames that
-  // differ only in white balance, matrix, exposure and curve -- and, with batch_oriented on every member, in rotation, fliph and flipv -- run as batched
+  // differ only in white balance, matrix, exposure and curve -- and, with batch_oriented on every member, in rotation, fliph and flipv, with batch_sensor in the sensor's size, crops, filter and levels -- run as batched
   // previews where batch_each_plan() says 2 (batch_previews on every member)
   static DeviceArray run_batch_each(const std::vector<const Pipeline *> &pipes, const std::vector<const void *> &raws, int out_type = IPK_OUT_F32,
                                     std::vector<size_t> *offsets = nullptr) {
@@ -506,6 +508,13 @@ inline void pointwise_chain_out_batch(const std::vector<const float *> &srcs4, s
   const ipk_chain_params *p = params.data();
   check(ipk_pointwise_chain_out_batch(srcs4.data(), width, height, monochrome ? 1 : 0, p, srcs4.size(), linear ? 1 : 0, out_type, dsts.data(), stream),
         "pointwise_chain_out_batch");
+}
+// ipk_scaled_demosaic_batch_each: n sensor frames with their own windows, levels and filters into n packed nwidth x nheight results, one launch per 64
+inline ipk_scaled_frame scaled_frame() { ipk_scaled_frame f{}; f.struct_size = (uint32_t)sizeof(f); return f; }
+inline void scaled_demosaic_batch_each(const std::vector<const void *> &srcs, const std::vector<ipk_scaled_frame> &frames, int src_type, int kind, size_t nwidth,
+                                       size_t nheight, float *dst4, void *stream = nullptr) {
+  if (frames.size() != srcs.size()) throw Error("scaled_demosaic_batch_each: as many frame records as frames");
+  check(ipk_scaled_demosaic_batch_each(srcs.data(), frames.data(), srcs.size(), src_type, kind, nwidth, nheight, dst4, stream), "scaled_demosaic_batch_each");
 }
 // the same with an orientation per frame (ipk_pointwise_chain_out_batch_oriented): dsts[i] receives frame i as OpTransform's image under orientations[i]
 // (ipk_orientation values; an empty vector: every frame Normal), height wide where the orientation transposes
