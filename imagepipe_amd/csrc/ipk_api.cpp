@@ -2974,28 +2974,9 @@ void HostLanes::release() {
 // ------------------------------------------------------------------------------------------
 // A caller looping Pipeline::run over the frames of a shoot (src/pipeline.rs:246-249: frames are independent), device pointers
 // ------------------------------------------------------------------------------------------
+// In order: the two frame-table primitives, the comparisons of two descriptors, the admission of one, the plan of n, the chunk walk, the drivers
 namespace {
-// IPK_FUSED_BATCH_PREVIEWS: a batch of staged frames whose gofloat + demosaic is the one scaling pass (gofloat_demosaic_one_pass) and whose every later op
-// is point-wise (OpRotateCrop a no-op; OpTransform too, or a permutation under IPK_FUSED_BATCH_ORIENTED) runs chunk by chunk as one scaling launch group into one RGBE scratch, then the chain over the
-// previews lying one after another.  dw * dh >= 256 is the one-pass chain's own floor, kept per frame: the batch uses the kernels a single frame would.
-// chunk: frames per scratch (at most 64, at most 256 MiB of RGBE); pass1_batched: pass 1 is the general scaling kernel's batch launch (the scratch slices
-// are 16-byte aligned), else one launch per frame of the kernel the frame selects
-struct BatchPreviews { size_t chunk; bool pass1_batched; };
-bool batches_previews(const ipk_pipeline_desc *d, const Negotiated &n, const Route &rt, size_t frames, BatchPreviews &bp) {
-  bp.chunk = 0; bp.pass1_batched = false;
-  if (!opted(d, IPK_FUSED_BATCH_PREVIEWS) || frames <= 1 || rt.kind != kStaged || !gofloat_demosaic_one_pass(d, n) || !n.rc.noop() || n.dw * n.dh < 256) return false;
-  if (!n.transform_noop) {
-    // IPK_FUSED_BATCH_ORIENTED: OpTransform rides in pass 2's loads (chain_out_batch_impl), where its image of the preview is the negotiated result
-    bool t, fx, fy; ipk::orientation_to_flips(n.orientation, t, fx, fy);
-    if (!opted(d, IPK_FUSED_BATCH_ORIENTED) || (t ? n.dh : n.dw) != n.fw || (t ? n.dw : n.dh) != n.fh) return false;
-  }
-  // (a descriptor no launch would take -- a preview of 2^24 pixels and more, whose byte count may wrap to 0, or a sensor side of 2^31 and more, which the
-  // kernel selection cannot convert -- still gets an answer here: a frame per chunk, no batch launch)
-  const size_t cap_px = (size_t)1 << 24;                                    // 256 MiB of RGBE
-  bp.chunk = n.dw > cap_px / n.dh ? 1 : std::min<size_t>(64, std::max<size_t>(1, ((size_t)256 << 20) / (n.dw * n.dh * 16)));
-  bp.pass1_batched = n.raw && dims_ok(n.r.width, n.r.height) && ipk::raw_scaled_demosaic_general(n.r.width, n.r.height, n.dw, n.dh, true, !n.cfa_branch);
-  return true;
-}
+// ---- the two frame-table primitives ----
 // ipk_scaled_demosaic_batch_each: every frame validated and admitted (its filter's device table fetched) before anything is enqueued, then one frame-table
 // launch per 64 frames (launch_raw_scaled_demosaic_each), its table in the scratch pool.  stage: the name marked behind every launch
 int scaled_batch_each_impl(const void *const *srcs, const ipk_scaled_frame *frames, size_t n, int src_type, int kind, size_t nwidth, size_t nheight, float *dst4,
@@ -3041,108 +3022,6 @@ int scaled_batch_each_impl(const void *const *srcs, const ipk_scaled_frame *fram
   }
   return IPK_OK;
 }
-// the sensor fields of a descriptor: what IPK_FUSED_BATCH_SENSOR lets differ inside a run (cfa_width / cfa_height are folded into cfa)
-bool same_bits(const float *a, const float *b, size_t n);
-bool same_sensor(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) {
-  return a.width == b.width && a.height == b.height && std::strcmp(a.cfa, b.cfa) == 0 && a.cfa_width == b.cfa_width && a.cfa_height == b.cfa_height &&
-         a.crop_top == b.crop_top && a.crop_right == b.crop_right && a.crop_bottom == b.crop_bottom && a.crop_left == b.crop_left &&
-         same_bits(a.blacklevels, b.blacklevels, 4) && same_bits(a.whitelevels, b.whitelevels, 4);
-}
-// The chunk walk both preview batches share (run_batch_previews, run_batch_each's varied runs): d states the levels, crops, filter and size limit of every
-// frame.  A chunk of one frame is single(i); a longer one gets its scratch, pass 1 -- the chunk's RGBE previews one after another, slice floats apart --
-// and then pass2(i0, m, rgbe, slice, tm), which enqueues the point-wise work of frames i0 .. i0 + m and marks its stages.
-// each / ngs (optional, n entries: a varied run under IPK_FUSED_BATCH_SENSOR whose frames differ in their sensor fields; bp.pass1_batched holds for every one
-// of them): frame i's levels, crops and filter are each[i]'s, its window ngs[i]'s.  A chunk whose frames agree in them is the uniform launch on the chunk's
-// first descriptor, another is ONE frame-table launch (scaled_batch_each_impl), marked "batch-each gofloat+demosaic"
-extern "C++" template <typename Single, typename Pass2>
-int run_preview_chunks(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, size_t n, void *stream, Single single,
-                       Pass2 pass2, const ipk_pipeline_desc *each = nullptr, const Negotiated *ngs = nullptr) {
-  const size_t slice = ng.dw * ng.dh * 4;
-  std::vector<ipk_scaled_frame> sf;
-  for (size_t i0 = 0; i0 < n; i0 += bp.chunk) {
-    const size_t m = std::min(bp.chunk, n - i0);
-    if (m == 1) { const int rc = single(i0); if (rc < 0) return rc; continue; }
-    StageTimer tm(S(stream));
-    Scratch sc(S(stream));
-    void *buf = nullptr;
-    int rc = sc.get(m * slice * sizeof(float), &buf); if (rc) return rc;
-    float *rgbe = static_cast<float *>(buf);
-    const ipk_pipeline_desc *const dc = each ? &each[i0] : d;              // the chunk's first descriptor states a uniform launch's sensor settings
-    const Negotiated &nc = each ? ngs[i0] : ng;
-    bool table = false;
-    if (each) for (size_t i = 1; i < m; ++i) table = table || !same_sensor(each[i0], each[i0 + i]);
-    if (table) {
-      sf.assign(m, ipk_scaled_frame{});
-      for (size_t i = 0; i < m; ++i) {
-        const ipk_pipeline_desc &di = each[i0 + i]; const Negotiated &ni = ngs[i0 + i];
-        ipk_scaled_frame &f = sf[i];
-        f.struct_size = (uint32_t)sizeof(f);
-        f.owidth = di.width; f.x = ni.r.x; f.y = ni.r.y; f.width = ni.r.width; f.height = ni.r.height;
-        std::memcpy(f.black4, di.blacklevels, sizeof(f.black4)); std::memcpy(f.white4, di.whitelevels, sizeof(f.white4));
-        std::memcpy(f.cfa, di.cfa, sizeof(f.cfa));
-      }
-      rc = scaled_batch_each_impl(srcs + i0, sf.data(), m, d->src_type, ng.cfa_branch ? -1 : (d->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO), ng.dw, ng.dh, rgbe, stream,
-                                  tm, "batch-each gofloat+demosaic");
-      if (rc < 0) return rc;
-    } else if (bp.pass1_batched) {
-      rc = nc.cfa_branch ? raw_scaled_demosaic_batch_impl(srcs + i0, m, dc->src_type, dc->width, nc.r.x, nc.r.y, nc.r.width, nc.r.height, dc->blacklevels[0],
-                                                          dc->whitelevels[0], dc->cfa, nc.dw, nc.dh, rgbe, stream)
-                         : plain_scale_down_batch_impl(srcs + i0, m, dc->src_type, dc->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO, dc->width, nc.r.x, nc.r.y, nc.r.width,
-                                                       nc.r.height, dc->blacklevels, dc->whitelevels, nc.dw, nc.dh, rgbe, stream);
-      if (rc < 0) return rc;
-    } else {
-      for (size_t i = 0; i < m; ++i) { rc = launch_gofloat_demosaic(dc, nc, srcs[i0 + i], nullptr, rgbe + i * slice, stream); if (rc < 0) return rc; }
-    }
-    if (!table) tm.mark("batch gofloat+demosaic");
-    rc = pass2(i0, m, rgbe, slice, tm); if (rc < 0) return rc;
-  }
-  return IPK_OK;
-}
-int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height, int monochrome, const ipk_chain_params *params, const int *orientations, size_t n,
-                         int linear, int out_type, void *const *dsts, void *stream, StageTimer &tm, const char *stage, const char *stage_oriented = nullptr);
-void chain_params_of(const ipk_pipeline_desc &d, ipk_chain_params &c) {
-  c.struct_size = (uint32_t)sizeof(c);
-  std::memcpy(c.wb_coeffs, d.wb_coeffs, sizeof(c.wb_coeffs));
-  std::memcpy(c.cam_to_xyz_normalized, d.cam_to_xyz_normalized, sizeof(c.cam_to_xyz_normalized));
-  c.exposure = d.exposure; c.npoints = d.npoints; std::memcpy(c.points, d.points, sizeof(c.points));
-}
-int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, void *const *dsts, size_t n,
-                       int out_type, int *used_fused, void *stream) {
-  const size_t out_bytes = ng.dw * ng.dh * 3 * out_elem_size(out_type);
-  const bool f32_out = out_type == IPK_OUT_F32;
-  const int monochrome = one_pass_monochrome(d, ng);
-  if (!ng.transform_noop) {
-    // IPK_FUSED_BATCH_ORIENTED: pass 2 is one frame-table launch per chunk, every record with the descriptor's orientation (a destination is not a
-    // slice of one flat image here, so frames following each other in memory gain nothing)
-    ipk_chain_params one; chain_params_of(*d, one);
-    std::vector<ipk_chain_params> cp; std::vector<const float *> s4; std::vector<int> ori;
-    return run_preview_chunks(d, ng, bp, srcs, n, stream,
-      [&](size_t i) { return ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); },
-      [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
-        cp.assign(m, one); ori.assign(m, ng.orientation); s4.resize(m);
-        for (size_t i = 0; i < m; ++i) s4[i] = rgbe + i * slice;
-        if (used_fused) *used_fused = 0;
-        const char *stage = f32_out ? "batch to_lab+basecurve+from_lab+gamma+transform" : "batch to_lab+basecurve+from_lab+gamma+transform+quantise";
-        return chain_out_batch_impl(s4.data(), ng.dw, ng.dh, monochrome, cp.data(), ori.data(), m, ng.linear, out_type, dsts + i0, stream, tm, stage);
-      });
-  }
-  return run_preview_chunks(d, ng, bp, srcs, n, stream,
-    [&](size_t i) { return ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); },
-    // pass 2: the chain once per maximal run of frames whose destinations follow each other in memory
-    [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
-      for (size_t j = 0; j < m;) {
-        size_t k = j + 1;
-        while (k < m && dsts[i0 + k] == static_cast<char *>(dsts[i0 + k - 1]) + out_bytes) ++k;
-        const int rc = ipk_pointwise_chain_out(rgbe + j * slice, ng.dw, (k - j) * ng.dh, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points,
-                                               d->npoints, ng.linear, out_type, dsts[i0 + j], stream);
-        if (rc < 0) return rc;
-        tm.mark(f32_out ? "batch to_lab+basecurve+from_lab+gamma" : "batch to_lab+basecurve+from_lab+gamma+quantise");
-        j = k;
-      }
-      return (int)IPK_OK;
-    });
-}
-
 // ipk_pointwise_chain_out_batch: every frame's parameters through PointwisePrep::prepare (so normalize_wbs, the spline, has_curve and fast_ok are the single
 // form's, per frame) before anything is enqueued, then one frame-table launch per 64 frames (launch_chain_batch), its table in the scratch pool.  stage: the
 // name marked behind every launch
@@ -3150,7 +3029,7 @@ int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const B
 // permutation folded into the loads -- height wide where the orientation transposes.  Null, or Normal / Unknown throughout: the launches of old.
 // stage_oriented (optional): the name behind a launch with at least one oriented frame, where it differs
 int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height, int monochrome, const ipk_chain_params *params, const int *orientations, size_t n,
-                         int linear, int out_type, void *const *dsts, void *stream, StageTimer &tm, const char *stage, const char *stage_oriented) {
+                         int linear, int out_type, void *const *dsts, void *stream, StageTimer &tm, const char *stage, const char *stage_oriented = nullptr) {
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   if (!dims_ok(width, height)) return fail(IPK_ERR_INVALID, "bad pointwise_chain_out_batch arguments");
   if (n == 0) return IPK_OK;
@@ -3196,134 +3075,254 @@ int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height,
   return IPK_OK;
 }
 
-// ---- n frames, n descriptors (ipk_pipeline_run_batch_each): the plan ----
-// Same-shaped: every field equal but the five OpToLab and OpBaseCurve read -- and, where both descriptors carry IPK_FUSED_BATCH_ORIENTED beside the two bits
-// it acts with, the three OpTransform reads (plan_each then holds the negotiated demosaic sizes against each other).  a and b are taken and folded (so cfa compares as the drivers read it and
-// padding never enters); sa / sb are the struct_size values the callers wrote.  Floats compare by their bits
-// sensor_ok (IPK_FUSED_BATCH_SENSOR; plan_each holds the rest of its rule): the eleven sensor fields -- same_sensor's -- are not compared either
+// ---- two descriptors compared.  Floats compare by their bits, cfa as the folded string the drivers read, padding never ----
 bool same_bits(const float *a, const float *b, size_t n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
+// the five fields OpToLab and OpBaseCurve read: what every run lets differ
+bool same_pointwise(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) {
+  return same_bits(a.wb_coeffs, b.wb_coeffs, 4) && same_bits(a.cam_to_xyz_normalized, b.cam_to_xyz_normalized, 12) && same_bits(&a.exposure, &b.exposure, 1) &&
+         a.npoints == b.npoints && same_bits(a.points, b.points, 128);
+}
+// the three OpTransform reads: what IPK_FUSED_BATCH_ORIENTED lets differ inside a run
 bool same_orientation(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) { return a.rotation == b.rotation && a.fliph == b.fliph && a.flipv == b.flipv; }
-bool same_shape(const ipk_pipeline_desc &a, uint32_t sa, const ipk_pipeline_desc &b, uint32_t sb, bool oriented_ok = false, bool sensor_ok = false) {
+// the eleven sensor fields: what IPK_FUSED_BATCH_SENSOR lets differ inside a run (cfa_width / cfa_height are folded into cfa)
+bool same_sensor(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) {
+  return a.width == b.width && a.height == b.height && std::strcmp(a.cfa, b.cfa) == 0 && a.cfa_width == b.cfa_width && a.cfa_height == b.cfa_height &&
+         a.crop_top == b.crop_top && a.crop_right == b.crop_right && a.crop_bottom == b.crop_bottom && a.crop_left == b.crop_left &&
+         same_bits(a.blacklevels, b.blacklevels, 4) && same_bits(a.whitelevels, b.whitelevels, 4);
+}
+// equal in the five, the three and the eleven: same-shaped descriptors that are one descriptor to the uniform batch (ipk_pipeline_run_batch)
+bool same_settings(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) { return same_pointwise(a, b) && same_orientation(a, b) && same_sensor(a, b); }
+// Same-shaped: every field equal but the five -- and but the three where oriented_ok, but the eleven where sensor_ok (plan_each says when a pair may).
+// a and b are taken and folded; sa / sb are the struct_size values the callers wrote
+bool same_shape(const ipk_pipeline_desc &a, uint32_t sa, const ipk_pipeline_desc &b, uint32_t sb, bool oriented_ok, bool sensor_ok) {
   return sa == sb && a.src_type == b.src_type && a.cpp == b.cpp && a.is_cfa == b.is_cfa && (sensor_ok || same_sensor(a, b)) &&
          same_bits(a.rotatecrop, b.rotatecrop, 5) && (oriented_ok || same_orientation(a, b)) && a.maxwidth == b.maxwidth &&
          a.maxheight == b.maxheight && a.linear == b.linear && a.allow_fused == b.allow_fused && a.use_fastpath == b.use_fastpath &&
          a.schedule == b.schedule && a.fuse_rotatecrop == b.fuse_rotatecrop &&
          a.reserved1 == b.reserved1 && a.fuse_scaledown == b.fuse_scaledown;
 }
-bool same_pointwise(const ipk_pipeline_desc &a, const ipk_pipeline_desc &b) {
-  return same_bits(a.wb_coeffs, b.wb_coeffs, 4) && same_bits(a.cam_to_xyz_normalized, b.cam_to_xyz_normalized, 12) && same_bits(&a.exposure, &b.exposure, 1) &&
-         a.npoints == b.npoints && same_bits(a.points, b.points, 128);
+
+// ---- one descriptor admitted ----
+// IPK_FUSED_BATCH_PREVIEWS: a batch of staged frames whose gofloat + demosaic is the one scaling pass (gofloat_demosaic_one_pass) and whose every later op
+// is point-wise (OpRotateCrop a no-op; OpTransform too, or a permutation under IPK_FUSED_BATCH_ORIENTED) runs chunk by chunk as one scaling launch group into one RGBE scratch, then the chain over the
+// previews lying one after another.  dw * dh >= 256 is the one-pass chain's own floor, kept per frame: the batch uses the kernels a single frame would.
+// chunk: frames per scratch (at most 64, at most 256 MiB of RGBE); pass1_batched: pass 1 is the general scaling kernel's batch launch (the scratch slices
+// are 16-byte aligned), else one launch per frame of the kernel the frame selects
+struct BatchPreviews { size_t chunk; bool pass1_batched; };
+bool batches_previews(const ipk_pipeline_desc *d, const Negotiated &n, const Route &rt, size_t frames, BatchPreviews &bp) {
+  bp.chunk = 0; bp.pass1_batched = false;
+  if (!opted(d, IPK_FUSED_BATCH_PREVIEWS) || frames <= 1 || rt.kind != kStaged || !gofloat_demosaic_one_pass(d, n) || !n.rc.noop() || n.dw * n.dh < 256) return false;
+  if (!n.transform_noop) {
+    // IPK_FUSED_BATCH_ORIENTED: OpTransform rides in pass 2's loads (chain_out_batch_impl), where its image of the preview is the negotiated result
+    bool t, fx, fy; ipk::orientation_to_flips(n.orientation, t, fx, fy);
+    if (!opted(d, IPK_FUSED_BATCH_ORIENTED) || (t ? n.dh : n.dw) != n.fw || (t ? n.dw : n.dh) != n.fh) return false;
+  }
+  // (a descriptor no launch would take -- a preview of 2^24 pixels and more, whose byte count may wrap to 0, or a sensor side of 2^31 and more, which the
+  // kernel selection cannot convert -- still gets an answer here: a frame per chunk, no batch launch)
+  const size_t cap_px = (size_t)1 << 24;                                    // 256 MiB of RGBE
+  bp.chunk = n.dw > cap_px / n.dh ? 1 : std::min<size_t>(64, std::max<size_t>(1, ((size_t)256 << 20) / (n.dw * n.dh * 16)));
+  bp.pass1_batched = n.raw && dims_ok(n.r.width, n.r.height) && ipk::raw_scaled_demosaic_general(n.r.width, n.r.height, n.dw, n.dh, true, !n.cfa_branch);
+  return true;
 }
 int take_folded(const ipk_pipeline_desc *d, ipk_pipeline_desc &out) {
   IPK_FOLD_CFA(ipk_pipeline_desc, d)
   out = *d;
   return IPK_OK;
 }
+// What the plan needs to know about one descriptor, derived in one pass (admit) and only read from there on; what a frame does not fill stays zero.
+//   fast     the frame takes the raster fast path.  It is never negotiated, and nothing else is filled
+//   ng       its negotiation; ng.dw x ng.dh is the demosaic size the frames of a run share
+//   rt, bp, batches   its route, and whether it would batch its own previews: batches_previews asked for two frames (the frame count enters that function
+//            through frames <= 1 alone, so one answer serves every run longer than one).  Under IPK_FUSED_BATCH_PREVIEWS only: without the bit the
+//            answer is no whatever the route, and none is chosen
+//   four     under IPK_FUSED_BATCH_SENSOR: the filter of a frame whose pass 1 is the batch launch has a fourth colour
+struct Admitted { bool fast, batches, four; Negotiated ng; Route rt; BatchPreviews bp; };
+int admit(const ipk_pipeline_desc &d, int out_type, Admitted &a) {
+  a.fast = ipk_pipeline_takes_fastpath(&d, out_type) == 1;
+  if (a.fast) { if (d.width < 1 || d.height < 1) return fail(IPK_ERR_INVALID, "empty source"); return IPK_OK; }
+  { const int rc = negotiate(&d, out_type, a.ng); if (rc) return rc; }
+  if (!opted(&d, IPK_FUSED_BATCH_PREVIEWS)) return IPK_OK;
+  choose_route(&d, a.ng, out_type, a.rt);
+  a.batches = batches_previews(&d, a.ng, a.rt, 2, a.bp);
+  if (a.batches && a.bp.pass1_batched && a.ng.cfa_branch && opted(&d, IPK_FUSED_BATCH_SENSOR)) {
+    ipk::Cfa cfa; a.four = ipk::Cfa::parse(d.cfa, cfa) && cfa.valid() && !cfa.three_colour();
+  }
+  return IPK_OK;
+}
+
+// ---- n frames, n descriptors (ipk_pipeline_run_batch_each): the plan ----
 enum { kEachSingle = 0, kEachUniform = 1, kEachVaried = 2 };
+// segs: what is executed, in order.  first, count: the segment's frames (a single segment is one frame); route: what runs them; run_first: the first frame
+// of the run of same-shaped descriptors the segment lies in (ipk_pipeline_batch_each_plan reports it).  A varied segment is its whole run: bp chunks it,
+// sensor says whether its frames differ in a sensor field (IPK_FUSED_BATCH_SENSOR)
 struct EachPlan {
   std::vector<ipk_pipeline_desc> d;                  // taken and folded
-  std::vector<int> route; std::vector<size_t> run_first;
-  struct Varied { Negotiated ng; BatchPreviews bp; bool sensor = false; };   // sensor: the run's frames differ in their sensor fields (IPK_FUSED_BATCH_SENSOR)
-  std::vector<Negotiated> ng;                        // of the frames that qualify for IPK_FUSED_BATCH_SENSOR (others: not read)
-  std::map<size_t, Varied> varied;                   // by the run's first frame
+  std::vector<Admitted> adm;
+  struct Segment { size_t first, count; int route; size_t run_first; BatchPreviews bp; bool sensor; };
+  std::vector<Segment> segs;
 };
 // validates every descriptor as ipk_pipeline_run does (and the curve's point count, as the batch driver does), then cuts the runs
 int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, EachPlan &p) {
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
   if (n && !descs) return fail(IPK_ERR_INVALID, "null argument");
   if (n > (size_t)1 << 20) return fail(IPK_ERR_INVALID, "batch too large");
-  p.d.resize(n); p.route.assign(n, kEachSingle); p.run_first.assign(n, 0);
+  p.d.resize(n); p.adm.assign(n, Admitted{}); p.segs.clear();
   std::vector<uint32_t> sizes(n);
-  // the raster fast path is decided by the five point-wise fields themselves (default_ops_other): a frame that takes it shares no run with one that
-  // does not, so every frame of a run is on the route ipk_pipeline_run would choose for it
-  std::vector<char> fast(n, 0);
-  // IPK_FUSED_BATCH_ORIENTED: a frame whose own batch of previews would fold OpTransform into pass 2 may differ from its neighbour in rotation, fliph and
-  // flipv too, while both negotiate the same demosaic size (the scaling pass's filter): ori[i] = the frame qualifies, dwh[i] = that size
-  std::vector<char> ori(n, 0);
-  std::vector<std::pair<size_t, size_t>> dwh(n);
-  // IPK_FUSED_BATCH_SENSOR: a frame whose own batch of previews runs pass 1 as the general kernel's batch launch may differ from its neighbour in the sensor
-  // fields (same_sensor) too, while both negotiate the same demosaic size and agree in whether the filter has a fourth colour (src_type, cpp and is_cfa,
-  // hence the kernel's layout and the chain's monochrome flag, count as shape anyway): sen[i] = the frame qualifies, four[i] = its filter has one
-  std::vector<char> sen(n, 0), four(n, 0);
-  p.ng.resize(n);
   for (size_t i = 0; i < n; ++i) {
     if (!descs[i]) return fail(IPK_ERR_INVALID, "null descriptor at index %zu", i);
     sizes[i] = descs[i]->struct_size;
     int rc = take_folded(descs[i], p.d[i]);
     if (!rc) rc = validate_desc(&p.d[i], out_type, kCheckFuse | kCheckCurve);
-    if (!rc) {
-      fast[i] = ipk_pipeline_takes_fastpath(&p.d[i], out_type) == 1;
-      if (fast[i]) { if (p.d[i].width < 1 || p.d[i].height < 1) rc = fail(IPK_ERR_INVALID, "empty source"); }
-      else {
-        Negotiated ng; rc = negotiate(&p.d[i], out_type, ng);
-        if (!rc && opted(&p.d[i], IPK_FUSED_BATCH_PREVIEWS) && opted(&p.d[i], IPK_FUSED_BATCH_ORIENTED)) {
-          Route rt; BatchPreviews bp;
-          choose_route(&p.d[i], ng, out_type, rt);
-          ori[i] = batches_previews(&p.d[i], ng, rt, 2, bp);
-          dwh[i] = {ng.dw, ng.dh};
-        }
-        if (!rc && opted(&p.d[i], IPK_FUSED_BATCH_PREVIEWS) && opted(&p.d[i], IPK_FUSED_BATCH_SENSOR)) {
-          Route rt; BatchPreviews bp;
-          choose_route(&p.d[i], ng, out_type, rt);
-          sen[i] = batches_previews(&p.d[i], ng, rt, 2, bp) && bp.pass1_batched;
-          dwh[i] = {ng.dw, ng.dh};
-          if (sen[i] && ng.cfa_branch) { ipk::Cfa cfa; four[i] = ipk::Cfa::parse(p.d[i].cfa, cfa) && cfa.valid() && !cfa.three_colour(); }
-          p.ng[i] = ng;
-        }
-      }
-    }
+    if (!rc) rc = admit(p.d[i], out_type, p.adm[i]);
     if (rc) { const std::string why = g_err; return fail(rc, "descriptor %zu: %s", i, why.c_str()); }
   }
-  for (size_t a = 0; a < n;) {
-    size_t b = a + 1;
-    while (b < n && fast[a] == fast[b] && same_shape(p.d[a], sizes[a], p.d[b], sizes[b], ori[a] && ori[b] && dwh[a] == dwh[b],
-                                                     sen[a] && sen[b] && dwh[a] == dwh[b] && four[a] == four[b])) ++b;
-    for (size_t i = a; i < b; ++i) p.run_first[i] = a;
-    const size_t m = b - a;
+  // A frame that would batch its own previews and carries `bit` may differ from its run's first frame in that bit's fields, where the first frame does
+  // too and both negotiate one demosaic size (the scaling pass's filter).  IPK_FUSED_BATCH_ORIENTED folds OpTransform into pass 2.  IPK_FUSED_BATCH_SENSOR
+  // needs pass 1 to be the general kernel's batch launch for both, and both to agree in whether the filter has a fourth colour (src_type, cpp and is_cfa,
+  // hence the kernel's layout and the chain's monochrome flag, count as shape anyway)
+  const auto frees = [&](size_t i, int bit) { return p.adm[i].batches && opted(&p.d[i], bit); };
+  for (size_t a = 0, b; a < n; a = b) {
+    const Admitted &A = p.adm[a];
+    for (b = a + 1; b < n; ++b) {
+      const Admitted &B = p.adm[b];
+      const bool one_size = A.ng.dw == B.ng.dw && A.ng.dh == B.ng.dh;
+      const bool oriented_ok = one_size && frees(a, IPK_FUSED_BATCH_ORIENTED) && frees(b, IPK_FUSED_BATCH_ORIENTED);
+      const bool sensor_ok = one_size && frees(a, IPK_FUSED_BATCH_SENSOR) && frees(b, IPK_FUSED_BATCH_SENSOR) && A.bp.pass1_batched && B.bp.pass1_batched &&
+                             A.four == B.four;
+      // the raster fast path is decided by the five point-wise fields themselves (default_ops_other): a frame that takes it shares no run with one that
+      // does not, so every frame of a run is on the route ipk_pipeline_run would choose for it
+      if (A.fast != B.fast || !same_shape(p.d[a], sizes[a], p.d[b], sizes[b], oriented_ok, sensor_ok)) break;
+    }
     bool all_equal = true;
-    EachPlan::Varied v; Route rt;
-    for (size_t i = a + 1; i < b; ++i) v.sensor = v.sensor || !same_sensor(p.d[a], p.d[i]);
-    for (size_t i = a + 1; i < b; ++i) all_equal = all_equal && same_pointwise(p.d[a], p.d[i]) && same_orientation(p.d[a], p.d[i]);
-    all_equal = all_equal && !v.sensor;
-    if (m > 1 && !all_equal && !fast[a] && opted(&p.d[a], IPK_FUSED_BATCH_PREVIEWS) &&
-        negotiate(&p.d[a], out_type, v.ng) == IPK_OK && (choose_route(&p.d[a], v.ng, out_type, rt), batches_previews(&p.d[a], v.ng, rt, m, v.bp))) {
-      for (size_t i = a; i < b; ++i) p.route[i] = kEachVaried;
-      p.varied[a] = v;
+    for (size_t i = a + 1; i < b; ++i) all_equal = all_equal && same_settings(p.d[a], p.d[i]);
+    if (b - a > 1 && !all_equal && A.batches) {
+      bool sensor = false;
+      for (size_t i = a + 1; i < b; ++i) sensor = sensor || !same_sensor(p.d[a], p.d[i]);
+      p.segs.push_back({a, b - a, kEachVaried, a, A.bp, sensor});
     } else {
-      for (size_t j = a; j < b;) {                   // maximal sub-runs of equal descriptors: the uniform batch, which keeps its own routes
-        size_t k = j + 1;
-        while (k < b && same_pointwise(p.d[j], p.d[k]) && same_orientation(p.d[j], p.d[k]) && same_sensor(p.d[j], p.d[k])) ++k;
-        if (k - j > 1) for (size_t i = j; i < k; ++i) p.route[i] = kEachUniform;
-        j = k;
+      for (size_t j = a, k; j < b; j = k) {          // maximal sub-runs of equal descriptors: the uniform batch, which keeps its own routes
+        for (k = j + 1; k < b && same_settings(p.d[j], p.d[k]); ++k) {}
+        p.segs.push_back({j, k - j, k - j > 1 ? (int)kEachUniform : (int)kEachSingle, a, BatchPreviews{0, false}, false});
       }
     }
-    a = b;
   }
   return IPK_OK;
 }
-// a varied run: the chunks and pass 1 of run_batch_previews on the run's first descriptor, then ONE frame-table launch per chunk, frame i's record from
-// descriptor i -- its composed orientation included, where the run's frames carry their own -- and its destination dsts[i] wherever it lies
-int run_batch_each_varied(const ipk_pipeline_desc *ds, const EachPlan::Varied &v, const Negotiated *ngs, const void *const *srcs, void *const *dsts, size_t n,
-                          int out_type, int *used_fused, void *stream) {
-  const int monochrome = one_pass_monochrome(ds, v.ng);
-  const char *stage = out_type == IPK_OUT_F32 ? "batch-each to_lab+basecurve+from_lab+gamma" : "batch-each to_lab+basecurve+from_lab+gamma+quantise";
-  const char *stage_oriented = out_type == IPK_OUT_F32 ? "batch-each to_lab+basecurve+from_lab+gamma+transform"
-                                                       : "batch-each to_lab+basecurve+from_lab+gamma+transform+quantise";
-  std::vector<ipk_chain_params> cp;
-  std::vector<const float *> s4;
-  std::vector<int> ori;
-  return run_preview_chunks(ds, v.ng, v.bp, srcs, n, stream,
-    [&](size_t i) { return ipk_pipeline_run(ds + i, srcs[i], dsts[i], out_type, used_fused, stream); },
-    [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
-      cp.resize(m); s4.resize(m); ori.resize(m);
+
+// ---- the chunk walk ----
+// a frame as the walk sees it: its descriptor and its negotiation
+struct FrameRef { const ipk_pipeline_desc *d; const Negotiated *ng; };
+// The chunk walk both preview batches share: frame(i) is frame i of n -- the same pair for every i in a uniform batch (run_batch_previews), the plan's
+// records in a varied run -- and all n negotiate one demosaic size.  A chunk of one frame is single(i); a longer one gets its scratch, pass 1 -- the
+// chunk's RGBE previews one after another, slice floats apart -- and then pass2(i0, m, rgbe, slice, tm), which enqueues the point-wise work of frames
+// i0 .. i0 + m and marks its stages.  Pass 1 of a chunk whose frames differ in a sensor field is ONE frame-table launch (scaled_batch_each_impl: frame
+// i's levels, crops and filter from its descriptor, its window from its negotiation), marked "batch-each gofloat+demosaic"; the plan lets them differ
+// only where bp.pass1_batched holds for every one.  Any other chunk is the uniform launch on the chunk's first descriptor.
+// sensor_varies: false where no two of the n frames differ in a sensor field (none is compared then)
+extern "C++" template <typename Frame, typename Single, typename Pass2>
+int run_preview_chunks(Frame frame, const BatchPreviews &bp, bool sensor_varies, const void *const *srcs, size_t n, void *stream, Single single, Pass2 pass2) {
+  const size_t slice = frame(0).ng->dw * frame(0).ng->dh * 4;
+  std::vector<ipk_scaled_frame> sf;
+  for (size_t i0 = 0; i0 < n; i0 += bp.chunk) {
+    const size_t m = std::min(bp.chunk, n - i0);
+    if (m == 1) { const int rc = single(i0); if (rc < 0) return rc; continue; }
+    StageTimer tm(S(stream));
+    Scratch sc(S(stream));
+    void *buf = nullptr;
+    int rc = sc.get(m * slice * sizeof(float), &buf); if (rc) return rc;
+    float *rgbe = static_cast<float *>(buf);
+    // The chunk's first frame states what the chunk shares.  In a varied run that is not the run's first frame: without a table the chunk's frames have
+    // its sensor fields, and everything else pass 1 reads -- src_type, cpp, is_cfa, the demosaic size -- is equal throughout the run
+    const FrameRef c = frame(i0);
+    const ipk_pipeline_desc *const dc = c.d; const Negotiated &nc = *c.ng;
+    bool table = false;
+    if (sensor_varies) for (size_t i = 1; i < m; ++i) table = table || !same_sensor(*dc, *frame(i0 + i).d);
+    if (table) {
+      sf.assign(m, ipk_scaled_frame{});
       for (size_t i = 0; i < m; ++i) {
-        chain_params_of(ds[i0 + i], cp[i]); s4[i] = rgbe + i * slice;
-        ori[i] = ipk::transform_orientation(ds[i0 + i].rotation, ds[i0 + i].fliph != 0, ds[i0 + i].flipv != 0);   // Negotiated::orientation of frame i
+        const ipk_pipeline_desc &di = *frame(i0 + i).d; const Negotiated &ni = *frame(i0 + i).ng;
+        ipk_scaled_frame &f = sf[i];
+        f.struct_size = (uint32_t)sizeof(f);
+        f.owidth = di.width; f.x = ni.r.x; f.y = ni.r.y; f.width = ni.r.width; f.height = ni.r.height;
+        std::memcpy(f.black4, di.blacklevels, sizeof(f.black4)); std::memcpy(f.white4, di.whitelevels, sizeof(f.white4));
+        std::memcpy(f.cfa, di.cfa, sizeof(f.cfa));
       }
-      if (used_fused) *used_fused = 0;
-      return chain_out_batch_impl(s4.data(), v.ng.dw, v.ng.dh, monochrome, cp.data(), ori.data(), m, v.ng.linear, out_type, dsts + i0, stream, tm, stage,
-                                  stage_oriented);
-    }, v.sensor ? ds : nullptr, v.sensor ? ngs : nullptr);
+      rc = scaled_batch_each_impl(srcs + i0, sf.data(), m, dc->src_type, nc.cfa_branch ? -1 : (dc->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO), nc.dw, nc.dh, rgbe,
+                                  stream, tm, "batch-each gofloat+demosaic");
+      if (rc < 0) return rc;
+    } else if (bp.pass1_batched) {
+      rc = nc.cfa_branch ? raw_scaled_demosaic_batch_impl(srcs + i0, m, dc->src_type, dc->width, nc.r.x, nc.r.y, nc.r.width, nc.r.height, dc->blacklevels[0],
+                                                          dc->whitelevels[0], dc->cfa, nc.dw, nc.dh, rgbe, stream)
+                         : plain_scale_down_batch_impl(srcs + i0, m, dc->src_type, dc->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO, dc->width, nc.r.x, nc.r.y, nc.r.width,
+                                                       nc.r.height, dc->blacklevels, dc->whitelevels, nc.dw, nc.dh, rgbe, stream);
+      if (rc < 0) return rc;
+    } else {
+      for (size_t i = 0; i < m; ++i) { rc = launch_gofloat_demosaic(dc, nc, srcs[i0 + i], nullptr, rgbe + i * slice, stream); if (rc < 0) return rc; }
+    }
+    if (!table) tm.mark("batch gofloat+demosaic");
+    rc = pass2(i0, m, rgbe, slice, tm); if (rc < 0) return rc;
+  }
+  return IPK_OK;
+}
+void chain_params_of(const ipk_pipeline_desc &d, ipk_chain_params &c) {
+  c.struct_size = (uint32_t)sizeof(c);
+  std::memcpy(c.wb_coeffs, d.wb_coeffs, sizeof(c.wb_coeffs));
+  std::memcpy(c.cam_to_xyz_normalized, d.cam_to_xyz_normalized, sizeof(c.cam_to_xyz_normalized));
+  c.exposure = d.exposure; c.npoints = d.npoints; std::memcpy(c.points, d.points, sizeof(c.points));
+}
+// Pass 2 of a chunk as ONE frame-table launch (chain_out_batch_impl): frame i's record from its own descriptor and negotiation -- its point-wise
+// parameters, its composed orientation -- its source the scratch's slice i, its destination dsts[i] wherever it lies (a destination is not a slice of one
+// flat image here, so frames following each other in memory gain nothing).  The stage is prefix + "to_lab+basecurve+from_lab+gamma", "+transform" behind a
+// launch with at least one oriented frame, "+quantise" for the 8- and 16-bit outputs
+extern "C++" template <typename Frame>
+int chain_pass2_each(Frame frame, size_t i0, size_t m, const float *rgbe, size_t slice, int out_type, void *const *dsts, int *used_fused, void *stream,
+                     StageTimer &tm, const char *prefix) {
+  std::vector<ipk_chain_params> cp(m); std::vector<const float *> s4(m); std::vector<int> ori(m);
+  for (size_t i = 0; i < m; ++i) { chain_params_of(*frame(i0 + i).d, cp[i]); s4[i] = rgbe + i * slice; ori[i] = frame(i0 + i).ng->orientation; }
+  if (used_fused) *used_fused = 0;
+  const std::string chain = std::string(prefix) + "to_lab+basecurve+from_lab+gamma", quantise = out_type == IPK_OUT_F32 ? "" : "+quantise";
+  const std::string stage = chain + quantise, stage_oriented = chain + "+transform" + quantise;
+  const FrameRef c = frame(i0);
+  return chain_out_batch_impl(s4.data(), c.ng->dw, c.ng->dh, one_pass_monochrome(c.d, *c.ng), cp.data(), ori.data(), m, c.ng->linear, out_type, dsts + i0, stream,
+                              tm, stage.c_str(), stage_oriented.c_str());
+}
+
+// ---- the drivers ----
+// n frames of one descriptor as batched previews.  Pass 2 is the chain over the previews lying one after another -- or, where OpTransform is not a no-op
+// (IPK_FUSED_BATCH_ORIENTED), the frame-table launch, every record with the descriptor's orientation
+int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const BatchPreviews &bp, const void *const *srcs, void *const *dsts, size_t n,
+                       int out_type, int *used_fused, void *stream) {
+  const size_t out_bytes = ng.dw * ng.dh * 3 * out_elem_size(out_type);
+  const bool f32_out = out_type == IPK_OUT_F32;
+  const int monochrome = one_pass_monochrome(d, ng);
+  const auto frame = [&](size_t) { return FrameRef{d, &ng}; };
+  return run_preview_chunks(frame, bp, false, srcs, n, stream,
+    [&](size_t i) { return ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); },
+    [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
+      if (!ng.transform_noop) return chain_pass2_each(frame, i0, m, rgbe, slice, out_type, dsts, used_fused, stream, tm, "batch ");
+      // the chain once per maximal run of frames whose destinations follow each other in memory
+      for (size_t j = 0; j < m;) {
+        size_t k = j + 1;
+        while (k < m && dsts[i0 + k] == static_cast<char *>(dsts[i0 + k - 1]) + out_bytes) ++k;
+        const int rc = ipk_pointwise_chain_out(rgbe + j * slice, ng.dw, (k - j) * ng.dh, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points,
+                                               d->npoints, ng.linear, out_type, dsts[i0 + j], stream);
+        if (rc < 0) return rc;
+        tm.mark(f32_out ? "batch to_lab+basecurve+from_lab+gamma" : "batch to_lab+basecurve+from_lab+gamma+quantise");
+        j = k;
+      }
+      return (int)IPK_OK;
+    });
+}
+// a varied segment of the plan: the chunks and pass 1 of run_batch_previews, frame i with descriptor i's own sensor settings where they differ, then the
+// frame-table launch per chunk, frame i's record from descriptor i
+int run_batch_each_varied(const EachPlan &p, const EachPlan::Segment &s, const void *const *srcs, void *const *dsts, int out_type, int *used_fused, void *stream) {
+  const size_t a = s.first;
+  const auto frame = [&](size_t i) { return FrameRef{&p.d[a + i], &p.adm[a + i].ng}; };
+  return run_preview_chunks(frame, s.bp, s.sensor, srcs + a, s.count, stream,
+    [&](size_t i) { return ipk_pipeline_run(&p.d[a + i], srcs[a + i], dsts[a + i], out_type, used_fused, stream); },
+    [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
+      return chain_pass2_each(frame, i0, m, rgbe, slice, out_type, dsts + a, used_fused, stream, tm, "batch-each ");
+    });
 }
 }  // namespace
 
@@ -3347,19 +3346,19 @@ int ipk_pipeline_run_batch(const ipk_pipeline_desc *d, const void *const *srcs, 
   for (size_t i = 0; i < n; ++i) if (!srcs[i] || !dsts[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
   if (used_fused) *used_fused = 0;
   if (n == 0) return IPK_OK;
-  // Is Pipeline::run for each frame exactly the fused raw launch with nothing behind it (OpTransform a no-op)?  Then the batch is one
-  // persistent launch per 64 frames (ipk_raw_to_srgb_batch).
-  Negotiated ng; Route rt;
-  if (n > 1 && negotiate(d, out_type, ng) == IPK_OK && ng.transform_noop && (choose_route(d, ng, out_type, rt), rt.kind == kFusedRaw)) {
-    const int rc = ipk_raw_to_srgb_batch(&rt.fp, srcs, dsts, n, stream);
-    if (rc == IPK_OK && used_fused) *used_fused = 1;
-    return rc;
+  Negotiated ng; Route rt; BatchPreviews bp;
+  if (n > 1 && negotiate(d, out_type, ng) == IPK_OK) {
+    choose_route(d, ng, out_type, rt);
+    // Is Pipeline::run for each frame exactly the fused raw launch with nothing behind it (OpTransform a no-op)?  Then the batch is one
+    // persistent launch per 64 frames (ipk_raw_to_srgb_batch).
+    if (ng.transform_noop && rt.kind == kFusedRaw) {
+      const int rc = ipk_raw_to_srgb_batch(&rt.fp, srcs, dsts, n, stream);
+      if (rc == IPK_OK && used_fused) *used_fused = 1;
+      return rc;
+    }
+    // Or a batch of previews under IPK_FUSED_BATCH_PREVIEWS: a scaling launch group and the chain per chunk (run_batch_previews)
+    if (batches_previews(d, ng, rt, n, bp)) return run_batch_previews(d, ng, bp, srcs, dsts, n, out_type, used_fused, stream);
   }
-  // Or a batch of previews under IPK_FUSED_BATCH_PREVIEWS: a scaling launch group and the chain per chunk (run_batch_previews)
-  BatchPreviews bp;
-  if (n > 1 && (d->allow_fused & IPK_FUSED_BATCH_PREVIEWS) && negotiate(d, out_type, ng) == IPK_OK &&
-      (choose_route(d, ng, out_type, rt), batches_previews(d, ng, rt, n, bp)))
-    return run_batch_previews(d, ng, bp, srcs, dsts, n, out_type, used_fused, stream);
   for (size_t i = 0; i < n; ++i) { const int rc = ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); if (rc < 0) return rc; }
   return IPK_OK;
 }
@@ -3392,7 +3391,8 @@ int ipk_scaled_demosaic_batch_each(const void *const *srcs, const void *frames, 
 int ipk_pipeline_batch_each_plan(const ipk_pipeline_desc *const *descs, size_t n, int out_type, int *route, size_t *run_first) {
   EachPlan p;
   { const int rc = plan_each(descs, n, out_type, p); if (rc) return rc; }
-  for (size_t i = 0; i < n; ++i) { if (route) route[i] = p.route[i]; if (run_first) run_first[i] = p.run_first[i]; }
+  for (const EachPlan::Segment &s : p.segs)
+    for (size_t i = s.first; i < s.first + s.count; ++i) { if (route) route[i] = s.route; if (run_first) run_first[i] = s.run_first; }
   return IPK_OK;
 }
 // n frames, n descriptors: the plan's runs in order -- a varied run as one scaling launch group and one frame-table launch per chunk, runs of equal
@@ -3407,23 +3407,19 @@ int ipk_pipeline_run_batch_each(const ipk_pipeline_desc *const *descs, const voi
     if (!srcs[i] || !dsts[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
     // a curve the launches would refuse, before anything is enqueued (every route but the fast path builds it)
     const ipk_pipeline_desc &d = p.d[i];
-    if (!curve_is_noop(d.exposure, d.npoints) && ipk_pipeline_takes_fastpath(&d, out_type) != 1) {
+    if (!curve_is_noop(d.exposure, d.npoints) && !p.adm[i].fast) {
       ipk::Spline sp;
       const int rc = build_curve(d.exposure, d.points, d.npoints, sp);
       if (rc) { const std::string why = g_err; return fail(rc, "descriptor %zu: %s", i, why.c_str()); }
     }
   }
   if (used_fused) *used_fused = 0;
-  for (size_t a = 0; a < n;) {
-    size_t b = a + 1;
-    while (b < n && p.route[b] == p.route[a] && p.run_first[b] == p.run_first[a] &&
-           (p.route[a] != kEachUniform || (same_pointwise(p.d[a], p.d[b]) && same_orientation(p.d[a], p.d[b]) && same_sensor(p.d[a], p.d[b])))) ++b;
-    int rc;
-    if (p.route[a] == kEachVaried) rc = run_batch_each_varied(&p.d[a], p.varied.at(a), &p.ng[a], srcs + a, dsts + a, b - a, out_type, used_fused, stream);
-    else if (p.route[a] == kEachUniform) rc = ipk_pipeline_run_batch(&p.d[a], srcs + a, dsts + a, b - a, out_type, used_fused, stream);
-    else { b = a + 1; rc = ipk_pipeline_run(&p.d[a], srcs[a], dsts[a], out_type, used_fused, stream); }
+  for (const EachPlan::Segment &s : p.segs) {
+    const size_t a = s.first;
+    const int rc = s.route == kEachVaried ? run_batch_each_varied(p, s, srcs, dsts, out_type, used_fused, stream)
+                 : s.route == kEachUniform ? ipk_pipeline_run_batch(&p.d[a], srcs + a, dsts + a, s.count, out_type, used_fused, stream)
+                                           : ipk_pipeline_run(&p.d[a], srcs[a], dsts[a], out_type, used_fused, stream);
     if (rc < 0) return rc;
-    a = b;
   }
   return IPK_OK;
 }

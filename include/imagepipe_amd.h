@@ -953,25 +953,27 @@ IPK_API int ipk_devices_sync(void);
  * (and its curve is built) BEFORE anything is enqueued: an invalid descriptor or a null srcs[i] / dsts[i] fails with IPK_ERR_INVALID, names the index in
  * ipk_last_error and writes nothing.  n = 0 is IPK_OK.  The host arrays are read before the call returns.
  * The plan, which ipk_pipeline_batch_each_plan reports without a GPU (route[i], run_first[i]; either may be NULL): two descriptors are SAME-SHAPED when
- * every field is equal except wb_coeffs, cam_to_xyz_normalized, exposure, npoints and points -- field by field, cfa as a string after the drivers' usual
- * folding, floats by their bits, padding not at all; struct_size, allow_fused, linear, schedule and the fuse flags count as shape.  Where BOTH
- * descriptors carry IPK_FUSED_BATCH_ORIENTED beside IPK_FUSED_ON | IPK_FUSED_BATCH_PREVIEWS, each would batch its own previews
- * (ipk_pipeline_batches_previews answers 1 for it) and both negotiate the same demosaic size (ipk_pipeline_sizes), rotation, fliph and flipv may
- * differ as well: eight fields instead of five.  The demosaic size decides the scaling pass's filter; under one maxwidth alone a Rotate90 / Rotate270
- * frame negotiates another one than a Normal frame (transform_forward swaps the sides before the clamp) and still cuts the run, under a square box
- * (maxwidth == maxheight) frames of equal source size agree, and fliph / flipv never enter the fold.  One thing the five
- * Where BOTH descriptors carry IPK_FUSED_BATCH_SENSOR beside IPK_FUSED_ON | IPK_FUSED_BATCH_PREVIEWS, each would batch its own previews with the general
- * scaling kernel's batch launch (ipk_pipeline_batches_previews answers 1 with pass1_batched = 1), both negotiate the same demosaic size and both agree in
- * whether the filter has a fourth colour, the SENSOR fields may differ too: width, height, cfa (cfa_width, cfa_height), crop_top / right / bottom / left,
- * blacklevels and whitelevels.  src_type, cpp and is_cfa still count as shape (they decide the kernel's instantiation, its layout and the chain's monochrome
- * flag), as do maxwidth and maxheight; the orientation rule above combines with this one unchanged.  A run whose frames differ in a sensor field is
- * route 2: pass 1 of a chunk whose frames differ in them is ONE ipk_scaled_demosaic_batch_each launch, frame i's window, levels and filter from descriptor
- * i's own negotiation, named "batch-each gofloat+demosaic"; a chunk whose frames agree in them is the uniform launch on the chunk's first descriptor under
- * the old name; pass 2 is what it is below.  One thing the five
- * fields themselves decide counts as shape too: ipk_pipeline_takes_fastpath (the raster fast path is taken for the DEFAULT ops only), so a raster with
- * default ops and an edited one are never same-shaped under IPK_OUT_U8 / IPK_OUT_U16, and every frame of a run is on the route ipk_pipeline_run would
- * choose for it.  The frames are cut, in order, into maximal runs of consecutive same-shaped descriptors; run_first[i] is the first frame of frame
- * i's run.  For a run of m frames:
+ * every field is equal -- field by field, cfa as a string after the drivers' usual folding, floats by their bits, padding not at all -- except the fields
+ * this rule lets differ.  struct_size, src_type, cpp, is_cfa, rotatecrop, maxwidth, maxheight, linear, allow_fused, use_fastpath, schedule and the fuse
+ * flags always count.  So does one thing the five fields below decide themselves: ipk_pipeline_takes_fastpath (the raster fast path is taken for the
+ * DEFAULT ops only), so a raster with default ops and an edited one are never same-shaped under IPK_OUT_U8 / IPK_OUT_U16, and every frame of a run is on
+ * the route ipk_pipeline_run would choose for it.
+ *   These FIVE may always differ: wb_coeffs, cam_to_xyz_normalized, exposure, npoints and points.
+ *   These THREE may differ -- rotation, fliph and flipv: eight fields instead of five -- when BOTH descriptors carry IPK_FUSED_BATCH_ORIENTED beside
+ *     IPK_FUSED_ON | IPK_FUSED_BATCH_PREVIEWS, each would batch its own previews (ipk_pipeline_batches_previews answers 1 for it) and both negotiate
+ *     the same demosaic size (ipk_pipeline_sizes).  The demosaic size decides the scaling pass's filter; under one maxwidth alone a Rotate90 / Rotate270
+ *     frame negotiates another one than a Normal frame (transform_forward swaps the sides before the clamp) and still cuts the run, under a square box
+ *     (maxwidth == maxheight) frames of equal source size agree, and fliph / flipv never enter the fold.
+ *   These ELEVEN may differ -- the SENSOR fields: width, height, cfa, cfa_width, cfa_height, crop_top / right / bottom / left, blacklevels and
+ *     whitelevels -- when BOTH descriptors carry IPK_FUSED_BATCH_SENSOR beside IPK_FUSED_ON | IPK_FUSED_BATCH_PREVIEWS, each would batch its own previews
+ *     with the general scaling kernel's batch launch (ipk_pipeline_batches_previews answers 1 with pass1_batched = 1), both negotiate the same demosaic
+ *     size and both agree in whether the filter has a fourth colour.  src_type, cpp and is_cfa count even then (they decide the kernel's instantiation, its
+ *     layout and the chain's monochrome flag), as do maxwidth and maxheight.  A run whose frames differ in a sensor field is route 2: pass 1 of a chunk
+ *     whose frames differ in them is ONE ipk_scaled_demosaic_batch_each launch, frame i's window, levels and filter from descriptor i's own negotiation,
+ *     named "batch-each gofloat+demosaic"; a chunk whose frames agree in them is the uniform launch on the chunk's first descriptor, named
+ *     "batch gofloat+demosaic"; pass 2 is what it is below.
+ * The two conditions are asked of a pair independently: it may meet either, both or neither.  The frames are cut, in order, into maximal runs of
+ * consecutive same-shaped descriptors; run_first[i] is the first frame of frame i's run.  For a run of m frames:
  *   route 2, varied previews: m > 1, ipk_pipeline_batches_previews(descs[run_first], out_type, m, ...) answers 1 (so allow_fused needs IPK_FUSED_ON |
  *     IPK_FUSED_BATCH_PREVIEWS: no new bit) and the descriptors are not all equal in the five (eight) fields.  Chunks follow that report's chunk; pass 1 is the
  *     uniform route's pass 1 -- one set of levels, crops and filter per chunk, or under IPK_FUSED_BATCH_SENSOR the frame-table launch above -- and pass 2 is ONE ipk_pointwise_chain_out_batch launch per chunk: source i

@@ -1,7 +1,7 @@
 """The plan of ipk_pipeline_run_batch_each under AddressSanitizer + UBSan (no GPU): tests/cpp/batch_plan.cpp -- batches whose frames differ in the sensor
 fields IPK_FUSED_BATCH_SENSOR lets vary, with every mask of bits 0, 8, 9 and 10, through exact-size heap descriptors and outputs, then seeded hostile
-batches -- built by the stand-alone programs' pattern rules in tests/cpp/Makefile (asked for by name, behind `make san`), run sanitized and plain: no report, the documented number of cases, equal digests.
-Nothing sanitized is loaded into python; the harness is tests/test_host_sanitizers.py's."""
+batches -- built by the stand-alone programs' pattern rules in tests/cpp/Makefile (asked for by name, behind `make san`), run sanitized and plain: no report, the documented number of cases, equal digests -- and the plain build's equal to
+tests/golden/batch_plan_digests.txt, the plan as recorded.  Nothing sanitized is loaded into python; the harness is tests/test_host_sanitizers.py's."""
 import os
 import subprocess
 
@@ -24,3 +24,9 @@ def plans(built):
 
 def test_batch_plan_under_asan_and_ubsan(plans):
     _check(plans["asan"], plans["plain"], {"plan_contract": CONTRACT, "plan_hostile": HOSTILE}, "batch_plan")
+
+
+def test_the_plan_is_the_recorded_one(plans):
+    """status, route and run_first of every case, as the plain build printed them before the plan became one record per descriptor and a list of runs"""
+    recorded = _sections(open(os.path.join(os.path.dirname(CPP), "golden", "batch_plan_digests.txt")).read())
+    assert plans["plain"] == recorded and set(recorded) == {"plan_contract", "plan_hostile"}, (plans["plain"], recorded)

@@ -297,7 +297,8 @@ def check_driver(ipa, orc, n, out, layout, oracle_frames=None, make=variant, key
     assert names[2 * multi:] == (singles[n - 1][2] if rest == 1 else []), (tag, names)
     hits = chunk_entries(ran)
     assert len(hits) == 1 and re.match(frames_tag(T, plain), hits[0]), (tag, sorted(ran))
-    assert len(eb.carriers(ran)) == 1, (tag, sorted(ran))
+    # one chain launch per chunk of several frames; the log keeps distinct entries, and fast_ok is the AND over ONE launch's frames: two chunks may differ in it
+    assert 1 <= len(eb.carriers(ran)) <= multi, (tag, sorted(ran))
     assert used == singles[n - 1][3] == 0, tag
     assert not any("batch" in e for s in singles for e in s[1]), tag
     for spec, f in fr:
@@ -327,14 +328,30 @@ def test_driver_f32_sources(ipa, orc):
     check_driver(ipa, orc, 5, OUT_U16, "reverse", src="f32", T="float")
 
 
+TRIPLES = [(0, 0, 0), (1, 0, 0), (2, 1, 0), (3, 0, 0), (0, 0, 1)]
+
+
+def oriented_variant(k, src="u16"):
+    """bits 9 and 10: frame k's own sensor settings and its own orientation, under the 23 x 23 box"""
+    r, h, v = TRIPLES[k % 5]
+    return variant(k, mask=MASK | ORIENTED, src=src, maxheight=23, rotation=r, fliph=h, flipv=v)
+
+
 def test_driver_with_orientations_too(ipa, orc):
     """bits 9 and 10: sensor settings and orientation both vary inside one run under the 23 x 23 box"""
-    triples = [(0, 0, 0), (1, 0, 0), (2, 1, 0), (3, 0, 0), (0, 0, 1)]
-    make = lambda k, src="u16": variant(k, mask=MASK | ORIENTED, src=src, maxheight=23, rotation=triples[k % 5][0], fliph=triples[k % 5][1],
-                                        flipv=triples[k % 5][2])
-    _, names, ran = check_driver(ipa, orc, 5, OUT_U8, "reverse", make=make, key="oriented")
+    _, names, ran = check_driver(ipa, orc, 5, OUT_U8, "reverse", make=oriented_variant, key="oriented")
     assert names == [S1E, "batch-each to_lab+basecurve+from_lab+gamma+transform+quantise"], names
     assert any("orient=1" in e for e in eb.carriers(ran)), sorted(ran)
+
+
+@pytest.mark.parametrize("make,key,stage2", [(variant, "mosaic", S2E[OUT_U8]),
+                                             (oriented_variant, "oriented", "batch-each to_lab+basecurve+from_lab+gamma+transform+quantise")],
+                         ids=["bits_0_8_10", "bits_0_8_9_10"])
+def test_driver_second_chunk_of_several_frames(ipa, orc, make, key, stage2):
+    """67 frames: a chunk of 64 and a chunk of 3, whose shared settings are those of ITS first frame (frame 64), not of the run's"""
+    _, names, ran = check_driver(ipa, orc, 67, OUT_U8, "reverse", oracle_frames=(0, 63, 64, 66), make=make, key=key)
+    assert names == [S1E, stage2, S1E, stage2], names
+    assert any("fast_ok=0" in e for e in eb.carriers(ran)), sorted(ran)    # frame 5's matrix, in the first chunk
 
 
 @pytest.mark.parametrize("kind,plain", [("mono", ",plain=1"), ("cpp3", ",plain=3")])
