@@ -18,7 +18,7 @@ from . import _lib
 from ._lib import (IpkError, FusedParams, PipelineDesc, ChainParams, ScaledFrame, OUT_F32, OUT_U8, OUT_U16, SRC_U16, SRC_F32, SRC_RGB8, SRC_RGB16,
                    OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN,
                    ROT_NORMAL, ROT_90, ROT_180, ROT_270, IPK_NOOP, PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO, FUSED_BATCH_PREVIEWS, FUSED_BATCH_ORIENTED,
-                   FUSED_BATCH_SENSOR)
+                   FUSED_BATCH_SENSOR, FUSED_BATCH_SIZES)
 
 __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", "RawImage", "OtherImage", "PipelineSettings", "PipelineGlobals", "PipelineOps",
            "Pipeline", "OpGoFloat", "OpDemosaic", "OpRotateCrop", "OpToLab", "OpBaseCurve", "OpFromLab", "OpGamma",
@@ -26,7 +26,8 @@ __all__ = ["init", "init_devices", "deal_frames", "Context", "lib", "OpBuffer", 
            "transform_window_footprint", "raw_scaled_demosaic_window", "raw_demosaic_scaled", "raster_scale_down_window", "scaled_window_footprint", "plain_scale_down",
            "plain_scale_down_window", "raw_scaled_demosaic_batch", "plain_scale_down_batch", "chain_params", "pointwise_chain_out_batch",
            "batch_each_plan", "run_batch_each", "PLAIN_RASTER", "PLAIN_RGB", "PLAIN_MONO", "FUSED_BATCH_PREVIEWS", "FUSED_BATCH_ORIENTED",
-           "FUSED_BATCH_SENSOR", "scaled_frame", "scaled_demosaic_batch_each",
+           "FUSED_BATCH_SENSOR", "scaled_frame", "scaled_demosaic_batch_each", "FUSED_BATCH_SIZES", "scaled_demosaic_batch_sized",
+           "pointwise_chain_out_batch_sized", "batch_each_chunks",
            "FusedPlan", "IpkError"]
 
 _initialized_device = None
@@ -616,6 +617,7 @@ class Pipeline:
         self.batch_previews = False           # ipk_pipeline_desc.allow_fused bit 8 (IPK_FUSED_BATCH_PREVIEWS): run_batch() runs downscaled previews as one scaling launch group and one point-wise pass per chunk of frames where batches_previews() says so
         self.batch_oriented = False           # ipk_pipeline_desc.allow_fused bit 9 (IPK_FUSED_BATCH_ORIENTED), set only together with batch_previews: batched previews take frames of any orientation (OpTransform folded into the point-wise pass), and run_batch_each lets rotation / fliph / flipv differ inside a run
         self.batch_sensor = False             # ipk_pipeline_desc.allow_fused bit 10 (IPK_FUSED_BATCH_SENSOR), set only together with batch_previews: run_batch_each lets width, height, cfa, the crops and the levels differ inside a run whose frames negotiate one demosaic size (one frame-table scaling launch per chunk)
+        self.batch_sizes = False              # ipk_pipeline_desc.allow_fused bit 11 (IPK_FUSED_BATCH_SIZES), set only together with batch_previews, and nothing without batch_oriented or batch_sensor: run_batch_each lets the frames of such a run negotiate their own demosaic sizes (one sized scaling launch and one sized point-wise launch per chunk)
         self.window_previews = False          # ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
 
     @staticmethod
@@ -697,6 +699,8 @@ class Pipeline:
                 d.allow_fused |= _lib.FUSED_BATCH_ORIENTED
             if self.batch_sensor:
                 d.allow_fused |= _lib.FUSED_BATCH_SENSOR
+            if self.batch_sizes:
+                d.allow_fused |= _lib.FUSED_BATCH_SIZES
         d.use_fastpath = int(st.use_fastpath)
         d.schedule = int(self.schedule)
         d.fuse_rotatecrop = int(self.fuse_rotatecrop)
@@ -1158,6 +1162,44 @@ def scaled_demosaic_batch_each(srcs: Sequence[torch.Tensor], frames, nwidth, nhe
     return out
 
 
+def scaled_demosaic_batch_sized(srcs: Sequence[torch.Tensor], frames, sizes, *, kind=-1, is_float=None, out: Optional[torch.Tensor] = None):
+    """ipk_scaled_demosaic_batch_sized: scaled_demosaic_batch_each with a result size per frame -- sizes[i] = (nwidth_i, nheight_i) -- as one sized
+    frame-table launch per 64 frames.  Returns the packed f32 device tensor: slice i holds nheight_i * nwidth_i * 4 floats behind the earlier slices and
+    is what the single-frame call gives for frame i at its own size."""
+    n = len(srcs)
+    if len(frames) != n or len(sizes) != n:
+        raise ValueError("scaled_demosaic_batch_sized: as many frame records and sizes as frames")
+    st = SRC_F32 if (srcs[0].dtype == torch.float32 if n else bool(is_float)) else SRC_U16
+    if out is None:
+        out = torch.empty(max(1, sum(int(w) * int(h) * 4 for w, h in sizes)), dtype=torch.float32, device="cuda")
+    arr = (ScaledFrame * max(n, 1))(*frames)
+    sz = (C.c_size_t * max(2 * n, 1))(*[int(v) for wh in sizes for v in wh])
+    _lib.check(lib().ipk_scaled_demosaic_batch_sized(_frame_ptrs(srcs), arr, sz, n, st, kind, out.data_ptr(), _stream()), "ipk_scaled_demosaic_batch_sized")
+    return out
+
+
+def pointwise_chain_out_batch_sized(srcs4: Sequence[torch.Tensor], sizes, params, *, monochrome=False, linear=False, out_type=OUT_F32,
+                                    outs: Optional[Sequence[torch.Tensor]] = None, orientations: Optional[Sequence[int]] = None):
+    """ipk_pointwise_chain_out_batch_sized: pointwise_chain_out_batch with a size per frame -- sizes[i] = (width_i, height_i) -- and, optionally, an
+    orientation per frame, as one sized frame-table launch per 64 frames.  Frame i is what the one-frame call of its size gives.  Returns the list of
+    output tensors (fresh ones are (height_i, width_i, 3), (width_i, height_i, 3) for the four transposing orientations; u16 bits in int16)."""
+    n = len(srcs4)
+    if len(params) != n or len(sizes) != n or (orientations is not None and len(orientations) != n):
+        raise ValueError("pointwise_chain_out_batch_sized: as many parameter sets, sizes (and orientations) as frames")
+    dt = {OUT_F32: torch.float32, OUT_U8: torch.uint8, OUT_U16: torch.int16}[out_type]
+    if outs is None:
+        t = [orientations is not None and 4 <= int(orientations[i]) <= 7 for i in range(n)]
+        outs = [torch.empty((w, h, 3) if t[i] else (h, w, 3), dtype=dt, device="cuda") for i, (w, h) in enumerate(sizes)]
+    if len(outs) != n or any(o.dtype != dt or o.numel() != int(w) * int(h) * 3 or not o.is_contiguous() for o, (w, h) in zip(outs, sizes)):
+        raise ValueError("pointwise_chain_out_batch_sized: outs must be %d contiguous %s tensors of each frame's own size" % (n, dt))
+    arr = (ChainParams * max(n, 1))(*params)
+    sz = (C.c_size_t * max(2 * n, 1))(*[int(v) for wh in sizes for v in wh])
+    ori = None if orientations is None else (C.c_int * max(n, 1))(*[int(r) for r in orientations])
+    _lib.check(lib().ipk_pointwise_chain_out_batch_sized(_frame_ptrs(srcs4), sz, int(bool(monochrome)), arr, ori, n, int(bool(linear)), out_type,
+                                                         _frame_ptrs(outs), _stream()), "ipk_pointwise_chain_out_batch_sized")
+    return list(outs)
+
+
 def chain_params(wb_coeffs=(1.0, 1.0, 1.0, 0.0), cam_to_xyz_normalized=None, exposure=0.0, points=()):
     """ipk_chain_params: the descriptor fields OpToLab and OpBaseCurve read, for one frame of pointwise_chain_out_batch.  points: (x, y) pairs"""
     p = ChainParams()
@@ -1215,6 +1257,16 @@ def batch_each_plan(pipes, out_type=OUT_F32):
     route, first = (C.c_int * max(n, 1))(), (C.c_size_t * max(n, 1))()
     _lib.check(lib().ipk_pipeline_batch_each_plan(dp, n, out_type, route, first), "ipk_pipeline_batch_each_plan")
     return [(int(route[i]), int(first[i])) for i in range(n)]
+
+
+def batch_each_chunks(pipes, out_type=OUT_F32):
+    """The chunks run_batch_each executes its plan in (ipk_pipeline_batch_each_chunks, host-only): per frame the first frame of its chunk -- the frames
+    that share one scratch and one pair of launches.  Batched previews are cut greedily: at most 64 frames and 256 MiB of RGBE previews per chunk."""
+    n = len(pipes)
+    _ds, dp = _desc_ptrs(pipes)
+    first = (C.c_size_t * max(n, 1))()
+    _lib.check(lib().ipk_pipeline_batch_each_chunks(dp, n, out_type, first), "ipk_pipeline_batch_each_chunks")
+    return [int(first[i]) for i in range(n)]
 
 
 def run_batch_each(pipes, srcs: Sequence[torch.Tensor], out_type=OUT_F32, outs: Optional[Sequence[torch.Tensor]] = None):

@@ -19,6 +19,7 @@ FUSED_PLAIN_PREVIEWS = 128
 FUSED_BATCH_PREVIEWS = 256
 FUSED_BATCH_ORIENTED = 512
 FUSED_BATCH_SENSOR = 1024
+FUSED_BATCH_SIZES = 2048
 PLAIN_RASTER, PLAIN_RGB, PLAIN_MONO = 0, 1, 2                                                          # ipk_plain_kind
 OR_NORMAL, OR_HFLIP, OR_ROT180, OR_VFLIP, OR_TRANSPOSE, OR_ROT90, OR_TRANSVERSE, OR_ROT270, OR_UNKNOWN = range(9)
 ROT_NORMAL, ROT_90, ROT_180, ROT_270 = range(4)
@@ -191,6 +192,10 @@ SIGNATURES = {
     "ipk_pipeline_run_batch": (C.c_int, [C.POINTER(PipelineDesc), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int), _vp]),
     "ipk_pipeline_run_batch_each": (C.c_int, [C.POINTER(C.POINTER(PipelineDesc)), C.POINTER(_vp), C.POINTER(_vp), _sz, C.c_int, C.POINTER(C.c_int), _vp]),
     "ipk_pipeline_batch_each_plan": (C.c_int, [C.POINTER(C.POINTER(PipelineDesc)), _sz, C.c_int, C.POINTER(C.c_int), _szp]),
+    "ipk_pipeline_batch_each_chunks": (C.c_int, [C.POINTER(C.POINTER(PipelineDesc)), _sz, C.c_int, _szp]),
+    "ipk_scaled_demosaic_batch_sized": (C.c_int, [C.POINTER(_vp), C.POINTER(ScaledFrame), _szp, _sz, C.c_int, C.c_int, _vp, _vp]),
+    "ipk_pointwise_chain_out_batch_sized": (C.c_int, [C.POINTER(_vp), _szp, C.c_int, C.POINTER(ChainParams), C.POINTER(C.c_int), _sz, C.c_int, C.c_int,
+                                                      C.POINTER(_vp), _vp]),
     "ipk_pointwise_chain_out_batch": (C.c_int, [C.POINTER(_vp), _sz, _sz, C.c_int, C.POINTER(ChainParams), _sz, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
     "ipk_pointwise_chain_out_batch_oriented": (C.c_int, [C.POINTER(_vp), _sz, _sz, C.c_int, C.POINTER(ChainParams), C.POINTER(C.c_int), _sz, C.c_int, C.c_int,
                                                          C.POINTER(_vp), _vp]),

@@ -2979,16 +2979,29 @@ namespace {
 // ---- the two frame-table primitives ----
 // ipk_scaled_demosaic_batch_each: every frame validated and admitted (its filter's device table fetched) before anything is enqueued, then one frame-table
 // launch per 64 frames (launch_raw_scaled_demosaic_each), its table in the scratch pool.  stage: the name marked behind every launch
+// sizes (optional, 2n values: nwidth_i, nheight_i; ipk_scaled_demosaic_batch_sized): frame i's own result size -- nwidth and nheight are not read, slice i
+// lies behind the earlier slices, and each group of 64 is one sized launch.  Equal sizes throughout are the call without them
 int scaled_batch_each_impl(const void *const *srcs, const ipk_scaled_frame *frames, size_t n, int src_type, int kind, size_t nwidth, size_t nheight, float *dst4,
-                           void *stream, StageTimer &tm, const char *stage) {
+                           void *stream, StageTimer &tm, const char *stage, const size_t *sizes = nullptr) {
   if (n == 0) return IPK_OK;
   if (kind == IPK_PLAIN_RASTER) return fail(IPK_ERR_UNSUPPORTED, "scaled_demosaic_batch_each: the raster scaler has no frame-table mode");
   if (kind != -1 && kind != IPK_PLAIN_RGB && kind != IPK_PLAIN_MONO) return fail(IPK_ERR_INVALID, "bad kind");
-  if (!srcs || !frames || !dst4 || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32) || n > (size_t)1 << 20)
+  if (n > (size_t)1 << 20) return fail(IPK_ERR_INVALID, "batch too large");
+  if (sizes) {
+    bool equal = true;
+    for (size_t i = 0; i < n; ++i) {
+      if (!dims_ok(sizes[2 * i], sizes[2 * i + 1])) return fail(IPK_ERR_INVALID, "sizes[%zu]: bad dimensions %zux%zu", i, sizes[2 * i], sizes[2 * i + 1]);
+      equal = equal && sizes[2 * i] == sizes[0] && sizes[2 * i + 1] == sizes[1];
+    }
+    nwidth = sizes[0]; nheight = sizes[1];                                   // equal throughout: the call without sizes
+    if (equal) sizes = nullptr;
+  }
+  if (!srcs || !frames || !dst4 || !dims_ok(nwidth, nheight) || (src_type != IPK_SRC_U16 && src_type != IPK_SRC_F32))
     return fail(IPK_ERR_INVALID, "bad scaled_demosaic_batch_each arguments");
   const bool plain = kind != -1;
   std::vector<ipk::ScaledFrameLaunch> fl(n);
   for (size_t i = 0; i < n; ++i) {
+    const size_t nw_i = sizes ? sizes[2 * i] : nwidth, nh_i = sizes ? sizes[2 * i + 1] : nheight;      // the frame's own result
     const ipk_scaled_frame &f = frames[i];
     if (!srcs[i]) return fail(IPK_ERR_INVALID, "null frame pointer at index %zu", i);
     if (f.struct_size != sizeof(ipk_scaled_frame))
@@ -3005,17 +3018,19 @@ int scaled_batch_each_impl(const void *const *srcs, const ipk_scaled_frame *fram
       if (rc) { const std::string why = g_err; return fail(rc, "frames[%zu]: %s", i, why.c_str()); }
       l.cfa48_dev = dev.cfa48;
     }
-    if (!ipk::raw_scaled_demosaic_general(f.width, f.height, nwidth, nheight, true, plain))
-      return fail(IPK_ERR_UNSUPPORTED, "frames[%zu]: %zux%zu -> %zux%zu selects a window-8 kernel, which has no frame-table mode", i, f.width, f.height, nwidth, nheight);
+    if (!ipk::raw_scaled_demosaic_general(f.width, f.height, nw_i, nh_i, true, plain))
+      return fail(IPK_ERR_UNSUPPORTED, "frames[%zu]: %zux%zu -> %zux%zu selects a window-8 kernel, which has no frame-table mode", i, f.width, f.height, nw_i, nh_i);
   }
-  const size_t slice = nwidth * nheight * 4;
+  const size_t slice = nwidth * nheight * 4;                                 // one size for all: the slices are this far apart
+  size_t off = 0;                                                            // sized: where the group's first slice begins
   for (size_t i0 = 0; i0 < n; i0 += ipk::kScaledEachMax) {
     const size_t m = std::min(ipk::kScaledEachMax, n - i0);
     Scratch sc(S(stream));
     void *table = nullptr;
     { const int rc = sc.get(ipk::scaled_each_table_bytes(m), &table); if (rc) return rc; }
     const int lrc = ipk::launch_raw_scaled_demosaic_each(fl.data() + i0, m, src_type == IPK_SRC_U16, plain ? (kind == IPK_PLAIN_MONO ? 1 : 3) : 0, nwidth, nheight,
-                                                         dst4 + i0 * slice, table, S(stream));
+                                                         dst4 + (sizes ? off : i0 * slice), table, S(stream), sizes ? sizes + 2 * i0 : nullptr);
+    if (sizes) for (size_t i = i0; i < i0 + m; ++i) off += sizes[2 * i] * sizes[2 * i + 1] * 4;
     if (lrc == -4) return fail(IPK_ERR_HIP, "scaled_demosaic_batch_each: the table upload or the launch could not be enqueued");
     if (lrc != 0) return fail(IPK_ERR_INVALID, "scaled_demosaic_batch_each: the launcher refused the frames");
     tm.mark(stage);
@@ -3028,15 +3043,30 @@ int scaled_batch_each_impl(const void *const *srcs, const ipk_scaled_frame *fram
 // orientations (optional, n ipk_orientation values): frame i leaves as OpTransform's image of its result -- its record gathers through frame_gather, the
 // permutation folded into the loads -- height wide where the orientation transposes.  Null, or Normal / Unknown throughout: the launches of old.
 // stage_oriented (optional): the name behind a launch with at least one oriented frame, where it differs
+// sizes (optional, 2n values: width_i, height_i; ipk_pointwise_chain_out_batch_sized): frame i's own size -- width and height are not read, every frame is
+// held to the bounds of a call of its own, and each group of 64 is one sized launch.  Equal sizes throughout are the call without them
 int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height, int monochrome, const ipk_chain_params *params, const int *orientations, size_t n,
-                         int linear, int out_type, void *const *dsts, void *stream, StageTimer &tm, const char *stage, const char *stage_oriented = nullptr) {
+                         int linear, int out_type, void *const *dsts, void *stream, StageTimer &tm, const char *stage, const char *stage_oriented = nullptr,
+                         const size_t *sizes = nullptr) {
   if (out_type < 0 || out_type > 2) return fail(IPK_ERR_INVALID, "bad out_type");
-  if (!dims_ok(width, height)) return fail(IPK_ERR_INVALID, "bad pointwise_chain_out_batch arguments");
+  if (sizes && n != 0) {
+    if (n > (size_t)1 << 20) return fail(IPK_ERR_INVALID, "batch too large");
+    bool equal = true;
+    for (size_t i = 0; i < n; ++i) {
+      if (!dims_ok(sizes[2 * i], sizes[2 * i + 1])) return fail(IPK_ERR_INVALID, "sizes[%zu]: bad dimensions %zux%zu", i, sizes[2 * i], sizes[2 * i + 1]);
+      if (out_type != IPK_OUT_F32 && sizes[2 * i] * sizes[2 * i + 1] < 256)
+        return fail(IPK_ERR_UNSUPPORTED, "sizes[%zu]: pointwise_chain_out_batch needs at least 256 pixels per frame for 8- and 16-bit outputs", i);
+      equal = equal && sizes[2 * i] == sizes[0] && sizes[2 * i + 1] == sizes[1];
+    }
+    width = sizes[0]; height = sizes[1];
+    if (equal) sizes = nullptr;
+  }
+  if (!sizes && !dims_ok(width, height)) return fail(IPK_ERR_INVALID, "bad pointwise_chain_out_batch arguments");
   if (n == 0) return IPK_OK;
   if (!srcs4 || !dsts || !params) return fail(IPK_ERR_INVALID, "null argument");
   if (n > (size_t)1 << 20) return fail(IPK_ERR_INVALID, "batch too large");
   const size_t npix = width * height, dalign = out_elem_size(out_type);
-  if (out_type != IPK_OUT_F32 && npix < 256)
+  if (!sizes && out_type != IPK_OUT_F32 && npix < 256)
     return fail(IPK_ERR_UNSUPPORTED, "pointwise_chain_out_batch needs at least 256 pixels per frame for 8- and 16-bit outputs");
   std::vector<PointwisePrep> pps(n);
   for (size_t i = 0; i < n; ++i) {
@@ -3053,21 +3083,24 @@ int chain_out_batch_impl(const float *const *srcs4, size_t width, size_t height,
   }
   std::vector<ipk::FusedLaunch> fl;
   std::vector<ipk::GatherSource> gs;
+  std::vector<size_t> np;
   for (size_t i0 = 0; i0 < n; i0 += ipk::kChainBatchMax) {
     const size_t m = std::min(ipk::kChainBatchMax, n - i0);
-    fl.clear(); gs.clear();
+    fl.clear(); gs.clear(); np.clear();
     bool oriented = false;
     for (size_t i = 0; i < m; ++i) {
       fl.push_back(pps[i0 + i].f);
+      const size_t wi = sizes ? sizes[2 * (i0 + i)] : width, hi = sizes ? sizes[2 * (i0 + i) + 1] : height;
       const int o = orientations ? orientations[i0 + i] : IPK_OR_NORMAL;
       ipk::GatherSource g = {0, 0, 0, 0};                                  // width 0: the flat walk
-      if (o != IPK_OR_NORMAL && o != IPK_OR_UNKNOWN) { g = frame_gather(width, height, o); oriented = true; }
+      if (o != IPK_OR_NORMAL && o != IPK_OR_UNKNOWN) { g = frame_gather(wi, hi, o); oriented = true; }
       gs.push_back(g);
+      np.push_back(wi * hi);
     }
     Scratch sc(S(stream));
     void *table = nullptr;
     { const int rc = sc.get(ipk::chain_batch_table_bytes(m), &table); if (rc) return rc; }
-    const int lrc = ipk::launch_chain_batch(fl.data(), m, npix, out_type, table, S(stream), oriented ? gs.data() : nullptr);
+    const int lrc = ipk::launch_chain_batch(fl.data(), m, npix, out_type, table, S(stream), oriented ? gs.data() : nullptr, sizes ? np.data() : nullptr);
     if (lrc == -4) return fail(IPK_ERR_HIP, "pointwise_chain_out_batch: the table upload or the launch could not be enqueued");
     if (lrc != 0) return fail(IPK_ERR_UNSUPPORTED, "pointwise_chain_out_batch: frame too small");
     tm.mark(oriented && stage_oriented ? stage_oriented : stage);
@@ -3185,7 +3218,9 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
     const Admitted &A = p.adm[a];
     for (b = a + 1; b < n; ++b) {
       const Admitted &B = p.adm[b];
-      const bool one_size = A.ng.dw == B.ng.dw && A.ng.dh == B.ng.dh;
+      // IPK_FUSED_BATCH_SIZES waives the one demosaic size where pass 1 of both is the general kernel's batch launch: the sized launches take such a chunk
+      const bool one_size = (A.ng.dw == B.ng.dw && A.ng.dh == B.ng.dh) ||
+                            (frees(a, IPK_FUSED_BATCH_SIZES) && frees(b, IPK_FUSED_BATCH_SIZES) && A.bp.pass1_batched && B.bp.pass1_batched);
       const bool oriented_ok = one_size && frees(a, IPK_FUSED_BATCH_ORIENTED) && frees(b, IPK_FUSED_BATCH_ORIENTED);
       const bool sensor_ok = one_size && frees(a, IPK_FUSED_BATCH_SENSOR) && frees(b, IPK_FUSED_BATCH_SENSOR) && A.bp.pass1_batched && B.bp.pass1_batched &&
                              A.four == B.four;
@@ -3212,32 +3247,60 @@ int plan_each(const ipk_pipeline_desc *const *descs, size_t n, int out_type, Eac
 // ---- the chunk walk ----
 // a frame as the walk sees it: its descriptor and its negotiation
 struct FrameRef { const ipk_pipeline_desc *d; const Negotiated *ng; };
+// The chunks of n frames, cut greedily in order: a chunk grows while it has fewer than 64 frames and its RGBE previews sum to at most 256 MiB, and a frame
+// that alone is larger (or whose byte count would wrap) is a chunk of its own.  For frames of one demosaic size that is batches_previews' chunk,
+// min(64, max(1, 256 MiB / slice)), from the first frame on.  Returns the length of the chunk that begins at frame i0
+extern "C++" template <typename Frame>
+size_t preview_chunk_len(Frame frame, size_t i0, size_t n) {
+  const size_t cap_px = (size_t)1 << 24;                                    // 256 MiB of RGBE
+  size_t m = 0, px = 0;
+  while (i0 + m < n && m < 64) {
+    const Negotiated &ng = *frame(i0 + m).ng;
+    const size_t own = ng.dh == 0 || ng.dw > cap_px / ng.dh ? cap_px + 1 : ng.dw * ng.dh;
+    if (m != 0 && own > cap_px - px) break;
+    px += std::min(own, cap_px); ++m;
+    if (own > cap_px) break;
+  }
+  return m;
+}
 // The chunk walk both preview batches share: frame(i) is frame i of n -- the same pair for every i in a uniform batch (run_batch_previews), the plan's
-// records in a varied run -- and all n negotiate one demosaic size.  A chunk of one frame is single(i); a longer one gets its scratch, pass 1 -- the
-// chunk's RGBE previews one after another, slice floats apart -- and then pass2(i0, m, rgbe, slice, tm), which enqueues the point-wise work of frames
-// i0 .. i0 + m and marks its stages.  Pass 1 of a chunk whose frames differ in a sensor field is ONE frame-table launch (scaled_batch_each_impl: frame
+// records in a varied run, whose frames negotiate one demosaic size unless IPK_FUSED_BATCH_SIZES let them differ.  A chunk (preview_chunk_len) of one frame is
+// single(i); a longer one gets its scratch, pass 1 -- the chunk's RGBE previews one after another, frame i0 + i at offs[i] floats -- and then
+// pass2(i0, m, rgbe, offs, sized, tm), which enqueues the point-wise work of frames i0 .. i0 + m and marks its stages.  Pass 1 of a chunk whose frames
+// differ in a sensor field is ONE frame-table launch (scaled_batch_each_impl: frame
 // i's levels, crops and filter from its descriptor, its window from its negotiation), marked "batch-each gofloat+demosaic"; the plan lets them differ
-// only where bp.pass1_batched holds for every one.  Any other chunk is the uniform launch on the chunk's first descriptor.
+// only where bp.pass1_batched holds for every one.  A chunk whose frames differ in demosaic size (sized) is the same call with every frame's own size: ONE
+// sized launch under the same name.  Any other chunk is the uniform launch on the chunk's first descriptor.
 // sensor_varies: false where no two of the n frames differ in a sensor field (none is compared then)
 extern "C++" template <typename Frame, typename Single, typename Pass2>
 int run_preview_chunks(Frame frame, const BatchPreviews &bp, bool sensor_varies, const void *const *srcs, size_t n, void *stream, Single single, Pass2 pass2) {
-  const size_t slice = frame(0).ng->dw * frame(0).ng->dh * 4;
   std::vector<ipk_scaled_frame> sf;
-  for (size_t i0 = 0; i0 < n; i0 += bp.chunk) {
-    const size_t m = std::min(bp.chunk, n - i0);
+  std::vector<size_t> offs, sizes;
+  for (size_t i0 = 0, m; i0 < n; i0 += m) {
+    m = preview_chunk_len(frame, i0, n);
     if (m == 1) { const int rc = single(i0); if (rc < 0) return rc; continue; }
+    // The chunk's first frame states what the chunk shares.  In a varied run that is not the run's first frame: without a table the chunk's frames have
+    // its sensor fields, and everything else pass 1 reads -- src_type, cpp, is_cfa, the demosaic size -- is equal throughout the chunk
+    const FrameRef c = frame(i0);
+    const ipk_pipeline_desc *const dc = c.d; const Negotiated &nc = *c.ng;
+    const size_t slice = nc.dw * nc.dh * 4;
+    offs.assign(m, 0); sizes.assign(2 * m, 0);
+    size_t total = 0;
+    bool sized = false;
+    for (size_t i = 0; i < m; ++i) {
+      const Negotiated &ni = *frame(i0 + i).ng;
+      offs[i] = total; sizes[2 * i] = ni.dw; sizes[2 * i + 1] = ni.dh; total += ni.dw * ni.dh * 4;
+      sized = sized || ni.dw != nc.dw || ni.dh != nc.dh;
+    }
     StageTimer tm(S(stream));
     Scratch sc(S(stream));
     void *buf = nullptr;
-    int rc = sc.get(m * slice * sizeof(float), &buf); if (rc) return rc;
+    int rc = sc.get(total * sizeof(float), &buf); if (rc) return rc;
     float *rgbe = static_cast<float *>(buf);
-    // The chunk's first frame states what the chunk shares.  In a varied run that is not the run's first frame: without a table the chunk's frames have
-    // its sensor fields, and everything else pass 1 reads -- src_type, cpp, is_cfa, the demosaic size -- is equal throughout the run
-    const FrameRef c = frame(i0);
-    const ipk_pipeline_desc *const dc = c.d; const Negotiated &nc = *c.ng;
-    bool table = false;
+    bool table = sized;
     if (sensor_varies) for (size_t i = 1; i < m; ++i) table = table || !same_sensor(*dc, *frame(i0 + i).d);
     if (table) {
+      if (sized && !bp.pass1_batched) return fail(IPK_ERR_INVALID, "internal: a chunk of differing demosaic sizes outside the general kernel's batch launch");
       sf.assign(m, ipk_scaled_frame{});
       for (size_t i = 0; i < m; ++i) {
         const ipk_pipeline_desc &di = *frame(i0 + i).d; const Negotiated &ni = *frame(i0 + i).ng;
@@ -3248,7 +3311,7 @@ int run_preview_chunks(Frame frame, const BatchPreviews &bp, bool sensor_varies,
         std::memcpy(f.cfa, di.cfa, sizeof(f.cfa));
       }
       rc = scaled_batch_each_impl(srcs + i0, sf.data(), m, dc->src_type, nc.cfa_branch ? -1 : (dc->cpp == 3 ? IPK_PLAIN_RGB : IPK_PLAIN_MONO), nc.dw, nc.dh, rgbe,
-                                  stream, tm, "batch-each gofloat+demosaic");
+                                  stream, tm, "batch-each gofloat+demosaic", sized ? sizes.data() : nullptr);
       if (rc < 0) return rc;
     } else if (bp.pass1_batched) {
       rc = nc.cfa_branch ? raw_scaled_demosaic_batch_impl(srcs + i0, m, dc->src_type, dc->width, nc.r.x, nc.r.y, nc.r.width, nc.r.height, dc->blacklevels[0],
@@ -3260,7 +3323,7 @@ int run_preview_chunks(Frame frame, const BatchPreviews &bp, bool sensor_varies,
       for (size_t i = 0; i < m; ++i) { rc = launch_gofloat_demosaic(dc, nc, srcs[i0 + i], nullptr, rgbe + i * slice, stream); if (rc < 0) return rc; }
     }
     if (!table) tm.mark("batch gofloat+demosaic");
-    rc = pass2(i0, m, rgbe, slice, tm); if (rc < 0) return rc;
+    rc = pass2(i0, m, rgbe, offs.data(), sized, tm); if (rc < 0) return rc;
   }
   return IPK_OK;
 }
@@ -3273,18 +3336,23 @@ void chain_params_of(const ipk_pipeline_desc &d, ipk_chain_params &c) {
 // Pass 2 of a chunk as ONE frame-table launch (chain_out_batch_impl): frame i's record from its own descriptor and negotiation -- its point-wise
 // parameters, its composed orientation -- its source the scratch's slice i, its destination dsts[i] wherever it lies (a destination is not a slice of one
 // flat image here, so frames following each other in memory gain nothing).  The stage is prefix + "to_lab+basecurve+from_lab+gamma", "+transform" behind a
-// launch with at least one oriented frame, "+quantise" for the 8- and 16-bit outputs
+// launch with at least one oriented frame, "+quantise" for the 8- and 16-bit outputs.  sized: the chunk's frames differ in demosaic size, and the launch
+// is the sized one on every frame's own
 extern "C++" template <typename Frame>
-int chain_pass2_each(Frame frame, size_t i0, size_t m, const float *rgbe, size_t slice, int out_type, void *const *dsts, int *used_fused, void *stream,
-                     StageTimer &tm, const char *prefix) {
-  std::vector<ipk_chain_params> cp(m); std::vector<const float *> s4(m); std::vector<int> ori(m);
-  for (size_t i = 0; i < m; ++i) { chain_params_of(*frame(i0 + i).d, cp[i]); s4[i] = rgbe + i * slice; ori[i] = frame(i0 + i).ng->orientation; }
+int chain_pass2_each(Frame frame, size_t i0, size_t m, const float *rgbe, const size_t *offs, bool sized, int out_type, void *const *dsts, int *used_fused,
+                     void *stream, StageTimer &tm, const char *prefix) {
+  std::vector<ipk_chain_params> cp(m); std::vector<const float *> s4(m); std::vector<int> ori(m); std::vector<size_t> sizes(sized ? 2 * m : 0);
+  for (size_t i = 0; i < m; ++i) {
+    const FrameRef f = frame(i0 + i);
+    chain_params_of(*f.d, cp[i]); s4[i] = rgbe + offs[i]; ori[i] = f.ng->orientation;
+    if (sized) { sizes[2 * i] = f.ng->dw; sizes[2 * i + 1] = f.ng->dh; }
+  }
   if (used_fused) *used_fused = 0;
   const std::string chain = std::string(prefix) + "to_lab+basecurve+from_lab+gamma", quantise = out_type == IPK_OUT_F32 ? "" : "+quantise";
   const std::string stage = chain + quantise, stage_oriented = chain + "+transform" + quantise;
   const FrameRef c = frame(i0);
   return chain_out_batch_impl(s4.data(), c.ng->dw, c.ng->dh, one_pass_monochrome(c.d, *c.ng), cp.data(), ori.data(), m, c.ng->linear, out_type, dsts + i0, stream,
-                              tm, stage.c_str(), stage_oriented.c_str());
+                              tm, stage.c_str(), stage_oriented.c_str(), sized ? sizes.data() : nullptr);
 }
 
 // ---- the drivers ----
@@ -3298,13 +3366,13 @@ int run_batch_previews(const ipk_pipeline_desc *d, const Negotiated &ng, const B
   const auto frame = [&](size_t) { return FrameRef{d, &ng}; };
   return run_preview_chunks(frame, bp, false, srcs, n, stream,
     [&](size_t i) { return ipk_pipeline_run(d, srcs[i], dsts[i], out_type, used_fused, stream); },
-    [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
-      if (!ng.transform_noop) return chain_pass2_each(frame, i0, m, rgbe, slice, out_type, dsts, used_fused, stream, tm, "batch ");
+    [&](size_t i0, size_t m, float *rgbe, const size_t *offs, bool sized, StageTimer &tm) {
+      if (!ng.transform_noop) return chain_pass2_each(frame, i0, m, rgbe, offs, sized, out_type, dsts, used_fused, stream, tm, "batch ");
       // the chain once per maximal run of frames whose destinations follow each other in memory
       for (size_t j = 0; j < m;) {
         size_t k = j + 1;
         while (k < m && dsts[i0 + k] == static_cast<char *>(dsts[i0 + k - 1]) + out_bytes) ++k;
-        const int rc = ipk_pointwise_chain_out(rgbe + j * slice, ng.dw, (k - j) * ng.dh, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points,
+        const int rc = ipk_pointwise_chain_out(rgbe + offs[j], ng.dw, (k - j) * ng.dh, monochrome, d->wb_coeffs, d->cam_to_xyz_normalized, d->exposure, d->points,
                                                d->npoints, ng.linear, out_type, dsts[i0 + j], stream);
         if (rc < 0) return rc;
         tm.mark(f32_out ? "batch to_lab+basecurve+from_lab+gamma" : "batch to_lab+basecurve+from_lab+gamma+quantise");
@@ -3320,8 +3388,8 @@ int run_batch_each_varied(const EachPlan &p, const EachPlan::Segment &s, const v
   const auto frame = [&](size_t i) { return FrameRef{&p.d[a + i], &p.adm[a + i].ng}; };
   return run_preview_chunks(frame, s.bp, s.sensor, srcs + a, s.count, stream,
     [&](size_t i) { return ipk_pipeline_run(&p.d[a + i], srcs[a + i], dsts[a + i], out_type, used_fused, stream); },
-    [&](size_t i0, size_t m, float *rgbe, size_t slice, StageTimer &tm) {
-      return chain_pass2_each(frame, i0, m, rgbe, slice, out_type, dsts + a, used_fused, stream, tm, "batch-each ");
+    [&](size_t i0, size_t m, float *rgbe, const size_t *offs, bool sized, StageTimer &tm) {
+      return chain_pass2_each(frame, i0, m, rgbe, offs, sized, out_type, dsts + a, used_fused, stream, tm, "batch-each ");
     });
 }
 }  // namespace
@@ -3387,12 +3455,46 @@ int ipk_scaled_demosaic_batch_each(const void *const *srcs, const void *frames, 
   return scaled_batch_each_impl(srcs, static_cast<const ipk_scaled_frame *>(frames), n, src_type, kind, nwidth, nheight, dst4, stream, tm,
                                 "scaled_demosaic_batch_each");
 }
+// the same with a result size per frame, the slices packed one behind another: one sized frame-table launch per 64
+int ipk_scaled_demosaic_batch_sized(const void *const *srcs, const void *frames, const size_t *sizes, size_t n, int src_type, int kind, float *dst4, void *stream) {
+  REQUIRE_INIT();
+  if (n && !sizes) return fail(IPK_ERR_INVALID, "null argument");
+  StageTimer tm(S(stream));
+  return scaled_batch_each_impl(srcs, static_cast<const ipk_scaled_frame *>(frames), n, src_type, kind, 0, 0, dst4, stream, tm, "scaled_demosaic_batch_sized", sizes);
+}
+// ipk_pointwise_chain_out_batch_oriented with a size per frame: one sized frame-table launch per 64
+int ipk_pointwise_chain_out_batch_sized(const float *const *srcs4, const size_t *sizes, int monochrome, const void *params, const int *orientations, size_t n,
+                                        int linear, int out_type, void *const *dsts, void *stream) {
+  REQUIRE_INIT();
+  if (n && !sizes) return fail(IPK_ERR_INVALID, "null argument");
+  StageTimer tm(S(stream));
+  return chain_out_batch_impl(srcs4, 1, 1, monochrome, static_cast<const ipk_chain_params *>(params), orientations, n, linear, out_type, dsts, stream, tm,
+                              "pointwise_chain_out_batch_sized", nullptr, sizes);
+}
 // The plan of ipk_pipeline_run_batch_each, for callers and CPU tests (no GPU)
 int ipk_pipeline_batch_each_plan(const ipk_pipeline_desc *const *descs, size_t n, int out_type, int *route, size_t *run_first) {
   EachPlan p;
   { const int rc = plan_each(descs, n, out_type, p); if (rc) return rc; }
   for (const EachPlan::Segment &s : p.segs)
     for (size_t i = s.first; i < s.first + s.count; ++i) { if (route) route[i] = s.route; if (run_first) run_first[i] = s.run_first; }
+  return IPK_OK;
+}
+// The chunks that plan is executed in (no GPU): chunk_first[i] is the first frame of the chunk frame i runs in.  A varied run's chunks are the walk's own
+// (preview_chunk_len); a run of equal descriptors that batches its previews is cut by the same rule from its first frame on; every other frame -- a
+// single one, or one of a uniform batch on another route, which has no scratch to share -- is its own
+int ipk_pipeline_batch_each_chunks(const ipk_pipeline_desc *const *descs, size_t n, int out_type, size_t *chunk_first) {
+  EachPlan p;
+  { const int rc = plan_each(descs, n, out_type, p); if (rc) return rc; }
+  if (!chunk_first) return IPK_OK;
+  for (const EachPlan::Segment &s : p.segs) {
+    const size_t a = s.first;
+    const auto frame = [&](size_t i) { return FrameRef{&p.d[a + i], &p.adm[a + i].ng}; };
+    const bool chunked = s.route == kEachVaried || (s.route == kEachUniform && p.adm[a].batches);
+    for (size_t i = 0, m; i < s.count; i += m) {
+      m = chunked ? preview_chunk_len(frame, i, s.count) : 1;
+      for (size_t j = i; j < i + m; ++j) chunk_first[a + j] = a + i;
+    }
+  }
   return IPK_OK;
 }
 // n frames, n descriptors: the plan's runs in order -- a varied run as one scaling launch group and one frame-table launch per chunk, runs of equal

@@ -675,9 +675,12 @@ constexpr int kBatchMax = 64;
 // k_raw_scaled_demosaic's batch mode (launch-uniform): on = 1, gridDim.z frames of one shape whose sources are src[0 .. gridDim.z); on = 0 (gridDim.z
 // == 1): the kernel's own src and dst arguments, src[] is not read
 // on = 2 (frame-table mode, launch_raw_scaled_demosaic_each): gridDim.z frames of one result size and layout, frame z described by frames[z]; src[] is not read
+// on = 3 (sized frame-table mode, the same launcher given per-frame sizes): as on = 2, and frame z's result size and its slice's place behind dst come from
+// frames[z] too; the grid is laid over the launch's widest and tallest result
 struct ScaledBatch { const void *src[kBatchMax]; uint32_t on; const struct ScaledFrame *frames; };
 // One frame of a frame-table launch: everything of TransformArgs that follows from a frame's own sensor window and levels, with its source and (mosaics) its
-// filter's 48 x 48 device table.  nwidth, nheight, layout and the output window stay the launch's
+// filter's 48 x 48 device table.  The layout stays the launch's; so do nwidth, nheight and the output window unless the launch is sized (on = 3), where
+// out_c1 x out_r1 is the frame's own result (its window is the whole of it) and dst_off the float offset of its slice: the sum of the earlier slices
 struct ScaledFrame {
   const void *src; const uint8_t *cfa48;
   uint64_t src_pitch, src_x, src_y;
@@ -685,6 +688,8 @@ struct ScaledFrame {
   float skip_x_x, skip_y_y, inv_skip_x_x, inv_skip_y_y;
   int fast_x, fast_y;
   float min0, range0, min1, range1, min2, range2;
+  uint32_t out_c1, out_r1;
+  uint64_t dst_off;
 };
 
 // OpGoFloat (CFA branch) + scaling::scaled_demosaic in one pass over the raw sensor frame: dst4 = scaled_demosaic(gofloat(src)).
@@ -692,6 +697,8 @@ struct ScaledFrame {
 // Batch mode (bp.on): blockIdx.z is the frame -- its source comes from bp, its result is the z-th out_rows x out_cols slice behind dst.  Nothing else a lane
 // computes depends on z: bounds, centres, weights, the CFA phase and the store's row and column are functions of the absolute row and column as ever.
 // Frame-table mode (bp.on == 2): the frame's sensor window, skips, levels and filter come from its ScaledFrame record as well; block-uniform as before
+// Sized frame-table mode (bp.on == 3): so do the frame's result size and its slice.  A block whose columns lie beyond its frame's width leaves behind the
+// filter barrier like any block beyond the launch's; a block row beyond its frame's height finds its row loop empty
 template <typename T>
 __global__ void k_raw_scaled_demosaic(const T *__restrict__ src0, TransformArgs a, const uint8_t *__restrict__ cfa480, float *__restrict__ dst0, ScaledBatch bp) {
   __shared__ uint8_t s_cfa[48 * 48];
@@ -699,7 +706,7 @@ __global__ void k_raw_scaled_demosaic(const T *__restrict__ src0, TransformArgs 
   const T *__restrict__ src = src0;
   const uint8_t *__restrict__ cfa48 = cfa480;
   float *__restrict__ dst = dst0;
-  if (bp.on == 2) {
+  if (bp.on >= 2) {
     // Frame-table mode: the block's frame brings its own window, skips, levels and filter.  One record, read through an address that depends on blockIdx.z
     // alone (scalar loads), replaces the launch's values; the walk below is the same code on them
     const ScaledFrame &f = bp.frames[blockIdx.z];
@@ -707,10 +714,11 @@ __global__ void k_raw_scaled_demosaic(const T *__restrict__ src0, TransformArgs 
     a.src_pitch = f.src_pitch; a.src_x = f.src_x; a.src_y = f.src_y; a.width = f.width; a.height = f.height;
     a.skip_x_x = f.skip_x_x; a.skip_y_y = f.skip_y_y; a.inv_skip_x_x = f.inv_skip_x_x; a.inv_skip_y_y = f.inv_skip_y_y; a.fast_x = f.fast_x; a.fast_y = f.fast_y;
     a.min0 = f.min0; a.range0 = f.range0; a.min1 = f.min1; a.range1 = f.range1; a.min2 = f.min2; a.range2 = f.range2;
+    if (bp.on == 3) { a.out_r0 = 0; a.out_c0 = 0; a.out_r1 = f.out_r1; a.out_c1 = f.out_c1; dst = dst0 + f.dst_off; }
   } else if (bp.on) {
     src = static_cast<const T *>(bp.src[blockIdx.z]);
   }
-  if (bp.on) dst = dst0 + (size_t)blockIdx.z * (a.out_r1 - a.out_r0) * (a.out_c1 - a.out_c0) * 4;
+  if (bp.on && bp.on != 3) dst = dst0 + (size_t)blockIdx.z * (a.out_r1 - a.out_r0) * (a.out_c1 - a.out_c0) * 4;
   if (mosaic) {
     for (int i = threadIdx.x; i < 48 * 48; i += blockDim.x) s_cfa[i] = cfa48[i];
     __syncthreads();
@@ -1296,23 +1304,30 @@ void launch_raw_scaled_demosaic(const ScaledDemosaicLaunch &l, hipStream_t s) {
 static int launch_status();
 size_t scaled_each_table_bytes(size_t n) { return n * sizeof(ScaledFrame); }
 int launch_raw_scaled_demosaic_each(const ScaledFrameLaunch *frames, size_t n, bool src_is_u16, int layout, size_t nwidth, size_t nheight, float *dst4, void *table_dev,
-                                    hipStream_t s) {
-  if (n == 0 || n > kScaledEachMax || !frames || !dst4 || !table_dev || (layout != 0 && layout != 1 && layout != 3) || nwidth < 1 || nheight < 1 ||
-      nwidth > 0xFFFFFFFFull || nheight > 0xFFFFFFFFull) return -1;
+                                    hipStream_t s, const size_t *sizes) {
+  if (n == 0 || n > kScaledEachMax || !frames || !dst4 || !table_dev || (layout != 0 && layout != 1 && layout != 3)) return -1;
+  // sized: frame i's own result, and the launch's nwidth x nheight the largest of each
+  if (sizes) { nwidth = 0; nheight = 0; for (size_t i = 0; i < n; ++i) { nwidth = std::max(nwidth, sizes[2 * i]); nheight = std::max(nheight, sizes[2 * i + 1]); } }
+  if (nwidth < 1 || nheight < 1 || nwidth > 0xFFFFFFFFull || nheight > 0xFFFFFFFFull) return -1;
   std::vector<ScaledFrame> table(n);
+  uint64_t dst_off = 0;
   for (size_t i = 0; i < n; ++i) {
     const ScaledFrameLaunch &l = frames[i];
+    const size_t nw_i = sizes ? sizes[2 * i] : nwidth, nh_i = sizes ? sizes[2 * i + 1] : nheight;      // the frame's own result
+    if (nw_i < 1 || nh_i < 1) return -1;
     if (!l.src || (layout == 0 && !l.cfa48_dev) || l.width == 0 || l.height == 0 || l.width > 0xFFFFFFFFull || l.height > 0xFFFFFFFFull || l.x > l.owidth || l.width > l.owidth - l.x ||
-        !raw_scaled_demosaic_general(l.width, l.height, nwidth, nheight, true, layout != 0)) return -1;
+        !raw_scaled_demosaic_general(l.width, l.height, nw_i, nh_i, true, layout != 0)) return -1;
     ScaledFrame &f = table[i];
     f.src = l.src; f.cfa48 = l.cfa48_dev;
     f.src_pitch = l.owidth; f.src_x = l.x; f.src_y = l.y; f.width = (uint32_t)l.width; f.height = (uint32_t)l.height;
-    f.skip_x_x = ((float)((int64_t)l.width - 1) - 0.0f) / ((float)(nwidth - 1));
-    f.skip_y_y = ((float)((int64_t)l.height - 1) - 0.0f) / ((float)(nheight - 1));
+    f.skip_x_x = ((float)((int64_t)l.width - 1) - 0.0f) / ((float)(nw_i - 1));
+    f.skip_y_y = ((float)((int64_t)l.height - 1) - 0.0f) / ((float)(nh_i - 1));
     f.inv_skip_x_x = 1.0f / f.skip_x_x; f.inv_skip_y_y = 1.0f / f.skip_y_y;
     f.fast_x = cdiv_host_ok(f.skip_x_x); f.fast_y = cdiv_host_ok(f.skip_y_y);
     f.min0 = l.black[0]; f.range0 = l.white[0] - l.black[0];
     f.min1 = l.black[1]; f.range1 = l.white[1] - l.black[1]; f.min2 = l.black[2]; f.range2 = l.white[2] - l.black[2];
+    f.out_c1 = (uint32_t)nw_i; f.out_r1 = (uint32_t)nh_i; f.dst_off = dst_off;
+    dst_off += (uint64_t)nw_i * nh_i * 4;
   }
   if (hipMemcpyAsync(table_dev, table.data(), n * sizeof(ScaledFrame), hipMemcpyHostToDevice, s) != hipSuccess) return -4;   // (pageable: consumed before it returns)
   // what the kernel takes from the launch: the result's size, the layout and the whole-frame output window (and transform_buffer's zero corner and cross
@@ -1323,11 +1338,14 @@ int launch_raw_scaled_demosaic_each(const ScaledFrameLaunch *frames, size_t n, b
   a.out_r0 = 0; a.out_r1 = (uint32_t)nheight; a.out_c0 = 0; a.out_c1 = (uint32_t)nwidth;
   ScaledBatch bp;
   for (int i = 0; i < kBatchMax; ++i) bp.src[i] = nullptr;
-  bp.on = 2; bp.frames = static_cast<const ScaledFrame *>(table_dev);
+  bp.on = sizes ? 3 : 2; bp.frames = static_cast<const ScaledFrame *>(table_dev);
   dim3 grid = grid_rows_few(nwidth, nheight, 128, (unsigned)(8192 / n));
   grid.z = (unsigned)n;
   // the digits describe no single frame: 0 throughout
-  const char *tag = layout == 3 ? "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,plain=3,batch=1,frames=1"
+  const char *tag = sizes ? (layout == 3 ? "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,plain=3,batch=1,frames=1,sized=1"
+                           : layout == 1 ? "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,plain=1,batch=1,frames=1,sized=1"
+                                         : "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,batch=1,frames=1,sized=1")
+                  : layout == 3 ? "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,plain=3,batch=1,frames=1"
                   : layout == 1 ? "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,plain=1,batch=1,frames=1"
                                 : "norm_fast=0,norm_light=0,fast_x=0,fast_y=0,xcd=0,batch=1,frames=1";
   if (src_is_u16) IPK_LAUNCH_TAG(tag, k_raw_scaled_demosaic<uint16_t>, grid, dim3(128), 0, s, static_cast<const uint16_t *>(nullptr), a, static_cast<const uint8_t *>(nullptr), dst4, bp);
@@ -1742,7 +1760,11 @@ struct FusedArgs {
   Mat9 rgbm;                  // XYZ_D65_33
   int has_curve, linear;
   uint32_t n_strips, n_segs;  // task grid: strips x row segments
-  uint32_t lc_base, lc_rem;   // lane-columns per strip: base (+1 for the first lc_rem strips)
+  union {
+  struct { uint32_t lc_base, lc_rem; };   // lane-columns per strip: base (+1 for the first lc_rem strips)
+  uint64_t frame_npix;        // the kernels over a 4-channel f32 buffer alone, which read none of the mosaic fields, and only from a record of their frame-table
+                              // mode (launch_chain_batch): the frame's own pixel count where the launch is sized; 0 (every other record) = the launch's npix
+  };
   const float *lab_table;
   const float *gam_table;     // SRGB_GAMMA_TRANSFORM, 8193 plain floats
   const LutPair *lab_pairs, *gam_pairs;   // the two tables as 8192 {v, dv} pairs (the LDS image of the pair form)
@@ -1780,6 +1802,9 @@ struct FusedArgs {
                               // host-set; sits in what was the struct's tail padding, so no other argument moved
 };
 static_assert(sizeof(FusedArgs) == 1640 && offsetof(FusedArgs, four) == 1636, "FusedArgs: `four` fills the tail padding; every other kernel argument keeps its offset");
+static_assert(offsetof(FusedArgs, frame_npix) == offsetof(FusedArgs, lc_base) && offsetof(FusedArgs, lc_rem) == offsetof(FusedArgs, lc_base) + 4 &&
+              offsetof(FusedArgs, lc_base) == offsetof(FusedArgs, n_segs) + 4 && offsetof(FusedArgs, lab_table) == offsetof(FusedArgs, lc_base) + 8,
+              "FusedArgs: frame_npix lies over lc_base / lc_rem, which stay where they were");
 
 // one image row as a lane sees it: its 4 samples and the neighbours left/right of them
 struct RowWin { float l, v0, v1, v2, v3, r; };
@@ -3497,11 +3522,12 @@ __global__ __launch_bounds__(1024) void k_pointwise_chain(FusedArgs a, uint64_t 
 // Frame-table mode (frames != null; launch_chain_batch): the grid's y plane is the frame, and the block takes EVERY argument from frames[blockIdx.y] -- a whole
 // FusedArgs per frame in device memory, filled by the host as chain_args fills the kernel's own: source, destination, multipliers, matrix, curve, has_curve,
 // fast_ok (linear, rgbm and the tables are the same in every record), and, where the frame carries an orientation, gather with its own W and steps: the
-// body reads the mode from the record it runs on, so one launch mixes flat and gathering frames (npix is the launch's: an orientation keeps the count).  The index is block-uniform and the table is read-only for the launch, so the record is
+// body reads the mode from the record it runs on, so one launch mixes flat and gathering frames (an orientation keeps the pixel count, which is the launch's unless the launch is sized, below).  The index is block-uniform and the table is read-only for the launch, so the record is
 // read with the uniform loads the kernel arguments are read with; the block fills s_par / s_knots / s_grid from it and walks its own frame's npix pixels, so
-// the clamped tail is the frame's.  The mode is chosen here, once per block: a launch without a table runs the body on its arguments as it always did.
+// the clamped tail is the frame's.  A sized launch's record brings the frame's own pixel count as well (frame_npix != 0): the chunk count, the clamped
+// tail and gather mode's last row are taken of it, and a block with no chunk left of a small frame only passes the barrier.  The mode is chosen here, once per block: a launch without a table runs the body on its arguments as it always did.
 __global__ __launch_bounds__(1024) void k_pointwise_chain_small(FusedArgs a, uint64_t npix, const FusedArgs *__restrict__ frames) {
-  if (IPK_RARE(frames != nullptr)) pointwise_chain_body<false, 1>(frames[blockIdx.y], npix);
+  if (IPK_RARE(frames != nullptr)) { const FusedArgs &f = frames[blockIdx.y]; pointwise_chain_body<false, 1>(f, f.frame_npix ? f.frame_npix : npix); }
   else pointwise_chain_body<false, 1>(a, npix);
 }
 // OpToLab alone: two resident blocks per CU (eight waves per SIMD) are the point of its two-pixel form, so the register budget is stated (64)
@@ -3756,11 +3782,13 @@ __device__ __forceinline__ void rgbe_chain_body(const FusedArgs &a, uint64_t npi
 }
 template <>
 __global__ __launch_bounds__(1024) void k_raster_chain<Rgbe32, 1>(FusedArgs a, uint64_t npix, const LutPair *__restrict__, const FusedArgs *__restrict__ frames) {
-  if (IPK_RARE(frames != nullptr)) rgbe_chain_body<1>(frames[blockIdx.y], npix); else rgbe_chain_body<1>(a, npix);
+  if (IPK_RARE(frames != nullptr)) { const FusedArgs &f = frames[blockIdx.y]; rgbe_chain_body<1>(f, f.frame_npix ? f.frame_npix : npix); }
+  else rgbe_chain_body<1>(a, npix);
 }
 template <>
 __global__ __launch_bounds__(1024) void k_raster_chain<Rgbe32, 2>(FusedArgs a, uint64_t npix, const LutPair *__restrict__, const FusedArgs *__restrict__ frames) {
-  if (IPK_RARE(frames != nullptr)) rgbe_chain_body<2>(frames[blockIdx.y], npix); else rgbe_chain_body<2>(a, npix);
+  if (IPK_RARE(frames != nullptr)) { const FusedArgs &f = frames[blockIdx.y]; rgbe_chain_body<2>(f, f.frame_npix ? f.frame_npix : npix); }
+  else rgbe_chain_body<2>(a, npix);
 }
 // the log tag of a k_raster_chain<uint8_t | uint16_t> launch: fast_ok alone, as ever, on launches that use neither mode (the log keeps the pointer: literals only)
 static const char *raster_tag(const FusedArgs &a) {
@@ -3793,23 +3821,29 @@ int launch_chain_quantised(const FusedLaunch &f, size_t npix, hipStream_t s, con
 // The frame-table launch of the chain (ipk_launch.hpp): frames[i]'s arguments as chain_args makes them for a single launch, uploaded stream-ordered into
 // table_dev, then ONE launch with a grid plane per frame
 size_t chain_batch_table_bytes(size_t n) { return n * sizeof(FusedArgs); }
-int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s, const GatherSource *gathers) {
-  if (n == 0 || n > kChainBatchMax || npix == 0 || out_type < 0 || out_type > 2 || (out_type != 0 && npix < 256) || !table_dev) return -1;
+int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s, const GatherSource *gathers, const size_t *npixs) {
+  if (n == 0 || n > kChainBatchMax || out_type < 0 || out_type > 2 || !table_dev) return -1;
+  // sized: frame i walks npixs[i] pixels, each held to the bounds of a launch of its own; the launch's npix, which sizes the grid, is the largest
+  if (npixs) { npix = 0; for (size_t i = 0; i < n; ++i) { if (npixs[i] == 0 || (out_type != 0 && npixs[i] < 256)) return -1; npix = std::max(npix, npixs[i]); } }
+  if (npix == 0 || (out_type != 0 && npix < 256)) return -1;
   std::vector<FusedArgs> table(n);
   bool fast_all = true, oriented = false;
   for (size_t i = 0; i < n; ++i) {
     table[i] = chain_args(frames[i]);
     table[i].gam_q8 = reinterpret_cast<const Q8Entry *>(frames[i].gam_q8);
     fast_all = fast_all && frames[i].fast_ok;
-    if (gathers && gathers[i].width != 0) {                                // this frame's record gathers: its own W and steps, the launch's npix
-      if (!set_gather(table[i], &gathers[i], npix)) return -1;
+    if (npixs) table[i].frame_npix = npixs[i];
+    if (gathers && gathers[i].width != 0) {                                // this frame's record gathers: its own W and steps over its own pixel count
+      if (!set_gather(table[i], &gathers[i], npixs ? npixs[i] : npix)) return -1;
       oriented = true;
     }
   }
   if (hipMemcpyAsync(table_dev, table.data(), n * sizeof(FusedArgs), hipMemcpyHostToDevice, s) != hipSuccess) return -4;   // (pageable: consumed before it returns)
   const unsigned cus = (unsigned)(frames[0].num_cus > 0 ? frames[0].num_cus : 256);
   const dim3 grid(chain_batch_blocks(npix, out_type, n, cus), (unsigned)n);
-  const char *tag = oriented ? (fast_all ? "fast_ok=1,batch=1,orient=1" : "fast_ok=0,batch=1,orient=1") : (fast_all ? "fast_ok=1,batch=1" : "fast_ok=0,batch=1");
+  const char *tag = npixs ? (oriented ? (fast_all ? "fast_ok=1,batch=1,orient=1,sized=1" : "fast_ok=0,batch=1,orient=1,sized=1")
+                                      : (fast_all ? "fast_ok=1,batch=1,sized=1" : "fast_ok=0,batch=1,sized=1"))
+                  : oriented ? (fast_all ? "fast_ok=1,batch=1,orient=1" : "fast_ok=0,batch=1,orient=1") : (fast_all ? "fast_ok=1,batch=1" : "fast_ok=0,batch=1");
   const FusedArgs *dev = static_cast<const FusedArgs *>(table_dev);
   if (out_type == 0) IPK_LAUNCH_TAG(tag, k_pointwise_chain_small, grid, dim3(1024), 0, s, table[0], (uint64_t)npix, dev);
   else if (out_type == 1) IPK_LAUNCH_TAG(tag, (k_raster_chain<Rgbe32, 1>), grid, dim3(1024), 0, s, table[0], (uint64_t)npix, (const LutPair *)nullptr, dev);

@@ -47,12 +47,14 @@ void selftest_task_queue(bool enabled);   // test hook: false = every following 
 // ipk_raw_scaled_demosaic_window, append win=1: [norm_fast=,...,xcd=,win=1]; the monochrome / three-sample launches of k_raw_scaled_demosaic by
 // ipk_plain_scale_down append plain=1 / plain=3 behind that; its batch launches -- ipk_raw_scaled_demosaic_batch / ipk_plain_scale_down_batch -- append
 // batch=1 behind all of it: [...,xcd=0,batch=1] / [...,xcd=0,plain=1,batch=1]; the frame-table launches -- ipk_scaled_demosaic_batch_each -- append frames=1
-// behind batch=1 and print the four digits in front as 0: [norm_fast=0,...,xcd=0,batch=1,frames=1]), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
+// behind batch=1 and print the four digits in front as 0: [norm_fast=0,...,xcd=0,batch=1,frames=1], the sized ones -- ipk_scaled_demosaic_batch_sized --
+// sized=1 behind that), k_raster_scale_down [win=1] on window launches only (whole frames: no tag),
 // k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain / k_fused_resample [fast_ok=] (0: every pixel takes the literal form); the gather
 // launches of k_pointwise_chain<false> / k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2> (a GatherSource: ipk_pipeline_run_cached_region) append
 // gather=1: [fast_ok=,gather=1] -- flat launches never carry the key; the frame-table launches of k_pointwise_chain_small / k_raster_chain<Rgbe32, 1 | 2>
 // (launch_chain_batch: ipk_pointwise_chain_out_batch) carry [fast_ok=,batch=1], fast_ok the AND over the launch's frames, and [fast_ok=,batch=1,orient=1]
-// when at least one frame's record gathers (ipk_pointwise_chain_out_batch_oriented);
+// when at least one frame's record gathers (ipk_pointwise_chain_out_batch_oriented), sized=1 behind either when the records bring their own pixel counts
+// (ipk_pointwise_chain_out_batch_sized);
 // k_raster_chain's launches by ipk_plain_to_srgb append rect=1 in rectangle mode (a rectangle narrower than the source's pitch) and levels=1 / levels=2
 // in the three-sample / monochrome raw sample modes, in that order: [fast_ok=,rect=1], [fast_ok=,levels=2], [fast_ok=,rect=1,levels=1] -- launches
 // that use neither mode (ipk_raster_to_srgb, ipk_pointwise_chain_out, a full-width raster rectangle) carry [fast_ok=] and nothing else;
@@ -121,8 +123,13 @@ inline bool raw_scaled_demosaic_general(size_t width, size_t height, size_t nwid
 struct ScaledFrameLaunch { const void *src; size_t owidth, x, y, width, height; float black[3], white[3]; const uint8_t *cfa48_dev; };
 constexpr size_t kScaledEachMax = 64;
 size_t scaled_each_table_bytes(size_t n);
+// sizes (optional, 2n entries: nwidth_i, nheight_i): the sized launch -- frame i has its own result size (nwidth and nheight are not read), its slice of
+// nwidth_i * nheight_i * 4 floats begins where the earlier slices of the launch end (16-byte aligned whenever dst4 is), and every frame must select the
+// general kernel for its own size.  The grid is laid over the widest and the tallest result; a block beyond its frame's columns leaves behind the filter
+// barrier, one beyond its rows finds its loop empty.  Slice i is bit-identical to the single launch of frame i at its size.  The tag appends sized=1
+// behind frames=1.  Null: the launch above
 int launch_raw_scaled_demosaic_each(const ScaledFrameLaunch *frames, size_t n, bool src_is_u16, int layout, size_t nwidth, size_t nheight, float *dst4, void *table_dev,
-                                    hipStream_t s);
+                                    hipStream_t s, const size_t *sizes = nullptr);
 
 void launch_tolab(const float *src4, size_t npix, const float *mul4, const float *cm12, const void *lab_pairs, float *dst3,
                   int num_cus, hipStream_t s);
@@ -224,7 +231,12 @@ inline unsigned chain_batch_blocks(size_t npix, int out_type, size_t n, unsigned
   const size_t chunks = out_type == 0 ? (npix + 127) / 128 : (npix + 255) / 256;
   return (unsigned)std::max<size_t>(1, std::min<size_t>((chunks + 15) / 16, (cus + n - 1) / n));
 }
-int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s, const GatherSource *gathers = nullptr);
+// npixs (optional, n entries): the sized launch -- frame i has npixs[i] pixels of its own (each within the bounds above: out_type 1 / 2 need 256), its record
+// says so, and a block takes the count from its record where it otherwise takes the launch's: chunk count, clamped tail, last chunk and gather mode's last
+// row are the frame's, bit-identical to a launch of that frame alone.  The grid's x is sized by the largest frame (npix is not read); blocks beyond a small
+// frame's chunks find no work.  The tag appends sized=1: [fast_ok=,batch=1,sized=1] / [fast_ok=,batch=1,orient=1,sized=1].  Null: the launch above
+int launch_chain_batch(const FusedLaunch *frames, size_t n, size_t npix, int out_type, void *table_dev, hipStream_t s, const GatherSource *gathers = nullptr,
+                       const size_t *npixs = nullptr);
 // run_other + OpToLab..OpGamma + quantisation in one pass over an RGB8 / RGB16 raster (npix >= 256; f.out_type selects the output)
 // plain (optional; ipk_plain_to_srgb): the launch covers a width-pixel-wide rectangle of npix pixels whose first sample is f.src, inside an image whose rows
 // are owidth pixels apart, and f.dst holds its npix * 3 packed samples.  levels: 0 the raster's samples; 1 a three-sample u16 raw, each channel

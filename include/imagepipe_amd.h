@@ -304,6 +304,19 @@ typedef struct { uint32_t struct_size;
 IPK_API int ipk_scaled_demosaic_batch_each(const void *const *srcs, const void *frames /* n ipk_scaled_frame */, size_t n, int src_type,
                                            int kind /* -1 mosaic, IPK_PLAIN_RGB, IPK_PLAIN_MONO */, size_t nwidth, size_t nheight, float *dst4,
                                            void *stream);
+/* The same with a result size per frame: sizes holds 2n values, nwidth_i and nheight_i, and slice i is bit-identical to ipk_raw_scaled_demosaic /
+ * ipk_plain_scale_down called with frame i's own arguments and size.  The slices are packed: slice i holds nwidth_i * nheight_i * 4 floats and begins at
+ * the sum of the earlier slices, so every slice is 16-byte aligned whenever dst4 is; nothing else is written.  One launch per 64 frames: the SIZED
+ * frame-table mode of k_raw_scaled_demosaic<T>, in which the record also brings the frame's result size and its slice's offset.  The grid is laid over
+ * the widest and the tallest result of the launch; a block beyond its own frame's columns leaves behind the (launch-uniform) filter barrier, a frame's
+ * row loop ends at its own height, and everything per pixel is the single launch's code on the frame's own values.  The tag appends sized=1:
+ * [...,xcd=0,batch=1,frames=1,sized=1], plain=1 / plain=3 in front of batch=1 as before.  Admission and errors are ipk_scaled_demosaic_batch_each's, per
+ * frame against its own size, the index named in ipk_last_error; an empty or oversized sizes entry is IPK_ERR_INVALID, the index named.  Everything is
+ * validated before anything is enqueued; n = 0 is IPK_OK.  When all sizes are equal the call is ipk_scaled_demosaic_batch_each with that size (the same
+ * launches and tags).  ipk_timing names each launch "scaled_demosaic_batch_sized". */
+IPK_API int ipk_scaled_demosaic_batch_sized(const void *const *srcs, const void *frames /* n ipk_scaled_frame */,
+                                            const size_t *sizes /* 2n: nwidth_i, nheight_i */, size_t n, int src_type,
+                                            int kind /* -1 mosaic, IPK_PLAIN_RGB, IPK_PLAIN_MONO */, float *dst4, void *stream);
 /* OpGoFloat::run_raw (CFA branch) followed by OpDemosaic::run's LAST branch -- demosaic::full, then scale_down_opbuf to nwidth x nheight
  * (src/ops/demosaic.rs:51-59: 1 < scale < minscale) -- in one launch over the raw sensor frame: ipk_raw_scaled_demosaic's sibling below minscale.  dst4
  * receives nwidth * nheight * 4 f32, bit for bit what ipk_gofloat_cfa_* -> ipk_demosaic_run write for such a frame (E = +0.0); the full-size 1- and
@@ -542,6 +555,17 @@ IPK_API int ipk_pointwise_chain_out_batch(const float *const *srcs4, size_t widt
 IPK_API int ipk_pointwise_chain_out_batch_oriented(const float *const *srcs4, size_t width, size_t height, int monochrome,
                                                    const void *params /* n ipk_chain_params */, const int *orientations /* n ipk_orientation, or NULL */,
                                                    size_t n, int linear, int out_type, void *const *dsts, void *stream);
+/* The same with a size per frame: sizes holds 2n values, width_i and height_i, and frame i is what ipk_pointwise_chain_out_batch_oriented gives a
+ * one-frame call of that size (orientations may be NULL).  One launch per 64 frames: in the frame-table mode a record may bring its frame's own pixel
+ * count, and the block then takes the chunk count, the clamped tail lanes, "the last chunk ends at the last pixel" and gather mode's last row of that
+ * count instead of the launch's; the grid is sized by the largest frame of the launch, and a block beyond a small frame's chunks finds no work.  The
+ * tag appends sized=1: [fast_ok=,batch=1,sized=1], orient=1 in front of sized=1 where a record gathers.  Validation is that call's, per frame: the
+ * floor of 256 pixels for 8 and 16 bits holds for EVERY frame (IPK_ERR_UNSUPPORTED), an empty or oversized sizes entry is IPK_ERR_INVALID, the index
+ * named in ipk_last_error, everything before anything is enqueued.  When all sizes are equal it is exactly that call: the same launches with the same
+ * tags.  ipk_timing names each launch "pointwise_chain_out_batch_sized". */
+IPK_API int ipk_pointwise_chain_out_batch_sized(const float *const *srcs4, const size_t *sizes /* 2n: width_i, height_i */, int monochrome,
+                                                const void *params /* n ipk_chain_params */, const int *orientations /* n ipk_orientation, or NULL */,
+                                                size_t n, int linear, int out_type, void *const *dsts, void *stream);
 /* The raster-source counterpart of ipk_raw_to_srgb: OpGoFloat::run_other (src/ops/gofloat.rs:171-201; RGB8 through
  * expand_srgb_gamma(input8bit(v)), RGB16 through input16bit(v)) + OpToLab + OpBaseCurve + OpFromLab + OpGamma (+ output8bit /
  * output16bit, src/pipeline.rs:408-414,455-461) in one pass from the width*height*3 source samples to width*height*3 outputs of
@@ -637,7 +661,12 @@ typedef struct {
                                       fields -- width, height, cfa, cfa_width, cfa_height, the four crops, blacklevels, whitelevels -- differ inside a run
                                       whose frames negotiate one demosaic size, the scaling pass of such a chunk as one frame-table launch.  Same
                                       contract: no hash, no result, no other driver or report depends on it; allow_fused = 1024 alone still means "on"
-                                      for every older route. */
+                                      for every older route.
+                                      Bit 11 (IPK_FUSED_BATCH_SIZES = 2048) acts beside bits 0 and 8 only, and changes nothing unless bit 9 or bit 10 is
+                                      set as well: ipk_pipeline_run_batch_each then lets the frames of such a run negotiate their own demosaic sizes,
+                                      a chunk of differing sizes as one sized scaling launch and one sized point-wise launch.  Same contract: no
+                                      hash, no result, no other driver or report depends on it; allow_fused = 2048 alone still means "on" for every
+                                      older route. */
   int use_fastpath;                /* PipelineSettings.use_fastpath (pipeline.rs:117; the reference defaults it to true) */
   /* later additions are appended (see ipk_fused_params) */
   int cfa_width, cfa_height;       /* as in ipk_fused_params: the tile's shape from the caller's CFA object, 0, 0 = from the string */
@@ -725,7 +754,7 @@ typedef enum {
                                       (ipk_pipeline_run_cached_region's): a flip keeps a lane's pixels consecutive in memory, forwards or backwards; a
                                       transposing orientation reads one source pixel per lane a source row apart.
                                       Out of scope: active rotatecrops in a batch; per-frame size limits inside one scaling launch (levels, crops
-                                      and filters: bit 10); the host-buffer batch drivers; band forms; the bit as a default; graph capture.
+                                      and filters: bit 10; demosaic sizes that differ under one limit: bit 11); the host-buffer batch drivers; band forms; the bit as a default; graph capture.
                                       Measured (profiles/r21_batch_oriented.txt; device-resident noise frames under a square box, every frame with its
                                       own wb_coeffs and exposure, wall clock, medians, ms per frame; the parent build's only offer -- a loop of
                                       ipk_pipeline_run -- -> ipk_pipeline_run_batch_each with the bit; the parent's spread is 0.0003 .. 0.0045 ms), every
@@ -750,7 +779,7 @@ typedef enum {
                                       and curves, batches above 64 frames, rasters and the window-8 geometries, previews larger than 400 wide (where
                                       the transposing gather's cost must grow towards the 3.3x of ipk_pipeline_run_cached_region's 24 MP region),
                                       the uniform route (ipk_pipeline_run_batch on one oriented descriptor), photo-like data */
-  IPK_FUSED_BATCH_SENSOR = 1024    /* bit 10 (beside bits 0 and 8; nothing without either; combines with bit 9): the frames of a batch of previews may
+  IPK_FUSED_BATCH_SENSOR = 1024,   /* bit 10 (beside bits 0 and 8; nothing without either; combines with bit 9): the frames of a batch of previews may
                                       carry their own sensor settings.  One camera's levels change with ISO and a folder holds more than one body, so
                                       ipk_pipeline_run_batch_each keeps frames in one run that differ in width, height, cfa, cfa_width, cfa_height, the
                                       crops, blacklevels or whitelevels, where each would batch its own previews through the general scaling kernel
@@ -760,7 +789,7 @@ typedef enum {
                                       loop of ipk_pipeline_run; a chunk whose frames agree in them is the uniform launch as before.  Without the bit
                                       every plan, launch, tag and stage name is what it was.  The carrier kernel: 49 VGPRs, no scratch, in both
                                       instantiations, before and after.
-                                      Out of scope: per-frame preview sizes (different demosaic sizes in one launch); batch forms of the window-8 kernels
+                                      Out of scope: per-frame preview sizes without bit 11 (IPK_FUSED_BATCH_SIZES); batch forms of the window-8 kernels
                                       and the raster scaler; active rotatecrops in a batch; the host-buffer batch drivers and the multi-device driver;
                                       band forms; the bit as a default; graph capture.
                                       Measured (profiles/r22_batch_sensor.txt; device-resident noise frames to u8, every frame with its own black and
@@ -781,6 +810,48 @@ typedef enum {
                                       samples: +0.002 ms (1.6 .. 1.9 %) both times; its disassembly holds the parent's vector loads one for one, the cause was not found.
                                       Not measured: f32 sources, f32 and 16-bit outputs, per-frame crops and filters inside one series, three-sample
                                       raws, batches above 64 frames, orientations beside sensor settings, mixed batches, photo-like data */
+  IPK_FUSED_BATCH_SIZES = 2048     /* bit 11 (beside bits 0 and 8; nothing unless bit 9 or bit 10 is set as well, because nothing else lets a size
+                                      differ): the frames of a batch of previews may negotiate their own demosaic size.  Under maxwidth alone a
+                                      Rotate90 frame negotiates another size than a Normal one (6000x4000 under maxwidth 256: 256x170 against
+                                      384x256), and so do two bodies of different aspect ratio; without this bit such a pair cuts the run, and an
+                                      alternating shoot is a loop of ipk_pipeline_run.  With it ipk_pipeline_run_batch_each waives the "one demosaic
+                                      size" condition of bits 9 and 10 for a pair of descriptors that both carry the bit, would both batch their own
+                                      previews, and both have pass1_batched = 1 (ipk_pipeline_batches_previews): the sized launch exists for the
+                                      general scaling kernel only.  maxwidth, maxheight and every field that counted before still count, and under
+                                      bit 10 both filters still agree in whether they have a fourth colour.  Such a run is route 2.  Its chunks are cut
+                                      greedily in order (ipk_pipeline_batch_each_chunks reports them): a chunk grows while it has fewer than 64 frames
+                                      and its RGBE previews sum to at most 256 MiB -- for frames of one size the chunk of old.  Pass 1 of a chunk whose
+                                      frames differ in demosaic size is ONE ipk_scaled_demosaic_batch_sized launch ("batch-each gofloat+demosaic"),
+                                      pass 2 ONE ipk_pointwise_chain_out_batch_sized launch (the "batch-each to_lab+..." names of old); a chunk whose
+                                      sizes agree takes the launches it took.  Without the bit every plan, launch, tag, stage name and result is what
+                                      it was.  The sized grid is laid over the largest frame of the chunk: blocks over a smaller frame's missing
+                                      columns or rows find no work, so a chunk wastes blocks in proportion to the spread of its sizes.
+                                      Out of scope: per-frame maxwidth / maxheight; the window-8 kernels and the raster scaler (they cut the run);
+                                      active rotatecrops in a batch; the host-buffer batch drivers and the multi-device driver; graph capture.
+                                      The carriers, before and after: k_raw_scaled_demosaic<T> 49 VGPRs in both instantiations,
+                                      k_pointwise_chain_small 82, k_raster_chain<Rgbe32, 1 | 2> 124 / 123, no scratch; no other kernel's disassembly
+                                      moved (the file below holds both tools' output).
+                                      Measured (profiles/r24_batch_sizes.txt; device-resident 24 MP RGGB u16 noise frames to u8, every frame with its
+                                      own wb_coeffs, wall clock, medians, ms per frame; the parent build's only offer -- its
+                                      ipk_pipeline_run_batch_each, which cuts such a run into a loop of ipk_pipeline_run -- -> this call with the bit;
+                                      the parent's spread is 0.0005 .. 0.0126 ms), n = 2 / 8 / 16 / 64: Normal / Rotate90 alternating under maxwidth 256
+                                      (256x170 beside 384x256): 0.180 -> 0.127, 0.185 -> 0.069, 0.184 -> 0.067, 0.182 -> 0.068; under maxwidth 400
+                                      (400x266 beside 600x400): 0.117 -> 0.089, 0.118 -> 0.072, 0.116 -> 0.069, 0.115 -> 0.067; a 3:2 and a 4:3 body
+                                      alternating under maxwidth 256 (256x170 beside 256x192): 0.211 -> 0.124, 0.222 -> 0.065, 0.214 -> 0.064, 0.213 ->
+                                      0.062: x1.3 .. x1.7 at n = 2, x1.6 .. x3.4 at n >= 8.  No measured case at n >= 8 was slower than the parent's
+                                      loop; none is excluded.  The price of the spread of sizes -- the sized call minus the mean of this build's two
+                                      equal-size runs of the same shapes, the wasted blocks of the sized grid and the larger records together: the
+                                      chunk mixing 256x170 with 384x256 +0.024 / +0.005 / -0.001 / +0.009 ms per frame at n = 2 / 8 / 16 / 64, over
+                                      all three series -0.001 .. +0.024 (the equal-size runs themselves vary by 0.01 between batch sizes: reported,
+                                      not bounded).  Outside the mode, parent -> this build, every reading inside the parent's spread:
+                                      ipk_raw_scaled_demosaic 6000x4000 -> 400x266 0.1209 -> 0.1187 ms (spread 0.0027), ipk_pointwise_chain_out to u8
+                                      at 2160x1440 0.0403 -> 0.0400 (0.0011) and at 6000x4000 0.1824 -> 0.1837 (0.0085), per call at n = 16: the
+                                      uniform batch 1.174 -> 1.183 (0.047), bit 9's equal-size launches 1.177 -> 1.187 (0.041), bit 10's 1.221 ->
+                                      1.248 (0.059) -- all three on the slower side of the median; no loss outside a spread was read.  bench.py,
+                                      alternating, MP/s: parent 232381 .. 235319, this build 233873 .. 234956.
+                                      Not measured: f32 sources, f32 and 16-bit outputs, other mosaics, monochrome and three-sample raws, more than
+                                      two sizes in a chunk, batches above 64 frames, chunks cut by the 256 MiB sum, orientation and sensor size
+                                      together, the host cost of the plan alone, photo-like data */
 } ipk_fused_mask;
 #define IPK_PIPELINE_DESC_INIT {(uint32_t)sizeof(ipk_pipeline_desc)}
 
@@ -962,7 +1033,8 @@ IPK_API int ipk_devices_sync(void);
  *   These THREE may differ -- rotation, fliph and flipv: eight fields instead of five -- when BOTH descriptors carry IPK_FUSED_BATCH_ORIENTED beside
  *     IPK_FUSED_ON | IPK_FUSED_BATCH_PREVIEWS, each would batch its own previews (ipk_pipeline_batches_previews answers 1 for it) and both negotiate
  *     the same demosaic size (ipk_pipeline_sizes).  The demosaic size decides the scaling pass's filter; under one maxwidth alone a Rotate90 / Rotate270
- *     frame negotiates another one than a Normal frame (transform_forward swaps the sides before the clamp) and still cuts the run, under a square box
+ *     frame negotiates another one than a Normal frame (transform_forward swaps the sides before the clamp) and still cuts the run unless both carry
+ *     IPK_FUSED_BATCH_SIZES (below), under a square box
  *     (maxwidth == maxheight) frames of equal source size agree, and fliph / flipv never enter the fold.
  *   These ELEVEN may differ -- the SENSOR fields: width, height, cfa, cfa_width, cfa_height, crop_top / right / bottom / left, blacklevels and
  *     whitelevels -- when BOTH descriptors carry IPK_FUSED_BATCH_SENSOR beside IPK_FUSED_ON | IPK_FUSED_BATCH_PREVIEWS, each would batch its own previews
@@ -972,6 +1044,11 @@ IPK_API int ipk_devices_sync(void);
  *     whose frames differ in them is ONE ipk_scaled_demosaic_batch_each launch, frame i's window, levels and filter from descriptor i's own negotiation,
  *     named "batch-each gofloat+demosaic"; a chunk whose frames agree in them is the uniform launch on the chunk's first descriptor, named
  *     "batch gofloat+demosaic"; pass 2 is what it is below.
+ *   The "same demosaic size" of both conditions is waived for a pair when BOTH descriptors carry IPK_FUSED_BATCH_SIZES as well, each would batch its own
+ *     previews and both have pass1_batched = 1 (the sized launch exists for the general kernel only).  Chunks are then cut greedily
+ *     (ipk_pipeline_batch_each_chunks); pass 1 of a chunk whose frames differ in demosaic size is ONE ipk_scaled_demosaic_batch_sized launch, named
+ *     "batch-each gofloat+demosaic", and pass 2 ONE ipk_pointwise_chain_out_batch_sized launch under the names below; a chunk whose sizes agree takes the
+ *     launches above.
  * The two conditions are asked of a pair independently: it may meet either, both or neither.  The frames are cut, in order, into maximal runs of
  * consecutive same-shaped descriptors; run_first[i] is the first frame of frame i's run.  For a run of m frames:
  *   route 2, varied previews: m > 1, ipk_pipeline_batches_previews(descs[run_first], out_type, m, ...) answers 1 (so allow_fused needs IPK_FUSED_ON |
@@ -986,7 +1063,7 @@ IPK_API int ipk_devices_sync(void);
  *     full-size launch and the uniform preview batch for callers who happen to have them;
  *   route 0, single: every other frame, through ipk_pipeline_run.
  * Out of scope: per-frame settings inside the persistent full-size launch ipk_raw_to_srgb_batch (one parameter set; full-size frames with varied
- * settings are route 0 each); per-frame preview sizes inside one scaling launch (they cut the run); non-Normal orientations without IPK_FUSED_BATCH_ORIENTED and active
+ * settings are route 0 each); per-frame preview sizes without IPK_FUSED_BATCH_SIZES (they cut the run), per-frame maxwidth / maxheight (they always do); non-Normal orientations without IPK_FUSED_BATCH_ORIENTED and active
  * rotatecrops inside a varied run (ipk_pipeline_batches_previews answers 0: frame by frame, or route 1 where identical); the host-buffer batch drivers;
  * the multi-device driver (it may follow by calling this one member by member); band forms; the bit as a default; graph capture (the table upload of
  * ipk_pointwise_chain_out_batch is a copy from pageable host memory).
@@ -1010,6 +1087,11 @@ IPK_API int ipk_pipeline_run_batch_each(const ipk_pipeline_desc *const *descs, c
 /* host-only, no GPU: the plan the call above follows.  IPK_ERR_INVALID for a null or invalid descriptor (the index is named in ipk_last_error) */
 IPK_API int ipk_pipeline_batch_each_plan(const ipk_pipeline_desc *const *descs, size_t n, int out_type,
                                          int *route /* n */, size_t *run_first /* n */);
+/* host-only, no GPU: the chunks that plan is executed in -- chunk_first[i] is the first frame of the chunk frame i runs in (the frames that share one
+ * scratch and one pair of launches).  A route-2 run, and a route-1 run that batches its previews, are cut greedily in order: a chunk grows while it has
+ * fewer than 64 frames and its RGBE previews sum to at most 256 MiB (for frames of one size: ipk_pipeline_batches_previews' chunk).  Every other frame is
+ * its own.  Validation is ipk_pipeline_batch_each_plan's; nothing is allocated for the frames */
+IPK_API int ipk_pipeline_batch_each_chunks(const ipk_pipeline_desc *const *descs, size_t n, int out_type, size_t *chunk_first /* n */);
 /* HOST frames in, HOST results out, over the device set: the drop-in for a caller looping Pipeline::run / output_8bit over a shoot on a
  * multi-GPU node.  One host thread per member runs ipk_host_pipeline_run_batch on the frames dealt to it (frame i -> member i mod N), so all
  * GPUs upload, compute and download concurrently; the caller's Vecs are the "gather".  Synchronous at return; results are what n calls of

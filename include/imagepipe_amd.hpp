@@ -308,6 +308,7 @@ class Pipeline {
   bool batch_previews = false;             // ipk_pipeline_desc.allow_fused bit 8 (IPK_FUSED_BATCH_PREVIEWS): run_batch() runs downscaled previews as one scaling launch group and one point-wise pass per chunk of frames where batches_previews() says so
   bool batch_oriented = false;             // ipk_pipeline_desc.allow_fused bit 9 (IPK_FUSED_BATCH_ORIENTED), set only together with batch_previews: batched previews take frames of any orientation (OpTransform folded into the point-wise pass), and run_batch_each lets rotation / fliph / flipv differ inside a run
   bool batch_sensor = false;               // ipk_pipeline_desc.allow_fused bit 10 (IPK_FUSED_BATCH_SENSOR), set only together with batch_previews: run_batch_each lets width, height, cfa, the crops and the levels differ inside a run whose frames negotiate one demosaic size
+  bool batch_sizes = false;                // ipk_pipeline_desc.allow_fused bit 11 (IPK_FUSED_BATCH_SIZES), set only together with batch_previews, and nothing without batch_oriented or batch_sensor: run_batch_each lets the frames of such a run negotiate their own demosaic sizes
   bool window_previews = false;            // ipk_pipeline_desc.allow_fused bit 3 (IPK_FUSED_WINDOW_PREVIEWS): regions of downscaled previews run as a window of the scaling gofloat + demosaic pass where windows_preview() says so
   int last_ops_run = 0xFF;                 // bit i: op i executed in the last run (0 = served from the cache)
   uint64_t source_id = 0;                  // identifies the frame inside a shared PipelineCache (extension, see the C header)
@@ -422,6 +423,7 @@ class Pipeline {
     if (batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_PREVIEWS;
     if (batch_oriented && batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_ORIENTED;
     if (batch_sensor && batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_SENSOR;
+    if (batch_sizes && batch_previews && d.allow_fused) d.allow_fused |= IPK_FUSED_BATCH_SIZES;
     return d;
   }
   // does the run take the one-launch route through its active OpRotateCrop (ipk_pipeline_fuses_rotatecrop; no GPU needed)?  out_type: IPK_OUT_*
@@ -485,6 +487,15 @@ class Pipeline {
     for (size_t i = 0; i < pipes.size(); ++i) plan[i] = {route[i], first[i]};
     return plan;
   }
+  // the chunks that plan is executed in (ipk_pipeline_batch_each_chunks; no GPU needed): per frame the first frame of its chunk
+  static std::vector<size_t> batch_each_chunks(const std::vector<const Pipeline *> &pipes, int out_type = IPK_OUT_F32) {
+    std::vector<ipk_pipeline_desc> ds(pipes.size());
+    std::vector<const ipk_pipeline_desc *> dp(pipes.size());
+    for (size_t i = 0; i < pipes.size(); ++i) { ds[i] = pipes[i]->desc(); dp[i] = &ds[i]; }
+    std::vector<size_t> first(pipes.size());
+    check(ipk_pipeline_batch_each_chunks(dp.data(), pipes.size(), out_type, first.data()), "pipeline_batch_each_chunks");
+    return first;
+  }
 
  private:
   explicit Pipeline(ImageSource img) : globals{std::move(img), PipelineSettings()}, ops(globals.image) {}
@@ -526,6 +537,22 @@ inline void pointwise_chain_out_batch_oriented(const std::vector<const float *> 
   const ipk_chain_params *p = params.data();
   check(ipk_pointwise_chain_out_batch_oriented(srcs4.data(), width, height, monochrome ? 1 : 0, p, orientations.empty() ? nullptr : orientations.data(),
                                                srcs4.size(), linear ? 1 : 0, out_type, dsts.data(), stream), "pointwise_chain_out_batch_oriented");
+}
+// ipk_scaled_demosaic_batch_sized: the same with a result size per frame -- sizes holds nwidth_i, nheight_i for every frame, the slices are packed
+inline void scaled_demosaic_batch_sized(const std::vector<const void *> &srcs, const std::vector<ipk_scaled_frame> &frames, const std::vector<size_t> &sizes,
+                                        int src_type, int kind, float *dst4, void *stream = nullptr) {
+  if (frames.size() != srcs.size() || sizes.size() != 2 * srcs.size()) throw Error("scaled_demosaic_batch_sized: as many frame records and size pairs as frames");
+  check(ipk_scaled_demosaic_batch_sized(srcs.data(), frames.data(), sizes.data(), srcs.size(), src_type, kind, dst4, stream), "scaled_demosaic_batch_sized");
+}
+// ipk_pointwise_chain_out_batch_sized: pointwise_chain_out_batch_oriented with a size per frame -- sizes holds width_i, height_i for every frame
+inline void pointwise_chain_out_batch_sized(const std::vector<const float *> &srcs4, const std::vector<size_t> &sizes, bool monochrome,
+                                            const std::vector<ipk_chain_params> &params, const std::vector<int> &orientations, bool linear, int out_type,
+                                            const std::vector<void *> &dsts, void *stream = nullptr) {
+  if (params.size() != srcs4.size() || dsts.size() != srcs4.size() || sizes.size() != 2 * srcs4.size() || (!orientations.empty() && orientations.size() != srcs4.size()))
+    throw Error("pointwise_chain_out_batch_sized: as many parameter sets, size pairs, orientations and destinations as frames");
+  const ipk_chain_params *p = params.data();
+  check(ipk_pointwise_chain_out_batch_sized(srcs4.data(), sizes.data(), monochrome ? 1 : 0, p, orientations.empty() ? nullptr : orientations.data(), srcs4.size(),
+                                            linear ? 1 : 0, out_type, dsts.data(), stream), "pointwise_chain_out_batch_sized");
 }
 
 // ---- several devices from ONE process (imagepipe_amd.h, "Several devices from ONE process") --------------------------------------------------
